@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: WaveGlow inference throughput (audio samples/s at 22.05 kHz).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the JSON line (``ms_per_step`` = the time of one
+timed step).  Everything else it can measure - the roofline, the CPU baseline, the exchange timing and the secondary
+rows below - runs only under ``--full``.  ``--dump-outputs DIR`` writes the waveforms of the last timed step (rank 0's)
+as ``DIR/audio.npy`` (float32, B x T); the mels and the noise are seeded, so equal arguments give equal inputs.
 
 A "step" is one pass of the hot path - ``WaveGlow.infer`` (glow.py:314-350 semantics) of
 BASELINE.json config 2: full WaveGlow (12 flows, 512 WN channels, 8 groups), fp32, on a batch
@@ -19,11 +24,11 @@ synchronize and the MAX over ranks is used.  Rank 0 prints ONE JSON line.  Two w
 
 Rank 0 synthesises the weights; for N > 1 the other ranks receive them through
 ``cookietts_amd.sharding.broadcast_state_dict`` (the once-per-model RCCL broadcast of SURVEY.md §8e).
-Beside the timed weak-scaling steps the per-request exchange of §8e is timed once per run:
+Under --full, beside the timed weak-scaling steps the per-request exchange of §8e is timed once per run:
 ``scatter_mels`` (rank 0 -> ranks) and ``gather_waves`` (direct point-to-point into rank 0), reported as
 ``exchange.{broadcast_ms, scatter_ms, gather_ms}``.
 
-Extra objects on the line:
+Extra objects on the line (--full; null or absent in a plain run):
   roofline     - the dominant kernel (WN in-layer conv-GEMM: dilated conv + cond + gate),
                  algorithmic FLOPs per launch / mean launch time measured with HIP events
                  inside the library on the launch stream, vs the MFMA peak of the dtype; beside it the
@@ -112,7 +117,37 @@ def parse_args(argv=None):
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="test hook for tests/test_bench_launcher.py: gloo on CPU with a stand-in step function; "
                          "exercises the launcher, the rank plumbing and sharding.py only - measures nothing")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline (in-library HIP-event timing of the timed steps), the CPU baseline, "
+                         "the exchange timing (N > 1: scatter / gather; N = 1: the world-size-1 RCCL dry run) and the "
+                         "secondary rows; the --rows / --cpu-* / --no-* options above shape these.  Off: setup, warm-up, the "
+                         "timed steps, --dump-outputs and the JSON line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (rank 0's waveforms) as DIR/audio.npy, float32")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 60 << 20           # all files of --dump-outputs together, .npy headers included, stay below 64 MB
+
+
+def dump_outputs(out_dir, arrays, seed=1234):
+    """Write each tensor of ``arrays`` as ``out_dir/<name>.npy`` in float32.  A tensor that does not fit in what is left of
+    DUMP_BUDGET_BYTES is replaced by a fixed, seeded sample of its flattened elements, in index order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes + 4096 > left:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, max(0, (left - 4096) // 4), replace=False))
+            a = a.reshape(-1)[idx]
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes + 4096
+        sys.stderr.write(f"[bench] wrote {os.path.join(out_dir, name + '.npy')} {tuple(a.shape)} float32\n")
 
 
 # ----------------------------------------------------------------------------- launcher ----
@@ -548,11 +583,12 @@ def worker(args, pre=None):
         exchange = {"broadcast_ms": (time.perf_counter() - t0) * 1e3, "broadcast_bytes": int(nbytes)}
 
     mel = torch.from_numpy(synthetic.synthetic_mel(B, F, seed=seed + rank)).to(device)   # resident in HBM
+    torch.manual_seed(seed + rank)                         # the noise of infer(): equal arguments, equal inputs of every step
 
     for _ in range(args.warmup):
         out = step_on(mel)
     fence()
-    timing = not args.no_kernel_timing and lib is not None
+    timing = args.full and not args.no_kernel_timing and lib is not None
     prof = _lib.Profile() if timing else None
     if timing:
         prof.bind()
@@ -566,6 +602,8 @@ def worker(args, pre=None):
     if timing:
         prof.unbind()
     assert out.shape == (B, T) and bool(torch.isfinite(out).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"audio": out})
 
     rank_ms = [elapsed / args.steps * 1e3]
     if world > 1:
@@ -580,7 +618,7 @@ def worker(args, pre=None):
 
     # the per-request exchange of SURVEY 8e, outside the timed steps: rank 0 holds world*B mels, scatters the
     # slices, every rank vocodes its slice, waves are gathered point-to-point into rank 0
-    if world > 1 and not args.no_exchange:
+    if world > 1 and args.full and not args.no_exchange:
         n_mel = cfg["n_mel_channels"]
         # config 3 ships bf16 mels (32 x 80 x 900 bf16 = 4.6 MB per rank); the fp32 path ships fp32
         xdtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
@@ -612,7 +650,7 @@ def worker(args, pre=None):
     # N = 1: the same exchange code on a world-size-1 RCCL group, outside the timed steps, so that broadcast / scatter /
     # gather have run on RCCL on this box before the first multi-GPU lease.  A failure here is
     # recorded, it never takes the headline line down.
-    if world == 1 and not selftest and not args.no_exchange and not args.no_exchange_dry_run:
+    if world == 1 and args.full and not selftest and not args.no_exchange and not args.no_exchange_dry_run:
         try:
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
             os.environ.setdefault("MASTER_PORT", str(_free_port()))
@@ -650,7 +688,7 @@ def worker(args, pre=None):
         roofline = wn_roofline(prof, cfg, args.dtype, args.gemm_mode, B, F, args.steps, elapsed, args.config) if timing else None
         cpu = pre["cpu"] if pre else None      # timed by main() before the GPU was touched (its aggregate leg starts children)
         rows, rows_s = None, None
-        which_rows = [] if (args.no_rows or world > 1 or selftest) else [r for r in args.rows.split(",") if r]
+        which_rows = [] if (not args.full or args.no_rows or world > 1 or selftest) else [r for r in args.rows.split(",") if r]
         if which_rows:
             rows, rows_s = run_rows(which_rows, model, cfg, lib, args, device)
         line = {
@@ -684,7 +722,7 @@ def main():
         # launcher role: nothing below this line in THIS process imports torch or touches HIP
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], timeout_s=args.launch_timeout))
     pre = None
-    if args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.selftest_launcher and args.dtype != "cpu":
+    if args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.selftest_launcher and args.dtype != "cpu":
         # The CPU baseline runs FIRST, while this process has made no HIP call: its aggregate leg starts child
         # processes, and nothing GPU-initialised may ever be forked / exec'd on this pool.  (Profiler runs pass
         # --cpu-frames 0: rocprofv3's preloaded library initialises the GPU before Python starts.)

@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
 dtype = sys.argv[1]
 for b in sys.argv[2:]:
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", b, "--frames", os.environ.get("FRAMES", "900"), "--no-rows", "--cpu-frames", "0", "--steps", "10", "--warmup", "3"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", b, "--frames", os.environ.get("FRAMES", "900"), "--full", "--no-rows", "--cpu-frames", "0", "--steps", "10", "--warmup", "3"]
     if dtype != "f32":
         cmd += ["--dtype", dtype]
     out = subprocess.run(cmd, capture_output=True, text=True).stdout

@@ -2,7 +2,7 @@
 # The one GPU-box runner: gpurun -- 'bash scripts/gpu.sh <task> [args...]'.  Output under gpurun_out/<tag>_*.
 #   tests [tag] [pytest args]   python -m pytest tests -m gpu <args>   (default: the whole suite)
 #   py <tag> <script.py> [args] run a python script, log to gpurun_out/<tag>.log
-#   bench <tag> [bench args]    python bench.py <args>, JSON line to gpurun_out/<tag>_bench.json
+#   bench <tag> [bench args]    python bench.py --full <args>, JSON line to <tag>_bench.json
 #   stats <tag> <prog> [args]   rocprofv3 --kernel-trace --stats of a python program -> gpurun_out/<tag>_kernel_stats.csv
 #   pmc <tag> <prog> [args]     scripts/pmc3.sh: three separate --pmc passes (FETCH_SIZE; WRITE_SIZE; SQ wait/busy) + pmc_summary.py
 #   ab <tag> <KNOB[=v]> [bench args]  bench.py with the environment knob off / on / off / on in one lease, one summary line each
@@ -23,6 +23,7 @@ case "$task" in
     timeout 3000 python "$@" > gpurun_out/${tag}.log 2>&1; echo "rc=$?"; tail -15 gpurun_out/${tag}.log ;;
   bench)
     tag=$1; shift
+    set -- --full "$@"          # the whole line: roofline, CPU baseline, exchange dry run and rows
     timeout 1500 python bench.py "$@" > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err; echo "rc=$?"
     tail -c 3000 gpurun_out/${tag}_bench.json; tail -5 gpurun_out/${tag}_bench.err ;;
   stats)
@@ -36,6 +37,7 @@ case "$task" in
     bash scripts/pmc3.sh "$@" ;;
   ab)
     tag=$1; knob=${2%%=*}; val=1; [[ "$2" == *=* ]] && val=${2#*=}; shift 2
+    set -- --full "$@"          # ab_summary.py reads the WN launch means of the roofline
     for rep in 1 2; do
       for mode in off on; do
         if [ $mode = on ]; then export $knob=$val; else unset $knob; fi

@@ -5,6 +5,7 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out; export TMPDIR=/tmp
 tag=$1; knob=${2%%=*}; val=1; [[ "$2" == *=* ]] && val=${2#*=}; shift 2
+set -- --full "$@"              # the in-layer launch mean comes from the roofline
 out=gpurun_out/${tag}_power_ab.txt
 echo "# bench.py --no-rows --cpu-frames 0 $* ; knob $knob=$val ; power = mean of the rocm-smi --showpower samples >= 70 % of the run's maximum" > $out
 for rep in 1 2; do
