@@ -783,6 +783,7 @@ void load_tuning_locked() {
     g_tune.wf_inject_abort = num("CTTS_WF_INJECT_ABORT", 0);
     g_tune.wf_queue_debug = num("CTTS_WF_QUEUE_DEBUG", 0);
     g_tune.f32_no_defer_skip = on("CTTS_F32_NO_DEFER_SKIP");
+    g_tune.f32_no_wn_fold = on("CTTS_F32_NO_WN_FOLD");
     g_tune.w4_debug = num("CTTS_BF16_W4_DEBUG", 0);
     g_tune_loaded = true;
 }

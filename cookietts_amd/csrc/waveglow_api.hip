@@ -33,6 +33,7 @@ struct Plan {
     int S;                              // speaker-embedding rows per flow, padded to a multiple of 32 (0: single speaker)
     int nch0, nch1h, nch_in, nch_rs;    // K chunks: cond0, cond1, in-layer, res/skip
     int mb_in;                          // M-blocks of the in-layer GEMM
+    int nch_in0f;                       // K chunks of layer 0's in-layer GEMM on the folded start: one per tap + cond
     std::vector<FlowDims> fd;
     // packed blob offsets (floats)
     size_t up_w, up_wp, up_b, cond0_A, cond0_b, cond1_A, cond1_b;
@@ -43,6 +44,9 @@ struct Plan {
         // deferred-skip form (round 4, profiles/r4_07_res_skip_experiments.txt): res rows per layer, skip rows of a group of
         // up to F32_SKIP_GROUP layers side by side along K
         std::vector<size_t> res_A, res_b, skip_A, skip_b;
+        // WN start / end folds (round 7): in0f_w = W_in,0[tap] . [W_start | b_start] as a dense [2C][FOLD_ROWS][ks] in_w, in0f_A its
+        // packed GATE matrix (+ the cond slice; bias = in_b[0]); skend_W = W_end . W_skip,i as [n_layers][C][2 n_half], skend_b = b'
+        size_t in0f_w, in0f_A, skend_W, skend_b;
     };
     std::vector<Flow> fl;
     size_t total;
@@ -81,6 +85,7 @@ int make_plan(const ctts_waveglow_config* cfg, Plan& p) {
     p.nch_in = (c.kernel_size * p.C + p.H) / GEMM_KC;
     p.nch_rs = p.C / GEMM_KC;
     p.mb_in = 2 * p.C / GEMM_BM;
+    p.nch_in0f = c.kernel_size + p.nch1h;
     // per-flow channel counts exactly as glow.py:251-265
     int n_half = c.n_group / 2, n_rem = c.n_group;
     p.fd.resize(c.n_flows);
@@ -121,6 +126,10 @@ int make_plan(const ctts_waveglow_config* cfg, Plan& p) {
             f.skip_A.push_back(take((size_t)p.mb_c() * p.group_layers(gi) * p.nch_rs * A_TILE));
             f.skip_b.push_back(take((size_t)p.mb_c() * GEMM_BM));
         }
+        f.in0f_w = take((size_t)2 * p.C * FOLD_ROWS * c.kernel_size);
+        f.in0f_A = take((size_t)p.mb_in * p.nch_in0f * A_TILE);
+        f.skend_W = take((size_t)c.n_layers * p.C * 2 * p.fd[k].n_half);
+        f.skend_b = take(2 * p.fd[k].n_half);
     }
     p.total = o;
     return CTTS_OK;
@@ -142,6 +151,8 @@ int make_geom(const Plan& p, int frames, Geom& g) {
 struct Workspace {
     float *audio, *spect, *spk, *h_tmp, *h_all, *x, *act, *out;
     float* act_all;     // deferred-skip form: the gated activations of every layer of a flow ([n_layers] x act)
+    float* a16;         // WN folds: layer 0's input [B][FOLD_ROWS][ld] = [audio_0; 1 on [0, L); 0]
+    float* skend;       // WN folds: the skip/end accumulator [B][2 n_half][ld] between the groups of a flow
     size_t total;  // floats
 };
 
@@ -159,6 +170,8 @@ void carve(const Plan& p, const Geom& g, int batch, float* base, Workspace& w) {
     w.out = take(B * p.C * g.ld);
     // gated activations of ONE skip group (its skip GEMM runs at the end of the group; the next group reuses the slots)
     w.act_all = take((size_t)std::min(p.c.n_layers, (int)Plan::F32_SKIP_GROUP) * B * p.C * g.ld);
+    w.a16 = take(B * FOLD_ROWS * g.ld);
+    w.skend = take(B * p.c.n_group * g.ld);
     w.total = o;
 }
 
@@ -251,25 +264,51 @@ int run_cond(const Plan& p, const Geom& g, const float* blob, const float* spect
     return launch_gemm_f32(GEMM_EPI_SPLIT, a, s);
 }
 
+// WN start / end folds of the fp32 infer path (the default; CTTS_F32_NO_WN_FOLD turns them off): layer 0 reads the FOLD_ROWS-row
+// [audio_0; 1; 0] instead of x, and the skip sum is never formed - a skip/end pass per group of kept activations accumulates its
+// 2 n_half-row image, and the last one of a flow is also the flow tail (coupling, inverse 1x1, un-squeeze into `wave`).
+struct WnFold { float* a16; float* skend; float* audio; float* wave; };
+
 int run_wn_stack(const Plan& p, const Geom& g, const float* blob, int k, const float* audio, const float* h_all,
-                 float* x, float* act, float* out, int batch, hipStream_t s, float* act_all = nullptr) {
+                 float* x, float* act, float* out, int batch, hipStream_t s, float* act_all = nullptr,
+                 const WnFold* fold = nullptr) {
     const auto& f = p.fl[k];
     const auto& d = p.fd[k];
     const long long cstride = (long long)p.C * g.ld;
     const long long hstride = (long long)p.c.n_flows * p.H * g.ld;
+    // x_0 is still formed: the res path x_1 = x_0 + W_res,0 act_0 needs it
     int rc = launch_wn_start(audio, blob + f.start_w, blob + f.start_b, x, batch, p.C, p.c.n_group, d.ch_off,
                              d.n_half, g.L, g.ld, g.pad, s);
     if (rc) return rc;
+    CTTS_CHECK_ARG(fold == nullptr || act_all != nullptr, "wn_stack: the folded form needs the kept activations");
+    if (fold && (rc = launch_wn_start_ones(audio, fold->a16, batch, p.c.n_group, d.ch_off, d.n_half, g.L, g.ld, g.pad, s)))
+        return rc;
     const int ncx = p.C / GEMM_KC;
     // Deferred-skip form (default since round 4; CTTS_F32_NO_DEFER_SKIP = the per-layer form; the fp32 analogue of the bf16 path's): every layer's gated activation is
     // kept, the per-layer launch computes the res rows only (x += W_res act), and the skip rows of up to four layers are
     // ONE contraction with K = 4 C at the end of the group.  Same products, different summation order of the skip sum.
-    const bool defer = act_all != nullptr && !tuning().f32_no_defer_skip;
+    const bool defer = act_all != nullptr && (fold != nullptr || !tuning().f32_no_defer_skip);
     const size_t act_stride = (size_t)batch * p.C * g.ld;
     for (int i = 0; i < p.c.n_layers; ++i) {
         const int dil = 1 << i;
         if (defer) act = act_all + (size_t)(i % Plan::F32_SKIP_GROUP) * act_stride;
-        {
+        if (fold && i == 0) {
+            // layer 0 on the folded start: K = 3 taps x FOLD_ROWS + cond, same GATE epilogue and bias
+            GemmArgs a = base_args(p, g, batch);
+            a.A = blob + f.in0f_A; a.bias = blob + f.in_b[0];
+            a.nseg = 4; a.interleave = 3; a.nch_total = p.nch_in0f; a.MB = p.mb_in;
+            const long long astride = (long long)FOLD_ROWS * g.ld;
+            a.seg[0] = {fold->a16, astride, 1, -dil, 0, 0};
+            a.seg[1] = {fold->a16, astride, 1, 0, 0, 0};
+            a.seg[2] = {fold->a16, astride, 1, dil, 0, 0};
+            a.seg[3] = {h_all + (size_t)k * p.H * g.ld, hstride, p.nch1h, 0, 0, 0};
+            a.dst0 = act; a.dst0_bstride = cstride;
+            a.M = 2 * p.C; a.pairC = p.C;
+            // slot 0 keeps bracketing EVERY in-layer launch (its contract: one entry per layer); slot 3 has this one alone
+            ProfScope ps(CTTS_PROF_WN_IN, s), ps0(CTTS_PROF_WN_IN0F, s);
+            rc = launch_gemm_f32(GEMM_EPI_GATE, a, s);
+            if (rc) return rc;
+        } else {
             GemmArgs a = base_args(p, g, batch);
             a.A = blob + f.in_A[i]; a.bias = blob + f.in_b[i];
             a.nseg = 4; a.interleave = 3; a.nch_total = p.nch_in; a.MB = p.mb_in;
@@ -293,12 +332,20 @@ int run_wn_stack(const Plan& p, const Geom& g, const float* blob, int k, const f
                 a.M = p.C; a.split = p.C;
                 a.dst0 = x; a.dst0_bstride = cstride; a.acc0 = 1;
                 a.dst1 = out; a.dst1_bstride = cstride; a.acc1 = 0;
-                ProfScope ps(CTTS_PROF_WN_RS, s);
+                ProfScope ps(fold ? CTTS_PROF_WN_RES_F : CTTS_PROF_WN_RS, s);
                 rc = launch_gemm_f32(GEMM_EPI_SPLIT, a, s);
                 if (rc) return rc;
             }
             const int gi = i / Plan::F32_SKIP_GROUP;
-            if (last || (i + 1) % Plan::F32_SKIP_GROUP == 0) {
+            if (fold && (last || (i + 1) % Plan::F32_SKIP_GROUP == 0)) {
+                const int E = 2 * d.n_half;
+                ProfScope ps(CTTS_PROF_WN_SKEND, s);
+                rc = launch_skip_end(act_all, (long long)act_stride, p.group_layers(gi),
+                                     blob + f.skend_W + (size_t)gi * Plan::F32_SKIP_GROUP * p.C * E, fold->skend, gi == 0, last,
+                                     blob + f.skend_b, blob + f.winv, fold->audio, fold->wave, batch, p.C, p.c.n_group, d.ch_off,
+                                     d.n_half, g.L, g.ld, g.pad, s);
+                if (rc) return rc;
+            } else if (last || (i + 1) % Plan::F32_SKIP_GROUP == 0) {
                 const int nl = p.group_layers(gi);
                 GemmArgs a = base_args(p, g, batch);
                 a.A = blob + f.skip_A[gi]; a.bias = blob + f.skip_b[gi];
@@ -774,7 +821,15 @@ int ctts_waveglow_pack_flow(const ctts_waveglow_config* cfg, int32_t k, const ct
                            w->rs_b[i] + (last ? 0 : C), C, p.mb_c() * GEMM_BM, gj == 0 ? 1 : 0);
         CTTS_CHECK_LAUNCH("skip_bias_f32");
     }
-    return CTTS_OK;
+    // WN start / end folds: layer 0 on [audio_0; 1] (K = [tap0, tap1, tap2] of one FOLD_ROWS chunk each, then the cond slice of
+    // layer 0; bias in_b[0] as packed above) and the skip rows seen through `end`
+    if ((rc = launch_fold_in0(w->in_w[0], w->start_w, w->start_b, blob + f.in0f_w, C, d.n_half, ks, s))) return rc;
+    for (int t = 0; t < ks; ++t)
+        if ((rc = launch_pack_a(blob + f.in0f_A, blob + f.in0f_w + t, GEMM_BM, p.mb_in, p.nch_in0f, 0, FOLD_ROWS, GEMM_EPI_GATE, C,
+                                2 * C, 0, (long long)FOLD_ROWS * ks, ks, s, ks, t))) return rc;
+    if ((rc = launch_pack_a(blob + f.in0f_A, w->cond_w[2], GEMM_BM, p.mb_in, p.nch_in0f, ks * FOLD_ROWS, H, GEMM_EPI_GATE, C,
+                            2 * C, 0, H, 1, s))) return rc;
+    return launch_fold_skend(w->rs_w, w->rs_b, w->end_w, w->end_b, blob + f.skend_W, blob + f.skend_b, C, p.c.n_layers, d.n_half, s);
 }
 
 size_t ctts_waveglow_workspace_bytes(const ctts_waveglow_config* cfg, int32_t batch, int32_t frames) {
@@ -856,9 +911,13 @@ int ctts_waveglow_infer_spk_f32(const ctts_waveglow_config* cfg, const void* pac
     if (rc) return rc;
     rc = run_cond(p, g, blob, w.spect, w.spk, w.h_tmp, w.h_all, batch, s);
     if (rc) return rc;
+    const Tuning t = tuning();
+    const bool folded = !t.f32_no_wn_fold && !t.f32_no_defer_skip;
     for (int k = p.c.n_flows - 1; k >= 0; --k) {
-        rc = run_wn_stack(p, g, blob, k, w.audio, w.h_all, w.x, w.act, w.out, batch, s, w.act_all);
+        const WnFold fw{w.a16, w.skend, w.audio, k == 0 ? wave : nullptr};
+        rc = run_wn_stack(p, g, blob, k, w.audio, w.h_all, w.x, w.act, w.out, batch, s, w.act_all, folded ? &fw : nullptr);
         if (rc) return rc;
+        if (folded) continue;        // the last skip/end pass of the flow was its tail
         rc = run_flow_tail(p, g, blob, k, w.out, w.audio, k == 0 ? wave : nullptr, batch, s);
         if (rc) return rc;
     }
@@ -876,7 +935,7 @@ int ctts_tuning_flags(void) {
            (t.wf_no_row_queue ? 32768 : 0) | (t.wf_row_queue_min >= 0 ? 65536 : 0) | (t.wf_inject_abort ? 131072 : 0) |
            (t.wf_queue_debug ? 262144 : 0) | (t.f32_no_round_split ? 524288 : 0) | (t.bf16_ps ? (1 << 20) : 0) |
            (t.bf16_no_ps ? (1 << 21) : 0) | (t.f32_splitk_w4 ? (1 << 22) : 0) | (t.taco_poll_delay_set ? (1 << 23) : 0) |
-           (t.taco_valu ? (1 << 24) : 0) | (t.up_no_mfma ? (1 << 25) : 0);
+           (t.taco_valu ? (1 << 24) : 0) | (t.up_no_mfma ? (1 << 25) : 0) | (t.f32_no_wn_fold ? (1 << 26) : 0);
 }
 
 int ctts_profile_create(void** handle) {

@@ -23,4 +23,16 @@ int launch_flow_tail(const float* out, float* audio, float* wave, const float* W
                      const float* Winv, int batch, int C, int G, int ch_off, int n_half, int L, int ld, int pad,
                      hipStream_t s);
 
+// WN start / end folds (fp32 WaveGlow): layer 0's in-layer weights on the FOLD_ROWS-row input [audio_0; 1; 0 ...] and the skip rows
+// seen through `end` (waveglow_kernels.hip).  Pack time: fp64 products rounded once to fp32.
+constexpr int FOLD_ROWS = 16;    // rows of the folded layer-0 input = one K chunk per tap (n_half <= 8 audio rows + the ones row)
+int launch_fold_in0(const float* in_w, const float* Ws, const float* bs, float* dst, int C, int n_half, int ks, hipStream_t s);
+int launch_fold_skend(const float* const* rs_w, const float* const* rs_b, const float* Wend, const float* bend, float* Wf,
+                      float* bf, int C, int n_layers, int n_half, hipStream_t s);
+int launch_wn_start_ones(const float* audio, float* a16, int batch, int G, int ch_off, int n_half, int L, int ld, int pad,
+                         hipStream_t s);
+int launch_skip_end(const float* act, long long act_stride, int nl, const float* Wf, float* acc, bool first, bool tail,
+                    const float* bf, const float* Winv, float* audio, float* wave, int batch, int C, int G, int ch_off,
+                    int n_half, int L, int ld, int pad, hipStream_t s);
+
 }  // namespace ctts

@@ -282,6 +282,52 @@ __global__ __launch_bounds__(256) void wn_start_kernel(const float* __restrict__
 }
 
 // -------------------------------------------------------------------- flow tail ----
+// (b, log_s) = (e[:h], e[h:]) of one thread's 4 time steps n..n+3; a1 = (a1 - b) / exp(log_s);
+// audio[ch_off : ch_off+2h] = Winv * [a0; a1]; optional un-squeeze to wave.   (glow.py:337-340, 349)
+template <int H>
+__device__ __forceinline__ void coupling_tail(float4 (&e)[2 * H], const float* sWinv, float* __restrict__ audio,
+                                              float* __restrict__ wave, int b, int G, int ch_off, int L, int n) {
+    constexpr int E = 2 * H;
+    float* ab = audio + ((size_t)b * G + ch_off) * L + n;
+    float4 a[E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) a[j] = *reinterpret_cast<const float4*>(ab + (size_t)j * L);
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+        a[H + j].x = (a[H + j].x - e[j].x) / expf(e[H + j].x);
+        a[H + j].y = (a[H + j].y - e[j].y) / expf(e[H + j].y);
+        a[H + j].z = (a[H + j].z - e[j].z) / expf(e[H + j].z);
+        a[H + j].w = (a[H + j].w - e[j].w) / expf(e[H + j].w);
+    }
+    float4 m[E];
+#pragma unroll
+    for (int i = 0; i < E; ++i) {
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            const float w = sWinv[i * E + j];
+            s.x = fmaf(w, a[j].x, s.x); s.y = fmaf(w, a[j].y, s.y);
+            s.z = fmaf(w, a[j].z, s.z); s.w = fmaf(w, a[j].w, s.w);
+        }
+        m[i] = s;
+    }
+    if (wave == nullptr) {
+#pragma unroll
+        for (int i = 0; i < E; ++i) *reinterpret_cast<float4*>(ab + (size_t)i * L) = m[i];
+    } else if constexpr (E % 4 == 0) {
+        // un-squeeze: wave[b][G*l + g] = audio[b][g][l]; on the last flow ch_off == 0 and E == G
+        float* wb = wave + (size_t)b * G * L + (size_t)n * G;
+        const float* mf = reinterpret_cast<const float*>(m);   // m[i].{x,y,z,w} = channel i, step n+{0..3}
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int i = 0; i < E; i += 4) {
+                float4 v = make_float4(mf[(i + 0) * 4 + s], mf[(i + 1) * 4 + s], mf[(i + 2) * 4 + s], mf[(i + 3) * 4 + s]);
+                *reinterpret_cast<float4*>(wb + s * G + i) = v;
+            }
+    }
+}
+
 // e = Wend * out + bend; (b, log_s) = (e[:h], e[h:]); a1 = (a1 - b) / exp(log_s);
 // audio[ch_off : ch_off+2h] = Winv * [a0; a1]; optional un-squeeze to wave.
 // (glow.py:222, 337-340, 349).  Workgroup = 4 waves x 256 time steps; each wave reduces a
@@ -331,43 +377,149 @@ __global__ __launch_bounds__(256) void flow_tail_kernel(const float* __restrict_
         }
         e[j].x += bj; e[j].y += bj; e[j].z += bj; e[j].w += bj;
     }
-    float* ab = audio + ((size_t)b * G + ch_off) * L + n;
-    float4 a[E];
-#pragma unroll
-    for (int j = 0; j < E; ++j) a[j] = *reinterpret_cast<const float4*>(ab + (size_t)j * L);
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        a[H + j].x = (a[H + j].x - e[j].x) / expf(e[H + j].x);
-        a[H + j].y = (a[H + j].y - e[j].y) / expf(e[H + j].y);
-        a[H + j].z = (a[H + j].z - e[j].z) / expf(e[H + j].z);
-        a[H + j].w = (a[H + j].w - e[j].w) / expf(e[H + j].w);
+    coupling_tail<H>(e, sWinv, audio, wave, b, G, ch_off, L, n);
+}
+
+
+// ------------------------------------------------------------- WN start / end folds ----
+// Both 1x1 convolutions at the ends of the WN stack are linear maps beside GEMMs whose outputs are used only through
+// them (glow.py:188-222), so they are folded into those GEMMs' weights once per pack, in fp64, rounded to fp32 once:
+//   layer 0:  W_in,0[tap] . x_0 = (W_in,0[tap] . [W_start | b_start]) . [a; 1]    (the 1 row is 0 where the conv zero-pads)
+//   end:      W_end . sum_i (W_skip,i act_i + b_skip,i) + b_end = sum_i (W_end . W_skip,i) act_i + b'
+
+// dst[o][r][t] (an in_w of FOLD_ROWS input channels): r < H: sum_c W_in[o][c][t] Ws[c][r]; r == H: sum_c W_in[o][c][t] bs[c]; else 0
+__global__ __launch_bounds__(256) void fold_in0_kernel(const float* __restrict__ in_w, const float* __restrict__ Ws,
+                                                       const float* __restrict__ bs, float* __restrict__ dst, int C, int H,
+                                                       int ks, int rows) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * FOLD_ROWS * ks) return;
+    const int t = idx % ks, r = (idx / ks) % FOLD_ROWS, o = idx / (ks * FOLD_ROWS);
+    double acc = 0.0;
+    if (r <= H) {
+        const float* wr = in_w + (size_t)o * C * ks + t;
+        for (int c = 0; c < C; ++c) acc += (double)wr[(size_t)c * ks] * (double)(r < H ? Ws[c * H + r] : bs[c]);
     }
-    float4 m[E];
+    dst[idx] = (float)acc;
+}
+
+// Wf[c][e] = sum_m W_end[e][m] W_skip[m][c]   (W_skip = rows [row_off, row_off + C) of res_skip_layers.i, [rows][C])
+__global__ __launch_bounds__(256) void fold_skend_w_kernel(const float* __restrict__ Wend, const float* __restrict__ rs_w,
+                                                           float* __restrict__ Wf, int C, int E, int row_off) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= C * E) return;
+    const int e = idx % E, c = idx / E;
+    double acc = 0.0;
+    for (int m = 0; m < C; ++m) acc += (double)Wend[(size_t)e * C + m] * (double)rs_w[(size_t)(row_off + m) * C + c];
+    Wf[idx] = (float)acc;
+}
+
+struct SkipBiasPtrs { const float* p[12]; int row_off[12]; };
+
+// bf[e] = b_end[e] + sum_m W_end[e][m] sum_i b_skip,i[m]
+__global__ __launch_bounds__(64) void fold_skend_b_kernel(const float* __restrict__ Wend, const float* __restrict__ bend,
+                                                          SkipBiasPtrs sb, int n_layers, float* __restrict__ bf, int C, int E) {
+    const int e = threadIdx.x;
+    if (e >= E) return;
+    double acc = 0.0;
+    for (int m = 0; m < C; ++m) {
+        double bm = 0.0;
+        for (int i = 0; i < n_layers; ++i) bm += (double)sb.p[i][sb.row_off[i] + m];
+        acc += (double)Wend[(size_t)e * C + m] * bm;
+    }
+    bf[e] = (float)(acc + (double)bend[e]);
+}
+
+// a16[b][r][:] over the whole padded row: r < H: audio[b][ch_off + r][n], r == H: 1, other rows 0; 0 outside [pad, pad + L)
+template <int H>
+__global__ __launch_bounds__(256) void wn_start_ones_kernel(const float* __restrict__ audio, float* __restrict__ a16, int G,
+                                                            int ch_off, int L, int ld, int pad) {
+    const int col = (blockIdx.x * 256 + threadIdx.x) * 4;
+    const int b = blockIdx.z;
+    if (col >= ld) return;
+    const int n = col - pad;
+    const bool in = n >= 0 && n < L;                           // pad, L multiples of 4: a float4 is all in or all out
+    float* dst = a16 + (size_t)b * FOLD_ROWS * ld + col;
 #pragma unroll
-    for (int i = 0; i < E; ++i) {
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int r = 0; r < FOLD_ROWS; ++r) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (in && r < H) v = *reinterpret_cast<const float4*>(audio + ((size_t)b * G + ch_off + r) * L + n);
+        else if (in && r == H) v = make_float4(1.f, 1.f, 1.f, 1.f);
+        *reinterpret_cast<float4*>(dst + (size_t)r * ld) = v;
+    }
+}
+
+// Skip/end pass of one skip group: e = sum_{j < nl} Wf_j . act_j over the group's kept gated activations (Wf_j = W_end . W_skip
+// of layer j, [C][E]), first group: acc = e; later groups: e += acc, and then either acc = e, or (TAIL, the last group) e += b'
+// and the flow tail of flow_tail_kernel.  Same reduction shape as flow_tail_kernel: 4 waves x 256 time steps, each wave a
+// quarter of the channels of every layer, NG 16-byte loads in flight per lane, partial sums meet in LDS.  Every workgroup
+// owns its columns: deterministic.
+template <int H, bool TAIL>
+__global__ __launch_bounds__(256) void skip_end_kernel(const float* __restrict__ act, long long act_stride, int nl,
+                                                       const float* __restrict__ Wf, float* __restrict__ acc, int first,
+                                                       const float* __restrict__ bf, const float* __restrict__ Winv,
+                                                       float* __restrict__ audio, float* __restrict__ wave,
+                                                       int C, int G, int ch_off, int L, int ld, int pad) {
+    constexpr int E = 2 * H;
+    constexpr int NG = E <= 4 ? 8 : E <= 8 ? 4 : 2;            // 16-byte loads per lane in flight (E x NG weights in SGPRs)
+    __shared__ __attribute__((aligned(16))) float part[3][E][256];
+    __shared__ float sWinv[E * E];
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int n = blockIdx.x * 256 + lane * 4;
+    if (TAIL && threadIdx.x < E * E) sWinv[threadIdx.x] = Winv[threadIdx.x];
+    float4 e[E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) e[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int cq = C / 4;                                       // a multiple of NG (C % 32 == 0)
+    const int cbeg = __builtin_amdgcn_readfirstlane(wv * cq);
+    for (int l = 0; l < nl; ++l) {
+        // columns beyond L inside the padded row are readable (never used)
+        const float* ob = act + (size_t)l * act_stride + (size_t)b * C * ld + pad + n;
+        const float* wl = Wf + (size_t)l * C * E;
+        for (int c = cbeg; c < cbeg + cq; c += NG) {
+            float4 v[NG];
+#pragma unroll
+            for (int k = 0; k < NG; ++k) v[k] = *reinterpret_cast<const float4*>(ob + (size_t)(c + k) * ld);
+#pragma unroll
+            for (int k = 0; k < NG; ++k)
+#pragma unroll
+                for (int j = 0; j < E; ++j) {
+                    const float w = wl[(c + k) * E + j];
+                    e[j].x = fmaf(w, v[k].x, e[j].x); e[j].y = fmaf(w, v[k].y, e[j].y);
+                    e[j].z = fmaf(w, v[k].z, e[j].z); e[j].w = fmaf(w, v[k].w, e[j].w);
+                }
+        }
+    }
+    if (wv > 0) {
+#pragma unroll
+        for (int j = 0; j < E; ++j) *reinterpret_cast<float4*>(&part[wv - 1][j][lane * 4]) = e[j];
+    }
+    __syncthreads();
+    if (wv != 0 || n >= L) return;
+    float* ab = acc + (size_t)b * E * ld + pad + n;
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const float4 pv = *reinterpret_cast<const float4*>(&part[q][j][lane * 4]);
+            e[j].x += pv.x; e[j].y += pv.y; e[j].z += pv.z; e[j].w += pv.w;
+        }
+        if (!first) {
+            const float4 pv = *reinterpret_cast<const float4*>(ab + (size_t)j * ld);
+            e[j].x += pv.x; e[j].y += pv.y; e[j].z += pv.z; e[j].w += pv.w;
+        }
+    }
+    if constexpr (!TAIL) {
+#pragma unroll
+        for (int j = 0; j < E; ++j) *reinterpret_cast<float4*>(ab + (size_t)j * ld) = e[j];
+    } else {
 #pragma unroll
         for (int j = 0; j < E; ++j) {
-            const float w = sWinv[i * E + j];
-            s.x = fmaf(w, a[j].x, s.x); s.y = fmaf(w, a[j].y, s.y);
-            s.z = fmaf(w, a[j].z, s.z); s.w = fmaf(w, a[j].w, s.w);
+            const float bj = bf[j];
+            e[j].x += bj; e[j].y += bj; e[j].z += bj; e[j].w += bj;
         }
-        m[i] = s;
-    }
-    if (wave == nullptr) {
-#pragma unroll
-        for (int i = 0; i < E; ++i) *reinterpret_cast<float4*>(ab + (size_t)i * L) = m[i];
-    } else if constexpr (E % 4 == 0) {
-        // un-squeeze: wave[b][G*l + g] = audio[b][g][l]; on the last flow ch_off == 0 and E == G
-        float* wb = wave + (size_t)b * G * L + (size_t)n * G;
-        const float* mf = reinterpret_cast<const float*>(m);   // m[i].{x,y,z,w} = channel i, step n+{0..3}
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int i = 0; i < E; i += 4) {
-                float4 v = make_float4(mf[(i + 0) * 4 + s], mf[(i + 1) * 4 + s], mf[(i + 2) * 4 + s], mf[(i + 3) * 4 + s]);
-                *reinterpret_cast<float4*>(wb + s * G + i) = v;
-            }
+        coupling_tail<H>(e, sWinv, audio, wave, b, G, ch_off, L, n);
     }
 }
 
@@ -489,6 +641,82 @@ int launch_flow_tail(const float* out, float* audio, float* wave, const float* W
     }
 #undef CTTS_TAIL_CASE
     CTTS_CHECK_LAUNCH("flow_tail");
+    return CTTS_OK;
+}
+
+int launch_fold_in0(const float* in_w, const float* Ws, const float* bs, float* dst, int C, int n_half, int ks, hipStream_t s) {
+    CTTS_CHECK_ARG(n_half >= 1 && n_half < FOLD_ROWS, "fold_in0: n_half=%d", n_half);
+    const int n = 2 * C * FOLD_ROWS * ks;
+    hipLaunchKernelGGL(fold_in0_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in_w, Ws, bs, dst, C, n_half, ks, 2 * C);
+    CTTS_CHECK_LAUNCH("fold_in0");
+    return CTTS_OK;
+}
+
+int launch_fold_skend(const float* const* rs_w, const float* const* rs_b, const float* Wend, const float* bend, float* Wf,
+                      float* bf, int C, int n_layers, int n_half, hipStream_t s) {
+    const int E = 2 * n_half;
+    CTTS_CHECK_ARG(n_layers >= 1 && n_layers <= 12 && E <= 64, "fold_skend: n_layers=%d n_half=%d", n_layers, n_half);
+    SkipBiasPtrs sb{};
+    for (int i = 0; i < n_layers; ++i) {
+        CTTS_CHECK_ARG(rs_w[i] && rs_b[i], "fold_skend: NULL layer %d weights", i);
+        const int row_off = i < n_layers - 1 ? C : 0;          // skip rows: [C, 2C), or all C rows of the last layer
+        sb.p[i] = rs_b[i];
+        sb.row_off[i] = row_off;
+        hipLaunchKernelGGL(fold_skend_w_kernel, dim3((C * E + 255) / 256), dim3(256), 0, s, Wend, rs_w[i], Wf + (size_t)i * C * E,
+                           C, E, row_off);
+    }
+    hipLaunchKernelGGL(fold_skend_b_kernel, dim3(1), dim3(64), 0, s, Wend, bend, sb, n_layers, bf, C, E);
+    CTTS_CHECK_LAUNCH("fold_skend");
+    return CTTS_OK;
+}
+
+int launch_wn_start_ones(const float* audio, float* a16, int batch, int G, int ch_off, int n_half, int L, int ld, int pad,
+                         hipStream_t s) {
+    CTTS_CHECK_ARG(L % 4 == 0 && ld % 4 == 0 && pad % 4 == 0, "wn_start_ones: L=%d ld=%d pad=%d", L, ld, pad);
+    dim3 grid((ld / 4 + 255) / 256, 1, batch);
+#define CTTS_ONES_CASE(H)                                                                                     \
+    case H:                                                                                                   \
+        hipLaunchKernelGGL(wn_start_ones_kernel<H>, grid, dim3(256), 0, s, audio, a16, G, ch_off, L, ld, pad); \
+        break;
+    switch (n_half) {
+        CTTS_ONES_CASE(1) CTTS_ONES_CASE(2) CTTS_ONES_CASE(3) CTTS_ONES_CASE(4)
+        CTTS_ONES_CASE(5) CTTS_ONES_CASE(6) CTTS_ONES_CASE(7) CTTS_ONES_CASE(8)
+        default:
+            set_error("wn_start_ones: n_half=%d unsupported (1..8)", n_half);
+            return CTTS_E_ARG;
+    }
+#undef CTTS_ONES_CASE
+    CTTS_CHECK_LAUNCH("wn_start_ones");
+    return CTTS_OK;
+}
+
+int launch_skip_end(const float* act, long long act_stride, int nl, const float* Wf, float* acc, bool first, bool tail,
+                    const float* bf, const float* Winv, float* audio, float* wave, int batch, int C, int G, int ch_off,
+                    int n_half, int L, int ld, int pad, hipStream_t s) {
+    CTTS_CHECK_ARG(L % 4 == 0 && C % 32 == 0 && ld % 4 == 0 && pad % 4 == 0 && nl >= 1, "skip_end: L=%d C=%d nl=%d", L, C, nl);
+    CTTS_CHECK_ARG(acc != nullptr || (first && tail), "skip_end: a group after the first needs the accumulator");
+    CTTS_CHECK_ARG(!tail || wave == nullptr || (ch_off == 0 && 2 * n_half == G && G % 4 == 0),
+                   "skip_end: un-squeeze needs the full group (ch_off=%d n_half=%d G=%d)", ch_off, n_half, G);
+    dim3 grid((L + 255) / 256, batch);
+    const int fi = first ? 1 : 0;
+#define CTTS_SKEND_CASE(H)                                                                                                \
+    case H:                                                                                                               \
+        if (tail)                                                                                                         \
+            hipLaunchKernelGGL((skip_end_kernel<H, true>), grid, dim3(256), 0, s, act, act_stride, nl, Wf, acc, fi, bf, Winv, \
+                               audio, wave, C, G, ch_off, L, ld, pad);                                                    \
+        else                                                                                                              \
+            hipLaunchKernelGGL((skip_end_kernel<H, false>), grid, dim3(256), 0, s, act, act_stride, nl, Wf, acc, fi, bf, Winv, \
+                               audio, wave, C, G, ch_off, L, ld, pad);                                                    \
+        break;
+    switch (n_half) {
+        CTTS_SKEND_CASE(1) CTTS_SKEND_CASE(2) CTTS_SKEND_CASE(3) CTTS_SKEND_CASE(4)
+        CTTS_SKEND_CASE(5) CTTS_SKEND_CASE(6) CTTS_SKEND_CASE(7) CTTS_SKEND_CASE(8)
+        default:
+            set_error("skip_end: n_half=%d unsupported (1..8)", n_half);
+            return CTTS_E_ARG;
+    }
+#undef CTTS_SKEND_CASE
+    CTTS_CHECK_LAUNCH("skip_end");
     return CTTS_OK;
 }
 
