@@ -112,7 +112,6 @@ __device__ __forceinline__ void build_chunk_table(const BGemmArgs& a, unsigned l
 //   map_mode 2 (MB == 2): XCD x owns BOTH m-blocks of the column tiles 8q + x, on ids 8 apart: the B tile of the
 //     memory-bound res / skip GEMMs is fetched from HBM once instead of twice (round 5: FETCH_SIZE of these launches was
 //     the B bytes twice plus the read-modify-write destination, profiles/r3_01_pmc_config3_bf16_b32.json);
-//   map_mode 3 (MB == 4, experiment CTTS_BF16_MAP=2): all four m-blocks of a tile on one XCD.
 // Returns false for the ids beyond the last tile (the grid is rounded up to whole groups).
 __device__ __forceinline__ bool block_map(const BGemmArgs& a, int id, int& mb, int& tile, int& b) {
     int gt;
@@ -124,10 +123,6 @@ __device__ __forceinline__ bool block_map(const BGemmArgs& a, int id, int& mb, i
         const int x = id & 7, j = id >> 3;
         mb = j & 1;
         gt = (j >> 1) * 8 + x;
-    } else if (a.map_mode == 3) {
-        const int x = id & 7, j = id >> 3;
-        mb = j & 3;
-        gt = (j >> 2) * 8 + x;
     } else {
         mb = id % a.MB;
         gt = id / a.MB;
@@ -259,7 +254,7 @@ __device__ __forceinline__ void bf16_epilogue(const BGemmArgs& a, f32x16 (&acc)[
 // NW = waves along N: 2 -> 256 threads, block tile 256 x 128; 4 -> 512 threads, block tile 256 x 256 (one
 // workgroup per CU).  The wide tile stages 1/3 fewer bytes per FLOP: at bf16 MFMA rates the CU's vector-memory
 // path (64 B/clk) is the co-bottleneck of the narrow tile (PMC: MFMA busy 44 %, issue-stalled 48 %).
-template <int EPI, bool GLDS, int NW, bool F16 = false>
+template <int EPI, int NW, bool F16 = false>
 __global__ __launch_bounds__(128 * NW, 2) void conv_gemm_bf16_kernel(const BGemmArgs a) {
     constexpr int NT = 128 * NW;                            // threads
     constexpr int BN = 64 * NW;
@@ -268,7 +263,7 @@ __global__ __launch_bounds__(128 * NW, 2) void conv_gemm_bf16_kernel(const BGemm
     constexpr int NA = A_UNITS / NT;                        // 16-byte units per thread per stage (A)
     constexpr int NB_ = B_UNITS / NT;                       // (B) == 2 for both shapes
     static_assert(NB_ == 2, "B staging assumes 2 units per thread");
-    constexpr int NSTAGE = GLDS ? 3 : 2;
+    constexpr int NSTAGE = 3;
     __shared__ __attribute__((aligned(16))) u32x4 lds[NSTAGE * STAGE_UNITS + BGEMM_PP_MAX_CHUNKS / 2];
     unsigned long long* tab = reinterpret_cast<unsigned long long*>(lds + NSTAGE * STAGE_UNITS);
 
@@ -299,27 +294,6 @@ __global__ __launch_bounds__(128 * NW, 2) void conv_gemm_bf16_kernel(const BGemm
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    u32x4 ra0, ra1, ra2, ra3, rb0, rb1;
-
-#define CTTS_ISSUE_LOADS()                                                                      \
-    do {                                                                                        \
-        ra0 = ap[0]; ra1 = ap[NT];                                                              \
-        if constexpr (NA > 2) { ra2 = ap[2 * NT]; ra3 = ap[3 * NT]; }                           \
-        ap += A_UNITS;                                                                          \
-        gunit_ptr bp = (gunit_ptr)tab[ich++] + boff_units;                                      \
-        rb0 = bp[0];                                                                            \
-        rb1 = bp[g2_units];                                                                     \
-    } while (0)
-
-#define CTTS_STORE_LDS(buf)                                                                     \
-    do {                                                                                        \
-        u32x4* As_ = lds + (buf) * STAGE_UNITS + t;                                             \
-        u32x4* Bs_ = lds + (buf) * STAGE_UNITS + A_UNITS + t;                                   \
-        As_[0] = ra0; As_[NT] = ra1;                                                            \
-        if constexpr (NA > 2) { As_[2 * NT] = ra2; As_[3 * NT] = ra3; }                         \
-        Bs_[0] = rb0; Bs_[NT] = rb1;                                                            \
-    } while (0)
-
     // Direct global->LDS staging (global_load_lds_dwordx4): no VGPR round trip, no ds_write pass.  The LDS image
     // is lane-linear by construction (unit index == thread index + 256 j), which is what the DMA needs: the
     // destination is a wave-uniform base + lane * 16 B.
@@ -340,30 +314,20 @@ __global__ __launch_bounds__(128 * NW, 2) void conv_gemm_bf16_kernel(const BGemm
     } while (0)
 
     const int nch = a.nch_total;
-    if constexpr (GLDS) {
-        // 3 LDS stages, DMA issued TWO chunks ahead: a bf16 chunk is only ~0.5k MFMA cycles per wave, far less than
-        // the loaded-memory latency, so a one-chunk prefetch leaves the matrix pipe waiting on vmcnt.  Six DMAs per
-        // thread per chunk -> `vmcnt(6)` = "everything but the newest chunk has landed".  Raw s_barrier: a
-        // __syncthreads() would add vmcnt(0) and drain the DMA queue.
-        CTTS_ISSUE_GLDS(0);
-        if (nch > 1) CTTS_ISSUE_GLDS(1);
-        if (nch > 1) { if constexpr (NA > 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    } else {
-        CTTS_ISSUE_LOADS();
-        CTTS_STORE_LDS(0);
-        __syncthreads();
-    }
+    // 3 LDS stages, DMA issued TWO chunks ahead: a bf16 chunk is only ~0.5k MFMA cycles per wave, far less than the loaded-memory
+    // latency, so a one-chunk prefetch leaves the matrix pipe waiting on vmcnt.  Six DMAs per thread per chunk -> `vmcnt(6)` =
+    // "everything but the newest chunk has landed".  Raw s_barrier: a __syncthreads() would add vmcnt(0) and drain the DMA queue.
+    CTTS_ISSUE_GLDS(0);
+    if (nch > 1) CTTS_ISSUE_GLDS(1);
+    if (nch > 1) { if constexpr (NA > 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
 
     int cur = 0;
     for (int ch = 0; ch < nch; ++ch) {
-        const bool more = GLDS ? ch + 2 < nch : ch + 1 < nch;
-        if (more) {
-            if constexpr (GLDS) { const int nb = cur >= 1 ? cur - 1 : 2; CTTS_ISSUE_GLDS(nb); }   // (cur + 2) % 3
-            else CTTS_ISSUE_LOADS();
-        }
+        const bool more = ch + 2 < nch;
+        if (more) { const int nb = cur >= 1 ? cur - 1 : 2; CTTS_ISSUE_GLDS(nb); }   // (cur + 2) % 3
         const u32x4* As = lds + cur * STAGE_UNITS + wm * 128 + l31;
         const u32x4* Bs = lds + cur * STAGE_UNITS + A_UNITS + wn * 64 + l31;
         u32x4 av[2][4], bv[2][2];
@@ -387,20 +351,12 @@ __global__ __launch_bounds__(128 * NW, 2) void conv_gemm_bf16_kernel(const BGemm
         __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-        if constexpr (GLDS) {
-            if (more) { if constexpr (NA > 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }   // chunk ch+1 landed, ch+2 in flight
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            cur = cur == 2 ? 0 : cur + 1;
-        } else {
-            if (more) CTTS_STORE_LDS(cur ^ 1);
-            __syncthreads();
-            cur ^= 1;
-        }
+        if (more) { if constexpr (NA > 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }   // chunk ch+1 landed, ch+2 in flight
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        cur = cur == 2 ? 0 : cur + 1;
     }
-#undef CTTS_ISSUE_LOADS
-#undef CTTS_STORE_LDS
 #undef CTTS_ISSUE_GLDS
 
     bf16_epilogue<EPI, false, F16>(a, acc, lds, t, mb, wm, wn, b, n0, l31, lhi);
@@ -829,183 +785,6 @@ __global__ __launch_bounds__(512) void conv_gemm_bf16_ps_kernel(const BGemmArgs 
 #undef CTTS_PS_ZERO
 #undef CTTS_UNIFORM64
 #undef CTTS_WAIT_VM
-}
-
-// Four-wave form of the 256 x 256 block: 256 threads = 2(M) x 2(N) waves, ONE wave per SIMD, wave tile 128 x 128 =
-// 4 x 4 tiles of v_mfma_f32_32x32x16_bf16 (256 accumulator registers, the whole AGPR half of the 512-register file).
-// Why: a fragment is one ds_read_b128 per lane = 1 KiB per wave, and the CU's LDS moves 128 B/clk.  The 128 x 64 wave
-// tile of the kernels above reads 12 fragments per 16 MFMAs: 8 waves x 12 KiB = 96 KiB of LDS reads plus 32 KiB of
-// DMA writes per K chunk = 1024 LDS cycles, exactly the 1024 matrix-pipe cycles of the chunk - both pipes would have
-// to run at 100 % at once, and the measured interval is ~1950 cycles.  The 128 x 128 wave tile reads 16 fragments per
-// 32 MFMAs: 64 + 32 KiB = 768 LDS cycles against the same 1024 MFMA cycles.
-// Pipeline: NS = 4 stages of 32 KiB filled by global_load_lds DMA three chunks ahead; per chunk ONE barrier, placed
-// between the two k-steps: [ds_read k-step 1 | 16 MFMAs of k-step 0] barrier [DMA chunk+4, ds_read k-step 0 of the
-// next chunk | 16 MFMAs of k-step 1], so every fragment read has 512 matrix-pipe cycles to land and the stage of
-// chunk c is free for DMA as soon as the barrier inside chunk c has passed (its k-step-1 fragments are in registers).
-__device__ unsigned long long g_w4_stamps[8];   // DBG == 3: {loop cycles, loop 100 MHz ticks, epilogue cycles, prologue cycles}
-
-template <int EPI, int DBG = 0>   // DBG bits (timing experiments only): 1 = no DMA after the prologue, 2 = no MFMA (both: wrong results), 4 = stamps
-__global__ __launch_bounds__(256) void conv_gemm_bf16_w4_kernel(const BGemmArgs a) {
-    constexpr int NT = 256, BN = 256, NS = 4;
-    constexpr int B_UNITS = 4 * BN;
-    constexpr int STAGE_UNITS = A_UNITS + B_UNITS;
-    __shared__ __attribute__((aligned(16))) u32x4 lds[NS * STAGE_UNITS + BGEMM_PP_MAX_CHUNKS / 2];
-    typedef unsigned long long u64;
-    u64* tab = reinterpret_cast<u64*>(lds + NS * STAGE_UNITS);
-
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, lhi = lane >> 5;
-
-    int mb, tile, b;
-    if (!block_map(a, blockIdx.x, mb, tile, b)) return;
-    const int n0 = tile * BN;
-    const int nch = a.nch_total;
-
-    build_chunk_table(a, tab, t, mb, b, n0);
-    // per-thread byte offsets inside a chunk: B unit (g, n) = (j, t), A unit t + 256 j, j = 0..3
-    const unsigned boff = (unsigned)(t * 16), bstep = (unsigned)(a.ld * 16);
-    const unsigned aoff = (unsigned)(t * 16);
-    typedef const __attribute__((address_space(1))) char* gbyte_ptr;
-    const gbyte_ptr abase = (gbyte_ptr)a.A + (size_t)mb * nch * (A_UNITS * 16);
-
-    f32x16 acc[2][4][2];                                    // [64-column half][mt][nt]
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[h][i][j][r] = 0.0f;
-
-    typedef __attribute__((address_space(3))) u32x4* lds_ptr;
-#define CTTS_W4_DMA(buf, c, ub)                                                                     \
-    do {                                                                                            \
-        lds_ptr la_ = (lds_ptr)(lds + (buf) * STAGE_UNITS + wave * 64);                             \
-        const gbyte_ptr ac_ = abase + (size_t)(c) * (A_UNITS * 16) + aoff;                          \
-        const gbyte_ptr bc_ = (gbyte_ptr)(ub) + boff;                                               \
-        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                            \
-            __builtin_amdgcn_global_load_lds((gunit_ptr)(ac_ + j_ * (NT * 16)), la_ + j_ * NT, 16, 0, 0); \
-        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                            \
-            __builtin_amdgcn_global_load_lds((gunit_ptr)(bc_ + j_ * bstep), la_ + A_UNITS + j_ * NT, 16, 0, 0); \
-    } while (0)
-#define CTTS_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-#define CTTS_UNIFORM64(v) \
-    (((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)((v) >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(v)))
-    // wait until at most `k` chunks (8 DMAs each, in order) of this thread's DMAs are still in flight
-#define CTTS_W4_WAIT_CHUNKS(k)                                                                      \
-    do {                                                                                            \
-        if ((k) >= 3) CTTS_WAIT_VM(24);                                                             \
-        else if ((k) == 2) CTTS_WAIT_VM(16);                                                        \
-        else if ((k) == 1) CTTS_WAIT_VM(8);                                                         \
-        else CTTS_WAIT_VM(0);                                                                       \
-    } while (0)
-
-    const unsigned long long st0 = (DBG & 4) ? __builtin_readcyclecounter() : 0;
-    __syncthreads();                                        // table visible
-    {
-        const int npro = nch < NS ? nch : NS;
-        for (int c = 0; c < npro; ++c) {
-            const u64 ub = CTTS_UNIFORM64(tab[c]);
-            CTTS_W4_DMA(c, c, ub);
-        }
-        CTTS_W4_WAIT_CHUNKS(npro - 1);                      // chunk 0 landed (own DMAs), the rest in flight
-    }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-
-    u32x4 fa[2][4], fb[2][4];                               // [k-step][tile] fragments
-    // With one wave per SIMD nothing else fills the matrix pipe while this wave issues other instructions: every
-    // ds_read / DMA is issued in the 32-cycle shadow of ONE MFMA (order pinned by sched_barrier), never in a burst.
-#define CTTS_W4_FRAG1(ks, i, buf)                                                                   \
-    do {                                                                                            \
-        if ((i) < 4) fa[ks][(i)] = lds[(buf) * STAGE_UNITS + (2 * (ks) + lhi) * BGEMM_BM + wm * 128 + l31 + (i) * 32]; \
-        else fb[ks][(i) - 4] = lds[(buf) * STAGE_UNITS + A_UNITS + (2 * (ks) + lhi) * BN + wn * 128 + l31 + ((i) - 4) * 32]; \
-    } while (0)
-#define CTTS_W4_MFMA1(ks, mt, nt)                                                                   \
-    do {                                                                                            \
-        if ((DBG & 2)) acc[(nt) >> 1][mt][(nt) & 1][0] += __builtin_bit_cast(float, fa[ks][mt][0] ^ fb[ks][nt][0]); \
-        else acc[(nt) >> 1][mt][(nt) & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                \
-            *reinterpret_cast<const bf16x8*>(&fa[ks][mt]),                                          \
-            *reinterpret_cast<const bf16x8*>(&fb[ks][nt]), acc[(nt) >> 1][mt][(nt) & 1], 0, 0, 0);  \
-    } while (0)
-    // SGPR base + 32-bit lane offset per piece (see the skewed kernel's DMA)
-    unsigned w4_lane[8];
-#pragma unroll
-    for (int j_ = 0; j_ < 8; ++j_) w4_lane[j_] = j_ < 4 ? aoff + (unsigned)(j_ * (NT * 16)) : boff + (unsigned)(j_ - 4) * bstep;
-#define CTTS_W4_DMA1(buf, c, ub, j)                                                                 \
-    do {                                                                                            \
-        lds_ptr la_ = (lds_ptr)(lds + (buf) * STAGE_UNITS + wave * 64);                             \
-        unsigned o_ = w4_lane[(j)];                                                                 \
-        asm volatile("" : "+v"(o_));                                                                \
-        if ((j) < 4)                                                                                \
-            __builtin_amdgcn_global_load_lds((gunit_ptr)(abase + (size_t)(c) * (A_UNITS * 16) + o_), la_ + (j) * NT, 16, 0, 0); \
-        else                                                                                        \
-            __builtin_amdgcn_global_load_lds((gunit_ptr)((gbyte_ptr)(ub) + o_), la_ + A_UNITS + ((j) - 4) * NT, 16, 0, 0); \
-    } while (0)
-#define CTTS_SB() __builtin_amdgcn_sched_barrier(0)
-
-#pragma unroll
-    for (int i = 0; i < 8; ++i) CTTS_W4_FRAG1(0, i, 0);
-    int cur = 0;
-    const unsigned long long st1 = (DBG & 4) ? __builtin_readcyclecounter() : 0;
-    const unsigned long long rt1 = (DBG & 4) ? __builtin_amdgcn_s_memrealtime() : 0;
-    // One chunk.  STEADY: chunk ch + NS exists (DMA issued, constant vmcnt); otherwise the tail (no DMA, draining waits).
-#define CTTS_W4_CHUNK(STEADY)                                                                       \
-    do {                                                                                            \
-        const int nxt = cur == NS - 1 ? 0 : cur + 1;                                                \
-        /* k-step 0: MFMA m (row-major over the 4 x 4 tiles); k-step-1 fragment i is read behind MFMA i + 1 */ \
-        u64 tnext = 0;                                                                              \
-        _Pragma("unroll") for (int m = 0; m < 16; ++m) {                                            \
-            CTTS_W4_MFMA1(0, m >> 2, m & 3);                                                        \
-            CTTS_SB();                                                                              \
-            if (m >= 1 && m <= 8) CTTS_W4_FRAG1(1, m - 1, cur);                                     \
-            if (STEADY && m == 9) tnext = tab[ch + NS];                                             \
-            CTTS_SB();                                                                              \
-        }                                                                                           \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* k-step-1 fragments, table entry */    \
-        if ((DBG & 1)) CTTS_WAIT_VM(0);                                                              \
-        else if (STEADY) CTTS_WAIT_VM(8 * (NS - 2));       /* own DMAs of chunk ch+1 landed */      \
-        else CTTS_W4_WAIT_CHUNKS(nch - ch - 2);                                                     \
-        __builtin_amdgcn_s_barrier();                      /* chunk ch+1 visible; stage `cur` is free */ \
-        CTTS_SB();                                                                                  \
-        /* k-step 1: next chunk's k-step-0 fragments behind MFMAs 1..8, the DMA of chunk ch + NS behind 8..15 */ \
-        const bool more = STEADY || ch + 1 < nch;                                                   \
-        const u64 ub = STEADY ? CTTS_UNIFORM64(tnext) : 0;                                          \
-        _Pragma("unroll") for (int m = 0; m < 16; ++m) {                                            \
-            CTTS_W4_MFMA1(1, m >> 2, m & 3);                                                        \
-            CTTS_SB();                                                                              \
-            if (m >= 1 && m <= 8 && more) CTTS_W4_FRAG1(0, m - 1, nxt);                             \
-            if (STEADY && !(DBG & 1) && m >= 8) CTTS_W4_DMA1(cur, ch + NS, ub, m - 8);                \
-            CTTS_SB();                                                                              \
-        }                                                                                           \
-        cur = nxt;                                                                                  \
-    } while (0)
-    int ch = 0;
-    for (; ch + NS < nch; ++ch) CTTS_W4_CHUNK(true);
-    for (; ch < nch; ++ch) CTTS_W4_CHUNK(false);
-#undef CTTS_W4_CHUNK
-#undef CTTS_W4_FRAG1
-#undef CTTS_W4_MFMA1
-#undef CTTS_W4_DMA1
-#undef CTTS_SB
-#undef CTTS_W4_FRAGS
-#undef CTTS_W4_MFMA
-#undef CTTS_W4_DMA
-#undef CTTS_W4_WAIT_CHUNKS
-#undef CTTS_UNIFORM64
-#undef CTTS_WAIT_VM
-    const unsigned long long st2 = (DBG & 4) ? __builtin_readcyclecounter() : 0;
-    const unsigned long long rt2 = (DBG & 4) ? __builtin_amdgcn_s_memrealtime() : 0;
-    bf16_epilogue<EPI>(a, acc[0], lds, t, mb, wm, 2 * wn, b, n0, l31, lhi);
-    bf16_epilogue<EPI>(a, acc[1], lds, t, mb, wm, 2 * wn + 1, b, n0, l31, lhi);
-    if ((DBG & 4) && blockIdx.x == 1000 && t == 0) {
-        g_w4_stamps[0] = st2 - st1; g_w4_stamps[1] = rt2 - rt1;
-        g_w4_stamps[2] = __builtin_readcyclecounter() - st2; g_w4_stamps[3] = st1 - st0; g_w4_stamps[4] = nch;
-    }
 }
 
 // dst packed [MB][nch][4][256][8]; thread = one 16-byte unit (mb, chunk, g, r)

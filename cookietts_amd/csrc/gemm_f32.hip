@@ -742,28 +742,20 @@ void load_tuning_locked() {
     g_tune.f32_no_small = on("CTTS_F32_NO_SMALL");
     g_tune.f32_force_small = on("CTTS_F32_FORCE_SMALL");
     g_tune.f32_no_splitk = on("CTTS_F32_NO_SPLITK");
-    g_tune.f32_splitk_w4 = on("CTTS_F32_SPLITK_W4");
     g_tune.f32_no_round_split = on("CTTS_F32_NO_ROUND_SPLIT");
     g_tune.no_xcd_pair = on("CTTS_GEMM_NO_XCD_PAIR");
-    g_tune.bf16_no_glds = on("CTTS_BF16_NO_GLDS");
     g_tune.bf16_no_wide = on("CTTS_BF16_NO_WIDE");
     g_tune.bf16_no_pp = on("CTTS_BF16_NO_PP");
     // (512 until round 5.  One utterance of config 2 is 452 wide tiles: 17.7 -> 15.7 ms per call in the half mode with the wide block;
     //  450 frames = 228 tiles 11.0 -> 10.4; at 225 frames = 116 tiles the narrow block is ahead, 8.8 vs 9.2: profiles/r5_61)
     g_tune.bf16_wide_min = num("CTTS_BF16_WIDE_MIN", 192);
-    g_tune.bf16_w4 = on("CTTS_BF16_W4");
-    g_tune.bf16_pp_stages = num("CTTS_BF16_PP_STAGES", 3);
-    g_tune.bf16_map = num("CTTS_BF16_MAP", 0);
     g_tune.bf16_ps = on("CTTS_BF16_PS");
     g_tune.bf16_no_ps = on("CTTS_BF16_NO_PS");
-    g_tune.bf16_ps_stages = num("CTTS_BF16_PS_STAGES", 4) == 3 ? 3 : 4;
     g_tune.wf_no_fuse = on("CTTS_WF_NO_FUSE");
     g_tune.taco_no_fuse = on("CTTS_TACO_NO_FUSE");
     g_tune.taco_valu = on("CTTS_TACO_VALU");
     g_tune.up_no_mfma = on("CTTS_UP_NO_MFMA");
     g_tune.taco_bg_no_pipe = on("CTTS_TACO_BG_NO_PIPE");
-    { const char* e = getenv("CTTS_TACO_BG_SHAPE"); g_tune.taco_bg_shape = e ? atoi(e) : 0; }
-    { const char* e = getenv("CTTS_TACO_BG_DEBUG"); g_tune.taco_bg_debug = e ? atoi(e) : 0; }
     {
         // measured: profiles/r5_59_taco_poll_delay.txt, r5_62 (0x10000 = straight to the full sweep; ctx: 128 is 0.3 us faster still but
         // 144 is already behind - the attention workgroups' answer must not beat the delay - so it stays a quarter below that edge)
@@ -784,7 +776,6 @@ void load_tuning_locked() {
     g_tune.wf_queue_debug = num("CTTS_WF_QUEUE_DEBUG", 0);
     g_tune.f32_no_defer_skip = on("CTTS_F32_NO_DEFER_SKIP");
     g_tune.f32_no_wn_fold = on("CTTS_F32_NO_WN_FOLD");
-    g_tune.w4_debug = num("CTTS_BF16_W4_DEBUG", 0);
     g_tune_loaded = true;
 }
 }  // namespace

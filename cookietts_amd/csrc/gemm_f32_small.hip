@@ -1203,11 +1203,6 @@ __device__ __forceinline__ void gate_rs_splitk_tile(ARGS& a, const int tile, con
     if constexpr (!FRESH) S_STAMP_DRAIN(7);
 }
 
-template <int SEGS>
-__global__ __launch_bounds__(256, 2) void conv_gemm_f32_gate_rs_splitk_kernel(const GemmArgs a, const int ntiles_s) {
-    gate_rs_splitk_tile<SEGS, false, const GemmArgs>(a, blockIdx.x % ntiles_s, blockIdx.x / ntiles_s);
-}
-
 // ---- the split-K tile on EIGHT waves (round 5; per-layer launches only, i.e. batch 1) ------------------------------------
 // At batch 1 the tile above runs ONE wave per SIMD on 226 CUs: nobody covers a wave's LDS reads, DMA issue and barrier waits, and
 // the main loop takes 27.5 us for 20 us of matrix work (profiles/r5_21).  Same 128 x 64 tile, same stages, same K order, but
@@ -1564,7 +1559,6 @@ struct WfRowArgs {
     unsigned int epoch;                // > 0, unique per launch within a call
     unsigned int timeout_ticks;        // of s_memrealtime (100 MHz)
     int ntiles_k;                      // 64-column tiles per batch item (the split-K body's items)
-    int debug;                         // CTTS_WF_QUEUE_DEBUG (diagnosis only): 1 no dependency waits, 2 no tile body, 8 release fence (L2 write-back), 64 two workgroups per CU at every size
 };
 
 // BODY 0: items are 128 x 128 tiles (gate_rs_small_tile, neighbours t - 1 .. t + 1); BODY 1: 128 x 64 tiles of the split-K body
@@ -1664,7 +1658,7 @@ __global__ __launch_bounds__(256, 2) void wf_row_persistent_kernel(const WfRowAr
         // Every thread calls it once per item: the (<= 2 HALO + 1) polling threads spin on their neighbour flags of the previous
         // stage, the barrier closes the wait.  false: the launch is being aborted.
         auto wait_deps = [&]() -> bool {
-            if (gs > 0 && t < 2 * HALO + 1 && !(w.debug & 1)) {
+            if (gs > 0 && t < 2 * HALO + 1) {
                 const int tt = tile + t - HALO;
                 if (tt >= tile - halo && tt <= tile + halo && tt >= 0 && tt < ntiles) {
                     const unsigned int* f = w.flags + (size_t)(gs - 1) * per_layer + b * ntiles + tt;
@@ -1699,15 +1693,15 @@ __global__ __launch_bounds__(256, 2) void wf_row_persistent_kernel(const WfRowAr
             if (__builtin_amdgcn_readfirstlane(s_abort)) return false;
             // Acquire.  Everything another workgroup wrote inside this launch is read with sc1 loads / sc1 DMA (GemmSeg.fresh, the
             // tail's atomic loads), which is what makes the relaxed flag protocol correct today; the invalidate (buffer_inv sc1)
-            // makes it correct for a plain load of such data too, should one ever be added.  CTTS_WF_QUEUE_DEBUG=256
-            // leaves it out (A/B: profiles/r5_17_wf_queue_acquire_ab.txt).
-            if (!(w.debug & 256)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            // makes it correct for a plain load of such data too, should one ever be added (its cost was measured in
+            // profiles/r5_17_wf_queue_acquire_ab.txt).
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             return true;
         };
         typedef const __attribute__((address_space(4))) GemmArgs const_args;         // scalar loads of the descriptor
-        if (BODY == 1 && layer < w.nlayers && !(w.debug & (2 | 512))) {
-            // split-K item: the tile's data-independent prologue runs BEFORE the wait (CTTS_WF_QUEUE_DEBUG=512: after it, as the
-            // 128 x 128 items and the tail stage do)
+        if (BODY == 1 && layer < w.nlayers) {
+            // split-K item: the tile's data-independent prologue runs BEFORE the wait (the 128 x 128 items and the tail stage wait
+            // first)
             const_args& a = *((const_args*)w.layers + (size_t)row * w.nlayers + layer);
             if constexpr (BODY == 1) gate_rs_splitk_tile<SEGS, true, const_args>(a, tile, b, wait_deps);
             if (__builtin_amdgcn_readfirstlane(s_abort)) break;
@@ -1716,18 +1710,16 @@ __global__ __launch_bounds__(256, 2) void wf_row_persistent_kernel(const WfRowAr
             if (layer == w.nlayers) {
                 typedef const __attribute__((address_space(4))) WfTailDesc const_tail;
                 wf_tail_start_tile<BODY == 1 ? 64 : 128, const_tail>(*((const_tail*)w.tails + row), tile, b, s_tail);
-            } else if (!(w.debug & 2)) {
+            } else if constexpr (BODY == 0) {        // (a split-K layer item took the branch above)
                 const_args& a = *((const_args*)w.layers + (size_t)row * w.nlayers + layer);
-                if constexpr (BODY == 1) gate_rs_splitk_tile<SEGS, true, const_args>(a, tile, b);
-                else gate_rs_small_tile<SEGS, true, const_args>(a, tile, b);
+                gate_rs_small_tile<SEGS, true, const_args>(a, tile, b);
             }
         }
         // Release.  Every result was stored at agent scope (sc1: written THROUGH this XCD's L2), so a store is visible to the
         // agent once it is acknowledged: vmcnt(0) of every thread, then the barrier, then the flag.  The formal release fence
         // adds `buffer_wbl2 sc1`, a walk of the whole L2 for dirty lines that are not there: measured 226.9 ms per call with it
-        // against 166.0 without (config 4, B = 8; CTTS_WF_QUEUE_DEBUG=8 brings it back for A/B).
-        if (w.debug & 8) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // against 166.0 without (config 4, B = 8).
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                   // ... for every thread of the item; the LDS is free; s_item has been read
         if (t == 0) {
             __hip_atomic_store(w.flags + (size_t)gs * per_layer + rem, w.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1790,24 +1782,19 @@ int launch_gemm_f32_small(int epi, const GemmArgs& a, hipStream_t stream) {
         const long long nblk = (long long)nt * a.batch;
         CTTS_CHECK_ARG(nblk > 0 && nblk < (1ll << 31), "gemm (split-K fused shape): grid %lld", nblk);
         constexpr size_t LDS = K_LDS_FLOATS * sizeof(float);         // above the 64 KiB default: opt in once per kernel
-        const bool w8 = !tuning().f32_splitk_w4;                     // eight waves per tile (two per SIMD), CTTS_F32_SPLITK_W4: four
-        const int vi = (a.nseg <= 4 ? 0 : 1) + (w8 ? 2 : 0);
-        const void* fns[4] = {reinterpret_cast<const void*>(conv_gemm_f32_gate_rs_splitk_kernel<4>),
-                              reinterpret_cast<const void*>(conv_gemm_f32_gate_rs_splitk_kernel<GEMM_MAX_SEG>),
-                              reinterpret_cast<const void*>(conv_gemm_f32_gate_rs_splitk8_kernel<4>),
+        const int vi = a.nseg <= 4 ? 0 : 1;
+        const void* fns[2] = {reinterpret_cast<const void*>(conv_gemm_f32_gate_rs_splitk8_kernel<4>),
                               reinterpret_cast<const void*>(conv_gemm_f32_gate_rs_splitk8_kernel<GEMM_MAX_SEG>)};
         {   // once per process and kernel (one process per GPU); a failure is reported by every call that meets it
             static std::mutex mu;
-            static bool attr_set[4] = {false, false, false, false};
+            static bool attr_set[2] = {false, false};
             std::lock_guard<std::mutex> lk(mu);
             if (!attr_set[vi]) {
                 CTTS_CHECK_HIP(hipFuncSetAttribute(fns[vi], hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
                 attr_set[vi] = true;
             }
         }
-        if (vi == 0) hipLaunchKernelGGL((conv_gemm_f32_gate_rs_splitk_kernel<4>), dim3((unsigned)nblk), dim3(256), LDS, stream, a, nt);
-        else if (vi == 1) hipLaunchKernelGGL((conv_gemm_f32_gate_rs_splitk_kernel<GEMM_MAX_SEG>), dim3((unsigned)nblk), dim3(256), LDS, stream, a, nt);
-        else if (vi == 2) hipLaunchKernelGGL((conv_gemm_f32_gate_rs_splitk8_kernel<4>), dim3((unsigned)nblk), dim3(512), LDS, stream, a, nt);
+        if (vi == 0) hipLaunchKernelGGL((conv_gemm_f32_gate_rs_splitk8_kernel<4>), dim3((unsigned)nblk), dim3(512), LDS, stream, a, nt);
         else hipLaunchKernelGGL((conv_gemm_f32_gate_rs_splitk8_kernel<GEMM_MAX_SEG>), dim3((unsigned)nblk), dim3(512), LDS, stream, a, nt);
         note_gemm_loop(16 | 32);                                     // fp32 MFMA whatever the mode (see cookietts_hip.h)
         CTTS_CHECK_LAUNCH("conv_gemm_f32_gate_rs_splitk");
@@ -1872,7 +1859,6 @@ int launch_wf_row_persistent(const GemmArgs* layers_dev, const WfTailDesc* tails
     w.layers = layers_dev; w.tails = tails_dev; w.nrows = nrows; w.nlayers = nlayers; w.ntiles_s = wf_row_tiles(L, 0); w.ntiles_k = wf_row_tiles(L, 1); w.batch = batch;
     w.counter = counter; w.flags = flags; w.abort_word = abort_word; w.epoch = epoch;
     w.timeout_ticks = 100u * 1000u * 1000u;                             // 1 s without a single item being claimed, twice in a row (a whole call is ~0.2 s)
-    w.debug = tuning().wf_queue_debug;
     CTTS_CHECK_ARG(layers_dev && counter && flags && abort_word && epoch > 0 && nlayers >= 1 && nrows >= 1 && batch >= 1 &&
                        w.ntiles_s >= 1 && (body == 0 || body == 1), "waveflow row launch: bad argument");
     const int n_cu = wf_row_cus();
@@ -1881,7 +1867,7 @@ int launch_wf_row_persistent(const GemmArgs* layers_dev, const WfTailDesc* tails
     // straggler it waits for and halve that one's matrix pipe (config 4, batch 1: 55 ms per call with 2 per CU)
     const long long per_layer = (long long)(body == 1 ? w.ntiles_k : w.ntiles_s) * batch;
     long long want = std::min<long long>(2ll * n_cu, std::min<long long>((long long)nrows * nlayers * per_layer, 2 * per_layer));
-    if (per_layer <= n_cu && !(w.debug & 64)) want = per_layer;
+    if (per_layer <= n_cu && !(tuning().wf_queue_debug & 64)) want = per_layer;     // (CTTS_WF_QUEUE_DEBUG=64: two per CU at every size)
     const dim3 grid((unsigned)std::max<long long>(want, 1));
     const int vi = max_nseg <= 4 ? 0 : 1;
     if (body == 1) {

@@ -415,7 +415,7 @@ __device__ __forceinline__ void attn_pre_body(const AttnArgs& a, float* apre, in
 constexpr int BGA_DM = 512, BGA_A = 256;
 constexpr int BGA_POST_LDS_BYTES = ((BGA_W * BGA_DM + 128) * 4 + 1023) / 1024 * 1024;
 __device__ __forceinline__ void attn_post_body(const AttnArgs& a, const float* __restrict__ qbuf, const float* __restrict__ apre,
-                                               const int* __restrict__ astart, int dbg, float* lds, int b) {
+                                               const int* __restrict__ astart, float* lds, int b) {
     float* memw = lds;                                     // [BGA_W][Dm] (16-byte aligned)
     float* en = memw + BGA_W * BGA_DM;                     // [64]
     float* wts = en + 64;                                  // [64] (16-byte aligned)
@@ -425,7 +425,6 @@ __device__ __forceinline__ void attn_post_body(const AttnArgs& a, const float* _
     const int s = astart[b];
     const int len = a.lengths[b];
     const float pos_old = a.pos[b], sf_raw = a.scalars[1];     // (used by one lane after the softmax: requested here)
-    if (!(dbg & 8))
     {   // memory window -> LDS: row tt = 16-byte units [tt * Dm / 4, ...), one wave-instruction = 64 units = 256 floats
         const int upr = a.Dm / 4;                          // units per row (Dm % 256 == 0 is not required: units beyond are masked)
         const int total = W * upr;
@@ -461,7 +460,7 @@ __device__ __forceinline__ void attn_post_body(const AttnArgs& a, const float* _
             float e = 0.f;
 #pragma unroll
             for (int j = 0; j < NJ; ++j)      // ~2-ulp tanh on exp2 / rcp (taco_math.h; libm's costs 4 us of this kernel's 12)
-                if (lane + 64 * j < a.A) e = fmaf(vv[j], (dbg & 1) ? x[i][j] + qv[j] : tmath::acc_tanh(x[i][j] + qv[j]), e);
+                if (lane + 64 * j < a.A) e = fmaf(vv[j], tmath::acc_tanh(x[i][j] + qv[j]), e);
             ev[i] = e;
         }
         tmath::wave_totals<NE>(ev);                     // DPP network: no LDS-crossbar round trips
@@ -492,7 +491,6 @@ __device__ __forceinline__ void attn_post_body(const AttnArgs& a, const float* _
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this thread's share of the memory window has landed
     __syncthreads();
-    if (!(dbg & 2))
     for (int d = 2 * t; d < a.Dm; d += 512) {              // dims d, d + 1: one 8-byte LDS read per window row
         float wreg[BGA_W + 3];
 #pragma unroll
@@ -510,7 +508,6 @@ __device__ __forceinline__ void attn_post_body(const AttnArgs& a, const float* _
         }
         *reinterpret_cast<float2*>(&a.ctx[(size_t)b * a.Dm + d]) = make_float2(c0[0] + c1[0], c0[1] + c1[1]);
     }
-    if (!(dbg & 4))
     for (int p = t; p < a.T; p += 256) {
         const float wgt = (p >= s && p < s + W) ? wts[p - s] : 0.f;
         a.w[(size_t)b * a.T + p] = wgt;
@@ -520,9 +517,9 @@ __device__ __forceinline__ void attn_post_body(const AttnArgs& a, const float* _
 }
 
 __global__ __launch_bounds__(256) void attn_post_kernel(const AttnArgs a, const float* __restrict__ qbuf, const float* __restrict__ apre,
-                                                        const int* __restrict__ astart, int dbg) {
+                                                        const int* __restrict__ astart) {
     extern __shared__ __attribute__((aligned(16))) bg_u4 bg_lds[];
-    attn_post_body(a, qbuf, apre, astart, dbg, reinterpret_cast<float*>(bg_lds), blockIdx.x);
+    attn_post_body(a, qbuf, apre, astart, reinterpret_cast<float*>(bg_lds), blockIdx.x);
 }
 
 // ---- kernels and launch shapes ---------------------------------------------------------------------------------------------
@@ -534,11 +531,11 @@ __global__ __launch_bounds__(WAVES * 64) void bg_kernel(const BgArgs a) {
 
 // the attention RNN's launch: workgroups [0, nblk) are the cell's, [nblk, nblk + batch) (of grid row 0) the attention's part 1
 template <int MTW, int NT, int S, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void bg_cell_attn_kernel(const BgArgs a, int nblk, const AttnArgs at, float* apre, int* astart, int dbg) {
+__global__ __launch_bounds__(WAVES * 64) void bg_cell_attn_kernel(const BgArgs a, int nblk, const AttnArgs at, float* apre, int* astart) {
     extern __shared__ __attribute__((aligned(16))) bg_u4 bg_lds[];
     static_assert(sizeof(BgAttnLds) <= bg_lds_bytes<MTW, NT, S, WAVES>(), "the attention scratch shares the ring");
     if ((int)blockIdx.x < nblk) bg_body<MTW, NT, S, WAVES, BG_EPI_CELL>(a, bg_lds, blockIdx.x, blockIdx.y);
-    else if (blockIdx.y == 0 && !(dbg & 32)) attn_pre_body(at, apre, astart, *reinterpret_cast<BgAttnLds*>(bg_lds), blockIdx.x - nblk);
+    else if (blockIdx.y == 0) attn_pre_body(at, apre, astart, *reinterpret_cast<BgAttnLds*>(bg_lds), blockIdx.x - nblk);
 }
 
 // more than 64 KiB of dynamic LDS has to be allowed per kernel, once (per instantiation: the flag is a template static)
@@ -566,16 +563,15 @@ int bg_allow_lds(int bytes) {
 //   16 items: attention RNN MTW 2 (160 workgroups, 1.5 W), decoder RNNs MTW 1 (192, 2 W: as 96 they are per-CU bound)
 //   32 items: MTW 2, NT 2 (2 W);  64 k items: MTW 2, NT 4 (3 W), grid.y = k
 // attn != NULL: the attention's part 1 rides along (the attention RNN's launch).
-#define BG_CELL_SHAPES(X) X(4, 1, 6, 4) X(2, 1, 8, 4) X(1, 1, 8, 4) X(2, 1, 6, 8) X(1, 1, 8, 8) \
-    X(4, 2, 4, 4) X(2, 2, 5, 4) X(1, 2, 8, 4) X(2, 2, 4, 8) X(2, 4, 4, 4) X(2, 4, 3, 4) X(1, 4, 3, 4) X(2, 4, 3, 8)
-inline void bg_cell_shape(int nb_pad, bool att, int shape, int& mtw, int& nt, int& st, int& wvs) {
+// (MTW, NT, S, waves) by padded batch: the four shapes below; the other shapes of the sweep lost (profiles/r6_07).
+#define BG_CELL_SHAPES(X) X(2, 1, 8, 4) X(1, 1, 8, 4) X(2, 2, 5, 4) X(2, 4, 4, 4)
+inline void bg_cell_shape(int nb_pad, bool att, int& mtw, int& nt, int& st, int& wvs) {
     mtw = nb_pad <= 16 ? 1 : 2; nt = nb_pad <= 16 ? 1 : nb_pad <= 32 ? 2 : 4; st = nb_pad <= 16 ? 8 : nb_pad <= 32 ? 5 : 4; wvs = 4;
     if (att && nb_pad <= 16) mtw = 2;
-    if (shape > 0) { wvs = shape >= 1000 ? 8 : 4; mtw = shape % 1000 / 100; st = shape % 100; }   // A/B knob: CTTS_TACO_BG_SHAPE = (1000: eight waves) + 100 MTW + S
 }
-inline int bg_launch_cell(const BgArgs& a, int nb_pad, const AttnArgs* attn, float* apre, int* astart, int batch, int shape, hipStream_t s) {
+inline int bg_launch_cell(const BgArgs& a, int nb_pad, const AttnArgs* attn, float* apre, int* astart, int batch, hipStream_t s) {
     int mtw, nt, st, wvs;
-    bg_cell_shape(nb_pad, attn != nullptr, shape, mtw, nt, st, wvs);
+    bg_cell_shape(nb_pad, attn != nullptr, mtw, nt, st, wvs);
     const int ny = nb_pad <= 32 ? 1 : nb_pad / 64;
     int rc = CTTS_E_ARG;
     bool found = false;
@@ -587,7 +583,7 @@ inline int bg_launch_cell(const BgArgs& a, int nb_pad, const AttnArgs* attn, flo
         const int nblk = (a.tiles + M - 1) / M;                                                                                   \
         if (attn) {                                                                                                               \
             if ((rc = BG_ALLOW_LDS((bg_cell_attn_kernel<M, N, SS, WV>), LDS))) return rc;                                         \
-            hipLaunchKernelGGL((bg_cell_attn_kernel<M, N, SS, WV>), dim3(nblk + batch, ny), dim3(64 * WV), LDS, s, a, nblk, *attn, apre, astart, tuning().taco_bg_debug); \
+            hipLaunchKernelGGL((bg_cell_attn_kernel<M, N, SS, WV>), dim3(nblk + batch, ny), dim3(64 * WV), LDS, s, a, nblk, *attn, apre, astart);                        \
         } else {                                                                                                                  \
             if ((rc = BG_ALLOW_LDS((bg_kernel<M, N, SS, WV, BG_EPI_CELL>), LDS))) return rc;                                      \
             hipLaunchKernelGGL((bg_kernel<M, N, SS, WV, BG_EPI_CELL>), dim3(nblk, ny), dim3(64 * WV), LDS, s, a);                 \
@@ -636,11 +632,11 @@ __global__ __launch_bounds__(512) void bg_multi8_kernel(const BgArgs small, int 
 }
 // 256 threads: attention part 2 (one block per item) + up to two EARLY cell roles of shape <M, N, SS, 4>
 template <int M, int N, int SS>
-__global__ __launch_bounds__(256) void bg_post_multi4_kernel(const AttnArgs at, const float* qbuf, const float* apre, const int* astart, int dbg,
+__global__ __launch_bounds__(256) void bg_post_multi4_kernel(const AttnArgs at, const float* qbuf, const float* apre, const int* astart,
                                                              int n_post, const BgArgs c0, int n0, int nblk0, const BgArgs c1, int n1, int nblk1) {
     extern __shared__ __attribute__((aligned(16))) bg_u4 bg_lds[];
     int r = blockIdx.x;
-    if (r < n_post) { attn_post_body(at, qbuf, apre, astart, dbg, reinterpret_cast<float*>(bg_lds), r); return; }
+    if (r < n_post) { attn_post_body(at, qbuf, apre, astart, reinterpret_cast<float*>(bg_lds), r); return; }
     r -= n_post;
     if (r < n0) { bg_body<M, N, SS, 4, BG_EPI_CELL>(c0, bg_lds, r % nblk0, r / nblk0); return; }
     r -= n0;
@@ -652,12 +648,6 @@ __global__ __launch_bounds__(256) void bg_post_multi4_kernel(const AttnArgs at, 
 inline int bg_launch_multi8(BgRoles& m, int nb_pad, hipStream_t s) {
     const int ny = nb_pad <= 32 ? 1 : nb_pad / 64;
     const int M = 2;
-    {   // timing experiments (CTTS_TACO_BG_DEBUG; wrong results): 64 = without the EARLY roles, 128 = without the small stage, 256 = without attention part 1
-        const int dbg = tuning().taco_bg_debug;
-        if (dbg & 64) m.n_cell[0] = m.n_cell[1] = 0;
-        if (dbg & 128) m.n_small = 0;
-        if (dbg & 256) m.pre = nullptr;
-    }
     for (int i = 0; i < 2; ++i) {
         m.nblk_cell[i] = m.n_cell[i] ? (m.cell[i].tiles + M - 1) / M : 1;
         m.n_cell[i] = m.n_cell[i] ? m.nblk_cell[i] * ny : 0;
@@ -690,7 +680,7 @@ inline int bg_launch_post_multi4(const AttnArgs& at, const float* qbuf, const fl
         const int nb0 = (c0.tiles + MM - 1) / MM, nb1 = (c1.tiles + MM - 1) / MM;                                 \
         if ((rc = BG_ALLOW_LDS((bg_post_multi4_kernel<MM, N, SS>), LDS))) return rc;                              \
         hipLaunchKernelGGL((bg_post_multi4_kernel<MM, N, SS>), dim3(batch + (nb0 + nb1) * ny), dim3(256), LDS, s, at, qbuf, apre, astart, \
-                           tuning().taco_bg_debug, batch, c0, nb0 * ny, nb0, c1, nb1 * ny, nb1);                  \
+                           batch, c0, nb0 * ny, nb0, c1, nb1 * ny, nb1);                                          \
     }
     if (nb_pad <= 16) BG_P4(1, 1, 8)
     else if (nb_pad <= 32) BG_P4(2, 2, 5)

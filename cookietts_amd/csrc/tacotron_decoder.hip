@@ -812,8 +812,7 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
     const auto& c = p.c;
     const int NB = ws_rows(p, batch);
     const int Pn = c.prenet_dim, Ra = c.attention_rnn_dim, Rd = c.decoder_rnn_dim, Rd2 = c.second_decoder_rnn_dim, Dm = c.memory_dim;
-    const int shape = tuning().taco_bg_shape;
-    const bool pipe = NB <= 64 && shape == 0 && !tuning().taco_bg_no_pipe;
+    const bool pipe = NB <= 64 && !tuning().taco_bg_no_pipe;
     const int nyb = NB / 16;
     int rc;
     // the three cells' GEMMs for a given step parity (cur = step & 1): X pieces and state, K range / partial mode set by the caller
@@ -874,7 +873,7 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
         const AttnArgs at = attn_args(step), at_next = attn_args(step + 1);
         // 1: attention RNN on [prenet | context | decoder hidden], recurrent on its own hidden state (model.py:707-717); in the plain
         // schedule the attention's part 1 rides along, in the pipelined one it ran in the previous step's launch 7
-        if ((rc = bg_launch_cell(pipe ? final_(att_args(cur), 0, aP, 2) : att_args(cur), NB, pipe ? nullptr : &at, w.apre, w.astart, batch, shape, s))) return rc;
+        if ((rc = bg_launch_cell(pipe ? final_(att_args(cur), 0, aP, 2) : att_args(cur), NB, pipe ? nullptr : &at, w.apre, w.astart, batch, s))) return rc;
         BgArgs q{};     // 2: query rows (model.py:126)
         q.W = blob + p.bg_q.off; q.rows = p.bg_q.rows; q.batch = batch;
         bg_set_x(q, p.bg_q, w.att_h[nxt], Ra, nullptr, 0, nullptr, 0, nullptr, 0);
@@ -888,15 +887,15 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
             if ((rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, batch, early(dec_args(cur), dC, dK, 1),
                                             early(d2_args(cur), sD, sK, 0), NB, s))) return rc;
             // 4, 5: decoder RNN on [attention hidden | context] (model.py:741-747), second decoder RNN on its output (:749-755)
-            if ((rc = bg_launch_cell(final_(dec_args(cur), dA, dC, 2), NB, nullptr, nullptr, nullptr, batch, shape, s))) return rc;
-            if ((rc = bg_launch_cell(final_(d2_args(cur), 0, sD, 1), NB, nullptr, nullptr, nullptr, batch, shape, s))) return rc;
+            if ((rc = bg_launch_cell(final_(dec_args(cur), dA, dC, 2), NB, nullptr, nullptr, nullptr, batch, s))) return rc;
+            if ((rc = bg_launch_cell(final_(d2_args(cur), 0, sD, 1), NB, nullptr, nullptr, nullptr, batch, s))) return rc;
         } else {
             if ((rc = bg_launch_small<BG_EPI_LINEAR>(q, NB, s))) return rc;
             if ((rc = BG_ALLOW_LDS(attn_post_kernel, BGA_POST_LDS_BYTES))) return rc;
-            hipLaunchKernelGGL(attn_post_kernel, dim3(batch), dim3(256), BGA_POST_LDS_BYTES, s, at, w.qbuf, w.apre, w.astart, tuning().taco_bg_debug);
+            hipLaunchKernelGGL(attn_post_kernel, dim3(batch), dim3(256), BGA_POST_LDS_BYTES, s, at, w.qbuf, w.apre, w.astart);
             CTTS_CHECK_LAUNCH("attn_post");
-            if ((rc = bg_launch_cell(dec_args(cur), NB, nullptr, nullptr, nullptr, batch, shape, s))) return rc;
-            if ((rc = bg_launch_cell(d2_args(cur), NB, nullptr, nullptr, nullptr, batch, shape, s))) return rc;
+            if ((rc = bg_launch_cell(dec_args(cur), NB, nullptr, nullptr, nullptr, batch, s))) return rc;
+            if ((rc = bg_launch_cell(d2_args(cur), NB, nullptr, nullptr, nullptr, batch, s))) return rc;
         }
         const unsigned char* keep = step + 1 < max_steps ? keep_masks + (size_t)(step + 1) * 2 * batch * Pn : nullptr;
         BgArgs pr{}, w2{};

@@ -928,14 +928,14 @@ int ctts_last_gemm_loop(void) { return last_gemm_loop(); }
 int ctts_tuning_reload(void) { reload_tuning(); return CTTS_OK; }
 int ctts_tuning_flags(void) {
     const Tuning t = tuning();
-    return (t.f32_no_glds ? 1 : 0) | (t.no_xcd_pair ? 2 : 0) | (t.bf16_no_glds ? 4 : 0) | (t.bf16_no_wide ? 8 : 0) |
-           (t.bf16_no_pp ? 16 : 0) | (t.bf16_w4 ? 32 : 0) | (t.bf16_pp_stages == 4 ? 64 : 0) | (t.wf_no_fuse ? 128 : 0) |
-           (t.taco_no_fuse ? 256 : 0) | (t.f32_no_small ? 512 : 0) | (t.f32_force_small ? 1024 : 0) | (t.f32_no_splitk ? 2048 : 0) |
-           (t.wf_no_vec_interp ? 4096 : 0) | (t.f32_no_defer_skip ? 8192 : 0) | (t.wf_no_region_split ? 16384 : 0) |
-           (t.wf_no_row_queue ? 32768 : 0) | (t.wf_row_queue_min >= 0 ? 65536 : 0) | (t.wf_inject_abort ? 131072 : 0) |
-           (t.wf_queue_debug ? 262144 : 0) | (t.f32_no_round_split ? 524288 : 0) | (t.bf16_ps ? (1 << 20) : 0) |
-           (t.bf16_no_ps ? (1 << 21) : 0) | (t.f32_splitk_w4 ? (1 << 22) : 0) | (t.taco_poll_delay_set ? (1 << 23) : 0) |
-           (t.taco_valu ? (1 << 24) : 0) | (t.up_no_mfma ? (1 << 25) : 0) | (t.f32_no_wn_fold ? (1 << 26) : 0);
+    return (t.f32_no_glds ? 1 : 0) | (t.no_xcd_pair ? 2 : 0) | (t.bf16_no_wide ? 8 : 0) | (t.bf16_no_pp ? 16 : 0) |
+           (t.wf_no_fuse ? 128 : 0) | (t.taco_no_fuse ? 256 : 0) | (t.f32_no_small ? 512 : 0) | (t.f32_force_small ? 1024 : 0) |
+           (t.f32_no_splitk ? 2048 : 0) | (t.wf_no_vec_interp ? 4096 : 0) | (t.f32_no_defer_skip ? 8192 : 0) |
+           (t.wf_no_region_split ? 16384 : 0) | (t.wf_no_row_queue ? 32768 : 0) | (t.wf_row_queue_min >= 0 ? 65536 : 0) |
+           (t.wf_inject_abort ? 131072 : 0) | (t.wf_queue_debug ? 262144 : 0) | (t.f32_no_round_split ? 524288 : 0) |
+           (t.bf16_ps ? (1 << 20) : 0) | (t.bf16_no_ps ? (1 << 21) : 0) | (t.taco_poll_delay_set ? (1 << 23) : 0) |
+           (t.taco_valu ? (1 << 24) : 0) | (t.up_no_mfma ? (1 << 25) : 0) | (t.f32_no_wn_fold ? (1 << 26) : 0) |
+           (t.taco_bg_no_pipe ? (1 << 27) : 0);
 }
 
 int ctts_profile_create(void** handle) {

@@ -1,4 +1,5 @@
-"""Timing of the WaveFlow row queue at config 4 under the CTTS_WF_QUEUE_DEBUG bits (children: one setting per process)."""
+"""Timing of the WaveFlow row queue at config 4 in its forms (children: one setting per process).
+   python scripts/debug/wf_queue_time.py B:F:SETTING[,B:F:SETTING ...]"""
 import os
 import subprocess
 import sys
@@ -21,8 +22,9 @@ print("ms", " ".join("%.1f" % t for t in ts), "loop", _lib.lib().ctts_last_gemm_
 '''
 cases = [tuple(int(x) for x in c.split(":")) for c in sys.argv[1].split(",")]
 for B, F, dbg in cases:
-    # debug >= 0: queue forced, CTTS_WF_QUEUE_DEBUG = debug (+ 1024: CTTS_F32_NO_SPLITK, i.e. the 128 x 128 body at every size);
-    # -1: queue off; -2: library default
+    # debug >= 0: queue forced, CTTS_WF_QUEUE_DEBUG = debug (16 / 32: the 128 x 128 / split-K body, 64: two workgroups per CU at
+    # every size, 128: one launch per row; + 1024: CTTS_F32_NO_SPLITK, i.e. the 128 x 128 body at every size); -1: queue off;
+    # -2: library default
     env = dict(os.environ)
     if dbg >= 0:
         env["CTTS_WF_ROW_QUEUE_MIN"] = "1"

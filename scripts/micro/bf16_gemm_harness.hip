@@ -33,7 +33,7 @@ static bf16_t* random_bf16(size_t n, float scale) {
     return d;
 }
 
-struct Form { const char* name; int kind, ns; };   // kind 0 = pp (per tile), 1 = ps (persistent stream)
+struct Form { const char* name; int kind; };   // kind 0 = pp (per tile), 1 = ps (persistent stream), 2 = ps with stamps
 
 template <int EPI>
 static void launch(const Form& f, BGemmArgs b, int cus) {
@@ -43,10 +43,6 @@ static void launch(const Form& f, BGemmArgs b, int cus) {
         hipLaunchKernelGGL((conv_gemm_bf16_pp_kernel<EPI, 3>), dim3((unsigned)blocks), dim3(512), 0, 0, b);
     } else if (f.kind == 2) {
         hipLaunchKernelGGL((conv_gemm_bf16_ps_kernel<EPI, 4, 1>), dim3(cus / 16 * 16), dim3(512), 0, 0, b);
-    } else if (f.kind == 3) {
-        hipLaunchKernelGGL((conv_gemm_bf16_ps_kernel<EPI, 3, 1>), dim3(cus / 16 * 16), dim3(512), 0, 0, b);
-    } else if (f.ns == 3) {
-        hipLaunchKernelGGL((conv_gemm_bf16_ps_kernel<EPI, 3>), dim3(cus / 16 * 16), dim3(512), 0, 0, b);
     } else {
         hipLaunchKernelGGL((conv_gemm_bf16_ps_kernel<EPI, 4>), dim3(cus / 16 * 16), dim3(512), 0, 0, b);
     }
@@ -107,8 +103,7 @@ int main(int argc, char** argv) {
         cases.push_back({accum ? "skip SPLIT += (K=2048)" : "skip SPLIT = (K=2048)", BGEMM_EPI_SPLIT, a, 2.0 * 512 * 2048 * (double)B * L,
                          (accum ? 6.0 : 5.0) * C * 2 * (double)B * L, accum != 0});
     }
-    const Form forms[] = {{"pp per tile, 3 stages (round 3)", 0, 3}, {"ps persistent stream, 4 stages", 1, 4}, {"ps persistent stream, 3 stages", 1, 3},
-                          {"ps 4 stages with stamps", 2, 4}, {"ps 3 stages with stamps", 3, 3}};
+    const Form forms[] = {{"pp per tile, 3 stages (round 3)", 0}, {"ps persistent stream, 4 stages", 1}, {"ps 4 stages with stamps", 2}};
 
     hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
     std::vector<unsigned int> href(xn / 2), hdst(xn / 2);

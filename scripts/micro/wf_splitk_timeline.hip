@@ -7,8 +7,8 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DCTTS_SMALL_GEMM_STAMPS -I include -I cookietts_amd/csrc \
 //       scripts/micro/wf_splitk_timeline.hip -o /tmp/wf_splitk_timeline && /tmp/wf_splitk_timeline
 // Variants of the main loop (timing only, results garbage): -DCTTS_EXP_NO_MFMA (no matrix work), -DCTTS_EXP_NO_DMA (stages
-// never re-filled), -DCTTS_EXP_NO_LDSREAD (operands stay in registers) - these three act on the FOUR-wave tile (run with W4=1).
-// Default: the eight-wave tile of round 5 (two waves per SIMD); W4=1 in the environment: the four-wave tile.
+// never re-filled), -DCTTS_EXP_NO_LDSREAD (operands stay in registers).  The layer runs on the eight-wave tile of round 5 (two
+// waves per SIMD), the only per-layer split-K launch.
 // profiles/r4_19_wf_splitk_timeline.txt, r5_21, r5_31.
 #include <hip/hip_runtime.h>
 
@@ -23,7 +23,7 @@
 namespace ctts {
 // the symbols the kernel file takes from the rest of the library
 void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
-Tuning tuning() { Tuning t{}; t.f32_splitk_w4 = getenv("W4") != nullptr; return t; }   // W4=1: the four-wave tile (the form before round 5)
+Tuning tuning() { return Tuning{}; }
 void reload_tuning() {}
 bool gemm_mode_is_split(int) { return false; }
 int gemm_split_level(int) { return 0; }
@@ -88,7 +88,7 @@ int main() {
         CK(hipEventRecord(e1, st));
         CK(hipStreamSynchronize(st));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
-        printf("rep %d: %d fused layers, %.1f us per layer (%d workgroups of %s waves)\n", rep, layers, ms * 1000 / layers, blocks, getenv("W4") ? "four" : "eight");
+        printf("rep %d: %d fused layers, %.1f us per layer (%d workgroups of eight waves)\n", rep, layers, ms * 1000 / layers, blocks);
     }
     std::vector<unsigned long long> h((size_t)blocks * 8);
     CK(hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost));

@@ -113,7 +113,7 @@ def test_waveflow_fused_layer_small_shapes(hip_lib_path, tuning, name):
     the K halves on wave pairs: the default at this size) sums (even chunks) + (odd chunks) and agrees to fp32 summation
     noise - its eight-wave form (the default of the per-layer launches) and its four-wave form (the row queue's items) are
     bit-identical; every shape meets the reference golden."""
-    from cookietts_amd import WaveFlow
+    from cookietts_amd import WaveFlow, _lib
     g = np.load(os.path.join(GOLDEN, f"waveflow_{name}.npz"))
     cfg = synthetic.WAVEFLOW_CONFIGS[str(g["config_key"])]
     m = WaveFlow(**cfg)
@@ -121,9 +121,13 @@ def test_waveflow_fused_layer_small_shapes(hip_lib_path, tuning, name):
     m = m.cuda().eval()
     z, mel = torch.from_numpy(g["z"]).cuda(), torch.from_numpy(np.pad(g["mel"], ((0, 0), (0, 0), (0, 1)))).cuda()
     splitk, _ = m.inverse(z, mel, return_CPU=False)
-    tuning.set("CTTS_F32_SPLITK_W4")                        # four waves per split-K tile (until round 5) instead of eight: same sums
+    tuning.set("CTTS_WF_ROW_QUEUE_MIN", "1")                # the row queue at this size, with the split-K body: the four-wave
+    tuning.set("CTTS_WF_QUEUE_DEBUG", "32")                 # tile instead of the per-layer launches' eight-wave one: same sums
     assert torch.equal(splitk, m.inverse(z, mel, return_CPU=False)[0])
-    tuning.clear("CTTS_F32_SPLITK_W4")
+    code = _lib.lib().ctts_last_gemm_loop()
+    assert code & 64 and code & 32, "the row queue did not run with the split-K body"
+    tuning.clear("CTTS_WF_QUEUE_DEBUG")
+    tuning.clear("CTTS_WF_ROW_QUEUE_MIN")
     tuning.set("CTTS_F32_NO_SPLITK")
     small, _ = m.inverse(z, mel, return_CPU=False)
     tuning.set("CTTS_F32_NO_SMALL")
