@@ -219,6 +219,11 @@ SIGNATURES = {
     "ctts_wgax_workspace_bytes": (C.c_size_t, [C.POINTER(WgaxConfig), C.c_int32, C.c_int64]),
     "ctts_wgax_inverse_f32": (C.c_int, [C.POINTER(WgaxConfig), _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP,
                                         C.c_int32, C.c_int64, _FP, C.c_size_t, _FP]),
+    "ctts_wgax_packed_f16_bytes": (C.c_size_t, [C.POINTER(WgaxConfig)]),
+    "ctts_wgax_pack_flow_f16": (C.c_int, [C.POINTER(WgaxConfig), C.c_int32, C.POINTER(WgaxFlowWeights), _FP, _FP]),
+    "ctts_wgax_workspace_f16_bytes": (C.c_size_t, [C.POINTER(WgaxConfig), C.c_int32, C.c_int64]),
+    "ctts_wgax_inverse_f16": (C.c_int, [C.POINTER(WgaxConfig), _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP,
+                                        C.c_int32, C.c_int64, _FP, C.c_size_t, _FP]),
     "ctts_replicate_halo_f32": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "ctts_embed_rows_f32": (C.c_int, [_FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, _FP]),

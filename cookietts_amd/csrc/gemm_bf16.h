@@ -52,6 +52,15 @@ struct BGemmArgs {
     // destinations are read as hi + lo.  The K side of the split is expressed with segments (x_hi*W_hi + x_lo*W_hi +
     // x_hi*W_lo as three segments over the two planes and two packed weight parts).
     long long lo_off;
+    // GATE only: optional fp32 addend before the gate (the ax WN's conditioning rows, glow_ax.py:362-373, 389-390), padded
+    // layout [B][2*pairC][addend_ld] in DENSE row order (row c -> tanh input, row pairC + c -> sigmoid input) - the fields
+    // and the arithmetic of GemmArgs (gemm_f32.h): addend_frames = F > 0 -> F columns per row, linearly interpolated to the
+    // L columns of the launch (align_corners=True) with the fp32 epilogue's own expressions, so the interpolation weights
+    // are bit-equal between the two paths; 0 -> read at sample rate.  NULL (every glow.py launch): no addend, and the kernel
+    // instantiation that knows none.  Built for f16 = 1 (all four block shapes); a bf16 launch with an addend is refused.
+    const float* addend; long long addend_bstride;
+    int addend_ld, addend_pad;
+    int addend_frames;
 };
 
 // dense weight row of block-local row r of M-block mb (same pairing as the fp32 kernel), -1 = padding
@@ -90,6 +99,19 @@ __host__ __device__ inline float bf16_to_f32(bf16_t h) {
 // IEEE half (round to nearest even; overflow -> inf, subnormals kept): raw bits in the same 16-bit storage type.  Device only.
 __device__ __forceinline__ bf16_t f32_to_f16_rne(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
 __device__ __forceinline__ float f16_to_f32(bf16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+
+// Half-wave exchange (v_permlane32_swap): lanes 32..63 of x swap with lanes 0..31 of y.  Device only.
+__device__ __forceinline__ void swap_halves(unsigned int& x, unsigned int& y) {
+    const auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+    x = r[0];
+    y = r[1];
+}
+__device__ __forceinline__ void swap_halves(float& x, float& y) {
+    unsigned int a = __builtin_bit_cast(unsigned int, x), b = __builtin_bit_cast(unsigned int, y);
+    swap_halves(a, b);
+    x = __builtin_bit_cast(float, a);
+    y = __builtin_bit_cast(float, b);
+}
 
 // two fp32 -> packed bf16 (round to nearest even): one v_cvt_pk_bf16_f32 on the device
 __host__ __device__ __forceinline__ unsigned int pack_bf16x2(float lo, float hi) {

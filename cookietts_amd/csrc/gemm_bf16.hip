@@ -26,12 +26,14 @@ int launch_pack_a_bf16(bf16_t* dst, const float* src, int MB, int nch_total, int
 namespace {
 // The four block shapes, in order of preference: persistent (ps, 4 LDS stages), ping-pong (pp, 3 stages), wide 256 x 256, narrow
 // 256 x 128 (gemm_bf16_kernels.h).  One list for both operand types: F16 = IEEE half.
-template <int EPI, bool F16>
+// ADD: the GATE epilogue with the fp32 addend - instantiated for IEEE half only (the ax WaveGlow's half-storage path is its one
+// user; launch_gemm_bf16 refuses a bf16 launch with an addend instead of quietly dropping it).
+template <int EPI, bool F16, bool ADD = false>
 void launch_bf16_shape(const BGemmArgs& b, bool ps, bool pp, bool wide, dim3 pg, dim3 grid, hipStream_t stream) {
-    if (ps) hipLaunchKernelGGL((conv_gemm_bf16_ps_kernel<EPI, 4, 0, F16>), pg, dim3(512), 0, stream, b);
-    else if (wide && pp) hipLaunchKernelGGL((conv_gemm_bf16_pp_kernel<EPI, 3, F16>), grid, dim3(512), 0, stream, b);
-    else if (wide) hipLaunchKernelGGL((conv_gemm_bf16_kernel<EPI, 4, F16>), grid, dim3(512), 0, stream, b);
-    else hipLaunchKernelGGL((conv_gemm_bf16_kernel<EPI, 2, F16>), grid, dim3(256), 0, stream, b);
+    if (ps) hipLaunchKernelGGL((conv_gemm_bf16_ps_kernel<EPI, 4, 0, F16, ADD>), pg, dim3(512), 0, stream, b);
+    else if (wide && pp) hipLaunchKernelGGL((conv_gemm_bf16_pp_kernel<EPI, 3, F16, ADD>), grid, dim3(512), 0, stream, b);
+    else if (wide) hipLaunchKernelGGL((conv_gemm_bf16_kernel<EPI, 4, F16, ADD>), grid, dim3(512), 0, stream, b);
+    else hipLaunchKernelGGL((conv_gemm_bf16_kernel<EPI, 2, F16, ADD>), grid, dim3(256), 0, stream, b);
 }
 }  // namespace
 
@@ -65,6 +67,11 @@ int launch_gemm_bf16(int epi, const BGemmArgs& a, hipStream_t stream) {
                                             b.M <= b.MB * BGEMM_BM),
                    "gemm_bf16: M=%d pairC=%d MB=%d split=%d", b.M, b.pairC, b.MB, b.split);
     CTTS_CHECK_ARG(!b.f16 || b.lo_off == 0, "gemm_bf16: the split (hi + lo) form exists for bf16 only");
+    // the fp32 addend of the GATE epilogue: whole 32-channel tiles (no row is clamped), frames inside a row of the addend tensor
+    CTTS_CHECK_ARG(!b.addend || (epi == BGEMM_EPI_GATE && b.f16 && b.lo_off == 0 && b.pairC % 32 == 0 && b.addend_frames >= 0 && b.addend_pad >= 0 &&
+                                 b.addend_ld >= b.addend_pad + (b.addend_frames > 0 ? b.addend_frames : b.L)),
+                   "gemm_bf16: addend (GATE in IEEE half only; pairC=%d, frames=%d, ld=%d, pad=%d)", b.pairC, b.addend_frames, b.addend_ld,
+                   b.addend_pad);
     long long blocks = (long long)b.MB * b.ntiles * b.batch;
     b.map_mode = 0;
     const long long tiles = (long long)b.ntiles * b.batch;
@@ -90,7 +97,8 @@ int launch_gemm_bf16(int epi, const BGemmArgs& a, hipStream_t stream) {
     const bool use_ps = ps && ps_grid >= 16;
     const dim3 grid((unsigned)blocks), pg((unsigned)(use_ps ? ps_grid : 1));
     if (epi == BGEMM_EPI_GATE) {
-        if (b.f16) launch_bf16_shape<BGEMM_EPI_GATE, true>(b, use_ps, pp, wide, pg, grid, stream);
+        if (b.addend) launch_bf16_shape<BGEMM_EPI_GATE, true, true>(b, use_ps, pp, wide, pg, grid, stream);
+        else if (b.f16) launch_bf16_shape<BGEMM_EPI_GATE, true>(b, use_ps, pp, wide, pg, grid, stream);
         else launch_bf16_shape<BGEMM_EPI_GATE, false>(b, use_ps, pp, wide, pg, grid, stream);
     } else {
         if (b.f16) launch_bf16_shape<BGEMM_EPI_SPLIT, true>(b, use_ps, pp, wide, pg, grid, stream);

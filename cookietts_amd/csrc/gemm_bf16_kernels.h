@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "gemm_bf16.h"
+#include "gemm_f32.h"    // gemm_lerp: the interpolation of the GATE addend, shared with the fp32 epilogue
 
 namespace ctts {
 
@@ -52,19 +53,6 @@ __device__ __forceinline__ float fast_gate(float u0, float u1) {
 // split-bf16: low halves of two values whose high halves are the packed pair `hi` (lo = bf16(v - float(hi)))
 __device__ __forceinline__ unsigned int pack2_residual(float v0, float v1, unsigned int hi) {
     return pack2<false>(v0 - __builtin_bit_cast(float, hi << 16), v1 - __builtin_bit_cast(float, hi & 0xffff0000u));
-}
-
-// Half-wave exchange (v_permlane32_swap): lanes 32..63 of x swap with lanes 0..31 of y.
-__device__ __forceinline__ void swap_halves(unsigned int& x, unsigned int& y) {
-    const auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
-    x = r[0];
-    y = r[1];
-}
-__device__ __forceinline__ void swap_halves(float& x, float& y) {
-    unsigned int a = __builtin_bit_cast(unsigned int, x), b = __builtin_bit_cast(unsigned int, y);
-    swap_halves(a, b);
-    x = __builtin_bit_cast(float, a);
-    y = __builtin_bit_cast(float, b);
 }
 
 // Chunk c -> global byte address of its B rows (channel group 0, column n0 + shift) for this workgroup: the segment /
@@ -133,6 +121,37 @@ __device__ __forceinline__ bool block_map(const BGemmArgs& a, int id, int& mb, i
     return true;
 }
 
+// The ax WN's fp32 conditioning addend for one unit pair (register groups 2 qp, 2 qp + 1 of a 32 x 32 tile: 16 channels of
+// one column) of the GATE epilogue, added in front of the gate as (acc + bias) + addend like the fp32 epilogue
+// (gemm_f32.hip).  ad0 / ad1 point at this lane's first row (channel crow + 4 lhi) of the tanh half at frame i0 / i1; `interp`
+// (uniform) = frame rate, interpolated with weights l0 / l1, else read as it is.  Read from global memory, so the persistent
+// kernel's "no barrier in a STAGED epilogue" rule holds.  Used by the ADD instantiations of the kernels only - a
+// compile-time choice (the launcher picks it from BGemmArgs.addend): as a uniform run-time branch the second copy of the
+// epilogue doubled the GATE kernels' code and cost the launches WITHOUT an addend 1.0-1.2 % of a config 3 step
+// (profiles/r8_03_addend_runtime_branch_vs_parent.jsonl); with ADD = false a kernel is the code it was before the addend existed.
+__device__ __forceinline__ void bf16_gate_addend(const BGemmArgs& a, int qp, const float* ad0, const float* ad1, bool interp,
+                                                 float l0, float l1, float (&add0)[2][4], float (&add1)[2][4]) {
+    float s00[2][4], s01[2][4], s10[2][4], s11[2][4];        // all loads of the pair in flight before the first use
+    const size_t sig = (size_t)a.pairC * a.addend_ld;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t ro = (size_t)(8 * (2 * qp + h) + j) * a.addend_ld;
+            s00[h][j] = ad0[ro];
+            s10[h][j] = ad0[ro + sig];
+            s01[h][j] = interp ? ad1[ro] : 0.f;
+            s11[h][j] = interp ? ad1[ro + sig] : 0.f;
+        }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            add0[h][j] = interp ? gemm_lerp(l0, s00[h][j], l1, s01[h][j]) : s00[h][j];
+            add1[h][j] = interp ? gemm_lerp(l0, s10[h][j], l1, s11[h][j]) : s10[h][j];
+        }
+}
+
 // Epilogue shared by the block shapes.  32x32 C/D layout: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5):
 // for a fixed register group q = r>>2 the lane holds 4 consecutive channels (8q + 4*lhi + 0..3) of one column,
 // i.e. half of a 16-byte K8 unit, lanes l and l+32 complete the unit.  The natural 8-byte accesses are
@@ -141,7 +160,7 @@ __device__ __forceinline__ bool block_map(const BGemmArgs& a, int id, int& mb, i
 // global access is one 16-byte unit per lane (consecutive lanes -> consecutive units).
 // STAGED: `lds` already holds this m-block's 256 bias values (the persistent kernel stages them once per workgroup and
 // must not pass a barrier here: its LDS-DMA of the next tile is in flight).
-template <int EPI, bool STAGED = false, bool F16 = false>
+template <int EPI, bool STAGED = false, bool F16 = false, bool ADD = false>
 __device__ __forceinline__ void bf16_epilogue(const BGemmArgs& a, f32x16 (&acc)[4][2], u32x4* lds, int t, int mb, int wm,
                                               int wn, int b, int n0, int l31, int lhi) {
     float* bias_s = reinterpret_cast<float*>(lds);
@@ -159,8 +178,31 @@ __device__ __forceinline__ void bf16_epilogue(const BGemmArgs& a, f32x16 (&acc)[
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
                 const int n = n0 + wn * 64 + nt * 32 + l31;
+                // the ax WN's conditioning addend: column of this lane -> frames i0, i1 and weights l0, l1, the expressions
+                // of the fp32 GATE epilogue; a ragged tile's columns >= L are computed on column L - 1, not stored
+                [[maybe_unused]] const float *ad0 = nullptr, *ad1 = nullptr;
+                [[maybe_unused]] float l0 = 1.0f, l1 = 0.0f;
+                if constexpr (ADD) {
+                    const int nn = min(n, a.L - 1);
+                    int i0 = nn, i1 = nn;
+                    if (a.addend_frames > 0) {               // uniform
+                        const int F = a.addend_frames;
+                        const float scale = a.L > 1 ? (float)(F - 1) / (float)(a.L - 1) : 0.f;
+                        const float real = scale * (float)nn;
+                        i0 = (int)real;
+                        i1 = i0 + 1 < F ? i0 + 1 : F - 1;
+                        l1 = real - (float)i0;
+                        l0 = 1.0f - l1;
+                    }
+                    const float* ad = a.addend + (size_t)b * a.addend_bstride + a.addend_pad +
+                                      (size_t)(cbase + mt * 32 + 4 * lhi) * a.addend_ld;
+                    ad0 = ad + i0;
+                    ad1 = ad + i1;
+                }
 #pragma unroll
                 for (int qp = 0; qp < 2; ++qp) {
+                    [[maybe_unused]] float add0[2][4], add1[2][4];
+                    if constexpr (ADD) bf16_gate_addend(a, qp, ad0, ad1, a.addend_frames > 0, l0, l1, add0, add1);
                     unsigned int pk[2][2], pl[2][2];         // [group of the pair][dword]: high halves, low halves
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
@@ -169,8 +211,9 @@ __device__ __forceinline__ void bf16_epilogue(const BGemmArgs& a, f32x16 (&acc)[
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const int row = 8 * q + 4 * lhi + j;
-                            const float u0 = acc[mt][nt][4 * q + j] + bias[mt * 32 + row];
-                            const float u1 = acc[mt + 2][nt][4 * q + j] + bias[64 + mt * 32 + row];
+                            float u0 = acc[mt][nt][4 * q + j] + bias[mt * 32 + row];
+                            float u1 = acc[mt + 2][nt][4 * q + j] + bias[64 + mt * 32 + row];
+                            if constexpr (ADD) { u0 += add0[h][j]; u1 += add1[h][j]; }
                             v[j] = fast_gate(u0, u1);
                         }
                         pk[h][0] = pack2<F16>(v[0], v[1]);
@@ -254,7 +297,7 @@ __device__ __forceinline__ void bf16_epilogue(const BGemmArgs& a, f32x16 (&acc)[
 // NW = waves along N: 2 -> 256 threads, block tile 256 x 128; 4 -> 512 threads, block tile 256 x 256 (one
 // workgroup per CU).  The wide tile stages 1/3 fewer bytes per FLOP: at bf16 MFMA rates the CU's vector-memory
 // path (64 B/clk) is the co-bottleneck of the narrow tile (PMC: MFMA busy 44 %, issue-stalled 48 %).
-template <int EPI, int NW, bool F16 = false>
+template <int EPI, int NW, bool F16 = false, bool ADD = false>   // ADD: GATE with the fp32 addend (bf16_gate_addend)
 __global__ __launch_bounds__(128 * NW, 2) void conv_gemm_bf16_kernel(const BGemmArgs a) {
     constexpr int NT = 128 * NW;                            // threads
     constexpr int BN = 64 * NW;
@@ -359,7 +402,7 @@ __global__ __launch_bounds__(128 * NW, 2) void conv_gemm_bf16_kernel(const BGemm
     }
 #undef CTTS_ISSUE_GLDS
 
-    bf16_epilogue<EPI, false, F16>(a, acc, lds, t, mb, wm, wn, b, n0, l31, lhi);
+    bf16_epilogue<EPI, false, F16, ADD>(a, acc, lds, t, mb, wm, wn, b, n0, l31, lhi);
 }
 
 // Skewed ("ping-pong") form of the 256 x 256 block (512 threads = 8 waves, one workgroup per CU, two waves per
@@ -372,7 +415,7 @@ __global__ __launch_bounds__(128 * NW, 2) void conv_gemm_bf16_kernel(const BGemm
 // LDS: NS stages x 32 KiB (NS - 1 chunks of DMA in flight).  Both halves read chunk k inside interval k; the DMA
 // issued in interval k (chunk k+NS-1) rewrites the buffer of chunk k-1, read by both before the closing barrier of
 // interval k-1; a thread passes that barrier only after its own DMAs of chunk k have landed (counted vmcnt).
-template <int EPI, int NS, bool F16 = false>
+template <int EPI, int NS, bool F16 = false, bool ADD = false>
 __global__ __launch_bounds__(512, 2) void conv_gemm_bf16_pp_kernel(const BGemmArgs a) {
     constexpr int NT = 512, BN = 256;
     constexpr int B_UNITS = 4 * BN;
@@ -518,7 +561,7 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_bf16_pp_kernel(const BGemmAr
 #undef CTTS_UNIFORM64
 #undef CTTS_WAIT_VM
     if (wm) __builtin_amdgcn_s_setprio(0);
-    bf16_epilogue<EPI, false, F16>(a, acc, lds, t, mb, wm, wn, b, n0, l31, lhi);
+    bf16_epilogue<EPI, false, F16, ADD>(a, acc, lds, t, mb, wm, wn, b, n0, l31, lhi);
 }
 
 // Persistent form of the skewed 256 x 256 block (round 5).  The per-tile kernel above pays, per workgroup and with nothing
@@ -544,7 +587,7 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_bf16_pp_kernel(const BGemmAr
 // The epilogue's stores are younger than the interval's DMA and only ADD to the outstanding count: the waits stay safe.
 __device__ unsigned long long g_ps_stamps[32];   // DBG: [wave half][{tile cycles, epilogue cycles, 100 MHz ticks of the tile, tiles}]
 
-template <int EPI, int NS, int DBG = 0, bool F16 = false>   // DBG (harness only): 1 = s_memtime stamps of workgroup 100, third tile
+template <int EPI, int NS, int DBG = 0, bool F16 = false, bool ADD = false>   // DBG (harness only): 1 = s_memtime stamps of workgroup 100, third tile
 __global__ __launch_bounds__(512) void conv_gemm_bf16_ps_kernel(const BGemmArgs a) {
     constexpr int NT = 512, BN = 256, MAXC = BGEMM_PP_MAX_CHUNKS;
     constexpr int B_UNITS = 4 * BN;
@@ -716,7 +759,7 @@ __global__ __launch_bounds__(512) void conv_gemm_bf16_ps_kernel(const BGemmArgs 
         /* lane ids laundered: keeps the epilogue's address arithmetic out of the chunk loop's live registers (LICM) */ \
         int l31_ = l31, lhi_ = lhi;                                                                 \
         asm volatile("" : "+v"(l31_), "+v"(lhi_));                                                  \
-        bf16_epilogue<EPI, true, F16>(a, acc, bias_lds, t, mb, wm, wn, gt_done / a.ntiles, (gt_done % a.ntiles) * BN, l31_, lhi_); \
+        bf16_epilogue<EPI, true, F16, ADD>(a, acc, bias_lds, t, mb, wm, wn, gt_done / a.ntiles, (gt_done % a.ntiles) * BN, l31_, lhi_); \
         CTTS_PS_ZERO();                                                                             \
         if ((DBG & 1) && blockIdx.x == 100 && tiles_done == 2 && lane == 0 && wn == 0) {            \
             unsigned long long* o_ = g_ps_stamps + 4 * wm;                                          \

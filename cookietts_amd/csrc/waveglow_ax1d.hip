@@ -20,9 +20,19 @@
 // three elementwise launches = 58 us of the 1.1 ms a notebook-config flow takes at batch 1).
 // `output` starts from the first layer's skip (glow_ax.py:405-410): 0 + r == r exactly, so the SPLIT epilogue's
 // "store on layer 0, accumulate afterwards" is bit-identical.
+//
+// IEEE-half storage form (the ctts_wgax_*_f16 entry points; what the reference's `.half()` asks of this model): the three
+// C-row tensors x, act and the skip sum are IEEE half in the K8-blocked layout of gemm_bf16.h ([B][C/8][ld][8]: one 16-byte
+// unit = 8 channels of one time step), in-layer and res/skip weights are packed as half, their products run on
+// v_mfma_f32_32x32x16_f16 with fp32 accumulation (launch_gemm_bf16, f16 = 1).  Everything that is not a C-row tensor stays
+// fp32: the <= 32 latent rows, `start` / `end` weights, every bias, coupling, mixing, and the conditioning rows, which enter
+// as the fp32 addend of the 16-bit GATE epilogue with the fp32 path's own interpolation arithmetic.  Rounding points (each a
+// round-to-nearest-even to half): the packed weights once; x after `start` and after every x + res; the gated activations;
+// the skip sum after every layer's accumulation.  GTU only: the plan refuses the other thirteen gated units.
 #include <algorithm>
 #include <vector>
 
+#include "gemm_bf16.h"
 #include "gemm_f32.h"
 #include "waveglow_kernels.h"
 
@@ -32,13 +42,16 @@ namespace {
 constexpr size_t ALIGN_F = 64;
 inline size_t align_up(size_t v) { return (v + ALIGN_F - 1) / ALIGN_F * ALIGN_F; }
 constexpr int A_TILE = GEMM_KC * GEMM_BM;
+constexpr int AH_TILE = BGEMM_KC * BGEMM_BM / 2;   // floats of one packed half A stage ([4][256][8] halves)
+static_assert(BGEMM_BM == GEMM_BM, "the half form shares the fp32 form's M-blocks and packed bias");
 constexpr int AX_MAX_GROUP = 32;     // LDS of the mixing kernels: (n*n + n*256 + n) floats <= 37 KB
 
 struct AxFlowDims { int n_rem, n_half, ch_off; };
 
 struct AxPlan {
     ctts_wgax_config c;
-    int C, nch_in, nch_c, mb_in;
+    bool half;                  // IEEE-half storage form: the A entries of `fl` are packed halves (offsets stay in floats)
+    int C, nch_in, nch_c, mb_in;   // K chunks: of GEMM_KC channels, of BGEMM_KC in the half form
     std::vector<AxFlowDims> fd;
     struct Flow {
         size_t start_w, start_b, end_w, end_b, winv;
@@ -50,7 +63,7 @@ struct AxPlan {
     int rs_mb(int layer) const { return (rs_rows(layer) + GEMM_BM - 1) / GEMM_BM; }
 };
 
-int make_ax_plan(const ctts_wgax_config* cfg, AxPlan& p) {
+int make_ax_plan(const ctts_wgax_config* cfg, AxPlan& p, bool half = false) {
     CTTS_CHECK_ARG(cfg != nullptr, "wgax: config is NULL");
     p.c = *cfg;
     const auto& c = p.c;
@@ -67,8 +80,18 @@ int make_ax_plan(const ctts_wgax_config* cfg, AxPlan& p) {
     CTTS_CHECK_ARG(c.mixing != CTTS_MIX_PERMUTE || c.n_flows % 2 == 0, "wgax: PermuteHeight requires even n_flows");
     CTTS_CHECK_ARG(c.gated_unit >= 0 && c.gated_unit < GATE_KINDS && (c.merge_res_skip == 0 || c.merge_res_skip == 1),
                    "wgax: gated_unit=%d merge_res_skip=%d", c.gated_unit, c.merge_res_skip);
+    p.half = half;
+    if (half) {
+        // the 16-bit GATE epilogue is tanh * sigmoid and has no run-time unit switch; of the other thirteen units the four
+        // sin(16 x) ones leave the 1e-3 waveform bound with half activations, the rest no known checkpoint uses
+        CTTS_CHECK_ARG(c.gated_unit == GATE_GTU, "wgax f16: gated_unit=%d - half storage is built for GTU (tanh * sigmoid) only",
+                       c.gated_unit);
+        CTTS_CHECK_ARG(c.kernel_size * (c.n_channels / BGEMM_KC) <= BGEMM_MAX_CHUNKS,
+                       "wgax f16: kernel_size=%d x n_channels=%d is %d K chunks, the 16-bit GEMM takes %d", c.kernel_size,
+                       c.n_channels, c.kernel_size * (c.n_channels / BGEMM_KC), BGEMM_MAX_CHUNKS);
+    }
     p.C = c.n_channels;
-    p.nch_c = p.C / GEMM_KC;
+    p.nch_c = p.C / (half ? BGEMM_KC : GEMM_KC);
     p.nch_in = c.kernel_size * p.nch_c;
     p.mb_in = (2 * p.C + GEMM_BM - 1) / GEMM_BM;
     int n_rem = c.n_group;
@@ -90,9 +113,10 @@ int make_ax_plan(const ctts_wgax_config* cfg, AxPlan& p) {
         f.end_b = take((size_t)2 * d.n_half);
         f.winv = take((size_t)d.n_rem * d.n_rem);
         for (int i = 0; i < c.n_layers; ++i) {
-            f.in_A.push_back(take((size_t)p.mb_in * p.nch_in * A_TILE));
+            const size_t a_tile = half ? AH_TILE : A_TILE;
+            f.in_A.push_back(take((size_t)p.mb_in * p.nch_in * a_tile));
             f.in_b.push_back(take((size_t)p.mb_in * GEMM_BM));
-            f.rs_A.push_back(take((size_t)p.rs_mb(i) * p.nch_c * A_TILE));
+            f.rs_A.push_back(take((size_t)p.rs_mb(i) * p.nch_c * a_tile));
             f.rs_b.push_back(take((size_t)p.rs_mb(i) * GEMM_BM));
         }
     }
@@ -114,16 +138,18 @@ int make_ax_geom(const AxPlan& p, long long samples, AxGeom& g) {
     return CTTS_OK;
 }
 
+// x, act, out: fp32 [B][C][ld], or (half form) K8-blocked halves [B][C/8][ld][8] in half the floats
 struct AxWs { float *audio, *x, *act, *out; size_t total; };
 
 void ax_carve(const AxPlan& p, const AxGeom& g, int batch, float* base, AxWs& w) {
+    const size_t per = p.half ? 2 : 1;                          // elements of a C-row tensor per float
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o = align_up(o + n); return base ? base + r : nullptr; };
     const size_t B = batch;
     w.audio = take(B * p.c.n_group * g.ld);
-    w.x = take(B * p.C * g.ld);
-    w.act = take(B * p.C * g.ld);
-    w.out = take(B * p.C * g.ld);
+    w.x = take(B * p.C * g.ld / per);                           // (ld is a multiple of 32)
+    w.act = take(B * p.C * g.ld / per);
+    w.out = take(B * p.C * g.ld / per);
     w.total = o;
 }
 
@@ -174,6 +200,11 @@ __global__ __launch_bounds__(256) void ax_unsqueeze_kernel(const float* __restri
 //            fma (em:283: F.conv1d with W^-1) - after the coupling when mix_first, before `start` otherwise
 //   start    x[c] = bs[c] + sum_{j < h'} Ws[c][j] * a[ch_off' + j]   (glow_ax.py:376): C rows x (K = h' <= 16) on the same
 //            MFMA, a wave per 32 channels, B fragments from the LDS rows, accumulators initialised with the bias
+// H16 (the half-storage form): `out` is read and `x` written as K8-blocked halves.  A lane's 16 B-fragment values of a
+// 32-channel chunk are two 16-byte units per column (channel groups 4 q + 2 lhi, + 1: k-step ks pairs channels 16 lhi + ks
+// of the two half-waves, and the weight fragment follows) instead of 16 dword loads, converted to fp32; `start` rounds its
+// fp32 tile to half and stores one unit (8 channels of one time step) per lane after the half-wave exchange of the 16-bit
+// GEMM epilogues.  Latent rows, e, coupling, NaN -> 0 and both mixings are the same fp32 code.
 struct AxPerm { int src[AX_MAX_GROUP]; };
 
 struct AxBoundary {
@@ -181,7 +212,7 @@ struct AxBoundary {
     int G, C, L, ld, pad, mixing, ignore_nan;
     // flow k just finished its layers (do_couple)
     int do_couple, ch_off, h, mix_after;
-    const float* out;           // [B][C][ld] skip sum
+    const void* out;            // skip sum: fp32 [B][C][ld]; H16: halves [B][C/8][ld][8]
     const float *end_w, *end_b; // [2h][C], [2h]
     const float* winv;          // [2h][2h] (CONV1X1 and mix_after)
     AxPerm perm;
@@ -190,7 +221,7 @@ struct AxBoundary {
     const float* s_winv;
     AxPerm s_perm;
     const float *start_w, *start_b;   // [C][h'], [C]
-    float* x;                   // [B][C][ld]
+    void* x;                    // same layout as `out`
 };
 
 typedef float axb_f32x16 __attribute__((ext_vector_type(16)));
@@ -231,6 +262,9 @@ __device__ __forceinline__ void axb_mix(float* sa, float* sb, float* sW, int* sP
     for (int i = wave; i < n; i += AXB_WAVES) sa[(off + i) * AXB_COLS + lane] = sb[i * AXB_COLS + lane];
 }
 
+typedef unsigned int axb_u32x4 __attribute__((ext_vector_type(4)));   // one 16-byte K8 unit
+
+template <bool H16>
 __global__ __launch_bounds__(AXB_THREADS) void ax_boundary_kernel(const AxBoundary p) {
     __shared__ float smem[AXB_LDS_FLOATS];
     float* sa = smem;                                   // [G][64]  latent rows of this tile
@@ -260,18 +294,34 @@ __global__ __launch_bounds__(AXB_THREADS) void ax_boundary_kernel(const AxBounda
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-        const float* ob = p.out + (size_t)b * C * p.ld + p.pad;
         const int col0 = min(l0 + l31, p.L - 1), col1 = min(l0 + 32 + l31, p.L - 1);
-        const float* wrow = p.end_w + (size_t)min(l31, n - 1) * C + lhi;
         const float wmask = l31 < n ? 1.f : 0.f;         // rows >= n of the 32-row tile: zero weights
         for (int q = wave; q < C / 32; q += AXB_WAVES) {
             float av[16], b0[16], b1[16];
+            if constexpr (H16) {
+                const axb_u32x4* ob = static_cast<const axb_u32x4*>(p.out) + (size_t)b * (C / 8) * p.ld + p.pad;
+                const axb_u32x4* og = ob + (size_t)(4 * q + 2 * lhi) * p.ld;
+                const axb_u32x4 u00 = og[col0], u01 = og[p.ld + col0], u10 = og[col1], u11 = og[p.ld + col1];
+                const float* wrow = p.end_w + (size_t)min(l31, n - 1) * C + q * 32 + 16 * lhi;
 #pragma unroll
-            for (int ks = 0; ks < 16; ++ks) {
-                av[ks] = wrow[q * 32 + 2 * ks];
-                const float* orow = ob + (size_t)(q * 32 + 2 * ks + lhi) * p.ld;
-                b0[ks] = orow[col0];
-                b1[ks] = orow[col1];
+                for (int ks = 0; ks < 16; ++ks) av[ks] = wrow[ks];
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    b0[2 * d] = f16_to_f32((bf16_t)(u00[d] & 0xffff)); b0[2 * d + 1] = f16_to_f32((bf16_t)(u00[d] >> 16));
+                    b0[8 + 2 * d] = f16_to_f32((bf16_t)(u01[d] & 0xffff)); b0[9 + 2 * d] = f16_to_f32((bf16_t)(u01[d] >> 16));
+                    b1[2 * d] = f16_to_f32((bf16_t)(u10[d] & 0xffff)); b1[2 * d + 1] = f16_to_f32((bf16_t)(u10[d] >> 16));
+                    b1[8 + 2 * d] = f16_to_f32((bf16_t)(u11[d] & 0xffff)); b1[9 + 2 * d] = f16_to_f32((bf16_t)(u11[d] >> 16));
+                }
+            } else {
+                const float* ob = static_cast<const float*>(p.out) + (size_t)b * C * p.ld + p.pad;
+                const float* wrow = p.end_w + (size_t)min(l31, n - 1) * C + lhi;
+#pragma unroll
+                for (int ks = 0; ks < 16; ++ks) {
+                    av[ks] = wrow[q * 32 + 2 * ks];
+                    const float* orow = ob + (size_t)(q * 32 + 2 * ks + lhi) * p.ld;
+                    b0[ks] = orow[col0];
+                    b1[ks] = orow[col1];
+                }
             }
 #pragma unroll
             for (int ks = 0; ks < 16; ++ks) {
@@ -321,7 +371,7 @@ __global__ __launch_bounds__(AXB_THREADS) void ax_boundary_kernel(const AxBounda
         for (int g = first_dirty + wave; g < G; g += AXB_WAVES) ab[(size_t)g * p.ld + l] = sa[g * AXB_COLS + lane];
     if (p.do_start) {
         const int hs = p.s_h;
-        float* xb = p.x + (size_t)b * C * p.ld + p.pad;
+        float* xb = H16 ? nullptr : static_cast<float*>(p.x) + (size_t)b * C * p.ld + p.pad;
         // B fragments of the K = 16 (h' zero-padded) contraction: the same for every 32-channel tile of this wave
         float b0[8], b1[8];
 #pragma unroll
@@ -351,7 +401,25 @@ __global__ __launch_bounds__(AXB_THREADS) void ax_boundary_kernel(const AxBounda
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
                 const int col = l0 + nt * 32 + l31;
-                if (col < p.L) {
+                if constexpr (H16) {
+                    // register group g = r >> 2 holds channels c0 + 8 g + 4 lhi + 0..3 of this column: half a unit.  Groups in
+                    // pairs, one half-wave exchange per dword: lane l then holds unit 2 gp, lane l + 32 unit 2 gp + 1
+                    axb_u32x4* xu = static_cast<axb_u32x4*>(p.x) + (size_t)b * (C / 8) * p.ld + p.pad;
+#pragma unroll
+                    for (int gp = 0; gp < 2; ++gp) {
+                        unsigned int pk[2][2];
+#pragma unroll
+                        for (int hh = 0; hh < 2; ++hh) {
+                            const int r0 = 4 * (2 * gp + hh);
+                            pk[hh][0] = pack_f16x2(acc[nt][r0], acc[nt][r0 + 1]);
+                            pk[hh][1] = pack_f16x2(acc[nt][r0 + 2], acc[nt][r0 + 3]);
+                        }
+                        swap_halves(pk[0][0], pk[1][0]);
+                        swap_halves(pk[0][1], pk[1][1]);
+                        if (col < p.L)
+                            xu[(size_t)(c0 / 8 + 2 * gp + lhi) * p.ld + col] = axb_u32x4{pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
+                    }
+                } else if (col < p.L) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
                         xb[(size_t)(c0 + (r & 3) + 8 * (r >> 2) + 4 * lhi) * p.ld + col] = acc[nt][r];
@@ -381,10 +449,16 @@ size_t ctts_wgax_packed_bytes(const ctts_wgax_config* cfg) {
     return p.total * sizeof(float);
 }
 
-int ctts_wgax_pack_flow(const ctts_wgax_config* cfg, int32_t k, const ctts_wgax_flow_weights* w, void* packed,
-                        void* stream) {
+size_t ctts_wgax_packed_f16_bytes(const ctts_wgax_config* cfg) {
     AxPlan p;
-    int rc = make_ax_plan(cfg, p); if (rc) return rc;
+    if (make_ax_plan(cfg, p, true)) return 0;
+    return p.total * sizeof(float);
+}
+
+static int wgax_pack_flow(const ctts_wgax_config* cfg, int32_t k, const ctts_wgax_flow_weights* w, void* packed,
+                          void* stream, bool half) {
+    AxPlan p;
+    int rc = make_ax_plan(cfg, p, half); if (rc) return rc;
     CTTS_CHECK_ARG(k >= 0 && k < p.c.n_flows && w && packed, "wgax pack_flow: bad argument (flow %d)", k);
     hipStream_t s = as_stream(stream);
     float* blob = static_cast<float*>(packed);
@@ -406,26 +480,51 @@ int ctts_wgax_pack_flow(const ctts_wgax_config* cfg, int32_t k, const ctts_wgax_
     if ((rc = d2d(f.end_b, w->end_b, (size_t)2 * d.n_half))) return rc;
     for (int i = 0; i < p.c.n_layers; ++i) {
         CTTS_CHECK_ARG(w->in_w[i] && w->in_b[i] && w->rs_w[i] && w->rs_b[i], "wgax pack_flow: NULL layer %d weights", i);
-        // K = [per 16-channel slab: tap 0 .. tap ks-1];  in_w[i] is [2C][C][ks]
-        for (int t = 0; t < ks; ++t)
-            if ((rc = launch_pack_a(blob + f.in_A[i], w->in_w[i] + t, GEMM_BM, p.mb_in, p.nch_in, 0, C, GEMM_EPI_GATE, C, 2 * C,
-                                    0, (long long)C * ks, ks, s, ks, t))) return rc;
+        // K = [per 16-channel slab (32-channel in the half form): tap 0 .. tap ks-1];  in_w[i] is [2C][C][ks]
+        for (int t = 0; t < ks; ++t) {
+            if (half) rc = launch_pack_a_bf16(reinterpret_cast<bf16_t*>(blob + f.in_A[i]), w->in_w[i] + t, p.mb_in, p.nch_in, 0, C,
+                                              BGEMM_EPI_GATE, C, 2 * C, 0, (long long)C * ks, ks, s, ks, t, 0, 1);
+            else rc = launch_pack_a(blob + f.in_A[i], w->in_w[i] + t, GEMM_BM, p.mb_in, p.nch_in, 0, C, GEMM_EPI_GATE, C, 2 * C,
+                                    0, (long long)C * ks, ks, s, ks, t);
+            if (rc) return rc;
+        }
         if ((rc = launch_pack_bias(blob + f.in_b[i], GEMM_BM, p.mb_in, w->in_b[i], 0, nullptr, 0, GEMM_EPI_GATE, C, 2 * C,
                                    s))) return rc;
         const int rows = p.rs_rows(i);
-        if ((rc = launch_pack_a(blob + f.rs_A[i], w->rs_w[i], GEMM_BM, p.rs_mb(i), p.nch_c, 0, C, GEMM_EPI_SPLIT, C, rows, 0,
-                                C, 1, s))) return rc;
+        if (half) rc = launch_pack_a_bf16(reinterpret_cast<bf16_t*>(blob + f.rs_A[i]), w->rs_w[i], p.rs_mb(i), p.nch_c, 0, C,
+                                          BGEMM_EPI_SPLIT, C, rows, 0, C, 1, s, 1, 0, 0, 1);
+        else rc = launch_pack_a(blob + f.rs_A[i], w->rs_w[i], GEMM_BM, p.rs_mb(i), p.nch_c, 0, C, GEMM_EPI_SPLIT, C, rows, 0,
+                                C, 1, s);
+        if (rc) return rc;
         if ((rc = launch_pack_bias(blob + f.rs_b[i], GEMM_BM, p.rs_mb(i), w->rs_b[i], 0, nullptr, 0, GEMM_EPI_SPLIT, C,
                                    rows, s))) return rc;
     }
     return CTTS_OK;
 }
 
-size_t ctts_wgax_workspace_bytes(const ctts_wgax_config* cfg, int32_t batch, int64_t samples) {
+int ctts_wgax_pack_flow(const ctts_wgax_config* cfg, int32_t k, const ctts_wgax_flow_weights* w, void* packed,
+                        void* stream) {
+    return wgax_pack_flow(cfg, k, w, packed, stream, false);
+}
+
+int ctts_wgax_pack_flow_f16(const ctts_wgax_config* cfg, int32_t k, const ctts_wgax_flow_weights* w, void* packed,
+                            void* stream) {
+    return wgax_pack_flow(cfg, k, w, packed, stream, true);
+}
+
+static size_t wgax_workspace_bytes(const ctts_wgax_config* cfg, int32_t batch, int64_t samples, bool half) {
     AxPlan p; AxGeom g; AxWs w;
-    if (make_ax_plan(cfg, p) || make_ax_geom(p, samples, g) || batch < 1) return 0;
+    if (make_ax_plan(cfg, p, half) || make_ax_geom(p, samples, g) || batch < 1) return 0;
     ax_carve(p, g, batch, nullptr, w);
     return w.total * sizeof(float);
+}
+
+size_t ctts_wgax_workspace_bytes(const ctts_wgax_config* cfg, int32_t batch, int64_t samples) {
+    return wgax_workspace_bytes(cfg, batch, samples, false);
+}
+
+size_t ctts_wgax_workspace_f16_bytes(const ctts_wgax_config* cfg, int32_t batch, int64_t samples) {
+    return wgax_workspace_bytes(cfg, batch, samples, true);
 }
 
 int ctts_replicate_halo_f32(float* x, int32_t batch, int32_t C, int32_t T, int32_t ld, int32_t pad, int32_t halo,
@@ -439,11 +538,11 @@ int ctts_replicate_halo_f32(float* x, int32_t batch, int32_t C, int32_t T, int32
     return CTTS_OK;
 }
 
-int ctts_wgax_inverse_f32(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,
-                          int32_t cond_ld, int32_t cond_pad, int32_t frames, float* audio, int32_t batch,
-                          int64_t samples, void* workspace, size_t workspace_bytes, void* stream) {
+static int wgax_inverse(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,
+                        int32_t cond_ld, int32_t cond_pad, int32_t frames, float* audio, int32_t batch,
+                        int64_t samples, void* workspace, size_t workspace_bytes, void* stream, bool half) {
     AxPlan p; AxGeom g; AxWs w;
-    int rc = make_ax_plan(cfg, p); if (rc) return rc;
+    int rc = make_ax_plan(cfg, p, half); if (rc) return rc;
     rc = make_ax_geom(p, samples, g); if (rc) return rc;
     CTTS_CHECK_ARG(packed && z && cond && audio && workspace && batch >= 1 && frames >= 1 && cond_ld >= frames + cond_pad,
                    "wgax inverse: bad argument");
@@ -487,7 +586,9 @@ int ctts_wgax_inverse_f32(const ctts_wgax_config* cfg, const void* packed, const
             q.s_winv = blob + f.winv; q.start_w = blob + f.start_w; q.start_b = blob + f.start_b; q.x = w.x;
             if (p.c.mixing == CTTS_MIX_PERMUTE) ax_permutation(next, d.n_rem, q.s_perm.src);
         }
-        hipLaunchKernelGGL(ax_boundary_kernel, dim3((L + AXB_COLS - 1) / AXB_COLS, batch), dim3(AXB_THREADS), 0, s, q);
+        const dim3 bgrid((L + AXB_COLS - 1) / AXB_COLS, batch);
+        if (half) hipLaunchKernelGGL(ax_boundary_kernel<true>, bgrid, dim3(AXB_THREADS), 0, s, q);
+        else hipLaunchKernelGGL(ax_boundary_kernel<false>, bgrid, dim3(AXB_THREADS), 0, s, q);
         CTTS_CHECK_LAUNCH("ax_boundary");
         return CTTS_OK;
     };
@@ -497,6 +598,39 @@ int ctts_wgax_inverse_f32(const ctts_wgax_config* cfg, const void* packed, const
         const float* fr = cond + (size_t)k * batch * 2 * C * nl * cond_ld;
         for (int i = 0; i < nl; ++i) {
             const int dil = p.c.dilation_w[i] > 0 ? p.c.dilation_w[i] : 1 << i;
+            // merge_res_skip: every layer's C rows are skip rows and x stays the `start` output (glow_ax.py:401-416)
+            const bool last = i == nl - 1 || p.c.merge_res_skip;
+            if (half) {
+                // the same two launches on half tensors: conditioning as the fp32 addend of the 16-bit GATE epilogue, x += res
+                // as a 16-bit read-modify-write, the skip sum stored by layer 0 and accumulated (one rounding per layer) after it
+                bf16_t *xh = reinterpret_cast<bf16_t*>(w.x), *acth = reinterpret_cast<bf16_t*>(w.act),
+                       *outh = reinterpret_cast<bf16_t*>(w.out);
+                BGemmArgs a{};
+                a.f16 = 1;
+                a.ld = g.ld; a.pad = g.pad; a.L = L; a.ntiles = g.ntiles; a.batch = batch;
+                a.A = reinterpret_cast<const bf16_t*>(blob + f.in_A[i]); a.bias = blob + f.in_b[i];
+                a.nseg = ks; a.interleave = ks; a.nch_total = p.nch_in; a.MB = p.mb_in;
+                for (int t = 0; t < ks; ++t) a.seg[t] = {xh, cstride, p.nch_c, (t - ks / 2) * dil, 0};
+                a.dst0 = acth; a.dst0_bstride = cstride;
+                a.M = 2 * C; a.pairC = C;
+                a.addend = fr + (size_t)i * 2 * C * cond_ld;
+                a.addend_bstride = (long long)2 * C * nl * cond_ld;
+                a.addend_ld = cond_ld; a.addend_pad = cond_pad;
+                a.addend_frames = frames == L ? 0 : frames;
+                if ((rc = launch_gemm_bf16(BGEMM_EPI_GATE, a, s))) return rc;
+                BGemmArgs r{};
+                r.f16 = 1;
+                r.ld = g.ld; r.pad = g.pad; r.L = L; r.ntiles = g.ntiles; r.batch = batch;
+                r.A = reinterpret_cast<const bf16_t*>(blob + f.rs_A[i]); r.bias = blob + f.rs_b[i];
+                r.nseg = 1; r.nch_total = p.nch_c; r.MB = p.rs_mb(i);
+                r.seg[0] = {acth, cstride, p.nch_c, 0, 0};
+                r.M = p.rs_rows(i);
+                r.dst0 = xh; r.dst0_bstride = cstride; r.acc0 = 1;
+                r.dst1 = outh; r.dst1_bstride = cstride; r.acc1 = i > 0 ? 1 : 0;
+                r.split = last ? 0 : C;
+                if ((rc = launch_gemm_bf16(BGEMM_EPI_SPLIT, r, s))) return rc;
+                continue;
+            }
             {
                 GemmArgs a = base_args();
                 a.A = blob + f.in_A[i]; a.bias = blob + f.in_b[i];
@@ -514,8 +648,6 @@ int ctts_wgax_inverse_f32(const ctts_wgax_config* cfg, const void* packed, const
                 if ((rc = launch_gemm_f32(GEMM_EPI_GATE, a, s))) return rc;
             }
             {
-                // merge_res_skip: every layer's C rows are skip rows and x stays the `start` output (glow_ax.py:401-416)
-                const bool last = i == nl - 1 || p.c.merge_res_skip;
                 GemmArgs a = base_args();
                 a.A = blob + f.rs_A[i]; a.bias = blob + f.rs_b[i];
                 a.nseg = 1; a.nch_total = p.nch_c; a.MB = p.rs_mb(i);
@@ -532,6 +664,20 @@ int ctts_wgax_inverse_f32(const ctts_wgax_config* cfg, const void* packed, const
     hipLaunchKernelGGL(ax_unsqueeze_kernel, lgrid, dim3(256), 0, s, w.audio, audio, G, L, g.ld, g.pad);
     CTTS_CHECK_LAUNCH("ax_unsqueeze");
     return CTTS_OK;
+}
+
+int ctts_wgax_inverse_f32(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,
+                          int32_t cond_ld, int32_t cond_pad, int32_t frames, float* audio, int32_t batch,
+                          int64_t samples, void* workspace, size_t workspace_bytes, void* stream) {
+    return wgax_inverse(cfg, packed, z, cond, cond_ld, cond_pad, frames, audio, batch, samples, workspace, workspace_bytes,
+                        stream, false);
+}
+
+int ctts_wgax_inverse_f16(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,
+                          int32_t cond_ld, int32_t cond_pad, int32_t frames, float* audio, int32_t batch,
+                          int64_t samples, void* workspace, size_t workspace_bytes, void* stream) {
+    return wgax_inverse(cfg, packed, z, cond, cond_ld, cond_pad, frames, audio, batch, samples, workspace, workspace_bytes,
+                        stream, true);
 }
 
 }  // extern "C"

@@ -130,17 +130,22 @@ class WaveGlowVocoder(torch.nn.Module):
         """``load_hifigan`` calls ``vocoder.half()`` (text2speech.py:261): the reference's request for its reduced-precision mode.
         The parameters - and hence the dtype the server casts its mels to - stay fp32 masters in every case.
 
-        * glow.py model: the WN stacks run on IEEE-half storage and fp16 MFMA with fp32 accumulation
-          (``set_compute_dtype(torch.float16)``, the reference's own half mode: inside the 1e-3 waveform bound).
-        * ax model (what cookietts' own trainer writes: WaveFlow, 1-D ax WaveGlow): every conv-GEMM takes its products on the
-          bf16 matrix pipe as hi + lo splits with fp32 accumulation (``set_f32_gemm_mode("bf16x3")``: three bf16 products per
-          MAC, tensors stay fp32) - 1.3-2x the fp32 MFMA rate where a launch is arithmetic-bound (the notebook's 1-D WaveGlow:
-          124 -> 186x real time at batch 1, 146 -> 291x at 8; WaveFlow config 4 at batch 8: 163 -> 110 ms), <= 7e-6 RMS
-          from the fp32 reference.  Half STORAGE is not built for the ax core: its batch-1 launches are latency-bound
-          (64-256 channels), where narrower tensors buy nothing.
+        * IEEE-half storage (``set_compute_dtype(torch.float16)``, the reference's own half mode): a glow.py model, and a
+          1-D ax WaveGlow (``waveflow=False``, what cookietts' own trainer writes and its inference notebook times) with the
+          GTU unit.  The WN stacks' activations live as IEEE half, their products run on the f16 matrix pipe with fp32
+          accumulation; latent rows, couplings, mixing and the conditioning side stay fp32.  3e-4 (glow.py) / 5e-4 (ax
+          notebook model) RMS from the fp32 reference, inside the 1e-3 waveform bound.
+        * split bf16 (``set_f32_gemm_mode("bf16x3")``: three bf16 products per MAC with fp32 accumulation, tensors stay fp32,
+          <= 7e-6 RMS from the fp32 reference, 1.3-2x the fp32 MFMA rate where a launch is arithmetic-bound): every other ax
+          model.  WaveFlow (``waveflow=True``) by decision - its <= 128-channel row queue is latency-bound, narrower tensors
+          buy nothing there; a 1-D model with another gated unit, or one whose in-layer K exceeds the 16-bit GEMM's chunk
+          table, because half storage is not built for it (``set_compute_dtype`` says which).
         """
         if self.is_ax:
-            self.waveglow.set_f32_gemm_mode("bf16x3")
+            try:
+                self.waveglow.set_compute_dtype(torch.float16)
+            except NotImplementedError:
+                self.waveglow.set_f32_gemm_mode("bf16x3")
         else:
             self.waveglow.set_compute_dtype(torch.float16)
         return self

@@ -7,7 +7,8 @@ Host-side mirror of ``/root/reference/CookieTTS/_4_mtw/waveglow/efficient_model_
 * ``waveflow=True``: ``WaveFlowCoupling`` + ``WN_2d`` (efficient_modules.py:19-65, glow_ax.py:421-635) ->
   ``ctts_waveflow_inverse_f32`` / ``ctts_waveflow_inverse_cond_f32``;
 * ``waveflow=False``: ``AffineCouplingBlock`` + the 1-D ``WN`` (efficient_modules.py:68-105, glow_ax.py:245-418) ->
-  ``ctts_wgax_inverse_f32``;
+  ``ctts_wgax_inverse_f32``, or ``ctts_wgax_inverse_f16`` (IEEE-half WN activations, f16 matrix pipe, GTU only) after
+  ``set_compute_dtype(torch.float16)``;
 * on both: ``PermuteHeight`` or ``InvertibleConv1x1`` mixing in either ``mix_first`` order, early outputs, all
   fourteen gated units, ``merge_res_skip`` / ``res_skip=False``, per-layer dilations, speaker embeddings at model and
   WN level, the model-level conditioning stack (plain / residual / 1x1-conv residual, rezero), multi-layer WN
@@ -454,6 +455,7 @@ class WaveGlow(nn.Module):
         self._packed = None
         self._ws = {}
         self._f32_gemm_mode = None
+        self._compute_dtype = torch.float32
         _cache.hook_invalidate(self)
 
     # ------------------------------------------------------------------ plumbing ----
@@ -479,6 +481,37 @@ class WaveGlow(nn.Module):
         _lib.model_gemm_mode(mode)
         self._f32_gemm_mode = mode
         self._invalidate()            # the conditioning operators carry the mode in their packed descriptors
+        return self
+
+    def set_compute_dtype(self, dtype):
+        """Storage and product format of the 1-D core's (``waveflow=False``) WN stacks: ``torch.float32`` (default) or
+        ``torch.float16`` - the reference's ``.half()``: x, the gated activations and the skip sum live as IEEE half in
+        the K8-blocked layout, in-layer and res/skip products run on the f16 matrix pipe with fp32 accumulation
+        (``ctts_wgax_inverse_f16``).  The latent rows, the coupling, the mixing matrices, ``start`` / ``end``, every
+        bias and the whole conditioning side stay fp32, and so do the parameters (fp32 masters); switching back to
+        ``torch.float32`` restores the fp32 path bit for bit.
+
+        ``NotImplementedError`` - here, not at the first ``infer`` - for what half storage is not built for:
+        ``waveflow=True`` (the 2-D core's <= 128-channel row queue is latency-bound: narrower tensors buy nothing there,
+        ``set_f32_gemm_mode("bf16x3")`` is its reduced-precision mode), a gated unit other than GTU (the 16-bit gate
+        epilogue is tanh * sigmoid only; the sin(16 x) units would leave the 1e-3 waveform bound), or a plan the library
+        refuses (kernel_size * n_channels / 32 beyond the 16-bit GEMM's chunk table)."""
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"compute dtype must be torch.float32 or torch.float16, not {dtype!r}")
+        if dtype == torch.float16:
+            if self.waveflow:
+                raise NotImplementedError("half storage is not built for waveflow=True (latency-bound row queue); "
+                                          "use set_f32_gemm_mode('bf16x3')")
+            unit = str(self.WN_config.get('gated_unit', 'GTU')).upper()
+            if unit != 'GTU':
+                raise NotImplementedError(f"half storage is built for gated_unit='GTU' only, this model has {unit!r}")
+            lib = _lib.lib()
+            cfg = self.c_config_1d()
+            if lib.ctts_wgax_packed_f16_bytes(C.byref(cfg)) == 0:
+                raise NotImplementedError("half storage refused by the library: " + lib.ctts_last_error().decode())
+        if dtype != self._compute_dtype:
+            self._compute_dtype = dtype
+            self._invalidate()        # the packed blob and the workspaces are per format
         return self
 
     def c_config_1d(self):
@@ -546,7 +579,9 @@ class WaveGlow(nn.Module):
             nbytes = lib.ctts_waveflow_packed_bytes(C.byref(cfg))
         else:
             cfg = self.c_config_1d()
-            nbytes = lib.ctts_wgax_packed_bytes(C.byref(cfg))
+            half = self._compute_dtype == torch.float16
+            nbytes = (lib.ctts_wgax_packed_f16_bytes if half else lib.ctts_wgax_packed_bytes)(C.byref(cfg))
+            pack_flow = lib.ctts_wgax_pack_flow_f16 if half else lib.ctts_wgax_pack_flow
         if nbytes == 0:
             raise _lib.HipLibraryError("unsupported ax-core config: " + lib.ctts_last_error().decode())
         sep = self.waveflow and isinstance(self.WN[0].WN.in_layers[0], nn.ModuleList)
@@ -590,8 +625,7 @@ class WaveGlow(nn.Module):
                         self.convinv[k].W_inverse = W_inverse[..., None]
                         keep.append(W_inverse)
                         fw.w_inverse = W_inverse.data_ptr()
-                    _lib.check(lib.ctts_wgax_pack_flow(C.byref(cfg), k, C.byref(fw), _lib.ptr(blob), stream),
-                               f"ctts_wgax_pack_flow({k})")
+                    _lib.check(pack_flow(C.byref(cfg), k, C.byref(fw), _lib.ptr(blob), stream), f"ctts_wgax_pack_flow({k})")
                     continue
                 fw = _lib.WaveFlowFlowWeights()
                 fw.start_w = self._dense(wn.start, stream, keep).data_ptr()
@@ -848,7 +882,8 @@ class WaveGlow(nn.Module):
                            "WaveFlow.inverse (an earlier call on a workspace that is being replaced)")
 
     def _inverse_1d(self, z, cond, speaker_ids, return_CPU):
-        """waveflow=False: efficient_model_ax.py:279-357 with AffineCouplingBlock + 1-D WN (ctts_wgax_inverse_f32)."""
+        """waveflow=False: efficient_model_ax.py:279-357 with AffineCouplingBlock + 1-D WN (ctts_wgax_inverse_f32, or
+        ctts_wgax_inverse_f16 after ``set_compute_dtype(torch.float16)``)."""
         device = cond.device
         blob, ops = self._ensure_packed(device)
         lib = _lib.lib()
@@ -858,10 +893,13 @@ class WaveGlow(nn.Module):
         B, T = zz.shape
         assert mel.shape[0] == B and mel.shape[1] == self.n_mel_channels * (2 if self.has_logvar_channels else 1)
         assert T % self.n_group == 0, "z length is not a multiple of n_group"
-        key = (device, B, T)
+        half = self._compute_dtype == torch.float16
+        inverse_fn, name = (lib.ctts_wgax_inverse_f16, "ctts_wgax_inverse_f16") if half else \
+            (lib.ctts_wgax_inverse_f32, "ctts_wgax_inverse_f32")
+        key = (device, B, T, self._compute_dtype)
         ws = self._ws.get(key)
         if ws is None:
-            nbytes = lib.ctts_wgax_workspace_bytes(C.byref(cfg), B, T)
+            nbytes = (lib.ctts_wgax_workspace_f16_bytes if half else lib.ctts_wgax_workspace_bytes)(C.byref(cfg), B, T)
             if nbytes == 0:
                 raise _lib.HipLibraryError("ax WaveGlow workspace query failed: " + lib.ctts_last_error().decode())
             self._ws = {}
@@ -870,9 +908,8 @@ class WaveGlow(nn.Module):
         with torch.cuda.device(device):
             stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             frames, ld, n_cond = self._cond_frames(ops, mel, speaker_ids, stream, out_steps=T // self.n_group)
-            _lib.check(lib.ctts_wgax_inverse_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(zz), _lib.ptr(frames), ld, PAD,
-                                                 n_cond, _lib.ptr(audio), B, T, _lib.ptr(ws), ws.numel() * 4,
-                                                 stream), "ctts_wgax_inverse_f32")
+            _lib.check(inverse_fn(C.byref(cfg), _lib.ptr(blob), _lib.ptr(zz), _lib.ptr(frames), ld, PAD, n_cond,
+                                  _lib.ptr(audio), B, T, _lib.ptr(ws), ws.numel() * 4, stream), name)
             if self.vol_scaling:
                 _lib.check(lib.ctts_vol_unscale_f32(_lib.ptr(audio), audio.numel(), stream), "ctts_vol_unscale_f32")
             if self.preempthasis:

@@ -438,6 +438,18 @@ size_t ctts_wgax_workspace_bytes(const ctts_wgax_config* cfg, int32_t batch, int
 int ctts_wgax_inverse_f32(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,
                           int32_t cond_ld, int32_t cond_pad, int32_t frames, float* audio, int32_t batch,
                           int64_t samples, void* workspace, size_t workspace_bytes, void* stream);
+/* IEEE-half storage form of the same model (what the reference's `.half()` asks for): the C-row tensors x, act and the skip
+ * sum live as IEEE half in the K8-blocked layout, in-layer and res/skip products run on the f16 matrix pipe with fp32
+ * accumulation; latent rows, start / end weights, biases, coupling, mixing and `cond` stay fp32.  Same arguments as the
+ * functions above, its own packed blob and workspace.  gated_unit must be CTTS GTU (0) and kernel_size * n_channels / 32
+ * at most 253: the size queries return 0 (ctts_last_error names the reason) and the others CTTS_E_ARG otherwise. */
+size_t ctts_wgax_packed_f16_bytes(const ctts_wgax_config* cfg);
+int ctts_wgax_pack_flow_f16(const ctts_wgax_config* cfg, int32_t flow, const ctts_wgax_flow_weights* w,
+                            void* packed, void* stream);
+size_t ctts_wgax_workspace_f16_bytes(const ctts_wgax_config* cfg, int32_t batch, int64_t samples);
+int ctts_wgax_inverse_f16(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,
+                          int32_t cond_ld, int32_t cond_pad, int32_t frames, float* audio, int32_t batch,
+                          int64_t samples, void* workspace, size_t workspace_bytes, void* stream);
 /* padding_mode='replicate' of the conditioning convs (efficient_model_ax.py:90, glow_ax.py:311): fill the `halo`
  * columns either side of the valid range of x [B][C][ld] with the edge values, before a ctts_conv1d_f32 reads them. */
 int ctts_replicate_halo_f32(float* x, int32_t batch, int32_t C, int32_t T, int32_t ld, int32_t pad, int32_t halo,

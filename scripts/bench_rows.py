@@ -32,6 +32,7 @@ def timed(fn, warmup, steps):
 
 
 FP32_MFMA_PEAK_TFLOPS = 157.3
+F16_MFMA_PEAK_TFLOPS = 2500.0      # MI355X_MICROARCH.md: dense bf16 / f16 MFMA (v_mfma_f32_32x32x16_f16 takes the bf16 form's cycles)
 
 
 def gemm_loop_label():
@@ -159,33 +160,82 @@ def row_waveglow_ax_notebook(args):
     Speed Testing.ipynb" cells 2-6: ax core, waveflow=False, 48 flows, n_group 24, 8 x 256 WN, 'permute' mixing,
     speaker embeddings, 3-layer cond stack, batch 1, one 5.8375 s clip at 48 kHz (hop 600 -> 468 mel frames):
     1.27 s = 4.60x real time (eager, fp16), 1.125 s = 5.19x (jit-traced), GPU not stated.  Same model shape, same
-    clip length, batch 1 here; fp32 (the reference ran .half())."""
+    clip length, batch 1 here; fp32, or with ``--dtype f16`` what the reference ran: ``.half()`` = IEEE-half WN activations
+    on the f16 matrix pipe (``set_compute_dtype(torch.float16)``), priced against the nominal f16 MFMA peak."""
+    m, cfg = _ax_notebook_model()
+    _mode(m, args)
+    f16 = getattr(args, "dtype", "f32") == "f16"
+    if f16:
+        m.set_compute_dtype(torch.float16)
+    rows = []
+    for B in _batches(args, (1, 8)):
+        mel, ids = _ax_notebook_input(cfg, B)
+        dt = timed(lambda: m.infer(mel, speaker_ids=ids, sigma=1.0, return_CPU=False), args.warmup, args.steps)
+        rows.append(_ax_notebook_row(cfg, B, dt, "f16" if f16 else "f32"))
+    return rows
+
+
+def _ax_notebook_model():
     from cookietts_amd.waveglow_ax import WaveGlow
     cfg = synthetic.WAVEGLOW_AX_CONFIGS["notebook"]
     m = WaveGlow(**cfg)
     m.load_state_dict(synthetic.to_torch(synthetic.waveglow_ax_state_dict(cfg, seed=1234)))
-    m = m.cuda().eval()
-    _mode(m, args)
+    return m.cuda().eval(), cfg
+
+
+AX_NOTEBOOK_FRAMES = 468                                          # -> (F - 1) * 600 = 280 200 samples = 5.8375 s
+
+
+def _ax_notebook_input(cfg, B):
+    mel = torch.from_numpy(synthetic.synthetic_mel(B, AX_NOTEBOOK_FRAMES, cfg["n_mel_channels"])).cuda()
+    return mel, torch.zeros(B, dtype=torch.int64).cuda()
+
+
+def _ax_notebook_row(cfg, B, dt, dtype):
+    F = AX_NOTEBOOK_FRAMES
+    peak = F16_MFMA_PEAK_TFLOPS if dtype == "f16" else FP32_MFMA_PEAK_TFLOPS
+    samples = B * (F - 1) * cfg["hop_length"]                 # infer() pads one frame and trims one hop
+    wn = cfg["WN_config"]
+    C, nl = wn["n_channels"], wn["n_layers"]
+    flop = 2.0 * cfg["n_flows"] * nl * (3 * C * 2 * C + 2 * C * C) * (samples / cfg["n_group"])   # in + res/skip GEMMs
+    return {"row": "W5/notebook", "metric": "real-time factor (48 kHz), ax WaveGlow waveflow=False, 48 flows x 8 x 256, "
+                                                "n_group 24, 160x468 mel (5.84 s clip)",
+                "value": samples / dt / 48000.0, "unit": "x real time (48 kHz)", "batch": B, "ms_per_call": dt * 1e3,
+                "samples_per_s": samples / dt, "rtf_22k_equiv": samples / dt / 48000.0 * 48 / 22, "dtype": dtype,
+                "reference_published": {"eager_fp16_rtf_48k": 4.5977, "jit_fp16_rtf_48k": 5.1905, "batch": 1,
+                                        "hardware": "not stated", "source": "BASELINE.md section 1"},
+                "vs_reference_eager": (samples / dt / 48000.0) / 4.5977 if B == 1 else None,
+                "roofline": {"kernel": "ax 1-D WN in-layer + res/skip conv-GEMMs", "bound": "mfma", "achieved": flop / dt / 1e12,
+                             "peak": peak, "unit": "TFLOP/s", "frac": flop / dt / 1e12 / peak, "traffic": None}}
+
+
+def row_waveglow_ax_notebook_ab(args):
+    """The notebook row's three arms - fp32 MFMA, split bf16 (``bf16x3``), IEEE-half storage (``f16``) - in ONE process: one
+    model per arm, the arms alternated ``--reps`` times after a warm-up of each, one line per (arm, batch) with every
+    repetition's time, the median and the spread.  Compare arms of the same run only."""
+    arms = []
+    for name in ("f32", "bf16x3", "f16"):
+        m, cfg = _ax_notebook_model()
+        if name == "bf16x3":
+            m.set_f32_gemm_mode("bf16x3")
+        if name == "f16":
+            m.set_compute_dtype(torch.float16)
+        arms.append((name, m))
     rows = []
     for B in _batches(args, (1, 8)):
-        F = 468                                                   # -> (F - 1) * 600 = 280 200 samples = 5.8375 s
-        mel = torch.from_numpy(synthetic.synthetic_mel(B, F, cfg["n_mel_channels"])).cuda()
-        ids = torch.zeros(B, dtype=torch.int64).cuda()
-        dt = timed(lambda: m.infer(mel, speaker_ids=ids, sigma=1.0, return_CPU=False), args.warmup, args.steps)
-        samples = B * (F - 1) * cfg["hop_length"]                 # infer() pads one frame and trims one hop
-        wn = cfg["WN_config"]
-        C, nl = wn["n_channels"], wn["n_layers"]
-        flop = 2.0 * cfg["n_flows"] * nl * (3 * C * 2 * C + 2 * C * C) * (samples / cfg["n_group"])   # in + res/skip GEMMs
-        rows.append({"row": "W5/notebook", "metric": "real-time factor (48 kHz), ax WaveGlow waveflow=False, 48 flows x 8 x 256, "
-                                                     "n_group 24, 160x468 mel (5.84 s clip)",
-                     "value": samples / dt / 48000.0, "unit": "x real time (48 kHz)", "batch": B, "ms_per_call": dt * 1e3,
-                     "samples_per_s": samples / dt, "rtf_22k_equiv": samples / dt / 48000.0 * 48 / 22, "dtype": "f32",
-                     "reference_published": {"eager_fp16_rtf_48k": 4.5977, "jit_fp16_rtf_48k": 5.1905, "batch": 1,
-                                             "hardware": "not stated", "source": "BASELINE.md section 1"},
-                     "vs_reference_eager": (samples / dt / 48000.0) / 4.5977 if B == 1 else None,
-                     "roofline": {"kernel": "ax 1-D WN in-layer + res/skip conv-GEMMs", "bound": "mfma", "achieved": flop / dt / 1e12,
-                                  "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": flop / dt / 1e12 / FP32_MFMA_PEAK_TFLOPS,
-                                  "traffic": None}})
+        mel, ids = _ax_notebook_input(cfg, B)
+        times = {name: [] for name, _ in arms}
+        for name, m in arms:
+            timed(lambda: m.infer(mel, speaker_ids=ids, sigma=1.0, return_CPU=False), args.warmup, 1)
+        for _ in range(getattr(args, "reps", 5)):
+            for name, m in arms:
+                times[name].append(timed(lambda: m.infer(mel, speaker_ids=ids, sigma=1.0, return_CPU=False), 0, args.steps))
+        for name, _ in arms:
+            t = sorted(times[name])
+            row = _ax_notebook_row(cfg, B, t[len(t) // 2], "f16" if name == "f16" else "f32")
+            row.update({"arm": name, "reps_ms": [x * 1e3 for x in times[name]], "ms_min": t[0] * 1e3, "ms_max": t[-1] * 1e3,
+                        "spread_frac": (t[-1] - t[0]) / t[len(t) // 2]})
+            rows.append(row)
     return rows
 
 
@@ -306,12 +356,15 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--gemm-mode", default="f32", choices=["f32", "bf16x3", "bf16x6"],
                     help="main loop of the rows' fp32 conv-GEMMs, set on each model (model.set_f32_gemm_mode)")
+    ap.add_argument("--dtype", default="f32", choices=["f32", "f16"],
+                    help="waveglow_ax: f16 = IEEE-half storage of the WN stacks (model.set_compute_dtype(torch.float16))")
+    ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab: repetitions of every arm (alternated)")
     ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts) to these batch sizes (PMC passes)")
     args = ap.parse_args()
     fns = {"waveflow": row_waveflow, "waveflow_table": row_waveflow_table, "waveflow_author": row_waveflow_author, "tacotron": row_tacotron, "stft": row_stft,
-           "waveglow_ax": row_waveglow_ax_notebook, "waveglow_ax_untts": row_waveglow_ax_untts}
+           "waveglow_ax": row_waveglow_ax_notebook, "waveglow_ax_ab": row_waveglow_ax_notebook_ab, "waveglow_ax_untts": row_waveglow_ax_untts}
     for r in args.rows.split(","):
         out = fns[r](args)
         for line in (out if isinstance(out, list) else [out]):
-            line["f32_gemm_mode"] = args.gemm_mode    # set on every model of the row (model.set_f32_gemm_mode)
+            line["f32_gemm_mode"] = line.get("arm") if line.get("arm") in ("f32", "bf16x3") else args.gemm_mode    # set on every model of the row (model.set_f32_gemm_mode)
             print(json.dumps(line), flush=True)
