@@ -119,6 +119,14 @@ class Conv1dDesc(C.Structure):
                 ("slope", C.c_float), ("f32_gemm_mode", C.c_int32)]
 
 
+class HifiganConfig(C.Structure):
+    """``ctts_hifigan_config``."""
+    MAX_UPS, MAX_KERNELS, MAX_DILATIONS = 8, 4, 3
+    _fields_ = [(n, C.c_int32) for n in ("num_mels", "upsample_initial_channel", "resblock", "n_ups", "n_kernels")] + [
+        ("upsample_rates", C.c_int32 * 8), ("upsample_kernel_sizes", C.c_int32 * 8), ("resblock_kernel_sizes", C.c_int32 * 4),
+        ("resblock_dilation_sizes", (C.c_int32 * 3) * 4)]
+
+
 class TacoMemoryWeights(C.Structure):
     _fields_ = [(n, _FP) for n in ("sylps_w", "sylps_b", "speaker_embedding", "syl_w0", "syl_b0", "syl_w2", "syl_b2",
                                    "syl_res_weight", "tm_gamma", "tm_beta", "tm_mean", "tm_var", "tm_w", "tm_b")]
@@ -224,6 +232,12 @@ SIGNATURES = {
     "ctts_wgax_workspace_f16_bytes": (C.c_size_t, [C.POINTER(WgaxConfig), C.c_int32, C.c_int64]),
     "ctts_wgax_inverse_f16": (C.c_int, [C.POINTER(WgaxConfig), _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP,
                                         C.c_int32, C.c_int64, _FP, C.c_size_t, _FP]),
+    "ctts_hifigan_weight_floats": (C.c_size_t, [C.POINTER(HifiganConfig)]),
+    "ctts_hifigan_packed_bytes": (C.c_size_t, [C.POINTER(HifiganConfig)]),
+    "ctts_hifigan_pack_f32": (C.c_int, [C.POINTER(HifiganConfig), _FP, C.c_size_t, _FP, _FP]),
+    "ctts_hifigan_workspace_bytes": (C.c_size_t, [C.POINTER(HifiganConfig), C.c_int32, C.c_int32]),
+    "ctts_hifigan_forward_f32": (C.c_int, [C.POINTER(HifiganConfig), _FP, _FP, C.c_int32, _FP, C.c_int32, C.c_int32, _FP,
+                                           C.c_size_t, _FP]),
     "ctts_replicate_halo_f32": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "ctts_embed_rows_f32": (C.c_int, [_FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, _FP]),

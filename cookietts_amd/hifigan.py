@@ -1,0 +1,242 @@
+"""HiFi-GAN generator on the HIP path: the vocoder the reference's server loads
+(``_5_infer/t2s_server/text2speech.py:175-179, 258-263`` -> ``_4_mtw/hifigan/models.py:14-31, 94-148``).
+
+``Generator(h)`` has the reference's module tree and state-dict keys (``conv_pre.*``, ``ups.i.*``,
+``resblocks.n.convs1.m.*`` / ``convs2.m.*`` (ResBlock1) or ``convs.m.*`` (ResBlock2), ``conv_post.*``; each ``bias``,
+``weight_g``, ``weight_v``), ``remove_weight_norm()`` and ``forward(mel [B, num_mels, T]) -> [B, 1, T * prod(upsample_rates)]``.
+The whole forward is ``ctts_hifigan_forward_f32`` (csrc/hifigan.hip): one fp32 MFMA launch per conv, LeakyReLU / residual
+adds / the resblock mean / tanh inside those launches.  There is no CPU fallback: a CPU tensor raises.
+
+``.half()`` (text2speech.py:262): the parameters become fp16 - so ``next(vocoder.parameters()).dtype`` and the server's
+``mel.to(dtype)`` work unchanged - the products stay fp32 MFMA on the fp16-rounded weights, and the waveform comes back in the
+dtype of the mel it was given.  Options the kernels cannot run exactly raise ``NotImplementedError`` at construction.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import os
+
+import torch
+import torch.nn as nn
+
+from . import _cache, _lib
+from .waveglow_ax import _WNConv
+
+__all__ = ["Generator", "load_model", "AttrDict"]
+
+
+class AttrDict(dict):
+    """``config.json`` with attribute access, as the reference's loader hands it back (hifigan/env.py)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.__dict__ = self
+
+
+def _get(h, name):
+    return h[name] if isinstance(h, dict) else getattr(h, name)
+
+
+def check_config(h):
+    """Raise ``NotImplementedError`` naming the option for what the HIP generator does not run exactly."""
+    def refuse(what):
+        raise NotImplementedError(f"cookietts_amd.HiFiGANGenerator: {what} is not built on the HIP path")
+    resblock = str(_get(h, "resblock"))
+    if resblock not in ("1", "2"):
+        refuse(f"resblock={resblock!r} ('1' or '2')")
+    rates, ksz = list(_get(h, "upsample_rates")), list(_get(h, "upsample_kernel_sizes"))
+    rk, rd = list(_get(h, "resblock_kernel_sizes")), [list(d) for d in _get(h, "resblock_dilation_sizes")]
+    if not 1 <= len(rates) <= _lib.HifiganConfig.MAX_UPS or len(ksz) != len(rates):
+        refuse(f"upsample_rates with {len(rates)} stages / upsample_kernel_sizes with {len(ksz)} (1..{_lib.HifiganConfig.MAX_UPS}, equal)")
+    if not 1 <= len(rk) <= _lib.HifiganConfig.MAX_KERNELS or len(rd) != len(rk):
+        refuse(f"resblock_kernel_sizes with {len(rk)} entries / resblock_dilation_sizes with {len(rd)} "
+               f"(1..{_lib.HifiganConfig.MAX_KERNELS}, equal)")
+    need = 3 if resblock == "1" else 2
+    for j, (k, d) in enumerate(zip(rk, rd)):
+        if k % 2 == 0:
+            refuse(f"resblock_kernel_sizes[{j}]={k} (even: the reference's padding does not keep the length)")
+        if len(d) < need or len(d) > _lib.HifiganConfig.MAX_DILATIONS:
+            refuse(f"resblock_dilation_sizes[{j}]={d} (ResBlock{resblock} reads {need})")
+    for i, (u, k) in enumerate(zip(rates, ksz)):
+        if k < u or (k - u) % 2:
+            refuse(f"upsample_kernel_sizes[{i}]={k} with rate {u} (kernel - rate odd: the output is not rate * T long)")
+
+
+def c_config(h):
+    resblock = str(_get(h, "resblock"))
+    rates, ksz = list(_get(h, "upsample_rates")), list(_get(h, "upsample_kernel_sizes"))
+    rk, rd = list(_get(h, "resblock_kernel_sizes")), [list(d) for d in _get(h, "resblock_dilation_sizes")]
+    cfg = _lib.HifiganConfig(num_mels=int(_get(h, "num_mels")), upsample_initial_channel=int(_get(h, "upsample_initial_channel")),
+                             resblock=int(resblock) if resblock.isdigit() else 0,
+                             n_ups=len(rates), n_kernels=len(rk))
+    for i in range(min(len(rates), cfg.MAX_UPS)):
+        cfg.upsample_rates[i] = int(rates[i])
+        cfg.upsample_kernel_sizes[i] = int(ksz[i]) if i < len(ksz) else 0
+    for j in range(min(len(rk), cfg.MAX_KERNELS)):
+        cfg.resblock_kernel_sizes[j] = int(rk[j])
+        for m in range(min(len(rd[j]) if j < len(rd) else 0, cfg.MAX_DILATIONS)):
+            cfg.resblock_dilation_sizes[j][m] = int(rd[j][m])
+    return cfg
+
+
+class _ResBlock(nn.Module):
+    """Parameter tree of ResBlock1 (models.py:35-73: ``convs1`` / ``convs2``) or ResBlock2 (:75-92: ``convs``)."""
+
+    def __init__(self, kind, channels, kernel_size):
+        super().__init__()
+        def convs(n):
+            return nn.ModuleList([_WNConv((channels, channels, kernel_size)) for _ in range(n)])
+        if kind == "1":
+            self.convs1, self.convs2 = convs(3), convs(3)
+        else:
+            self.convs = convs(2)
+
+    def conv_list(self):
+        return list(self.convs1) + list(self.convs2) if hasattr(self, "convs1") else list(self.convs)
+
+
+class Generator(nn.Module):
+    """``hifigan.models.Generator`` (models.py:94-148) over ``ctts_hifigan_forward_f32``."""
+
+    def __init__(self, h):
+        super().__init__()
+        check_config(h)
+        self.h = h
+        rates, ksz = list(_get(h, "upsample_rates")), list(_get(h, "upsample_kernel_sizes"))
+        rk = list(_get(h, "resblock_kernel_sizes"))
+        C0 = int(_get(h, "upsample_initial_channel"))
+        self.num_kernels, self.num_upsamples = len(rk), len(rates)
+        self.upsample_factor = 1
+        for u in rates:
+            self.upsample_factor *= int(u)
+        self.conv_pre = _WNConv((C0, int(_get(h, "num_mels")), 7))
+        # ConvTranspose1d weight: [C_in, C_out, k]; weight norm's dim 0 is the INPUT channel there
+        self.ups = nn.ModuleList([_WNConv((C0 // 2 ** i, C0 // 2 ** (i + 1), k)) for i, k in enumerate(ksz)])
+        for i, up in enumerate(self.ups):
+            up.bias = nn.Parameter(torch.zeros(C0 // 2 ** (i + 1)))
+        self.resblocks = nn.ModuleList()
+        ch = C0
+        for i in range(len(rates)):
+            ch = C0 // 2 ** (i + 1)
+            for k in rk:
+                self.resblocks.append(_ResBlock(str(_get(h, "resblock")), ch, k))
+        self.conv_post = _WNConv((1, ch, 7))
+        self._cfg = c_config(h)
+        lib = _lib.lib()
+        if lib.ctts_hifigan_packed_bytes(C.byref(self._cfg)) == 0:
+            raise NotImplementedError("cookietts_amd.HiFiGANGenerator: refused by the library: " + lib.ctts_last_error().decode())
+        self._packed, self._ws = None, {}
+        _cache.hook_invalidate(self)
+
+    # ------------------------------------------------------------------ plumbing ----
+    def _invalidate(self):
+        self._packed, self._ws = None, {}
+
+    def _apply(self, fn, *a, **kw):
+        self._invalidate()
+        return super()._apply(fn, *a, **kw)
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        self._invalidate()
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    def repack(self):
+        self._invalidate()
+
+    def remove_weight_norm(self):
+        for m in self.modules():
+            if isinstance(m, _WNConv):
+                m.remove_weight_norm()
+        self._invalidate()
+
+    def _convs(self):
+        """Every conv in the order of the library's flat weight buffer (ctts_hifigan_weight_floats)."""
+        out = [self.conv_pre]
+        for i in range(self.num_upsamples):
+            out.append(self.ups[i])
+            for j in range(self.num_kernels):
+                out += self.resblocks[i * self.num_kernels + j].conv_list()
+        return out + [self.conv_post]
+
+    def folded_weights(self):
+        """[(weight, bias)] fp32 in ``_convs`` order: ``w = g * v / ||v||`` evaluated in fp32 on the stored parameters
+        (after ``.half()``: on the fp16-rounded ones)."""
+        out = []
+        for m in self._convs():
+            if getattr(m, "weight_v", None) is not None:
+                v, g = m.weight_v.detach().float(), m.weight_g.detach().float()
+                w = v * (g / v.flatten(1).norm(dim=1).view(g.shape))
+            else:
+                w = m.weight.detach().float()
+            out.append((w, m.bias.detach().float()))
+        return out
+
+    def _ensure_packed(self, device):
+        key = _cache.param_key(self)
+        if self._packed is not None and self._packed[0] == device and self._packed[2] == key:
+            return self._packed[1]
+        if device.type != 'cuda':
+            raise _lib.HipLibraryError("HiFi-GAN HIP path needs the model on a GPU (no CPU fallback)")
+        lib = _lib.lib()
+        with torch.cuda.device(device):
+            flat = torch.cat([t.reshape(-1) for wb in self.folded_weights() for t in wb]).to(device).contiguous()
+            n = lib.ctts_hifigan_weight_floats(C.byref(self._cfg))
+            nbytes = lib.ctts_hifigan_packed_bytes(C.byref(self._cfg))
+            blob = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            if flat.numel() != n:
+                raise _lib.HipLibraryError(f"HiFi-GAN: {flat.numel()} weights in the module tree, the library expects {n}")
+            _lib.check(lib.ctts_hifigan_pack_f32(C.byref(self._cfg), _lib.ptr(flat), flat.numel(), _lib.ptr(blob), stream),
+                       "ctts_hifigan_pack_f32")
+            torch.cuda.current_stream(device).synchronize()     # `flat` dies with this frame
+        self._packed = (device, blob, key)
+        return blob
+
+    # ------------------------------------------------------------------ forward ----
+    def forward(self, x):
+        if x.dim() != 3 or x.shape[1] != self._cfg.num_mels:
+            raise ValueError(f"mel must be [B, {self._cfg.num_mels}, T], got {tuple(x.shape)}")
+        if not x.is_cuda:
+            raise _lib.HipLibraryError("HiFi-GAN HIP path needs the mel on a GPU (no CPU fallback)")
+        device = x.device
+        blob = self._ensure_packed(device)
+        lib = _lib.lib()
+        B, _, T = x.shape
+        mel = x.detach().float().contiguous()
+        if T % 4:                                               # rows on 16-byte boundaries: vector staging in the first conv
+            mel = torch.nn.functional.pad(mel, (0, 4 - T % 4))
+        with torch.cuda.device(device):
+            ws = self._ws.get((device, B, T))
+            if ws is None:
+                nbytes = lib.ctts_hifigan_workspace_bytes(C.byref(self._cfg), B, T)
+                if nbytes == 0:
+                    raise _lib.HipLibraryError("ctts_hifigan_workspace_bytes: " + lib.ctts_last_error().decode())
+                self._ws.clear()
+                ws = self._ws[(device, B, T)] = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+            audio = torch.empty(B, 1, T * self.upsample_factor, dtype=torch.float32, device=device)
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            _lib.check(lib.ctts_hifigan_forward_f32(C.byref(self._cfg), _lib.ptr(blob), _lib.ptr(mel), mel.shape[2], _lib.ptr(audio),
+                                                    B, T, _lib.ptr(ws), ws.numel() * 4, stream), "ctts_hifigan_forward_f32")
+        return audio if x.dtype == torch.float32 else audio.to(x.dtype)
+
+
+def load_model(model_path, device='cuda', trust_checkpoint=False):
+    """``hifigan.models.load_model`` (models.py:14-31): ``config.json`` beside the checkpoint, key ``'generator'`` with the
+    weight-norm keys, weight norm removed after loading.  Returns ``(generator, h)``.
+
+    The checkpoint is read with ``weights_only=True`` (no pickle code execution); one that pickles other objects needs
+    ``trust_checkpoint=True`` - only for files you produced yourself."""
+    with open(os.path.join(os.path.split(model_path)[0], 'config.json')) as f:
+        h = AttrDict(json.loads(f.read()))
+    generator = Generator(h)
+    try:
+        cp_dict = torch.load(model_path, map_location='cpu', weights_only=True)
+    except Exception:
+        if not trust_checkpoint:
+            raise
+        cp_dict = torch.load(model_path, map_location='cpu', weights_only=False)
+    generator.load_state_dict(cp_dict['generator'])
+    generator = generator.to(device).eval()
+    generator.remove_weight_norm()
+    return generator, h

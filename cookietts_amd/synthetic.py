@@ -33,6 +33,9 @@ __all__ = [
     "tacotron_memory_in_dim",
     "tacotron_state_dict",
     "prenet_dropout_masks",
+    "HIFIGAN_CONFIGS",
+    "hifigan_config",
+    "hifigan_state_dict",
 ]
 
 
@@ -760,3 +763,71 @@ def prenet_dropout_masks(n_steps, batch, prenet_dim=256, seed=1234):
     """Keep-masks (uint8 0/1) for the prenet's always-on dropout (model.py:189-190): [steps, 2, B, dim]."""
     rng = np.random.default_rng(seed + 15485863)
     return (rng.random((n_steps, 2, batch, prenet_dim)) < 0.5).astype(np.uint8)
+
+
+# ---- HiFi-GAN generator (_4_mtw/hifigan/models.py:94-148; the config.json fields its constructor reads) --------------
+def hifigan_config(upsample_initial_channel=512, upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4), resblock="1",
+                   resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5), (1, 3, 5), (1, 3, 5)), num_mels=80,
+                   sampling_rate=22050, hop_size=256):
+    return dict(resblock=str(resblock), upsample_rates=list(upsample_rates), upsample_kernel_sizes=list(upsample_kernel_sizes),
+                upsample_initial_channel=upsample_initial_channel, resblock_kernel_sizes=list(resblock_kernel_sizes),
+                resblock_dilation_sizes=[list(d) for d in resblock_dilation_sizes], num_mels=num_mels,
+                sampling_rate=sampling_rate, hop_size=hop_size)
+
+
+HIFIGAN_CONFIGS = {
+    # the four configs the reference ships (config_v1.json, config_v2.json, config_v3.json, config_v1_48Khz.json)
+    "v1": hifigan_config(),
+    "v2": hifigan_config(upsample_initial_channel=128),
+    "v3": hifigan_config(upsample_initial_channel=256, upsample_rates=(8, 8, 4), upsample_kernel_sizes=(16, 16, 8), resblock="2",
+                         resblock_kernel_sizes=(3, 5, 7), resblock_dilation_sizes=((1, 2), (2, 6), (3, 12))),
+    "v1_48khz": hifigan_config(upsample_rates=(8, 8, 2, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4, 4), sampling_rate=44100,
+                               hop_size=512),
+    # toys: 2 stages, 32 -> 16 channels
+    "toy_rb1": hifigan_config(upsample_initial_channel=64, upsample_rates=(2, 2), upsample_kernel_sizes=(4, 4),
+                              resblock_kernel_sizes=(3, 7), resblock_dilation_sizes=((1, 3, 5), (1, 3, 5)), hop_size=4),
+    "toy_rb2": hifigan_config(upsample_initial_channel=64, upsample_rates=(2, 2), upsample_kernel_sizes=(4, 4), resblock="2",
+                              resblock_kernel_sizes=(3, 5), resblock_dilation_sizes=((1, 2), (2, 6)), hop_size=4),
+    "toy_rate4": hifigan_config(upsample_initial_channel=64, upsample_rates=(4, 2), upsample_kernel_sizes=(8, 4),
+                                resblock_kernel_sizes=(3, 11), resblock_dilation_sizes=((1, 3, 5), (1, 3, 5)), hop_size=8),
+}
+
+
+def hifigan_layers(cfg):
+    """(state-dict prefix, weight_v shape, transposed) of every conv of the generator, in module order."""
+    C0, n_k = cfg["upsample_initial_channel"], len(cfg["resblock_kernel_sizes"])
+    out = [("conv_pre", (C0, cfg["num_mels"], 7), False)]
+    ch = C0
+    for i, (u, ku) in enumerate(zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"])):
+        out.append((f"ups.{i}", (C0 // 2 ** i, C0 // 2 ** (i + 1), ku), True))
+    for i in range(len(cfg["upsample_rates"])):
+        ch = C0 // 2 ** (i + 1)
+        for j, k in enumerate(cfg["resblock_kernel_sizes"]):
+            p = f"resblocks.{i * n_k + j}"
+            if cfg["resblock"] == "1":
+                out += [(f"{p}.convs1.{m}", (ch, ch, k), False) for m in range(3)]
+                out += [(f"{p}.convs2.{m}", (ch, ch, k), False) for m in range(3)]
+            else:
+                out += [(f"{p}.convs.{m}", (ch, ch, k), False) for m in range(2)]
+    out.append(("conv_post", (1, ch, 7), False))
+    return out
+
+
+def hifigan_state_dict(cfg, seed=1234):
+    """Reference-format generator state dict (weight-norm keys).  The reference's own init (N(0, 0.01)) gives waveforms
+    near zero; here weight_v ~ N(0, 1), bias 0.05 N(0, 1) and weight_g such that every output row of a folded conv has
+    norm 0.8 U(0.8, 1.2) (a transposed conv, whose g is per INPUT channel: that times sqrt(C_out * rate / C_in), so its
+    outputs keep the input's scale), 0.5 for conv_post."""
+    rng = np.random.default_rng(seed)
+    rates = {f"ups.{i}": u for i, u in enumerate(cfg["upsample_rates"])}
+    sd = {}
+    for prefix, shape, transposed in hifigan_layers(cfg):
+        g = np.float32(0.8) * (np.float32(0.8) + np.float32(0.4) * rng.random((shape[0], 1, 1), dtype=np.float32))
+        if transposed:
+            g = g * np.float32(np.sqrt(shape[1] * rates[prefix] / shape[0]))
+        if prefix == "conv_post":
+            g = np.full((1, 1, 1), 0.5, np.float32)
+        sd[prefix + ".bias"] = np.float32(0.05) * rng.standard_normal((shape[1] if transposed else shape[0],), dtype=np.float32)
+        sd[prefix + ".weight_g"] = g.astype(np.float32)
+        sd[prefix + ".weight_v"] = rng.standard_normal(shape, dtype=np.float32)
+    return sd

@@ -455,6 +455,48 @@ int ctts_wgax_inverse_f16(const ctts_wgax_config* cfg, const void* packed, const
 int ctts_replicate_halo_f32(float* x, int32_t batch, int32_t C, int32_t T, int32_t ld, int32_t pad, int32_t halo,
                             void* stream);
 
+/* ---- HiFi-GAN generator: _4_mtw/hifigan/models.py:35-148 (the vocoder _5_infer/t2s_server/text2speech.py:258-263 loads) ---- */
+
+#define CTTS_HIFIGAN_MAX_UPS 8      /* upsampling stages */
+#define CTTS_HIFIGAN_MAX_KERNELS 4  /* resblocks per stage (len(resblock_kernel_sizes)) */
+#define CTTS_HIFIGAN_MAX_DILATIONS 3
+
+/* The fields of config.json that shape the generator (models.py:96-119).  Refused (size queries return 0, the other
+ * entry points CTTS_E_ARG, ctts_last_error names the field): resblock other than 1 / 2; an even resblock kernel or one
+ * above 11; a halo (k - 1) * dilation above 128; upsample kernel - rate odd or negative (the output would not be
+ * rate * T long); more than 4 live taps per upsampling phase; more stages / resblocks than the arrays hold;
+ * upsample_initial_channel not divisible by 2^n_ups. */
+typedef struct ctts_hifigan_config {
+    int32_t num_mels;
+    int32_t upsample_initial_channel;
+    int32_t resblock;                  /* 1: ResBlock1 (three c1 / c2 pairs), 2: ResBlock2 (two convs) */
+    int32_t n_ups;                     /* len(upsample_rates) */
+    int32_t n_kernels;                 /* len(resblock_kernel_sizes) */
+    int32_t upsample_rates[CTTS_HIFIGAN_MAX_UPS];
+    int32_t upsample_kernel_sizes[CTTS_HIFIGAN_MAX_UPS];
+    int32_t resblock_kernel_sizes[CTTS_HIFIGAN_MAX_KERNELS];
+    int32_t resblock_dilation_sizes[CTTS_HIFIGAN_MAX_KERNELS][CTTS_HIFIGAN_MAX_DILATIONS];   /* ResBlock2 reads [j][0..1] */
+} ctts_hifigan_config;
+
+/* Floats of the flat folded-weight buffer ctts_hifigan_pack_f32 reads: every conv's (weight, bias) after weight norm is
+ * folded (w = g * v / ||v||, models.py:138-146), concatenated in module order: conv_pre; then per stage i: ups.i
+ * (ConvTranspose1d weight [C_in][C_out][k]) followed by resblocks.(i * n_kernels + j) for j = 0.., each as convs1.0-2,
+ * convs2.0-2 (ResBlock1) or convs.0-1 (ResBlock2); conv_post last. */
+size_t ctts_hifigan_weight_floats(const ctts_hifigan_config* cfg);
+size_t ctts_hifigan_packed_bytes(const ctts_hifigan_config* cfg);
+/* weights: device, `weight_floats` fp32 as described above -> packed: device blob of ctts_hifigan_packed_bytes (the
+ * MFMA-tiled weights of every layer; transposed convs as their stride-1 phase convolutions). */
+int ctts_hifigan_pack_f32(const ctts_hifigan_config* cfg, const float* weights, size_t weight_floats, void* packed,
+                          void* stream);
+size_t ctts_hifigan_workspace_bytes(const ctts_hifigan_config* cfg, int32_t batch, int32_t frames);
+/* Generator.forward (models.py:121-137): mel [B][num_mels][mel_ld] (frames valid columns per row) ->
+ * audio [B][1][frames * prod(upsample_rates)] = tanh(conv_post(...)).  One launch per conv; LeakyReLU, residual adds, the
+ * sum over a stage's resblocks, its 1 / n_kernels and the tanh run inside those launches (csrc/hifigan.hip).  Arguments
+ * are validated before the first launch. */
+int ctts_hifigan_forward_f32(const ctts_hifigan_config* cfg, const void* packed, const float* mel, int32_t mel_ld,
+                             float* audio, int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
 /* ---- Tacotron2-TM decoder loop: _2_ttm/tacotron2_tm/model.py:668-767, 851-916 -------------- */
 
 /* Shapes from hparams.py (:201-258).  Built topology = the repo defaults: attention_type 0 with

@@ -239,6 +239,81 @@ def row_waveglow_ax_notebook_ab(args):
     return rows
 
 
+def _hifigan_pair(key):
+    """(HIP generator, baseline closure, cfg): the same synthetic weights behind ``cookietts_amd.HiFiGANGenerator`` and behind
+    the plain ``torch.nn.functional`` restatement (tests/hifigan_restatement.py, folded weights, fp32 on the same GPU)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import hifigan_restatement as hr
+    from cookietts_amd import HiFiGANGenerator
+    from cookietts_amd.hifigan import AttrDict
+    cfg = synthetic.HIFIGAN_CONFIGS[key]
+    sd = synthetic.hifigan_state_dict(cfg, seed=1234)
+    m = HiFiGANGenerator(AttrDict(cfg))
+    m.load_state_dict(synthetic.to_torch(sd))
+    m = m.cuda().eval()
+    w = hr.folded_weights(cfg, sd, torch.float32, "cuda")
+    return m, (lambda mel: hr.generator(cfg, w, mel)), cfg, hr
+
+
+def _event_ms(fn, steps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def row_hifigan(args):
+    """HiFi-GAN generator (the vocoder text2speech.py:258-263 loads): v1 at B = 1, 4, 16 x 80 x 900 (16 = the server's
+    vocoder_batch_size) and v1-48 kHz at B = 1.  Two arms alternated ``--reps`` times in one process after a warm-up of each
+    shape, timed by device events: ``hip`` = ctts_hifigan_forward_f32, ``torch`` = the same generator as plain
+    F.conv1d / F.conv_transpose1d calls in fp32 through PyTorch-ROCm (what a user gets today).  FLOP from the shapes
+    (hifigan_restatement.generator_macs); ``--batches`` restricts the v1 batch sizes; ``--arms hip`` for a profiler pass."""
+    rows = []
+    frames = 900
+    arms_on = getattr(args, "arms", "hip,torch").split(",")
+    for key, batches in (("v1", _batches(args, (1, 4, 16))), ("v1_48khz", (1,))):
+        m, base, cfg, hr = _hifigan_pair(key)
+        rate = cfg["sampling_rate"]
+        for B in batches:
+            mel = torch.from_numpy(synthetic.synthetic_mel(B, frames, cfg["num_mels"], seed=B)).cuda()
+            arms = [a for a in (("hip", lambda: m(mel)), ("torch", lambda: base(mel))) if a[0] in arms_on]
+            times = {n: [] for n, _ in arms}
+            with torch.no_grad():
+                outs = {}
+                for n, fn in arms:
+                    for _ in range(max(1, args.warmup)):
+                        outs[n] = fn()
+                    torch.cuda.synchronize()
+                for _ in range(getattr(args, "reps", 5)):
+                    for n, fn in arms:
+                        times[n].append(_event_ms(fn, args.steps))
+            flop = 2.0 * hr.generator_macs(cfg, frames) * B
+            samples = B * frames * m.upsample_factor
+            med = {n: sorted(t)[len(t) // 2] for n, t in times.items()}
+            row = {"row": "H/hifigan", "metric": f"HiFi-GAN {key} generator, fp32, {B} x {cfg['num_mels']} x {frames} mel, ms per call (device events)",
+                   "config": key, "batch": B, "frames": frames, "flop": flop,
+                   "arms": {n: {"reps_ms": t, "median_ms": med[n], "min_ms": min(t), "max_ms": max(t),
+                                "spread_frac": (max(t) - min(t)) / med[n]} for n, t in times.items()}}
+            if "hip" in med:
+                dt = med["hip"] * 1e-3
+                row.update({"value": med["hip"], "unit": "ms", "samples_per_sec": samples / dt, "rtf": samples / dt / rate,
+                            "roofline": {"kernel": "hg_conv_kernel (all launches of the call)", "bound": "mfma", "achieved": flop / dt / 1e12,
+                                         "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": flop / dt / 1e12 / FP32_MFMA_PEAK_TFLOPS,
+                                         "traffic": None}})
+            if "hip" in med and "torch" in med:
+                row["torch_over_hip"] = med["torch"] / med["hip"]
+                d = (outs["hip"].double() - outs["torch"].double())
+                row["hip_vs_torch_rel_rms"] = float(d.pow(2).mean().sqrt() / outs["torch"].double().pow(2).mean().sqrt())
+            rows.append(row)
+            del mel, outs
+        del m, base
+        torch.cuda.empty_cache()
+    return rows
+
+
 def row_tacotron(args, vocoder=None):
     """``vocoder``: a WaveGlow (config 2 weights) already on the GPU, or None to build one."""
     from cookietts_amd.tacotron2 import Tacotron2
@@ -360,8 +435,9 @@ if __name__ == "__main__":
                     help="waveglow_ax: f16 = IEEE-half storage of the WN stacks (model.set_compute_dtype(torch.float16))")
     ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab: repetitions of every arm (alternated)")
     ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts) to these batch sizes (PMC passes)")
+    ap.add_argument("--arms", default="hip,torch", help="hifigan: arms to run (hip alone for a profiler pass)")
     args = ap.parse_args()
-    fns = {"waveflow": row_waveflow, "waveflow_table": row_waveflow_table, "waveflow_author": row_waveflow_author, "tacotron": row_tacotron, "stft": row_stft,
+    fns = {"hifigan": row_hifigan, "waveflow": row_waveflow, "waveflow_table": row_waveflow_table, "waveflow_author": row_waveflow_author, "tacotron": row_tacotron, "stft": row_stft,
            "waveglow_ax": row_waveglow_ax_notebook, "waveglow_ax_ab": row_waveglow_ax_notebook_ab, "waveglow_ax_untts": row_waveglow_ax_untts}
     for r in args.rows.split(","):
         out = fns[r](args)
