@@ -1,0 +1,290 @@
+// HiFi-GAN generator: what the fp32 path (hifigan.hip) and the IEEE-half path (hifigan_f16.hip) share - the layer list of a
+// config with its refusals, the workspace geometry, the launch arguments and the sequence of launches of one forward.
+//
+// `esz` is the size of a stored activation / weight element: 4 = fp32 rows [C][ld], ld = roundup(L, 4); 2 = IEEE half in
+// the K8-blocked layout [ceil(C / 8)][ld][8], ld = L (a column of 8 channels is one 16-byte unit).
+#pragma once
+#include <algorithm>
+#include <type_traits>
+#include <vector>
+
+#include "common.h"
+
+namespace ctts {
+namespace {
+
+enum { HG_EPI_STORE = 0, HG_EPI_RES = 1, HG_EPI_TANH = 2 };
+enum { HG_SUM_FIRST = 1, HG_SUM_LAST = 2 };
+enum { HG_CONV = 0, HG_CONVT = 1 };
+
+constexpr int HG_MAX_KERNEL = 11;         // resblock kernel size (odd)
+constexpr int HG_MAX_HALO = 128;          // (k - 1) * dilation
+constexpr int HG_MAX_UP_TAPS = 5;         // taps of a phase convolution incl. the zero-weight ones
+constexpr int HG_LDS_MAX = 64 * 1024;     // dynamic LDS a launch may ask for
+constexpr int HG_LDS_KC16 = 40 * 1024;    // the larger K chunk only while four workgroups still fit a CU's LDS
+constexpr int HG_NARROW_BELOW = 1024;     // workgroups (4 per CU) under which the half-width block shape is launched
+
+// T = float (hifigan.hip) or _Float16 (hifigan_f16.hip)
+template <typename T>
+struct HgConvArgsT {
+    const T* A;            // packed weights of the layer
+    const float* bias;     // [MB * BM]
+    const T* x;            // input activations
+    const float* xf;       // half path only: the fp32 mel [B][Cin][x_ld] of conv_pre (x is NULL then)
+    long long x_bs;
+    int x_ld, x_vec;       // x_vec (fp32 path): rows are 16-byte aligned (float4 staging)
+    int Cin, L;            // valid input channels; valid columns (input and output share the column domain)
+    int ntap, dil, left;   // tap j reads column n + j * dil - left
+    float slope;           // LeakyReLU slope applied to x while staging (1 = none)
+    int M, MB, ntiles, nch;
+    int epi;
+    T* dst0; long long dst0_bs; int dst0_ld;
+    float* dstf;           // half path only: the fp32 waveform of HG_EPI_TANH
+    int up, cout;          // HG_EPI_STORE: up > 1 = interleaved phase store
+    const T* res; long long res_bs; int res_ld;
+    T* dst1; long long dst1_bs; int dst1_ld;
+    int sum_flags; float nk;
+};
+
+// ---- plan: the layer list of one config, shared by the size queries, the pack and the forward ----
+struct HgLayer {
+    int kind, Cin, M, cout, up, ku, pad, ntap, dil, left;
+    int MT, WM, KC, BM, BN, MB, nch, esz;
+    size_t w_off, b_off;         // floats into the caller's flat folded weights
+    size_t A_off, bias_off;      // bytes into the packed blob
+    int lds_bytes(int bn) const {
+        if (esz == 2) return (ntap * KC * BM + KC * (bn + (ntap - 1) * dil)) * 2;
+        const int aleft = (left + 3) & ~3;
+        const int XW = (bn + (ntap - 1) * dil - left + aleft + 3) & ~3;
+        return (ntap * KC * BM + KC * XW) * 4;
+    }
+    int lds_bytes() const { return lds_bytes(BN); }
+    size_t packed_elems() const { return (size_t)MB * nch * ntap * KC * BM; }
+};
+
+struct HgPlan {
+    ctts_hifigan_config c;
+    std::vector<HgLayer> layers;     // conv_pre, then per stage: ups_i, its n_k resblocks' convs in module order; conv_post last
+    std::vector<int> chans;          // channels after stage i
+    int n_steps;                     // convs1/convs2 pairs (ResBlock1: 3) or convs (ResBlock2: 2) per resblock
+    int esz;
+    long long up_total;              // prod(upsample_rates)
+    size_t weight_floats, packed_bytes;
+};
+
+inline size_t hg_align(size_t v) { return (v + 255) / 256 * 256; }      // bytes
+
+int hg_add_layer(HgPlan& p, int kind, int Cin, int M, int cout, int up, int ku, int pad, int ntap, int dil, int left, const char* what) {
+    HgLayer l{};
+    l.kind = kind; l.Cin = Cin; l.M = M; l.cout = cout; l.up = up; l.ku = ku; l.pad = pad; l.ntap = ntap; l.dil = dil; l.left = left;
+    l.esz = p.esz;
+    if (M <= 32) { l.MT = 1; l.WM = 1; }
+    else if (M <= 64) { l.MT = 2; l.WM = 1; }
+    else { l.MT = 2; l.WM = 2; }
+    l.BM = 32 * l.MT * l.WM;
+    l.BN = 64 * (4 / l.WM);
+    l.MB = (M + l.BM - 1) / l.BM;
+    // K chunk: 16 / 8 fp32 rows, 32 / 16 half rows (the f16 MFMA step is 16 deep): the same LDS bytes either way
+    const int kc_hi = p.esz == 2 ? 32 : 16, kc_lo = kc_hi / 2;
+    l.KC = kc_hi;
+    if (Cin <= kc_lo || l.lds_bytes() > HG_LDS_KC16) l.KC = kc_lo;
+    CTTS_CHECK_ARG(l.lds_bytes() <= HG_LDS_MAX, "hifigan: %s needs %d bytes of LDS (limit %d)", what, l.lds_bytes(), HG_LDS_MAX);
+    l.nch = (Cin + l.KC - 1) / l.KC;
+    l.w_off = p.weight_floats;
+    const size_t wn = kind == HG_CONV ? (size_t)M * Cin * ntap : (size_t)Cin * cout * ku;
+    l.b_off = l.w_off + wn;
+    p.weight_floats = l.b_off + (kind == HG_CONV ? M : cout);
+    l.A_off = p.packed_bytes;
+    l.bias_off = l.A_off + hg_align(l.packed_elems() * p.esz);
+    p.packed_bytes = l.bias_off + hg_align((size_t)l.MB * l.BM * sizeof(float));
+    p.layers.push_back(l);
+    return CTTS_OK;
+}
+
+int make_hg_plan(const ctts_hifigan_config* cfg, HgPlan& p, int esz) {
+    CTTS_CHECK_ARG(cfg != nullptr, "hifigan: config is NULL");
+    p.c = *cfg;
+    p.esz = esz;
+    const auto& c = p.c;
+    p.weight_floats = p.packed_bytes = 0;
+    CTTS_CHECK_ARG(c.num_mels >= 1 && c.num_mels <= 4096, "hifigan: num_mels=%d", c.num_mels);
+    CTTS_CHECK_ARG(c.resblock == 1 || c.resblock == 2, "hifigan: resblock=%d ('1' or '2')", c.resblock);
+    CTTS_CHECK_ARG(c.n_ups >= 1 && c.n_ups <= CTTS_HIFIGAN_MAX_UPS, "hifigan: upsample_rates has %d entries (1..%d)", c.n_ups,
+                   CTTS_HIFIGAN_MAX_UPS);
+    CTTS_CHECK_ARG(c.n_kernels >= 1 && c.n_kernels <= CTTS_HIFIGAN_MAX_KERNELS, "hifigan: resblock_kernel_sizes has %d entries (1..%d)",
+                   c.n_kernels, CTTS_HIFIGAN_MAX_KERNELS);
+    CTTS_CHECK_ARG(c.upsample_initial_channel >= (1 << c.n_ups) && c.upsample_initial_channel % (1 << c.n_ups) == 0 &&
+                       c.upsample_initial_channel <= 8192,
+                   "hifigan: upsample_initial_channel=%d (a multiple of 2^%d, <= 8192)", c.upsample_initial_channel, c.n_ups);
+    p.n_steps = c.resblock == 1 ? 3 : 2;
+    p.up_total = 1;
+    for (int i = 0; i < c.n_ups; ++i) {
+        const int u = c.upsample_rates[i], ku = c.upsample_kernel_sizes[i];
+        CTTS_CHECK_ARG(u >= 1 && u <= 64, "hifigan: upsample_rates[%d]=%d (1..64)", i, u);
+        CTTS_CHECK_ARG(ku >= u && (ku - u) % 2 == 0, "hifigan: upsample_kernel_sizes[%d]=%d with rate %d (kernel - rate even and >= 0: the output is rate * T long)", i, ku, u);
+        p.up_total *= u;
+        CTTS_CHECK_ARG(p.up_total <= (1 << 20), "hifigan: upsample_rates multiply to more than 2^20");
+    }
+    for (int j = 0; j < c.n_kernels; ++j) {
+        const int k = c.resblock_kernel_sizes[j];
+        CTTS_CHECK_ARG(k >= 1 && k % 2 == 1 && k <= HG_MAX_KERNEL, "hifigan: resblock_kernel_sizes[%d]=%d (odd, <= %d)", j, k, HG_MAX_KERNEL);
+        for (int m = 0; m < p.n_steps; ++m) {
+            const int d = c.resblock_dilation_sizes[j][m];
+            CTTS_CHECK_ARG(d >= 1 && (k - 1) * d <= HG_MAX_HALO, "hifigan: resblock_dilation_sizes[%d][%d]=%d with kernel %d (halo (k-1)*d <= %d)",
+                           j, m, d, k, HG_MAX_HALO);
+        }
+    }
+    int rc = hg_add_layer(p, HG_CONV, c.num_mels, c.upsample_initial_channel, 0, 1, 0, 0, 7, 1, 3, "conv_pre");
+    if (rc) return rc;
+    int C = c.upsample_initial_channel;
+    for (int i = 0; i < c.n_ups; ++i) {
+        const int u = c.upsample_rates[i], ku = c.upsample_kernel_sizes[i], pad = (ku - u) / 2;
+        const int left = (ku - 1 - pad) / u, jhi = (u - 1 + pad) / u;
+        CTTS_CHECK_ARG(left + jhi + 1 <= HG_MAX_UP_TAPS, "hifigan: upsample_kernel_sizes[%d]=%d with rate %d (at most %d taps per phase)", i, ku,
+                       u, HG_MAX_UP_TAPS - 1);
+        if ((rc = hg_add_layer(p, HG_CONVT, C, u * (C / 2), C / 2, u, ku, pad, left + jhi + 1, 1, left, "ups"))) return rc;
+        C /= 2;
+        p.chans.push_back(C);
+        for (int j = 0; j < c.n_kernels; ++j) {
+            const int k = c.resblock_kernel_sizes[j];
+            // module order: convs1.0-2 then convs2.0-2 (ResBlock1), convs.0-1 (ResBlock2)
+            for (int m = 0; m < p.n_steps; ++m) {
+                const int d = c.resblock_dilation_sizes[j][m];
+                if ((rc = hg_add_layer(p, HG_CONV, C, C, 0, 1, 0, 0, k, d, (k - 1) / 2 * d, "resblock conv"))) return rc;
+            }
+            if (c.resblock == 1)
+                for (int m = 0; m < 3; ++m)
+                    if ((rc = hg_add_layer(p, HG_CONV, C, C, 0, 1, 0, 0, k, 1, (k - 1) / 2, "resblock conv"))) return rc;
+        }
+    }
+    return hg_add_layer(p, HG_CONV, C, 1, 0, 1, 0, 0, 7, 1, 3, "conv_post");
+}
+
+struct HgGeom { size_t buf_elems; size_t total_elems; };
+
+inline int hg_ld(int esz, int L) { return esz == 2 ? L : round_up(L, 4); }          // row pitch in columns
+inline int hg_rows(int esz, int C) { return esz == 2 ? round_up(C, 8) : C; }        // stored channel rows
+
+// five activation buffers (stage input x, resblock sum xs, the c1 output, two ping-pong resblock states), each
+// batch * max over the tensors of the call of rows(C) * ld(L) elements
+int hg_geometry(const HgPlan& p, int batch, int frames, HgGeom& g) {
+    CTTS_CHECK_ARG(batch >= 1 && batch <= 4096, "hifigan: batch=%d (1..4096)", batch);
+    CTTS_CHECK_ARG(frames >= 1 && (long long)frames * p.up_total <= (1ll << 30), "hifigan: frames=%d (>= 1, frames * prod(rates) <= 2^30)", frames);
+    long long L = frames;
+    size_t mx = (size_t)hg_rows(p.esz, p.c.upsample_initial_channel) * hg_ld(p.esz, (int)L);
+    for (int i = 0; i < p.c.n_ups; ++i) {
+        L *= p.c.upsample_rates[i];
+        mx = std::max(mx, (size_t)hg_rows(p.esz, p.chans[i]) * (size_t)hg_ld(p.esz, (int)L));
+    }
+    g.buf_elems = hg_align(mx * (size_t)batch * p.esz) / p.esz;
+    g.total_elems = 5 * g.buf_elems;
+    return CTTS_OK;
+}
+
+// Generator.forward (models.py:121-137) as its sequence of launches; `launch(layer, args)` starts one conv.
+template <typename T, typename Launch>
+int hg_forward(const HgPlan& p, const HgGeom& g, const float* mel, int mel_ld, float* audio, int frames, T* ws, Launch launch) {
+    using Args = HgConvArgsT<T>;
+    constexpr bool kF32 = std::is_same<T, float>::value;
+    const auto& c = p.c;
+    const int esz = p.esz;
+    int rc;
+    T* X = ws;
+    T* XS = ws + g.buf_elems;
+    T* Tm = ws + 2 * g.buf_elems;
+    T* P[2] = {ws + 3 * g.buf_elems, ws + 4 * g.buf_elems};
+
+    size_t li = 0;
+    int L = frames, ld = hg_ld(esz, L);
+    int C = c.upsample_initial_channel;
+    {   // conv_pre (models.py:122) -> XS
+        Args a{};
+        if constexpr (kF32) a.x = mel; else a.xf = mel;
+        a.x_bs = (long long)c.num_mels * mel_ld; a.x_ld = mel_ld; a.L = L; a.slope = 1.0f;
+        a.epi = HG_EPI_STORE; a.dst0 = XS; a.dst0_bs = (long long)hg_rows(esz, C) * ld; a.dst0_ld = ld;
+        if ((rc = launch(p.layers[li++], a))) return rc;
+    }
+    for (int i = 0; i < c.n_ups; ++i) {
+        const int u = c.upsample_rates[i];
+        const int Lo = L * u, ldo = hg_ld(esz, Lo), Co = C / 2;
+        {   // x = ups[i](leaky_relu(x, 0.1)) (models.py:124-125): XS -> X, phases interleaved by the store
+            Args a{};
+            a.x = XS; a.x_bs = (long long)hg_rows(esz, C) * ld; a.x_ld = ld; a.L = L; a.slope = 0.1f;
+            a.epi = HG_EPI_STORE; a.dst0 = X; a.dst0_bs = (long long)hg_rows(esz, Co) * ldo; a.dst0_ld = ldo;
+            if ((rc = launch(p.layers[li++], a))) return rc;
+        }
+        L = Lo; ld = ldo; C = Co;
+        const long long bs = (long long)hg_rows(esz, C) * ld;
+        for (int j = 0; j < c.n_kernels; ++j) {   // every resblock reads the same X (models.py:127-132)
+            const size_t first = li;
+            li += (c.resblock == 1 ? 2 : 1) * p.n_steps;
+            const T* cur = X;
+            for (int m = 0; m < p.n_steps; ++m) {
+                const bool last = m == p.n_steps - 1;
+                const T* in = cur;
+                if (c.resblock == 1) {   // xt = c1(leaky_relu(x)) (models.py:60-62) -> Tm
+                    Args a{};
+                    a.x = cur; a.x_bs = bs; a.x_ld = ld; a.L = L; a.slope = 0.1f;
+                    a.epi = HG_EPI_STORE; a.dst0 = Tm; a.dst0_bs = bs; a.dst0_ld = ld;
+                    if ((rc = launch(p.layers[first + m], a))) return rc;
+                    in = Tm;
+                }
+                // x = c(leaky_relu(.)) + x (models.py:63-65 / :88-91); the last step feeds the stage's sum and its 1 / n_k
+                Args a{};
+                a.x = in; a.x_bs = bs; a.x_ld = ld; a.L = L; a.slope = 0.1f;
+                a.epi = HG_EPI_RES; a.res = cur; a.res_bs = bs; a.res_ld = ld;
+                if (!last) { a.dst0 = P[m & 1]; a.dst0_bs = bs; a.dst0_ld = ld; }
+                else {
+                    a.dst1 = XS; a.dst1_bs = bs; a.dst1_ld = ld; a.nk = (float)c.n_kernels;
+                    a.sum_flags = (j == 0 ? HG_SUM_FIRST : 0) | (j == c.n_kernels - 1 ? HG_SUM_LAST : 0);
+                }
+                if ((rc = launch(p.layers[first + (c.resblock == 1 ? 3 : 0) + m], a))) return rc;
+                cur = P[m & 1];
+            }
+        }
+    }
+    {   // tanh(conv_post(leaky_relu(x))) with F.leaky_relu's default slope 0.01 (models.py:134-136) -> audio [B][1][L]
+        Args a{};
+        a.x = XS; a.x_bs = (long long)hg_rows(esz, C) * ld; a.x_ld = ld; a.L = L; a.slope = 0.01f;
+        a.epi = HG_EPI_TANH;
+        if constexpr (kF32) a.dst0 = audio; else a.dstf = audio;
+        a.dst0_bs = L; a.dst0_ld = L;
+        if ((rc = launch(p.layers[li++], a))) return rc;
+    }
+    return CTTS_OK;
+}
+
+// the pack kernels' arguments (T as above); A is [MB][nch][ntap][KC][BM] in fp32, [MB][nch][ntap][KC / 8][BM][8] in half
+template <typename T>
+struct HgPackArgsT {
+    const float* w;        // HG_CONV: [M][Cin][k]; HG_CONVT: [Cin][cout][ku]
+    const float* b;        // [M] / [cout]
+    T* A;
+    float* bias;
+    int kind, Cin, M, cout, up, ku, pad, ntap, left, KC, BM, MB, nch;
+};
+
+template <typename T>
+HgPackArgsT<T> hg_pack_args(const HgLayer& l, const float* weights, void* packed) {
+    HgPackArgsT<T> a{};
+    char* out = static_cast<char*>(packed);
+    a.w = weights + l.w_off; a.b = weights + l.b_off;
+    a.A = reinterpret_cast<T*>(out + l.A_off); a.bias = reinterpret_cast<float*>(out + l.bias_off);
+    a.kind = l.kind; a.Cin = l.Cin; a.M = l.M; a.cout = l.cout > 0 ? l.cout : 1; a.up = l.up; a.ku = l.ku; a.pad = l.pad;
+    a.ntap = l.ntap; a.left = l.left; a.KC = l.KC; a.BM = l.BM; a.MB = l.MB; a.nch = l.nch;
+    return a;
+}
+
+// the folded weight (m, ci, tap j) of a layer from the caller's flat buffer; 0 outside the layer (padding rows / channels and
+// the dead taps of a transposed conv's phase)
+template <typename T>
+__device__ __forceinline__ float hg_weight_at(const HgPackArgsT<T>& p, int m, int ci, int j) {
+    if (m >= p.M || ci >= p.Cin) return 0.0f;
+    if (p.kind == HG_CONV) return p.w[((size_t)m * p.Cin + ci) * p.ntap + j];
+    const int ph = m / p.cout, co = m - ph * p.cout;
+    const int kk = p.up * (p.left - j) + ph + p.pad;
+    return (kk >= 0 && kk < p.ku) ? p.w[((size_t)ci * p.cout + co) * p.ku + kk] : 0.0f;
+}
+
+}  // namespace
+}  // namespace ctts

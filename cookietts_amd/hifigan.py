@@ -10,6 +10,10 @@ adds / the resblock mean / tanh inside those launches.  There is no CPU fallback
 ``.half()`` (text2speech.py:262): the parameters become fp16 - so ``next(vocoder.parameters()).dtype`` and the server's
 ``mel.to(dtype)`` work unchanged - the products stay fp32 MFMA on the fp16-rounded weights, and the waveform comes back in the
 dtype of the mel it was given.  Options the kernels cannot run exactly raise ``NotImplementedError`` at construction.
+
+``set_compute_dtype(torch.float16)`` selects the IEEE-half storage mode (``ctts_hifigan_forward_f16``, csrc/hifigan_f16.hip):
+weights and every stored activation in half, products on the f16 MFMA, fp32 accumulation.  It is independent of the parameter
+dtype; what the reference's server gets from ``vocoder.half()`` is ``vocoder.half().set_compute_dtype(torch.float16)`` here.
 """
 from __future__ import annotations
 
@@ -127,6 +131,7 @@ class Generator(nn.Module):
         if lib.ctts_hifigan_packed_bytes(C.byref(self._cfg)) == 0:
             raise NotImplementedError("cookietts_amd.HiFiGANGenerator: refused by the library: " + lib.ctts_last_error().decode())
         self._packed, self._ws = None, {}
+        self._compute_dtype = torch.float32
         _cache.hook_invalidate(self)
 
     # ------------------------------------------------------------------ plumbing ----
@@ -143,6 +148,30 @@ class Generator(nn.Module):
 
     def repack(self):
         self._invalidate()
+
+    def set_compute_dtype(self, dtype):
+        """Storage and product format of the whole generator: ``torch.float32`` (default: fp32 tensors, exact fp32 MFMA) or
+        ``torch.float16``: weights and every stored activation as IEEE half, products on the f16 matrix pipe, accumulation,
+        bias, residual add, resblock mean and tanh in fp32, one rounding per stored value (the rounding points are listed at
+        ``ctts_hifigan_forward_f16``).  Independent of the parameter dtype (``.half()`` alone keeps fp32 products); switching
+        back to ``torch.float32`` restores the fp32 path bit for bit.  Returns ``self``; the packed blob and the workspaces are
+        dropped when the mode changes and kept when it does not.  ``NotImplementedError`` - here, not at the first call - if
+        the library refuses the config in half storage."""
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"compute dtype must be torch.float32 or torch.float16, not {dtype!r}")
+        if dtype == torch.float16:
+            lib = _lib.lib()
+            if lib.ctts_hifigan_packed_f16_bytes(C.byref(self._cfg)) == 0:
+                raise NotImplementedError("cookietts_amd.HiFiGANGenerator: half storage refused by the library: "
+                                          + lib.ctts_last_error().decode())
+        if dtype != self._compute_dtype:
+            self._compute_dtype = dtype
+            self._invalidate()        # the packed blob and the workspaces are per format
+        return self
+
+    @property
+    def compute_dtype(self):
+        return self._compute_dtype
 
     def remove_weight_norm(self):
         for m in self.modules():
@@ -182,13 +211,14 @@ class Generator(nn.Module):
         with torch.cuda.device(device):
             flat = torch.cat([t.reshape(-1) for wb in self.folded_weights() for t in wb]).to(device).contiguous()
             n = lib.ctts_hifigan_weight_floats(C.byref(self._cfg))
-            nbytes = lib.ctts_hifigan_packed_bytes(C.byref(self._cfg))
+            f16 = self._compute_dtype == torch.float16
+            nbytes = (lib.ctts_hifigan_packed_f16_bytes if f16 else lib.ctts_hifigan_packed_bytes)(C.byref(self._cfg))
             blob = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
             stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             if flat.numel() != n:
                 raise _lib.HipLibraryError(f"HiFi-GAN: {flat.numel()} weights in the module tree, the library expects {n}")
-            _lib.check(lib.ctts_hifigan_pack_f32(C.byref(self._cfg), _lib.ptr(flat), flat.numel(), _lib.ptr(blob), stream),
-                       "ctts_hifigan_pack_f32")
+            name = "ctts_hifigan_pack_f16" if f16 else "ctts_hifigan_pack_f32"
+            _lib.check(getattr(lib, name)(C.byref(self._cfg), _lib.ptr(flat), flat.numel(), _lib.ptr(blob), stream), name)
             torch.cuda.current_stream(device).synchronize()     # `flat` dies with this frame
         self._packed = (device, blob, key)
         return blob
@@ -203,30 +233,34 @@ class Generator(nn.Module):
         blob = self._ensure_packed(device)
         lib = _lib.lib()
         B, _, T = x.shape
+        f16 = self._compute_dtype == torch.float16
+        ws_bytes = lib.ctts_hifigan_workspace_f16_bytes if f16 else lib.ctts_hifigan_workspace_bytes
+        fwd = "ctts_hifigan_forward_f16" if f16 else "ctts_hifigan_forward_f32"
         mel = x.detach().float().contiguous()
         if T % 4:                                               # rows on 16-byte boundaries: vector staging in the first conv
             mel = torch.nn.functional.pad(mel, (0, 4 - T % 4))
         with torch.cuda.device(device):
             ws = self._ws.get((device, B, T))
             if ws is None:
-                nbytes = lib.ctts_hifigan_workspace_bytes(C.byref(self._cfg), B, T)
+                nbytes = ws_bytes(C.byref(self._cfg), B, T)
                 if nbytes == 0:
                     raise _lib.HipLibraryError("ctts_hifigan_workspace_bytes: " + lib.ctts_last_error().decode())
                 self._ws.clear()
                 ws = self._ws[(device, B, T)] = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
             audio = torch.empty(B, 1, T * self.upsample_factor, dtype=torch.float32, device=device)
             stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            _lib.check(lib.ctts_hifigan_forward_f32(C.byref(self._cfg), _lib.ptr(blob), _lib.ptr(mel), mel.shape[2], _lib.ptr(audio),
-                                                    B, T, _lib.ptr(ws), ws.numel() * 4, stream), "ctts_hifigan_forward_f32")
+            _lib.check(getattr(lib, fwd)(C.byref(self._cfg), _lib.ptr(blob), _lib.ptr(mel), mel.shape[2], _lib.ptr(audio),
+                                         B, T, _lib.ptr(ws), ws.numel() * 4, stream), fwd)
         return audio if x.dtype == torch.float32 else audio.to(x.dtype)
 
 
-def load_model(model_path, device='cuda', trust_checkpoint=False):
+def load_model(model_path, device='cuda', trust_checkpoint=False, compute_dtype=None):
     """``hifigan.models.load_model`` (models.py:14-31): ``config.json`` beside the checkpoint, key ``'generator'`` with the
     weight-norm keys, weight norm removed after loading.  Returns ``(generator, h)``.
 
     The checkpoint is read with ``weights_only=True`` (no pickle code execution); one that pickles other objects needs
-    ``trust_checkpoint=True`` - only for files you produced yourself."""
+    ``trust_checkpoint=True`` - only for files you produced yourself.  ``compute_dtype`` (``torch.float32`` /
+    ``torch.float16``) is handed to ``Generator.set_compute_dtype``."""
     with open(os.path.join(os.path.split(model_path)[0], 'config.json')) as f:
         h = AttrDict(json.loads(f.read()))
     generator = Generator(h)
@@ -239,4 +273,6 @@ def load_model(model_path, device='cuda', trust_checkpoint=False):
     generator.load_state_dict(cp_dict['generator'])
     generator = generator.to(device).eval()
     generator.remove_weight_norm()
+    if compute_dtype is not None:
+        generator.set_compute_dtype(compute_dtype)
     return generator, h

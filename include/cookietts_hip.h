@@ -497,6 +497,24 @@ int ctts_hifigan_forward_f32(const ctts_hifigan_config* cfg, const void* packed,
                              float* audio, int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* IEEE-half storage mode of the same generator (csrc/hifigan_f16.hip): weights and every stored activation in IEEE half
+ * (K8-blocked [ceil(C / 8)][L][8]), products on the f16 MFMA, accumulation, bias, residual add, the resblock mean and tanh
+ * in fp32, one round-to-nearest-even rounding per stored value, IEEE overflow (no clamping).  Rounding points: the weight
+ * once from the fp32 folded value (biases stay fp32); the mel once while it is staged; leaky_relu as the stored half times
+ * the fp32 slope in fp32, rounded once; a conv's output as half(acc + bias [+ float(residual)]); the sum over a stage's
+ * resblocks as half(float(sum) + v) per resblock from the unrounded fp32 v, the last one divided by n_kernels in fp32
+ * before its rounding.  pack_f16 reads the same flat fp32 buffer as pack_f32; forward_f16 takes the fp32 mel and writes
+ * the fp32 waveform like forward_f32.  Same contract: every argument is validated before the first launch, the size
+ * queries return 0 (ctts_last_error names the option) for a config that is refused - exactly the configs the fp32
+ * queries refuse. */
+size_t ctts_hifigan_packed_f16_bytes(const ctts_hifigan_config* cfg);
+int ctts_hifigan_pack_f16(const ctts_hifigan_config* cfg, const float* weights, size_t weight_floats, void* packed,
+                          void* stream);
+size_t ctts_hifigan_workspace_f16_bytes(const ctts_hifigan_config* cfg, int32_t batch, int32_t frames);
+int ctts_hifigan_forward_f16(const ctts_hifigan_config* cfg, const void* packed, const float* mel, int32_t mel_ld,
+                             float* audio, int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
 /* ---- Tacotron2-TM decoder loop: _2_ttm/tacotron2_tm/model.py:668-767, 851-916 -------------- */
 
 /* Shapes from hparams.py (:201-258).  Built topology = the repo defaults: attention_type 0 with

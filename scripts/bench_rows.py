@@ -32,6 +32,7 @@ def timed(fn, warmup, steps):
 
 
 FP32_MFMA_PEAK_TFLOPS = 157.3
+HBM_PEAK_TBPS = 8.0                # MI355X_MICROARCH.md: HBM3E spec peak (6.29 TB/s measured with a float4 copy)
 F16_MFMA_PEAK_TFLOPS = 2500.0      # MI355X_MICROARCH.md: dense bf16 / f16 MFMA (v_mfma_f32_32x32x16_f16 takes the bf16 form's cycles)
 
 
@@ -255,6 +256,22 @@ def _hifigan_pair(key):
     return m, (lambda mel: hr.generator(cfg, w, mel)), cfg, hr
 
 
+def _hifigan_f16_pair(key):
+    """(HIP generator in the IEEE-half storage mode, baseline closure): a second instance on the same weights, so that the
+    alternated loop never repacks, and the restatement's plain F.conv1d generator with ``.half()`` weights through
+    PyTorch-ROCm - what a user of the reference gets today from ``vocoder.half()``."""
+    import hifigan_restatement as hr
+    from cookietts_amd import HiFiGANGenerator
+    from cookietts_amd.hifigan import AttrDict
+    cfg = synthetic.HIFIGAN_CONFIGS[key]
+    sd = synthetic.hifigan_state_dict(cfg, seed=1234)
+    m = HiFiGANGenerator(AttrDict(cfg))
+    m.load_state_dict(synthetic.to_torch(sd))
+    m = m.cuda().eval().set_compute_dtype(torch.float16)
+    w = {k: (a.half(), b.half()) for k, (a, b) in hr.folded_weights(cfg, sd, torch.float32, "cuda").items()}
+    return m, (lambda mel16: hr.generator(cfg, w, mel16))
+
+
 def _event_ms(fn, steps):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -270,16 +287,25 @@ def row_hifigan(args):
     vocoder_batch_size) and v1-48 kHz at B = 1.  Two arms alternated ``--reps`` times in one process after a warm-up of each
     shape, timed by device events: ``hip`` = ctts_hifigan_forward_f32, ``torch`` = the same generator as plain
     F.conv1d / F.conv_transpose1d calls in fp32 through PyTorch-ROCm (what a user gets today).  FLOP from the shapes
-    (hifigan_restatement.generator_macs); ``--batches`` restricts the v1 batch sizes; ``--arms hip`` for a profiler pass."""
+    (hifigan_restatement.generator_macs); ``--batches`` restricts the v1 batch sizes; ``--arms hip`` for a profiler pass.
+
+    Two more arms in the same alternated loop give a second row per shape, ``H/hifigan_f16``: ``hip_f16`` =
+    ctts_hifigan_forward_f16 (``set_compute_dtype(torch.float16)``: IEEE-half storage, f16 MFMA) and ``torch_f16`` = the plain
+    generator with ``.half()`` weights and mel through PyTorch-ROCm.  Its ``roofline`` carries both fractions - FLOP over the
+    f16 MFMA peak, algorithmic bytes (hifigan_f16_restatement.generator_bytes) over the HBM peak - and ``bound`` names the larger."""
     rows = []
     frames = 900
-    arms_on = getattr(args, "arms", "hip,torch").split(",")
+    arms_on = getattr(args, "arms", "hip,torch,hip_f16,torch_f16").split(",")
     for key, batches in (("v1", _batches(args, (1, 4, 16))), ("v1_48khz", (1,))):
         m, base, cfg, hr = _hifigan_pair(key)
+        m16, base16 = _hifigan_f16_pair(key) if ("hip_f16" in arms_on or "torch_f16" in arms_on) else (None, None)
+        import hifigan_f16_restatement as h16
         rate = cfg["sampling_rate"]
         for B in batches:
             mel = torch.from_numpy(synthetic.synthetic_mel(B, frames, cfg["num_mels"], seed=B)).cuda()
-            arms = [a for a in (("hip", lambda: m(mel)), ("torch", lambda: base(mel))) if a[0] in arms_on]
+            mel16 = mel.half()
+            arms = [a for a in (("hip", lambda: m(mel)), ("torch", lambda: base(mel)), ("hip_f16", lambda: m16(mel)),
+                                ("torch_f16", lambda: base16(mel16))) if a[0] in arms_on]
             times = {n: [] for n, _ in arms}
             with torch.no_grad():
                 outs = {}
@@ -296,7 +322,7 @@ def row_hifigan(args):
             row = {"row": "H/hifigan", "metric": f"HiFi-GAN {key} generator, fp32, {B} x {cfg['num_mels']} x {frames} mel, ms per call (device events)",
                    "config": key, "batch": B, "frames": frames, "flop": flop,
                    "arms": {n: {"reps_ms": t, "median_ms": med[n], "min_ms": min(t), "max_ms": max(t),
-                                "spread_frac": (max(t) - min(t)) / med[n]} for n, t in times.items()}}
+                                "spread_frac": (max(t) - min(t)) / med[n]} for n, t in times.items() if n in ("hip", "torch")}}
             if "hip" in med:
                 dt = med["hip"] * 1e-3
                 row.update({"value": med["hip"], "unit": "ms", "samples_per_sec": samples / dt, "rtf": samples / dt / rate,
@@ -307,11 +333,42 @@ def row_hifigan(args):
                 row["torch_over_hip"] = med["torch"] / med["hip"]
                 d = (outs["hip"].double() - outs["torch"].double())
                 row["hip_vs_torch_rel_rms"] = float(d.pow(2).mean().sqrt() / outs["torch"].double().pow(2).mean().sqrt())
-            rows.append(row)
-            del mel, outs
-        del m, base
+            if "hip" in med or "torch" in med:
+                rows.append(row)
+            if "hip_f16" in med or "torch_f16" in med:
+                rows.append(_hifigan_f16_row(key, cfg, B, frames, flop, samples, rate, times, med, outs, h16))
+            del mel, mel16, outs
+        del m, base, m16, base16
         torch.cuda.empty_cache()
     return rows
+
+
+def _hifigan_f16_row(key, cfg, B, frames, flop, samples, rate, times, med, outs, h16):
+    """The half-storage row of one shape: the f16 arms, the fp32 ``hip`` arm of the same loop as the ratio's denominator."""
+    nbytes = float(B * h16.generator_bytes(cfg, frames, 2))
+    row = {"row": "H/hifigan_f16", "metric": f"HiFi-GAN {key} generator, IEEE-half storage, {B} x {cfg['num_mels']} x {frames} mel, ms per call (device events)",
+           "config": key, "batch": B, "frames": frames, "flop": flop, "algorithmic_bytes": nbytes,
+           "arms": {n: {"reps_ms": t, "median_ms": med[n], "min_ms": min(t), "max_ms": max(t),
+                        "spread_frac": (max(t) - min(t)) / med[n]} for n, t in times.items() if n in ("hip_f16", "torch_f16")}}
+    if "hip_f16" in med:
+        dt = med["hip_f16"] * 1e-3
+        mfma_frac = flop / dt / 1e12 / F16_MFMA_PEAK_TFLOPS
+        hbm_frac = nbytes / dt / 1e12 / HBM_PEAK_TBPS
+        row.update({"value": med["hip_f16"], "unit": "ms", "samples_per_sec": samples / dt, "rtf": samples / dt / rate,
+                    "roofline": {"kernel": "hg_conv_f16_kernel (all launches of the call)", "bound": "hbm" if hbm_frac >= mfma_frac else "mfma",
+                                 "mfma": {"achieved": flop / dt / 1e12, "peak": F16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": mfma_frac},
+                                 "hbm": {"achieved": nbytes / dt / 1e12, "peak": HBM_PEAK_TBPS, "unit": "TB/s", "frac": hbm_frac},
+                                 "frac": max(hbm_frac, mfma_frac), "traffic": "algorithmic bytes from the shapes, not counters"}})
+        if "hip" in med:
+            row["hip_f32_over_hip_f16"] = med["hip"] / med["hip_f16"]
+        if "torch_f16" in med:
+            row["torch_f16_over_hip_f16"] = med["torch_f16"] / med["hip_f16"]
+            d = (outs["hip_f16"].double() - outs["torch_f16"].double())
+            row["hip_f16_vs_torch_f16_rel_rms"] = float(d.pow(2).mean().sqrt() / outs["torch_f16"].double().pow(2).mean().sqrt())
+        if "hip" in outs:
+            d = (outs["hip_f16"].double() - outs["hip"].double())
+            row["hip_f16_vs_hip_f32_rel_rms"] = float(d.pow(2).mean().sqrt() / outs["hip"].double().pow(2).mean().sqrt())
+    return row
 
 
 def row_tacotron(args, vocoder=None):
@@ -435,7 +492,8 @@ if __name__ == "__main__":
                     help="waveglow_ax: f16 = IEEE-half storage of the WN stacks (model.set_compute_dtype(torch.float16))")
     ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab: repetitions of every arm (alternated)")
     ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts) to these batch sizes (PMC passes)")
-    ap.add_argument("--arms", default="hip,torch", help="hifigan: arms to run (hip alone for a profiler pass)")
+    ap.add_argument("--arms", default="hip,torch,hip_f16,torch_f16",
+                    help="hifigan: arms to run (hip or hip_f16 alone for a profiler pass)")
     args = ap.parse_args()
     fns = {"hifigan": row_hifigan, "waveflow": row_waveflow, "waveflow_table": row_waveflow_table, "waveflow_author": row_waveflow_author, "tacotron": row_tacotron, "stft": row_stft,
            "waveglow_ax": row_waveglow_ax_notebook, "waveglow_ax_ab": row_waveglow_ax_notebook_ab, "waveglow_ax_untts": row_waveglow_ax_untts}
