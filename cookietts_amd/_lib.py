@@ -9,6 +9,8 @@ import ctypes as C
 import os
 import threading
 
+import torch
+
 from . import build as _build
 
 _LOCK = threading.Lock()
@@ -91,6 +93,7 @@ class WgaxFlowWeights(C.Structure):
 
 
 MIX_PERMUTE, MIX_CONV1X1 = 0, 1
+PAD = 8                # halo columns of the padded [B][C][ld] rows the conv / resample / pad primitives are handed
 N_SPEAKERS = 512       # CTTS_N_SPEAKERS
 
 
@@ -396,10 +399,23 @@ def lib():
     return _LIB
 
 
+def last_error():
+    """The library's message for the calling thread's last refusal (``ctts_last_error``)."""
+    msg = lib().ctts_last_error()
+    return msg.decode(errors='replace') if msg else ''
+
+
 def check(rc, what):
     if rc != 0:
-        msg = lib().ctts_last_error()
-        raise HipLibraryError(f"{what} failed (rc={rc}): {msg.decode(errors='replace') if msg else ''}")
+        raise HipLibraryError(f"{what} failed (rc={rc}): {last_error()}")
+
+
+def nbytes(fn, *args, what):
+    """Call a size query (``ctts_*_bytes``): the size, or HipLibraryError(``what``: the library's reason) when it answers 0."""
+    n = fn(*args)
+    if n == 0:
+        raise HipLibraryError(f"{what}: {last_error()}")
+    return n
 
 
 def ptr(t):
@@ -407,3 +423,8 @@ def ptr(t):
     if t is None:
         return None
     return C.c_void_p(t.data_ptr())
+
+
+def stream(device):
+    """The current torch stream of ``device`` as the ``hipStream_t`` argument of a C call."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)

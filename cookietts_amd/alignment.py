@@ -6,8 +6,6 @@ batch at text2speech.py:565-568.  The reference copies the gate row to the host 
 because ...") and runs a dozen small torch ops for the second; here each is one call into the HIP library
 (``csrc/alignment.hip``) and nothing leaves the GPU.  No CPU fallback: a CPU tensor or a missing library raises.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -30,7 +28,7 @@ def get_first_over_thresh(x, threshold):
         raise ValueError(f"get_first_over_thresh expects [B, T], got {tuple(x.shape)}")
     out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = _lib.stream(x.device)
         _lib.check(_lib.lib().ctts_first_over_thresh_f32(_lib.ptr(x), x.shape[0], x.shape[1], float(threshold),
                                                          _lib.ptr(out), stream), "ctts_first_over_thresh_f32")
     return out
@@ -52,7 +50,7 @@ def alignment_metric(alignments, input_lengths=None, output_lengths=None, enc_mi
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     out = torch.empty(B, 6, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         _lib.check(lib.ctts_alignment_metric_f32(_lib.ptr(al), _lib.ptr(il), _lib.ptr(ol), B, dec, enc,
                                                  float(enc_min_thresh), _lib.ptr(out), _lib.ptr(ws), nbytes, stream),
                    "ctts_alignment_metric_f32")

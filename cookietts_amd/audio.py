@@ -103,12 +103,10 @@ class STFT(torch.nn.Module):
         y = y.detach().float().contiguous()
         B, T = y.shape
         with torch.cuda.device(device):
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            stream = _lib.stream(device)
             key = (device, n_mel)
             if key not in self._packed:
-                nbytes = lib.ctts_stft_packed_bytes(C.byref(cfg))
-                if nbytes == 0:
-                    raise _lib.HipLibraryError("unsupported STFT config: " + lib.ctts_last_error().decode())
+                nbytes = _lib.nbytes(lib.ctts_stft_packed_bytes, C.byref(cfg), what="unsupported STFT config")
                 blob = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
                 fb = self.forward_basis.detach().float().squeeze(1).contiguous().to(device)
                 mb = None if mel_basis is None else mel_basis.detach().float().contiguous().to(device)
@@ -135,7 +133,7 @@ class STFT(torch.nn.Module):
         lib = _lib.lib()
         cfg = self._c_config(0)
         with torch.cuda.device(device):
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            stream = _lib.stream(device)
             key = (device, 0)
             if key not in self._packed:
                 self._run(torch.zeros(1, max(self.filter_length, self.hop_length * 2), device=device), want_mag=True)
@@ -148,9 +146,7 @@ class STFT(torch.nn.Module):
         wkey = (device, n_mel, B, T)
         ws = self._ws.pop(wkey, None)
         if ws is None:
-            nbytes = _lib.lib().ctts_stft_workspace_bytes(C.byref(cfg), B, T)
-            if nbytes == 0:
-                raise _lib.HipLibraryError("STFT workspace query failed: " + _lib.lib().ctts_last_error().decode())
+            nbytes = _lib.nbytes(_lib.lib().ctts_stft_workspace_bytes, C.byref(cfg), B, T, what="STFT workspace query failed")
             ws = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
             while len(self._ws) >= 2:
                 self._ws.pop(next(iter(self._ws)))

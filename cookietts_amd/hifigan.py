@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _cache, _lib
-from .waveglow_ax import _WNConv
+from ._wn import WNConv
 
 __all__ = ["Generator", "load_model", "AttrDict"]
 
@@ -90,7 +90,7 @@ class _ResBlock(nn.Module):
     def __init__(self, kind, channels, kernel_size):
         super().__init__()
         def convs(n):
-            return nn.ModuleList([_WNConv((channels, channels, kernel_size)) for _ in range(n)])
+            return nn.ModuleList([WNConv((channels, channels, kernel_size)) for _ in range(n)])
         if kind == "1":
             self.convs1, self.convs2 = convs(3), convs(3)
         else:
@@ -100,8 +100,9 @@ class _ResBlock(nn.Module):
         return list(self.convs1) + list(self.convs2) if hasattr(self, "convs1") else list(self.convs)
 
 
-class Generator(nn.Module):
+class Generator(_cache.PackedModule):
     """``hifigan.models.Generator`` (models.py:94-148) over ``ctts_hifigan_forward_f32``."""
+    GPU_ONLY = "HiFi-GAN HIP path needs the model on a GPU (no CPU fallback)"
 
     def __init__(self, h):
         super().__init__()
@@ -114,9 +115,9 @@ class Generator(nn.Module):
         self.upsample_factor = 1
         for u in rates:
             self.upsample_factor *= int(u)
-        self.conv_pre = _WNConv((C0, int(_get(h, "num_mels")), 7))
+        self.conv_pre = WNConv((C0, int(_get(h, "num_mels")), 7))
         # ConvTranspose1d weight: [C_in, C_out, k]; weight norm's dim 0 is the INPUT channel there
-        self.ups = nn.ModuleList([_WNConv((C0 // 2 ** i, C0 // 2 ** (i + 1), k)) for i, k in enumerate(ksz)])
+        self.ups = nn.ModuleList([WNConv((C0 // 2 ** i, C0 // 2 ** (i + 1), k)) for i, k in enumerate(ksz)])
         for i, up in enumerate(self.ups):
             up.bias = nn.Parameter(torch.zeros(C0 // 2 ** (i + 1)))
         self.resblocks = nn.ModuleList()
@@ -125,30 +126,14 @@ class Generator(nn.Module):
             ch = C0 // 2 ** (i + 1)
             for k in rk:
                 self.resblocks.append(_ResBlock(str(_get(h, "resblock")), ch, k))
-        self.conv_post = _WNConv((1, ch, 7))
+        self.conv_post = WNConv((1, ch, 7))
         self._cfg = c_config(h)
         lib = _lib.lib()
         if lib.ctts_hifigan_packed_bytes(C.byref(self._cfg)) == 0:
-            raise NotImplementedError("cookietts_amd.HiFiGANGenerator: refused by the library: " + lib.ctts_last_error().decode())
-        self._packed, self._ws = None, {}
+            raise NotImplementedError("cookietts_amd.HiFiGANGenerator: refused by the library: " + _lib.last_error())
         self._compute_dtype = torch.float32
-        _cache.hook_invalidate(self)
 
     # ------------------------------------------------------------------ plumbing ----
-    def _invalidate(self):
-        self._packed, self._ws = None, {}
-
-    def _apply(self, fn, *a, **kw):
-        self._invalidate()
-        return super()._apply(fn, *a, **kw)
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        self._invalidate()
-        return super().load_state_dict(state_dict, strict=strict, **kw)
-
-    def repack(self):
-        self._invalidate()
-
     def set_compute_dtype(self, dtype):
         """Storage and product format of the whole generator: ``torch.float32`` (default: fp32 tensors, exact fp32 MFMA) or
         ``torch.float16``: weights and every stored activation as IEEE half, products on the f16 matrix pipe, accumulation,
@@ -163,7 +148,7 @@ class Generator(nn.Module):
             lib = _lib.lib()
             if lib.ctts_hifigan_packed_f16_bytes(C.byref(self._cfg)) == 0:
                 raise NotImplementedError("cookietts_amd.HiFiGANGenerator: half storage refused by the library: "
-                                          + lib.ctts_last_error().decode())
+                                          + _lib.last_error())
         if dtype != self._compute_dtype:
             self._compute_dtype = dtype
             self._invalidate()        # the packed blob and the workspaces are per format
@@ -175,7 +160,7 @@ class Generator(nn.Module):
 
     def remove_weight_norm(self):
         for m in self.modules():
-            if isinstance(m, _WNConv):
+            if isinstance(m, WNConv):
                 m.remove_weight_norm()
         self._invalidate()
 
@@ -190,7 +175,8 @@ class Generator(nn.Module):
 
     def folded_weights(self):
         """[(weight, bias)] fp32 in ``_convs`` order: ``w = g * v / ||v||`` evaluated in fp32 on the stored parameters
-        (after ``.half()``: on the fp16-rounded ones)."""
+        (after ``.half()``: on the fp16-rounded ones).  Deliberately NOT ``_wn.folded_weight``: that one folds on the device
+        through ``ctts_fold_weightnorm_f32``, this one in torch, and the two need not round alike - the packed bits would move."""
         out = []
         for m in self._convs():
             if getattr(m, "weight_v", None) is not None:
@@ -202,11 +188,9 @@ class Generator(nn.Module):
         return out
 
     def _ensure_packed(self, device):
-        key = _cache.param_key(self)
-        if self._packed is not None and self._packed[0] == device and self._packed[2] == key:
-            return self._packed[1]
-        if device.type != 'cuda':
-            raise _lib.HipLibraryError("HiFi-GAN HIP path needs the model on a GPU (no CPU fallback)")
+        return self.packed(device, lambda: self._pack(device))
+
+    def _pack(self, device):
         lib = _lib.lib()
         with torch.cuda.device(device):
             flat = torch.cat([t.reshape(-1) for wb in self.folded_weights() for t in wb]).to(device).contiguous()
@@ -214,13 +198,12 @@ class Generator(nn.Module):
             f16 = self._compute_dtype == torch.float16
             nbytes = (lib.ctts_hifigan_packed_f16_bytes if f16 else lib.ctts_hifigan_packed_bytes)(C.byref(self._cfg))
             blob = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            stream = _lib.stream(device)
             if flat.numel() != n:
                 raise _lib.HipLibraryError(f"HiFi-GAN: {flat.numel()} weights in the module tree, the library expects {n}")
             name = "ctts_hifigan_pack_f16" if f16 else "ctts_hifigan_pack_f32"
             _lib.check(getattr(lib, name)(C.byref(self._cfg), _lib.ptr(flat), flat.numel(), _lib.ptr(blob), stream), name)
             torch.cuda.current_stream(device).synchronize()     # `flat` dies with this frame
-        self._packed = (device, blob, key)
         return blob
 
     # ------------------------------------------------------------------ forward ----
@@ -240,17 +223,11 @@ class Generator(nn.Module):
         if T % 4:                                               # rows on 16-byte boundaries: vector staging in the first conv
             mel = torch.nn.functional.pad(mel, (0, 4 - T % 4))
         with torch.cuda.device(device):
-            ws = self._ws.get((device, B, T))
-            if ws is None:
-                nbytes = ws_bytes(C.byref(self._cfg), B, T)
-                if nbytes == 0:
-                    raise _lib.HipLibraryError("ctts_hifigan_workspace_bytes: " + lib.ctts_last_error().decode())
-                self._ws.clear()
-                ws = self._ws[(device, B, T)] = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+            ws = self.workspace((device, B, T), lambda: _lib.nbytes(ws_bytes, C.byref(self._cfg), B, T,
+                                                                    what="ctts_hifigan_workspace_bytes"), zero=False)
             audio = torch.empty(B, 1, T * self.upsample_factor, dtype=torch.float32, device=device)
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             _lib.check(getattr(lib, fwd)(C.byref(self._cfg), _lib.ptr(blob), _lib.ptr(mel), mel.shape[2], _lib.ptr(audio),
-                                         B, T, _lib.ptr(ws), ws.numel() * 4, stream), fwd)
+                                         B, T, _lib.ptr(ws), ws.numel() * 4, _lib.stream(device)), fwd)
         return audio if x.dtype == torch.float32 else audio.to(x.dtype)
 
 

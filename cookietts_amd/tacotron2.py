@@ -34,6 +34,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _cache, _lib
+from ._lib import PAD          # halo of the padded [B][C][ld] layout used by the conv primitives (>= kernel_size // 2)
 
 __all__ = ["Tacotron2", "Decoder", "load_model", "stop_step"]
 
@@ -131,7 +132,9 @@ def stop_step(gate_logits, gate_threshold, gate_delay, max_decoder_steps, state=
 PERSIST_REPROBE_AFTER = 16     # inference() calls a decoder spends on the per-launch form before it tries the persistent form again
 
 
-class Decoder(nn.Module):
+class Decoder(_cache.PackedModule):
+    GPU_ONLY = "Tacotron2 decoder HIP path needs the model on a GPU (no CPU fallback)"
+
     def __init__(self, hparams):
         super().__init__()
         hp = hparams
@@ -176,15 +179,12 @@ class Decoder(nn.Module):
         self.gate_layer = LinearNorm(hp.second_decoder_rnn_dim + self.memory_dim, 1, bias=True, w_init_gain='sigmoid')
         self._attn_cfg = (hp.attention_dim, hp.attention_location_n_filters, hp.attention_location_kernel_size)
         self._memory_in_dim = hp.encoder_LSTM_dim + hp.speaker_embedding_dim + hp.torchMoji_crushedDim + 1
-        self._packed = None
-        self._ws = {}
-        self._xchg = {}
+        self._xchg = {}          # like _ws: the live geometry -> its persistent-form exchange buffers (None where not built)
         self.use_persistent = _PERSIST_ON      # False: the six-launches-per-step decoder (CTTS_TACO_NO_PERSIST=1 at import)
         # per-decoder state of the persistent form: "unprobed" (its next launch is checked synchronously), "ok", or
         # "disabled" (a probe found the 256 workgroups not co-resident; re-probed after PERSIST_REPROBE_AFTER calls)
         self._persist = "unprobed"
         self._persist_fallback_calls = 0
-        _cache.hook_invalidate(self)
 
     @property
     def persistent_state(self):
@@ -208,31 +208,22 @@ class Decoder(nn.Module):
             location_kernel_size=K, window_range=self.windowed_attention_range)
 
     def _invalidate(self):
-        self._packed, self._ws, self._xchg = None, {}, {}
-
-    def _apply(self, fn, *a, **kw):
-        self._invalidate()
-        return super()._apply(fn, *a, **kw)
+        super()._invalidate()
+        self._xchg = {}
 
     def _ensure_packed(self, device):
-        key = _cache.param_key(self)
-        if self._packed is not None and self._packed[0] == device and self._packed[2] == key:
-            return self._packed[1]
-        if device.type != 'cuda':
-            raise _lib.HipLibraryError("Tacotron2 decoder HIP path needs the model on a GPU (no CPU fallback)")
+        return self.packed(device, lambda: self._pack(device))
+
+    def _pack(self, device):
         lib = _lib.lib()
         cfg = self.c_config()
-        nbytes = lib.ctts_taco_decoder_packed_bytes(C.byref(cfg))
-        if nbytes == 0:
-            raise _lib.HipLibraryError("unsupported decoder config: " + lib.ctts_last_error().decode())
+        nbytes = _lib.nbytes(lib.ctts_taco_decoder_packed_bytes, C.byref(cfg), what="unsupported decoder config")
         keep = []
 
         def dev(t):
-            t = t.detach().float().contiguous()
             if t.device != device:
                 raise RuntimeError(f"parameter on {t.device}, input on {device}: move the model first")
-            keep.append(t)
-            return t.data_ptr()
+            return _cache.dev(t, keep)
 
         def lstm(cell):
             return _lib.LstmWeights(dev(cell.weight_ih), dev(cell.weight_hh), dev(cell.bias_ih), dev(cell.bias_hh))
@@ -255,12 +246,10 @@ class Decoder(nn.Module):
         w.windowed_att_pos_offset = float(off.detach().reshape(-1)[0]) if torch.is_tensor(off) else float(off)
         w.exp_smoothing_factor = float(self.exp_smoothing_factor.detach().reshape(-1)[0])
         with torch.cuda.device(device):
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             blob = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-            _lib.check(lib.ctts_taco_decoder_pack(C.byref(cfg), C.byref(w), _lib.ptr(blob), stream),
+            _lib.check(lib.ctts_taco_decoder_pack(C.byref(cfg), C.byref(w), _lib.ptr(blob), _lib.stream(device)),
                        "ctts_taco_decoder_pack")
             torch.cuda.current_stream(device).synchronize()
-        self._packed = (device, blob, key)
         return blob
 
     # --------------------------------------------------------------------- the path ----
@@ -292,17 +281,11 @@ class Decoder(nn.Module):
         per_ws = MAX_GROUP
         if B >= BATCHED_FROM:
             per_ws = max(MAX_GROUP, int(lib.ctts_taco_decoder_max_batch(C.byref(cfg))))
-        groups = [(g0, min(g0 + per_ws, B)) for g0 in range(0, B, per_ws)]
-        key = (device, B, T)
-        wss = self._ws.get(key)
-        if wss is None:
-            wss = []
-            for g0, g1 in groups:
-                nbytes = lib.ctts_taco_decoder_workspace_bytes(C.byref(cfg), g1 - g0, T)
-                if nbytes == 0:
-                    raise _lib.HipLibraryError("decoder workspace query failed: " + lib.ctts_last_error().decode())
-                wss.append(torch.empty(nbytes // 4, dtype=torch.float32, device=device))
-            self._ws = {key: wss}
+        groups = tuple((g0, min(g0 + per_ws, B)) for g0 in range(0, B, per_ws))
+        key = (device, B, T, groups)      # the grouping is part of the geometry: BATCHED_FROM and the library's limit decide it
+        wss = self.workspace(key, lambda: [_lib.nbytes(lib.ctts_taco_decoder_workspace_bytes, C.byref(cfg), g1 - g0, T,
+                                                       what="decoder workspace query failed") for g0, g1 in groups], zero=False)
+        assert len(wss) == len(groups), (len(wss), groups)
         masks = [keep_masks if len(groups) == 1 else keep_masks[:, :, g0:g1].contiguous() for g0, g1 in groups]
         # persistent form (one launch per block of steps, weight-stationary fresh columns, granule all-gathers) where the
         # library builds it for this shape and device (0 bytes otherwise: the six-launches-per-step form).  The exchange
@@ -321,6 +304,7 @@ class Decoder(nn.Module):
                 nb = lib.ctts_taco_decoder_persistent_bytes(C.byref(cfg), g1 - g0, T)
                 xchg.append(torch.zeros(nb // 8, dtype=torch.int64, device=device) if nb else None)
             self._xchg = {key: xchg}
+        assert len(xchg) == len(groups), (len(xchg), groups)
         xchg = list(xchg)
 
         def ctl_words(xb):
@@ -342,7 +326,7 @@ class Decoder(nn.Module):
         hidden = torch.zeros(B, self.second_decoder_rnn_dim + self.memory_dim, max_steps, dtype=torch.float32, device=device) \
             if return_hidden_state else None
         with torch.cuda.device(device):
-            stream_obj = torch.cuda.current_stream(device)
+            stream_obj = torch.cuda.current_stream(device)       # kept: the stop-rule events are recorded on it
             stream = C.c_void_p(stream_obj.cuda_stream)
             for (g0, g1), ws in zip(groups, wss):
                 _lib.check(lib.ctts_taco_decoder_init_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(mem[g0:g1]), _lib.ptr(lens[g0:g1]),
@@ -432,15 +416,10 @@ MAX_GROUP = 4      # utterances per persistent-decoder / packed-LSTM workspace (
 # groups of MAX_GROUP on the persistent kernel.  Measured (profiles/r6_05): the batched step costs 63-64 us from 5 to 16 rows, a
 # persistent group of <= 4 rows 22 us - two groups (<= 8 rows) are ahead of one batched call, three are not
 BATCHED_FROM = int(os.environ.get("CTTS_TACO_BATCHED_FROM", "9"))
-PAD = 8            # halo of the padded [B][C][ld] layout used by the conv primitives (>= kernel_size // 2)
 
 
 def _ld_for(T):
     return (T + 127) // 128 * 128 + 2 * PAD
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class _HipConv1d:
@@ -451,9 +430,7 @@ class _HipConv1d:
         w = conv.weight.detach().float().contiguous()
         b = conv.bias.detach().float().contiguous() if conv.bias is not None else None
         self.desc = _lib.Conv1dDesc(c_in=w.shape[1], c_out=w.shape[0], kernel_size=w.shape[2], act=act, slope=slope)
-        nbytes = lib.ctts_conv1d_packed_bytes(C.byref(self.desc))
-        if nbytes == 0:
-            raise _lib.HipLibraryError("unsupported conv1d: " + lib.ctts_last_error().decode())
+        nbytes = _lib.nbytes(lib.ctts_conv1d_packed_bytes, C.byref(self.desc), what="unsupported conv1d")
         self.blob = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
         bn_t = [None] * 4
         eps = 1e-5
@@ -462,16 +439,17 @@ class _HipConv1d:
             eps = bn.eps
         with torch.cuda.device(device):
             _lib.check(lib.ctts_conv1d_pack_f32(C.byref(self.desc), _lib.ptr(w), _lib.ptr(b), *[_lib.ptr(t) for t in bn_t],
-                                               eps, _lib.ptr(self.blob), _stream(device)), "ctts_conv1d_pack_f32")
+                                               eps, _lib.ptr(self.blob), _lib.stream(device)), "ctts_conv1d_pack_f32")
             torch.cuda.current_stream(device).synchronize()
 
     def __call__(self, x, y, accumulate, B, T, ld):
         _lib.check(_lib.lib().ctts_conv1d_f32(C.byref(self.desc), _lib.ptr(self.blob), _lib.ptr(x), _lib.ptr(y),
-                                             1 if accumulate else 0, B, T, ld, PAD, _stream(x.device)), "ctts_conv1d_f32")
+                                             1 if accumulate else 0, B, T, ld, PAD, _lib.stream(x.device)), "ctts_conv1d_f32")
 
 
-class Postnet(nn.Module):
+class Postnet(_cache.PackedModule):
     """model.py:196-228; ``forward`` runs the 6 convs (+BN+tanh, residual every 3) as ``ctts_conv1d`` operators."""
+    GPU_ONLY = "Tacotron2 HIP path needs GPU tensors (no CPU fallback)"
 
     def __init__(self, hparams):
         super().__init__()
@@ -491,23 +469,15 @@ class Postnet(nn.Module):
             prev_output_layer = is_out
             self.convolutions.append(nn.Sequential(*layers))
 
-    def _invalidate(self):
-        self._hip_ops = None
-
     def _ops(self, device):
-        key = _cache.param_key(self)
-        if getattr(self, "_hip_ops", None) is None or self._hip_ops[0] != device or self._hip_ops[-1] != key:
+        def build():
             n = len(self.convolutions)
             ops = []
             for i, seq in enumerate(self.convolutions):
                 is_out = (bool(self.b_res) and bool(i % self.b_res == 0)) or (i + 1 == n)
                 ops.append(_HipConv1d(seq[0].conv, None if is_out else seq[1], 0 if is_out else 2, 0.0, device))
-            self._hip_ops = (device, ops, key)
-        return self._hip_ops[1]
-
-    def _apply(self, fn, *a, **kw):
-        self._hip_ops = None
-        return super()._apply(fn, *a, **kw)
+            return ops
+        return self.packed(device, build)
 
     @torch.no_grad()
     def forward(self, x):
@@ -515,9 +485,7 @@ class Postnet(nn.Module):
         if self.training:
             raise RuntimeError("Postnet HIP path is inference-only: call .eval()")
         device = x.device
-        if device.type != 'cuda':
-            raise _lib.HipLibraryError("Tacotron2 HIP path needs GPU tensors (no CPU fallback)")
-        ops = self._ops(device)
+        ops = self._ops(device)           # raises for a CPU tensor
         lib = _lib.lib()
         B, M, T = x.shape
         ld = _ld_for(T)
@@ -525,7 +493,7 @@ class Postnet(nn.Module):
         n = len(self.convolutions)
         with torch.cuda.device(device):
             x_orig = torch.zeros(B, M, ld, dtype=torch.float32, device=device)
-            _lib.check(lib.ctts_pad_rows_f32(_lib.ptr(xd), M * T, T, _lib.ptr(x_orig), B, M, T, ld, PAD, _stream(device)),
+            _lib.check(lib.ctts_pad_rows_f32(_lib.ptr(xd), M * T, T, _lib.ptr(x_orig), B, M, T, ld, PAD, _lib.stream(device)),
                        "ctts_pad_rows_f32")
             cur = x_orig
             for i, op in enumerate(ops):
@@ -538,14 +506,15 @@ class Postnet(nn.Module):
                     op(cur, y, False, B, T, ld)
                     cur = y
             out = torch.empty(B, M, T, dtype=torch.float32, device=device)
-            _lib.check(lib.ctts_unpad_rows_f32(_lib.ptr(x_orig), _lib.ptr(out), M * T, T, B, M, T, ld, PAD, _stream(device)),
+            _lib.check(lib.ctts_unpad_rows_f32(_lib.ptr(x_orig), _lib.ptr(out), M * T, T, B, M, T, ld, PAD, _lib.stream(device)),
                        "ctts_unpad_rows_f32")
         return out.to(x.dtype)
 
 
-class Encoder(nn.Module):
+class Encoder(_cache.PackedModule):
     """model.py:231-316; ``forward`` runs embedding gather, 3 x (conv + BN + LeakyReLU) and the packed BiLSTM as
     HIP operators and returns the memory tensor's encoder part in place."""
+    GPU_ONLY = "Tacotron2 HIP path needs GPU tensors (no CPU fallback)"
 
     def __init__(self, hparams):
         super().__init__()
@@ -567,16 +536,8 @@ class Encoder(nn.Module):
         self.LReLU = nn.LeakyReLU(negative_slope=0.01)
         self.sylps_layer = LinearNorm(hp.encoder_LSTM_dim, 1)
 
-    def _apply(self, fn, *a, **kw):
-        self._hip_ops = None
-        return super()._apply(fn, *a, **kw)
-
-    def _invalidate(self):
-        self._hip_ops = None
-
     def _ops(self, device):
-        key = _cache.param_key(self)
-        if getattr(self, "_hip_ops", None) is None or self._hip_ops[0] != device or self._hip_ops[-1] != key:
+        def build():
             lib = _lib.lib()
             convs = [_HipConv1d(seq[0].conv, seq[1], 1, 0.01, device) for seq in self.convolutions]
             I, H = self.lstm.input_size, self.lstm.hidden_size
@@ -587,12 +548,12 @@ class Encoder(nn.Module):
                           for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
                     w = _lib.LstmWeights(*[t.data_ptr() for t in ts])
                     blob = torch.zeros(lib.ctts_lstm_seq_packed_bytes(I, H) // 4, dtype=torch.float32, device=device)
-                    _lib.check(lib.ctts_lstm_seq_pack_f32(C.byref(w), I, H, _lib.ptr(blob), _stream(device)),
+                    _lib.check(lib.ctts_lstm_seq_pack_f32(C.byref(w), I, H, _lib.ptr(blob), _lib.stream(device)),
                                "ctts_lstm_seq_pack_f32")
                     torch.cuda.current_stream(device).synchronize()
                     packs.append(blob)
-            self._hip_ops = (device, convs, packs, key)
-        return self._hip_ops[1], self._hip_ops[2]
+            return convs, packs
+        return self.packed(device, build)
 
     @torch.no_grad()
     def forward_into_memory(self, embedding_weight, text_seq, text_lengths, speaker_ids, memory_in, hn):
@@ -609,7 +570,7 @@ class Encoder(nn.Module):
         S = self.encoder_speaker_embed_dim
         I, H = self.lstm.input_size, self.lstm.hidden_size
         with torch.cuda.device(device):
-            st = _stream(device)
+            st = _lib.stream(device)
             x = torch.zeros(B, E + S, ld, dtype=torch.float32, device=device)
             spk_w = self.encoder_speaker_embedding.weight.detach().float().contiguous() if S else None
             emb_w = embedding_weight.detach().float().contiguous()
@@ -630,9 +591,7 @@ class Encoder(nn.Module):
                 per = 256
             for g0 in range(0, B, per):
                 g1 = min(g0 + per, B)
-                nbytes = lib.ctts_lstm_seq_workspace_bytes(H, g1 - g0, ld)
-                if nbytes == 0:
-                    raise _lib.HipLibraryError("lstm_seq workspace query failed: " + lib.ctts_last_error().decode())
+                nbytes = _lib.nbytes(lib.ctts_lstm_seq_workspace_bytes, H, g1 - g0, ld, what="lstm_seq workspace query failed")
                 # both directions in lockstep: one launch per time step instead of two (the layer is launch-bound)
                 ws = torch.empty(2, nbytes // 4, dtype=torch.float32, device=device)
                 _lib.check(lib.ctts_lstm_biseq_f32(_lib.ptr(packs[0]), _lib.ptr(packs[1]), _lib.ptr(x[g0:g1]),
@@ -707,9 +666,7 @@ class Tacotron2(nn.Module):
         keep = []
 
         def dev(t):
-            t = t.detach().float().contiguous()
-            keep.append(t)
-            return t.data_ptr()
+            return _cache.dev(t, keep)
         sn = self.sylps_net.seq_layers
         mw = _lib.TacoMemoryWeights(
             sylps_w=dev(self.encoder.sylps_layer.linear_layer.weight), sylps_b=dev(self.encoder.sylps_layer.linear_layer.bias),
@@ -732,7 +689,7 @@ class Tacotron2(nn.Module):
             _lib.check(lib.ctts_taco_memory_sylps_f32(C.byref(mw), _lib.ptr(hn), _lib.ptr(spk64), _lib.ptr(tmh), _lib.ptr(gts),
                                                      _lib.ptr(memory), _lib.ptr(pred_sylps), B, txt_T, enc_dim,
                                                      self.speaker_embedding_dim, sn[0].linear_layer.out_features, tmh.shape[1],
-                                                     self.tm_linear.out_features, _stream(device)), "ctts_taco_memory_sylps_f32")
+                                                     self.tm_linear.out_features, _lib.stream(device)), "ctts_taco_memory_sylps_f32")
         pred_mel, pred_gate, alignments, hidden = self.decoder.inference(memory, memory_lengths=text_lengths, keep_masks=keep_masks,
                                                                          fixed_steps=fixed_steps, return_hidden_state=return_hidden_state)
         pred_mel_postnet = self.postnet(pred_mel) if hasattr(self, 'postnet') else pred_mel

@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _cache, _lib
+from ._wn import WNConv, folded_weight
 
 __all__ = ["WaveGlow", "Invertible1x1Conv", "WN"]
 
@@ -42,25 +43,6 @@ class _Conv1dParams(nn.Module):
             self.bias = nn.Parameter(torch.empty(out_ch).uniform_(-bound, bound))
         else:
             self.register_parameter("bias", None)
-
-
-class _WeightNormConv1d(nn.Module):
-    """``nn.utils.weight_norm(nn.Conv1d(...))`` as stored in checkpoints: weight_g, weight_v, bias."""
-
-    def __init__(self, in_ch, out_ch, k):
-        super().__init__()
-        plain = _Conv1dParams(in_ch, out_ch, k)
-        v = plain.weight.data
-        self.bias = plain.bias
-        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(out_ch, 1, 1).clone())
-        self.weight_v = nn.Parameter(v.clone())
-
-    def remove_weight_norm(self):
-        if hasattr(self, "weight_v") and self.weight_v is not None:
-            v, g = self.weight_v.data, self.weight_g.data
-            w = v * (g / v.flatten(1).norm(dim=1).view(-1, 1, 1))
-            del self._parameters["weight_g"], self._parameters["weight_v"]
-            self.weight = nn.Parameter(w)
 
 
 class Invertible1x1Conv(nn.Module):
@@ -92,23 +74,38 @@ class WN(nn.Module):
             self.speaker_embed = nn.Embedding(_lib.N_SPEAKERS, speaker_embed_dim)
             self.speaker_embed.weight.data.mul_(0.05)
         hidden = 256  # glow.py:153
-        self.start = _WeightNormConv1d(n_in_channels, n_channels, 1)
+        self.start = WNConv((n_channels, n_in_channels, 1))
         self.end = _Conv1dParams(n_channels, 2 * n_in_channels, 1)
         self.end.weight.data.zero_()
         self.end.bias.data.zero_()
         self.cond_layers = nn.ModuleList([
-            _WeightNormConv1d(n_mel_channels + speaker_embed_dim, hidden, 1),
-            _WeightNormConv1d(hidden, hidden, 1),
-            _WeightNormConv1d(hidden, 2 * n_channels * n_layers, 1)])
+            WNConv((hidden, n_mel_channels + speaker_embed_dim, 1)),
+            WNConv((hidden, hidden, 1)),
+            WNConv((2 * n_channels * n_layers, hidden, 1))])
         self.in_layers = nn.ModuleList()
         self.res_skip_layers = nn.ModuleList()
         for i in range(n_layers):
-            self.in_layers.append(_WeightNormConv1d(n_channels, 2 * n_channels, kernel_size))
+            self.in_layers.append(WNConv((2 * n_channels, n_channels, kernel_size)))
             rs = 2 * n_channels if i < n_layers - 1 else n_channels
-            self.res_skip_layers.append(_WeightNormConv1d(n_channels, rs, 1))
+            self.res_skip_layers.append(WNConv((rs, n_channels, 1)))
 
 
-class WaveGlow(nn.Module):
+# arithmetic mode -> (bytes query of the 16-bit blob, its pack-flow call, workspace query, infer entry point).  Every mode packs
+# the fp32 blob too (upsampling, cond stacks, mixing); IEEE half shares the bf16 layouts, hence the bf16 size queries
+_MODES = {
+    "f32": (None, None, "ctts_waveglow_workspace_bytes", "ctts_waveglow_infer_spk_f32"),
+    "bf16": ("ctts_waveglow_packed_bf16_bytes", "ctts_waveglow_pack_flow_bf16", "ctts_waveglow_workspace_bf16_bytes",
+             "ctts_waveglow_infer_spk_bf16"),
+    "bf16x3": ("ctts_waveglow_packed_bf16x3_bytes", "ctts_waveglow_pack_flow_bf16x3", "ctts_waveglow_workspace_bf16x3_bytes",
+               "ctts_waveglow_infer_spk_bf16x3"),
+    "f16": ("ctts_waveglow_packed_bf16_bytes", "ctts_waveglow_pack_flow_f16", "ctts_waveglow_workspace_bf16_bytes",
+            "ctts_waveglow_infer_spk_f16"),
+}
+
+
+class WaveGlow(_cache.PackedModule):
+    GPU_ONLY = "WaveGlow HIP path needs the model on a GPU (no CPU fallback)"
+
     def __init__(self, yoyo, yoyo_WN, n_mel_channels, n_flows, n_group, n_early_every, n_early_size,
                  memory_efficient, spect_scaling, upsample_mode, WN_config, win_length, hop_length):
         super().__init__()
@@ -172,11 +169,8 @@ class WaveGlow(nn.Module):
             self.WN.append(WN(n_half, n_mel_channels * n_group, **WN_config))
         self.n_remaining_channels = n_remaining_channels
 
-        self._packed = None          # (device, fp32 blob, bf16 blob or None, param key)
-        _cache.hook_invalidate(self)
         self._compute_dtype = torch.float32
         self._f32_gemm_mode = None   # None: the library default; see set_f32_gemm_mode
-        self._workspaces = {}        # (device, B, F) -> zero-initialised workspace tensor
 
     # ------------------------------------------------------------------ plumbing ----
     def c_config(self):
@@ -199,19 +193,10 @@ class WaveGlow(nn.Module):
         return self
 
     def _invalidate(self):
-        self._packed = None
-        self._workspaces = {}
+        super()._invalidate()
         for m in self.convinv:
             if hasattr(m, 'W_inverse'):
                 del m.W_inverse
-
-    def _apply(self, fn, *a, **kw):
-        self._invalidate()
-        return super()._apply(fn, *a, **kw)
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        self._invalidate()
-        return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def set_compute_dtype(self, dtype):
         """torch.float32 (default: exact fp32 MFMA path), torch.bfloat16 (BASELINE config 3: WN GEMMs on
@@ -232,17 +217,13 @@ class WaveGlow(nn.Module):
         self._invalidate()
         return self
 
-    def _use_bf16(self):
-        """0 = fp32 MFMA, 1 = bf16, 3 = split bf16 (the number of bf16 products per contraction), 16 = IEEE half."""
+    def _mode(self):
+        """Key of ``_MODES``: what ``set_compute_dtype`` chose; ``model.bfloat16()`` selects bf16 through the parameter dtype."""
         if self._compute_dtype == "bf16x3":
-            return 3
+            return "bf16x3"
         if self._compute_dtype == torch.float16:
-            return 16
-        return 1 if (self._compute_dtype == torch.bfloat16 or next(self.parameters()).dtype == torch.bfloat16) else 0
-
-    def repack(self):
-        """Call after modifying parameters in place; the next infer re-ingests the weights."""
-        self._invalidate()
+            return "f16"
+        return "bf16" if (self._compute_dtype == torch.bfloat16 or next(self.parameters()).dtype == torch.bfloat16) else "f32"
 
     @staticmethod
     def remove_weightnorm(model):
@@ -252,21 +233,6 @@ class WaveGlow(nn.Module):
                 layer.remove_weight_norm()
         model._invalidate()
         return model
-
-    def _dense_weight(self, layer, stream, keep):
-        """fp32 contiguous folded conv weight on the model's device (fold runs in the HIP library)."""
-        lib = _lib.lib()
-        if getattr(layer, 'weight_v', None) is not None:
-            v = layer.weight_v.detach().float().contiguous()
-            g = layer.weight_g.detach().float().contiguous()
-            w = torch.empty_like(v)
-            _lib.check(lib.ctts_fold_weightnorm_f32(_lib.ptr(v), _lib.ptr(g), _lib.ptr(w), v.shape[0],
-                                                   v[0].numel(), stream), "ctts_fold_weightnorm_f32")
-            keep += [v, g, w]
-            return w
-        w = layer.weight.detach().float().contiguous()
-        keep.append(w)
-        return w
 
     @staticmethod
     def _scaled(t, alpha, stream, keep):
@@ -280,30 +246,23 @@ class WaveGlow(nn.Module):
         return y
 
     def _ensure_packed(self, device):
-        key = _cache.param_key(self)
-        if self._packed is not None and self._packed[0] == device and self._packed[3] == key:
-            return self._packed[1], self._packed[2]
-        if self._packed is not None:
-            self._invalidate()
-        if device.type != 'cuda':
-            raise _lib.HipLibraryError("WaveGlow HIP path needs the model on a GPU (no CPU fallback)")
-        use_bf16 = self._use_bf16()
+        """-> (fp32 blob, 16-bit blob or None) of the current parameters and mode."""
+        return self.packed(device, lambda: self._pack(device))
+
+    def _pack(self, device):
+        bytes16, pack16, _, _ = _MODES[self._mode()]
         lib = _lib.lib()
         for p in self.parameters():
             if p.device != device:
                 raise RuntimeError(f"parameter on {p.device}, input on {device}: move the model first")
         cfg = self.c_config()
-        nbytes = lib.ctts_waveglow_packed_bytes(C.byref(cfg))
-        if nbytes == 0:
-            raise _lib.HipLibraryError("unsupported WaveGlow config: " + lib.ctts_last_error().decode())
+        nbytes = _lib.nbytes(lib.ctts_waveglow_packed_bytes, C.byref(cfg), what="unsupported WaveGlow config")
         with torch.cuda.device(device):
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            stream = _lib.stream(device)
             blob = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
             bblob = None
-            if use_bf16:
-                nb = (lib.ctts_waveglow_packed_bf16x3_bytes if use_bf16 == 3 else lib.ctts_waveglow_packed_bf16_bytes)(C.byref(cfg))
-                if nb == 0:
-                    raise _lib.HipLibraryError("unsupported bf16 WaveGlow config: " + lib.ctts_last_error().decode())
+            if bytes16:
+                nb = _lib.nbytes(getattr(lib, bytes16), C.byref(cfg), what="unsupported bf16 WaveGlow config")
                 bblob = torch.zeros(nb // 2, dtype=torch.int16, device=device)
             keep = []
             up_w = self.upsample.weight.detach().float().contiguous()
@@ -324,23 +283,17 @@ class WaveGlow(nn.Module):
             for k in range(self.n_flows):
                 wn = self.WN[k]
                 fw = _lib.WaveGlowFlowWeights()
-
-                def dev(t):
-                    t = t.detach().float().contiguous()
-                    keep.append(t)
-                    return t.data_ptr()
-
-                fw.start_w = self._dense_weight(wn.start, stream, keep).data_ptr()
-                fw.start_b = dev(wn.start.bias)
+                fw.start_w = folded_weight(wn.start, stream, keep).data_ptr()
+                fw.start_b = _cache.dev(wn.start.bias, keep)
                 for j in range(3):
-                    fw.cond_w[j] = self._dense_weight(wn.cond_layers[j], stream, keep).data_ptr()
-                    fw.cond_b[j] = dev(wn.cond_layers[j].bias)
+                    fw.cond_w[j] = folded_weight(wn.cond_layers[j], stream, keep).data_ptr()
+                    fw.cond_b[j] = _cache.dev(wn.cond_layers[j].bias, keep)
                 arrs = {}
                 for name, layers in (("in", wn.in_layers), ("rs", wn.res_skip_layers)):
                     wa = (C.c_void_p * n_layers)()
                     ba = (C.c_void_p * n_layers)()
                     for i in range(n_layers):
-                        wt = self._dense_weight(layers[i], stream, keep)
+                        wt = folded_weight(layers[i], stream, keep)
                         bt = layers[i].bias.detach().float().contiguous()
                         if name == "rs" and hasattr(wn, 'alpha_i'):
                             # ReZero (glow.py:211-212): res_skip(acts) * alpha_i == (alpha*W) acts + alpha*b, folded once
@@ -350,8 +303,8 @@ class WaveGlow(nn.Module):
                     arrs[name] = (wa, ba)
                 fw.in_w, fw.in_b = arrs["in"]
                 fw.rs_w, fw.rs_b = arrs["rs"]
-                fw.end_w = dev(wn.end.weight)
-                fw.end_b = dev(wn.end.bias)
+                fw.end_w = _cache.dev(wn.end.weight, keep)
+                fw.end_b = _cache.dev(wn.end.bias, keep)
                 # glow.py:90-99: W.float().inverse(), cached on the module as W_inverse
                 W = self.convinv[k].conv.weight.detach().squeeze(-1)
                 W_inverse = W.float().cpu().inverse().to(device).contiguous()   # host fp32 inverse
@@ -359,33 +312,13 @@ class WaveGlow(nn.Module):
                 keep.append(W_inverse)
                 fw.w_inverse = W_inverse.data_ptr()
                 if wn.speaker_embed_dim:
-                    fw.speaker_embed = dev(wn.speaker_embed.weight)
+                    fw.speaker_embed = _cache.dev(wn.speaker_embed.weight, keep)
                 _lib.check(lib.ctts_waveglow_pack_flow(C.byref(cfg), k, C.byref(fw), _lib.ptr(blob), stream),
                            f"ctts_waveglow_pack_flow({k})")
                 if bblob is not None:
-                    pack16 = {1: lib.ctts_waveglow_pack_flow_bf16, 3: lib.ctts_waveglow_pack_flow_bf16x3,
-                          16: lib.ctts_waveglow_pack_flow_f16}[use_bf16]
-                    _lib.check(pack16(C.byref(cfg), k, C.byref(fw), _lib.ptr(bblob), stream),
-                               f"ctts_waveglow_pack_flow_bf16({k})")
+                    _lib.check(getattr(lib, pack16)(C.byref(cfg), k, C.byref(fw), _lib.ptr(bblob), stream), f"{pack16}({k})")
             torch.cuda.current_stream(device).synchronize()   # dense temporaries may now be freed
-        self._packed = (device, blob, bblob, key)
         return blob, bblob
-
-    def _workspace(self, device, B, F, bf16=False):
-        key = (device, B, F, bf16)
-        ws = self._workspaces.get(key)
-        if ws is None:
-            lib = _lib.lib()
-            cfg = self.c_config()
-            query = {0: lib.ctts_waveglow_workspace_bytes, 1: lib.ctts_waveglow_workspace_bf16_bytes,
-                     3: lib.ctts_waveglow_workspace_bf16x3_bytes, 16: lib.ctts_waveglow_workspace_bf16_bytes}[int(bf16)]
-            nbytes = query(C.byref(cfg), B, F)
-            if nbytes == 0:
-                raise _lib.HipLibraryError("workspace query failed: " + lib.ctts_last_error().decode())
-            self._workspaces.clear()     # one live geometry at a time
-            ws = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
-            self._workspaces[key] = ws
-        return ws
 
     def steps_for(self, frames):
         return frames * self.hop_length // self.n_group
@@ -421,20 +354,16 @@ class WaveGlow(nn.Module):
                 raise IndexError("speaker id out of range of the embedding table")
             ids = speaker_id.detach().to(device=device, dtype=torch.int64).reshape(-1).contiguous()
             assert ids.shape[0] == B, (tuple(ids.shape), B)
-        mode = self._use_bf16()
-        ws = self._workspace(device, B, F, bf16=mode)
-        wave = torch.empty(B, L * self.n_group, dtype=torch.float32, device=device)
+        mode = self._mode()
+        _, _, ws_bytes, infer = _MODES[mode]
         cfg = self.c_config()
+        ws = self.workspace((device, B, F, mode), lambda: _lib.nbytes(getattr(lib, ws_bytes), C.byref(cfg), B, F,
+                                                                      what="workspace query failed"))
+        wave = torch.empty(B, L * self.n_group, dtype=torch.float32, device=device)
+        blobs = (blob,) if bblob is None else (blob, bblob)        # the 16-bit entry points take both blobs
         with torch.cuda.device(device):
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            if bblob is not None:
-                name16 = {1: "ctts_waveglow_infer_spk_bf16", 3: "ctts_waveglow_infer_spk_bf16x3", 16: "ctts_waveglow_infer_spk_f16"}[mode]
-                _lib.check(getattr(lib, name16)(C.byref(cfg), _lib.ptr(blob), _lib.ptr(bblob), _lib.ptr(mel), _lib.ptr(z),
-                                                _lib.ptr(ids), _lib.ptr(wave), B, F, _lib.ptr(ws), ws.numel() * 4, stream), name16)
-            else:
-                _lib.check(lib.ctts_waveglow_infer_spk_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(mel), _lib.ptr(z),
-                                                          _lib.ptr(ids), _lib.ptr(wave), B, F, _lib.ptr(ws),
-                                                          ws.numel() * 4, stream), "ctts_waveglow_infer_spk_f32")
+            _lib.check(getattr(lib, infer)(C.byref(cfg), *map(_lib.ptr, blobs), _lib.ptr(mel), _lib.ptr(z), _lib.ptr(ids),
+                                           _lib.ptr(wave), B, F, _lib.ptr(ws), ws.numel() * 4, _lib.stream(device)), infer)
         return wave.to(spect.dtype)
 
     def infer(self, spect, speaker_id=None, sigma=1.0):

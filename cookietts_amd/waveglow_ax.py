@@ -27,8 +27,6 @@ NotImplementedError.  The conditioning stacks are composed on the host from oper
 from __future__ import annotations
 
 import ctypes as C
-import math
-
 import numpy as np
 
 import torch
@@ -36,31 +34,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _cache, _lib
+from ._wn import WNConv, folded_weight
+from ._lib import PAD          # halo of the frame-rate padded rows (>= k/2 of every cond conv, k <= 11)
 
 __all__ = ["WaveGlow"]
-
-
-class _WNConv(nn.Module):
-    """weight-normed conv parameters (weight_g, weight_v, bias) of arbitrary kernel rank."""
-
-    def __init__(self, shape):
-        super().__init__()
-        fan_in = 1
-        for d in shape[1:]:
-            fan_in *= d
-        v = torch.empty(*shape)
-        nn.init.kaiming_uniform_(v, a=math.sqrt(5))
-        bound = 1.0 / math.sqrt(fan_in)
-        self.bias = nn.Parameter(torch.empty(shape[0]).uniform_(-bound, bound))
-        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(shape[0], *([1] * (len(shape) - 1))).clone())
-        self.weight_v = nn.Parameter(v)
-
-    def remove_weight_norm(self):
-        if getattr(self, "weight_v", None) is not None:
-            v, g = self.weight_v.data, self.weight_g.data
-            w = v * (g / v.flatten(1).norm(dim=1).view(g.shape))
-            del self._parameters["weight_g"], self._parameters["weight_v"]
-            self.weight = nn.Parameter(w)
 
 
 class _WN2d(nn.Module):
@@ -72,7 +49,7 @@ class _WN2d(nn.Module):
         kh, kw = wn['kernel_size_h'], wn['kernel_size_w']
         self.n_layers, self.n_channels = n_layers, C_
         sdim = wn.get('speaker_embed_dim', 0)
-        self.start = _WNConv((C_, 1, 1, 1))
+        self.start = WNConv((C_, 1, 1, 1))
         self.end = nn.Module()
         self.end.weight = nn.Parameter(torch.zeros(2, C_, 1, 1))                # zero-init, glow_ax.py:454-457
         self.end.bias = nn.Parameter(torch.zeros(2))
@@ -88,15 +65,15 @@ class _WN2d(nn.Module):
                                                        wn['transposed_conv_scales'], False, False, False, False)
             cond_out = hid
         dims = [cond_in + sdim] + [wn['cond_hidden_channels']] * (wn['cond_layers'] - 1) + [cond_out]
-        self.cond_layers = nn.ModuleList([_WNConv((dims[l + 1], dims[l], k)) for l in range(wn['cond_layers'])])
+        self.cond_layers = nn.ModuleList([WNConv((dims[l + 1], dims[l], k)) for l in range(wn['cond_layers'])])
         if wn.get('seperable_conv', False) and not (kh == 1 and kw == 1):       # glow_ax.py:521-531
-            self.in_layers = nn.ModuleList([nn.ModuleList([_WNConv((C_, 1, kh, kw)), _WNConv((2 * C_, C_, 1, 1))])
+            self.in_layers = nn.ModuleList([nn.ModuleList([WNConv((C_, 1, kh, kw)), WNConv((2 * C_, C_, 1, 1))])
                                             for _ in range(n_layers)])
         else:
-            self.in_layers = nn.ModuleList([_WNConv((2 * C_, C_, kh, kw)) for _ in range(n_layers)])
+            self.in_layers = nn.ModuleList([WNConv((2 * C_, C_, kh, kw)) for _ in range(n_layers)])
         merge = bool(wn.get('merge_res_skip', False))                            # glow_ax.py:535-538
         self.res_skip_layers = nn.ModuleList([
-            _WNConv((2 * C_ if (i < n_layers - 1 and not merge) else C_, C_, 1, 1)) for i in range(n_layers)]
+            WNConv((2 * C_ if (i < n_layers - 1 and not merge) else C_, C_, 1, 1)) for i in range(n_layers)]
             if wn.get('res_skip', True) else [])                                 # res_skip=False: acts are the skip (:609)
 
 
@@ -110,7 +87,7 @@ class _WN1d(nn.Module):
         assert ks % 2 == 1 and C_ % 2 == 0
         self.n_layers, self.n_channels = n_layers, C_
         sdim = wn.get('speaker_embed_dim', 0)
-        self.start = _WNConv((C_, n_in, 1))
+        self.start = WNConv((C_, n_in, 1))
         self.end = nn.Module()
         self.end.weight = nn.Parameter(torch.zeros(2 * n_in, C_, 1))            # zero-init, glow_ax.py:278-281
         self.end.bias = nn.Parameter(torch.zeros(2 * n_in))
@@ -126,11 +103,11 @@ class _WN1d(nn.Module):
                                                        wn['transposed_conv_scales'], False, False, False, False)
             cond_out = hid
         dims = [cond_in + sdim] + [wn['cond_hidden_channels']] * (wn['cond_layers'] - 1) + [cond_out]
-        self.cond_layers = nn.ModuleList([_WNConv((dims[l + 1], dims[l], k)) for l in range(wn['cond_layers'])])
-        self.in_layers = nn.ModuleList([_WNConv((2 * C_, C_, ks)) for _ in range(n_layers)])
+        self.cond_layers = nn.ModuleList([WNConv((dims[l + 1], dims[l], k)) for l in range(wn['cond_layers'])])
+        self.in_layers = nn.ModuleList([WNConv((2 * C_, C_, ks)) for _ in range(n_layers)])
         merge = bool(wn.get('merge_res_skip', False))                            # glow_ax.py:352-355
         self.res_skip_layers = nn.ModuleList([
-            _WNConv((2 * C_ if (i < n_layers - 1 and not merge) else C_, C_, 1)) for i in range(n_layers)]
+            WNConv((2 * C_ if (i < n_layers - 1 and not merge) else C_, C_, 1)) for i in range(n_layers)]
             if wn.get('res_skip', True) else [])                                 # res_skip=False: acts are the skip (:401)
 
 
@@ -150,9 +127,6 @@ class _Coupling(nn.Module):
     def __init__(self, wn):
         super().__init__()
         self.WN = wn
-
-
-PAD = 8          # halo of the frame-rate padded rows (>= k/2 of every cond conv, k <= 11)
 
 
 def _act_code(name, negative_slope):
@@ -191,9 +165,7 @@ class _CondConv:
             wp, b, act = wp * 0.5, b * 0.5, 2
         self.desc = _lib.Conv1dDesc(c_in=self.c_in, c_out=out_c, kernel_size=k, act=act, slope=slope,
                                     f32_gemm_mode=gemm_mode)
-        nbytes = lib.ctts_conv1d_packed_bytes(C.byref(self.desc))
-        if nbytes == 0:
-            raise _lib.HipLibraryError("unsupported cond conv: " + lib.ctts_last_error().decode())
+        nbytes = _lib.nbytes(lib.ctts_conv1d_packed_bytes, C.byref(self.desc), what="unsupported cond conv")
         self.blob = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
         _lib.check(lib.ctts_conv1d_pack_f32(C.byref(self.desc), _lib.ptr(wp), _lib.ptr(b), None, None, None, None, 1e-5,
                                            _lib.ptr(self.blob), stream), "ctts_conv1d_pack_f32")
@@ -294,7 +266,9 @@ class _TransposedUpsampleNet(nn.Module):
         return [m for m in self.t_convs if isinstance(m, nn.ConvTranspose1d)]
 
 
-class WaveGlow(nn.Module):
+class WaveGlow(_cache.PackedModule):
+    GPU_ONLY = "WaveFlow HIP path needs the model on a GPU (no CPU fallback)"
+
     def __init__(self, n_mel_channels, n_flows, n_group, n_early_every, n_early_size, memory_efficient,
                  spect_scaling, upsample_mode, upsample_first, speaker_embed, cond_layers, cond_hidden_channels,
                  cond_output_channels, cond_kernel_size, cond_residual, cond_padding_mode, WN_config, win_length,
@@ -400,7 +374,7 @@ class WaveGlow(nn.Module):
                 self.res_conv = nn.Conv1d(self.cond_in_channels, out_c, 1)       # ax:80-81
             k = 2 * cond_kernel_size - 1                                         # ax:83
             dims = [self.cond_in_channels] + [cond_hidden_channels] * (cond_layers - 1) + [out_c]
-            self.cond_layers = nn.ModuleList([_WNConv((dims[l + 1], dims[l], k)) for l in range(cond_layers)])
+            self.cond_layers = nn.ModuleList([WNConv((dims[l + 1], dims[l], k)) for l in range(cond_layers)])
             wn_cond = out_c
         if self.upsample_early:                                                  # ax:116-126
             t_out = transposed_conv_output_dim if transposed_conv_output_dim is not None else wn_cond
@@ -452,11 +426,8 @@ class WaveGlow(nn.Module):
                         and self.shift_spect == 0. and self.scale_spect == 1.
                         and wn.get('cond_layers', 1) == 1 and wn.get('cond_kernel_size', 1) == 1
                         and self._act_wn[0] == 0)
-        self._packed = None
-        self._ws = {}
         self._f32_gemm_mode = None
         self._compute_dtype = torch.float32
-        _cache.hook_invalidate(self)
 
     # ------------------------------------------------------------------ plumbing ----
     def c_config(self):
@@ -508,7 +479,7 @@ class WaveGlow(nn.Module):
             lib = _lib.lib()
             cfg = self.c_config_1d()
             if lib.ctts_wgax_packed_f16_bytes(C.byref(cfg)) == 0:
-                raise NotImplementedError("half storage refused by the library: " + lib.ctts_last_error().decode())
+                raise NotImplementedError("half storage refused by the library: " + _lib.last_error())
         if dtype != self._compute_dtype:
             self._compute_dtype = dtype
             self._invalidate()        # the packed blob and the workspaces are per format
@@ -527,73 +498,40 @@ class WaveGlow(nn.Module):
                                f32_gemm_mode=_lib.model_gemm_mode(self._f32_gemm_mode))
 
     def _invalidate(self):
-        self._packed, self._ws = None, {}
+        super()._invalidate()
         for m in (self.convinv if isinstance(self.convinv, nn.ModuleList) else []):
             if hasattr(m, 'W_inverse'):
                 del m.W_inverse
 
-    def _apply(self, fn, *a, **kw):
-        self._invalidate()
-        return super()._apply(fn, *a, **kw)
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        self._invalidate()
-        return super().load_state_dict(state_dict, strict=strict, **kw)
-
-    def repack(self):
-        self._invalidate()
-
     def remove_weightnorm(self):
         for m in self.modules():
-            if isinstance(m, _WNConv):
+            if isinstance(m, WNConv):
                 m.remove_weight_norm()
         self._invalidate()
-
-    def _dense(self, layer, stream, keep):
-        lib = _lib.lib()
-        if getattr(layer, 'weight_v', None) is not None:
-            v = layer.weight_v.detach().float().contiguous()
-            g = layer.weight_g.detach().float().contiguous()
-            w = torch.empty_like(v)
-            _lib.check(lib.ctts_fold_weightnorm_f32(_lib.ptr(v), _lib.ptr(g), _lib.ptr(w), v.shape[0], v[0].numel(),
-                                                   stream), "ctts_fold_weightnorm_f32")
-            keep += [v, g, w]
-            return w
-        w = layer.weight.detach().float().contiguous()
-        keep.append(w)
-        return w
 
     def _ensure_packed(self, device):
         """-> (blob, cond_ops): packed WaveFlow weights, and (unless the cond layer is folded) the conv operators
         of the conditioning stacks {'model': [...], 'wn': [[...] per flow]}."""
-        key = _cache.param_key(self)
-        if self._packed is not None and self._packed[0] == device and self._packed[3] == key:
-            return self._packed[1], self._packed[2]
-        if device.type != 'cuda':
-            raise _lib.HipLibraryError("WaveFlow HIP path needs the model on a GPU (no CPU fallback)")
+        return self.packed(device, lambda: self._pack(device))
+
+    def _pack(self, device):
         lib = _lib.lib()
         wn_cfg = self.WN_config
         n_layers = wn_cfg['n_layers']
+        half = self._compute_dtype == torch.float16
         if self.waveflow:
             cfg = self.c_config()
-            nbytes = lib.ctts_waveflow_packed_bytes(C.byref(cfg))
+            size, pack_flow, name = lib.ctts_waveflow_packed_bytes, lib.ctts_waveflow_pack_flow, "ctts_waveflow_pack_flow"
         else:
             cfg = self.c_config_1d()
-            half = self._compute_dtype == torch.float16
-            nbytes = (lib.ctts_wgax_packed_f16_bytes if half else lib.ctts_wgax_packed_bytes)(C.byref(cfg))
-            pack_flow = lib.ctts_wgax_pack_flow_f16 if half else lib.ctts_wgax_pack_flow
-        if nbytes == 0:
-            raise _lib.HipLibraryError("unsupported ax-core config: " + lib.ctts_last_error().decode())
+            size = lib.ctts_wgax_packed_f16_bytes if half else lib.ctts_wgax_packed_bytes
+            pack_flow, name = (lib.ctts_wgax_pack_flow_f16 if half else lib.ctts_wgax_pack_flow), "ctts_wgax_pack_flow"
+        nbytes = _lib.nbytes(size, C.byref(cfg), what="unsupported ax-core config")
         sep = self.waveflow and isinstance(self.WN[0].WN.in_layers[0], nn.ModuleList)
         with torch.cuda.device(device):
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            stream = _lib.stream(device)
             blob = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
             keep = []
-
-            def dev(t):
-                t = t.detach().float().contiguous()
-                keep.append(t)
-                return t.data_ptr()
 
             def arr(fn):
                 a = (C.c_void_p * n_layers)()
@@ -606,51 +544,34 @@ class WaveGlow(nn.Module):
                 eye = torch.eye(wn_cfg['n_channels'], dtype=torch.float32, device=device).contiguous()
                 zero_b = torch.zeros(wn_cfg['n_channels'], dtype=torch.float32, device=device)
                 keep += [eye, zero_b]
+
             for k in range(self.n_flows):
+                # start / in / rs / end / w_inverse are the same fields in both cores' structs; the 2-D core adds cond and dw
                 wn = self.WN[k].WN
-                if not self.waveflow:
-                    fw = _lib.WgaxFlowWeights()
-                    fw.start_w = self._dense(wn.start, stream, keep).data_ptr()
-                    fw.start_b = dev(wn.start.bias)
-                    fw.in_w = arr(lambda i: self._dense(wn.in_layers[i], stream, keep).data_ptr())
-                    fw.in_b = arr(lambda i: dev(wn.in_layers[i].bias))
-                    fw.rs_w = arr(lambda i: eye.data_ptr() if no_rs else self._dense(wn.res_skip_layers[i], stream, keep).data_ptr())
-                    fw.rs_b = arr(lambda i: zero_b.data_ptr() if no_rs else dev(wn.res_skip_layers[i].bias))
-                    fw.end_w = dev(wn.end.weight)
-                    fw.end_b = dev(wn.end.bias)
-                    if self.channel_mixing == '1x1conv':
-                        # efficient_modules.py:271-276: W.float().inverse(), cached on the module as W_inverse
-                        W = self.convinv[k].weight.detach().squeeze(-1)
-                        W_inverse = W.float().cpu().inverse().to(device).contiguous()
-                        self.convinv[k].W_inverse = W_inverse[..., None]
-                        keep.append(W_inverse)
-                        fw.w_inverse = W_inverse.data_ptr()
-                    _lib.check(pack_flow(C.byref(cfg), k, C.byref(fw), _lib.ptr(blob), stream), f"ctts_wgax_pack_flow({k})")
-                    continue
-                fw = _lib.WaveFlowFlowWeights()
-                fw.start_w = self._dense(wn.start, stream, keep).data_ptr()
-                fw.start_b = dev(wn.start.bias)
-                if self._folded:
-                    fw.cond_w = self._dense(wn.cond_layers[0], stream, keep).data_ptr()
-                    fw.cond_b = dev(wn.cond_layers[0].bias)
+                fw = _lib.WaveFlowFlowWeights() if self.waveflow else _lib.WgaxFlowWeights()
                 gemm = (lambda i: wn.in_layers[i][1]) if sep else (lambda i: wn.in_layers[i])
-                fw.in_w = arr(lambda i: self._dense(gemm(i), stream, keep).data_ptr())
-                fw.in_b = arr(lambda i: dev(gemm(i).bias))
+                fw.start_w = folded_weight(wn.start, stream, keep).data_ptr()
+                fw.start_b = _cache.dev(wn.start.bias, keep)
+                if self._folded:
+                    fw.cond_w = folded_weight(wn.cond_layers[0], stream, keep).data_ptr()
+                    fw.cond_b = _cache.dev(wn.cond_layers[0].bias, keep)
+                fw.in_w = arr(lambda i: folded_weight(gemm(i), stream, keep).data_ptr())
+                fw.in_b = arr(lambda i: _cache.dev(gemm(i).bias, keep))
                 if sep:
-                    fw.dw_w = arr(lambda i: self._dense(wn.in_layers[i][0], stream, keep).data_ptr())
-                    fw.dw_b = arr(lambda i: dev(wn.in_layers[i][0].bias))
-                fw.rs_w = arr(lambda i: eye.data_ptr() if no_rs else self._dense(wn.res_skip_layers[i], stream, keep).data_ptr())
-                fw.rs_b = arr(lambda i: zero_b.data_ptr() if no_rs else dev(wn.res_skip_layers[i].bias))
-                fw.end_w = dev(wn.end.weight)
-                fw.end_b = dev(wn.end.bias)
-                if self.channel_mixing == '1x1conv':                            # efficient_modules.py:271-276
+                    fw.dw_w = arr(lambda i: folded_weight(wn.in_layers[i][0], stream, keep).data_ptr())
+                    fw.dw_b = arr(lambda i: _cache.dev(wn.in_layers[i][0].bias, keep))
+                fw.rs_w = arr(lambda i: eye.data_ptr() if no_rs else folded_weight(wn.res_skip_layers[i], stream, keep).data_ptr())
+                fw.rs_b = arr(lambda i: zero_b.data_ptr() if no_rs else _cache.dev(wn.res_skip_layers[i].bias, keep))
+                fw.end_w = _cache.dev(wn.end.weight, keep)
+                fw.end_b = _cache.dev(wn.end.bias, keep)
+                if self.channel_mixing == '1x1conv':
+                    # efficient_modules.py:271-276: W.float().inverse(), cached on the module as W_inverse
                     W = self.convinv[k].weight.detach().squeeze(-1)
                     W_inverse = W.float().cpu().inverse().to(device).contiguous()
                     self.convinv[k].W_inverse = W_inverse[..., None]
                     keep.append(W_inverse)
                     fw.w_inverse = W_inverse.data_ptr()
-                _lib.check(lib.ctts_waveflow_pack_flow(C.byref(cfg), k, C.byref(fw), _lib.ptr(blob), stream),
-                           f"ctts_waveflow_pack_flow({k})")
+                _lib.check(pack_flow(C.byref(cfg), k, C.byref(fw), _lib.ptr(blob), stream), f"{name}({k})")
             ops = None
             gm = _lib.model_gemm_mode(self._f32_gemm_mode)
             if not self._folded:
@@ -658,7 +579,7 @@ class WaveGlow(nn.Module):
                     out = []
                     for l, layer in enumerate(layers):
                         a = act if (act_last or l != len(layers) - 1) else (0, 0.0)
-                        out.append(_CondConv(self._dense(layer, stream, keep), layer.bias, a[0], a[1], device, stream, gm))
+                        out.append(_CondConv(folded_weight(layer, stream, keep), layer.bias, a[0], a[1], device, stream, gm))
                     return out
                 ops = {'model': stack(self.cond_layers, self._act_model, True),          # ax:293-297: every layer
                        'res_conv': (_CondConv(self.res_conv.weight.detach().float(), self.res_conv.bias, 0, 0.0, device, stream, gm)
@@ -675,7 +596,6 @@ class WaveGlow(nn.Module):
                        'wn': [stack(c.WN.cond_layers, self._act_wn, wn_cfg.get('cond_out_activation_func', True))
                               for c in self.WN]}                                       # glow_ax.py:573-577
             torch.cuda.current_stream(device).synchronize()
-        self._packed = (device, blob, ops, key)
         return blob, ops
 
     def _to_latent_length(self, h, B, rows_n, hT, hld, T, ld, dst, interpolate, stream):
@@ -821,37 +741,41 @@ class WaveGlow(nn.Module):
 
     # --------------------------------------------------------------------- the path ----
     def inverse(self, z, cond, speaker_ids=None, return_CPU=True):
-        """efficient_model_ax.py:279-357: z [B, T] (noise, sigma applied), cond [B, n_mel(*2), frames]."""
-        if not self.waveflow:
-            return self._inverse_1d(z, cond, speaker_ids, return_CPU)
+        """efficient_model_ax.py:279-357: z [B, T] (noise, sigma applied), cond [B, n_mel(*2), frames].  ``waveflow=True``:
+        WaveFlowCoupling + WN_2d (ctts_waveflow_inverse_f32 / _cond_f32); ``waveflow=False``: AffineCouplingBlock + the 1-D WN
+        (ctts_wgax_inverse_f32, or ctts_wgax_inverse_f16 after ``set_compute_dtype(torch.float16)``)."""
         device = cond.device
         blob, ops = self._ensure_packed(device)
         lib = _lib.lib()
-        cfg = self.c_config()
+        half = self._compute_dtype == torch.float16
+        if self.waveflow:
+            cfg, ws_bytes, what = self.c_config(), lib.ctts_waveflow_workspace_bytes, "WaveFlow workspace query failed"
+        else:
+            cfg, what = self.c_config_1d(), "ax WaveGlow workspace query failed"
+            ws_bytes = lib.ctts_wgax_workspace_f16_bytes if half else lib.ctts_wgax_workspace_bytes
         mel = cond.detach().float().contiguous()
         zz = z.detach().to(device=device, dtype=torch.float32).contiguous()
         B, T = zz.shape
         assert mel.shape[0] == B and mel.shape[1] == self.n_mel_channels * (2 if self.has_logvar_channels else 1)
-        key = (device, B, T)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = lib.ctts_waveflow_workspace_bytes(C.byref(cfg), B, T)
-            if nbytes == 0:
-                raise _lib.HipLibraryError("WaveFlow workspace query failed: " + lib.ctts_last_error().decode())
-            self._drop_workspaces()
-            ws = self._ws.setdefault(key, torch.zeros(nbytes // 4, dtype=torch.float32, device=device))
+        assert self.waveflow or T % self.n_group == 0, "z length is not a multiple of n_group"
+        ws = self.workspace((device, B, T, self._compute_dtype), lambda: _lib.nbytes(ws_bytes, C.byref(cfg), B, T, what=what))
         audio = torch.empty(B, T, dtype=torch.float32, device=device)
         with torch.cuda.device(device):
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            stream = _lib.stream(device)
             if self._folded:
                 _lib.check(lib.ctts_waveflow_inverse_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(zz), _lib.ptr(mel),
                                                         _lib.ptr(audio), B, T, mel.shape[2], _lib.ptr(ws),
                                                         ws.numel() * 4, stream), "ctts_waveflow_inverse_f32")
             else:
                 frames, ld, n_cond = self._cond_frames(ops, mel, speaker_ids, stream, out_steps=T // self.n_group)
-                _lib.check(lib.ctts_waveflow_inverse_cond_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(zz), _lib.ptr(frames),
-                                                             ld, PAD, _lib.ptr(audio), B, T, n_cond, _lib.ptr(ws),
-                                                             ws.numel() * 4, stream), "ctts_waveflow_inverse_cond_f32")
+                if self.waveflow:
+                    _lib.check(lib.ctts_waveflow_inverse_cond_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(zz), _lib.ptr(frames),
+                                                                 ld, PAD, _lib.ptr(audio), B, T, n_cond, _lib.ptr(ws),
+                                                                 ws.numel() * 4, stream), "ctts_waveflow_inverse_cond_f32")
+                else:
+                    name = "ctts_wgax_inverse_f16" if half else "ctts_wgax_inverse_f32"
+                    _lib.check(getattr(lib, name)(C.byref(cfg), _lib.ptr(blob), _lib.ptr(zz), _lib.ptr(frames), ld, PAD, n_cond,
+                                                  _lib.ptr(audio), B, T, _lib.ptr(ws), ws.numel() * 4, stream), name)
             if self.vol_scaling:       # ax:342-344
                 _lib.check(lib.ctts_vol_unscale_f32(_lib.ptr(audio), audio.numel(), stream), "ctts_vol_unscale_f32")
             if self.preempthasis:      # ax:351-355 (scipy lfilter on the host there; here on the device, in place)
@@ -859,11 +783,12 @@ class WaveGlow(nn.Module):
                                                   stream), "ctts_deemphasis_f32")
         if return_CPU:
             audio = audio.cpu()
-            # the copy synchronised the stream: a row-queue abort of THIS call is known now - raise instead of handing out
-            # its NaN audio (a call that stays on the device reports it through the next call on this workspace: CTTS_E_ABORT)
-            with torch.cuda.device(device):
-                _lib.check(lib.ctts_waveflow_abort_status(C.byref(cfg), B, T, _lib.ptr(ws), ws.numel() * 4, stream),
-                           "WaveFlow.inverse")
+            if self.waveflow:
+                # the copy synchronised the stream: a row-queue abort of THIS call is known now - raise instead of handing out
+                # its NaN audio (a call that stays on the device reports it through the next call on this workspace: CTTS_E_ABORT)
+                with torch.cuda.device(device):
+                    _lib.check(lib.ctts_waveflow_abort_status(C.byref(cfg), B, T, _lib.ptr(ws), ws.numel() * 4, stream),
+                               "WaveFlow.inverse")
         return audio, None
 
     def _drop_workspaces(self):
@@ -875,49 +800,11 @@ class WaveGlow(nn.Module):
             return
         lib = _lib.lib()
         cfg = self.c_config()
-        for (device, B, T), ws in old.items():
+        for (device, B, T, _), ws in old.items():
             with torch.cuda.device(device):
-                stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+                stream = _lib.stream(device)
                 _lib.check(lib.ctts_waveflow_abort_status(C.byref(cfg), B, T, _lib.ptr(ws), ws.numel() * 4, stream),
                            "WaveFlow.inverse (an earlier call on a workspace that is being replaced)")
-
-    def _inverse_1d(self, z, cond, speaker_ids, return_CPU):
-        """waveflow=False: efficient_model_ax.py:279-357 with AffineCouplingBlock + 1-D WN (ctts_wgax_inverse_f32, or
-        ctts_wgax_inverse_f16 after ``set_compute_dtype(torch.float16)``)."""
-        device = cond.device
-        blob, ops = self._ensure_packed(device)
-        lib = _lib.lib()
-        cfg = self.c_config_1d()
-        mel = cond.detach().float().contiguous()
-        zz = z.detach().to(device=device, dtype=torch.float32).contiguous()
-        B, T = zz.shape
-        assert mel.shape[0] == B and mel.shape[1] == self.n_mel_channels * (2 if self.has_logvar_channels else 1)
-        assert T % self.n_group == 0, "z length is not a multiple of n_group"
-        half = self._compute_dtype == torch.float16
-        inverse_fn, name = (lib.ctts_wgax_inverse_f16, "ctts_wgax_inverse_f16") if half else \
-            (lib.ctts_wgax_inverse_f32, "ctts_wgax_inverse_f32")
-        key = (device, B, T, self._compute_dtype)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = (lib.ctts_wgax_workspace_f16_bytes if half else lib.ctts_wgax_workspace_bytes)(C.byref(cfg), B, T)
-            if nbytes == 0:
-                raise _lib.HipLibraryError("ax WaveGlow workspace query failed: " + lib.ctts_last_error().decode())
-            self._ws = {}
-            ws = self._ws.setdefault(key, torch.zeros(nbytes // 4, dtype=torch.float32, device=device))
-        audio = torch.empty(B, T, dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            frames, ld, n_cond = self._cond_frames(ops, mel, speaker_ids, stream, out_steps=T // self.n_group)
-            _lib.check(inverse_fn(C.byref(cfg), _lib.ptr(blob), _lib.ptr(zz), _lib.ptr(frames), ld, PAD, n_cond,
-                                  _lib.ptr(audio), B, T, _lib.ptr(ws), ws.numel() * 4, stream), name)
-            if self.vol_scaling:
-                _lib.check(lib.ctts_vol_unscale_f32(_lib.ptr(audio), audio.numel(), stream), "ctts_vol_unscale_f32")
-            if self.preempthasis:
-                _lib.check(lib.ctts_deemphasis_f32(_lib.ptr(audio), _lib.ptr(audio), B, T, float(self.preempthasis),
-                                                  stream), "ctts_deemphasis_f32")
-        if return_CPU:
-            audio = audio.cpu()
-        return audio, None
 
     def _prep_spect(self, spect, artifact_trimming):
         p = next(self.parameters())

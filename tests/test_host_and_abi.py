@@ -233,3 +233,60 @@ def test_checkpoint_config_selects_the_model_class():
     assert not is_ax_config(cfg)
     m = waveglow_from_checkpoint({"model": synthetic.to_torch(synthetic.waveglow_state_dict(cfg, seed=1)), "waveglow_config": cfg})
     assert isinstance(m, WaveGlow) and not WaveGlowVocoder(m).is_ax
+
+
+def test_packed_module_base_owns_the_cache_rules():
+    """``_cache.PackedModule``: the packed value is served again while device and parameters stand, and rebuilt after everything
+    that can change them; one workspace geometry is live at a time.  (``packed`` looks at ``device.type`` only, so the rule is
+    checked here with a device object and no GPU.)"""
+    from cookietts_amd import _cache
+
+    class Tiny(_cache.PackedModule):
+        GPU_ONLY = "Tiny HIP path needs the model on a GPU (no CPU fallback)"
+
+        def __init__(self):
+            super().__init__()
+            self.lin = torch.nn.Linear(3, 2)
+            self.builds = 0
+
+        def get(self, device=torch.device("cuda", 0)):
+            def build():
+                self.builds += 1
+                return ("blob", self.builds)
+            return self.packed(device, build)
+
+    m = Tiny()
+    first = m.get()
+    assert m.get() is first and m.builds == 1                                   # nothing changed: reused
+    with torch.no_grad():
+        m.lin.weight.add_(1.0)                                                  # in-place update (an optimizer step)
+    assert m.get() == ("blob", 2)
+    m.half()
+    assert m._packed is None and m.get() == ("blob", 3)
+    m.float()
+    assert m._packed is None and m.get() == ("blob", 4) and m.get() == ("blob", 4)
+    m.load_state_dict({k: v.clone() for k, v in m.state_dict().items()})
+    assert m._packed is None and m.get() == ("blob", 5)
+    parent = torch.nn.Sequential(m)                                             # a parent's load never calls the child's override
+    parent.load_state_dict({k: v.clone() for k, v in parent.state_dict().items()})
+    assert m._packed is None and m.get() == ("blob", 6)
+    m.lin.weight.data.mul_(2.0)                                                 # bypasses the version counter ...
+    assert m.get() == ("blob", 6)
+    m.repack()                                                                  # ... which is what repack() is for
+    assert m.get() == ("blob", 7)
+    assert m.get(torch.device("cuda", 1)) == ("blob", 8)                        # another device
+    with pytest.raises(_lib.HipLibraryError, match="Tiny HIP path needs the model on a GPU"):
+        m.get(torch.device("cpu"))
+    assert m.builds == 8
+
+    cpu = torch.device("cpu")
+    ws = m.workspace((cpu, 1, 2), lambda: 64)
+    assert ws.shape == (16,) and ws.dtype == torch.float32 and not ws.any()
+    assert m.workspace((cpu, 1, 2), lambda: pytest.fail("size queried again for the live geometry")) is ws
+    with pytest.raises(_lib.HipLibraryError):                                   # a refused geometry leaves the live one alone
+        m.workspace((cpu, 9, 9), lambda: _lib.nbytes(lambda: 0, what="refused"))
+    assert list(m._ws) == [(cpu, 1, 2)]
+    two = m.workspace((cpu, 2, 2), lambda: [32, 8], zero=False)                 # a list of sizes: a list of buffers
+    assert [t.numel() for t in two] == [8, 2] and list(m._ws) == [(cpu, 2, 2)]   # one live geometry
+    m.repack()
+    assert m._ws == {} and m._packed is None

@@ -73,11 +73,9 @@ def test_batched_rows_do_not_depend_on_the_rest_of_the_batch(hip_lib_path):
     old = t2_from
     try:
         t2.BATCHED_FROM = 1 << 30                       # groups of MAX_GROUP in lockstep on the persistent / per-launch forms
-        m.decoder._ws, m.decoder._xchg = {}, {}
         grouped = m.decoder.inference(mem, lens, keep_masks=masks, fixed_steps=n)
     finally:
         t2.BATCHED_FROM = old
-        m.decoder._ws, m.decoder._xchg = {}, {}
     d = float((grouped[0] - full[0]).abs().max())
     print(f"batched vs groups of 4: mel L_inf {d:.2e}")
     assert d < 2e-5
