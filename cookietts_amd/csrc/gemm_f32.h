@@ -134,6 +134,14 @@ struct GemmArgs {
     // interpolated to the L columns of the launch (align_corners=True: position n reads n * (F-1)/(L-1)), the
     // arithmetic of ATen's upsample_linear1d (glow_ax.py:362-373) - the sample-rate tensor is never materialised
     int addend_frames;
+    // GATE (GTU) only, with a plain `addend`: a second addend of the same layout, strides and origin, added with a sign:
+    // u = ((acc + bias) + addend) + addend2_sign * addend2 - in that association in every kernel shape.  NULL = none.
+    const float* addend2; float addend2_sign;
+    // GATE (GTU) only: mapped store (the Winograd F(2,3) in-layer form of the fp32 WaveGlow, waveglow_api.hip).  map_d = d > 0: the
+    // launch's columns are PAIR columns; pair column q = map_col0 + n of a batch item is stored at the natural column
+    // (q / d) * 2d + q % d + map_par * d of dst0, and only when that lies below map_L.  `n < L` keeps testing the pair column.
+    // dst0 then points at column 0 of the natural tensor whatever part of the launch this is: map_col0 carries the origin.
+    int map_d, map_par, map_L, map_col0;
     int map_mode;         // block id -> (m-block, tile, batch) mapping, chosen by the launcher (see gemm_f32.hip)
     int gate;             // GateKind of a GATE launch (0 = GTU); != 0 is routed to GEMM_EPI_GATEX by the launcher
     int gemm_mode;        // CTTS_GEMM_DEFAULT (0: the library default, ctts_set_f32_gemm_mode) | CTTS_GEMM_F32 | CTTS_GEMM_BF16X3:

@@ -549,6 +549,13 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
                 const int n = n0 + wn * 64 + nt * 32 + l31;
                 if (n < a.L) {
                     float add0[16], add1[16];
+                    int ns = n;                                  // column of the store
+                    bool ns_ok = true;
+                    if (EPI == GEMM_EPI_GATE && a.map_d > 0) {   // uniform: pair column -> natural column
+                        const int q = a.map_col0 + n;
+                        ns = (q / a.map_d) * (2 * a.map_d) + q % a.map_d + a.map_par * a.map_d;
+                        ns_ok = ns < a.map_L;
+                    }
                     if ((EPI == GEMM_EPI_GATE || EPI == GEMM_EPI_GATEX) && a.addend && a.addend_frames > 0) {   // uniform: interpolated addend
                         const int F = a.addend_frames;
                         const float scale = a.L > 1 ? (float)(F - 1) / (float)(a.L - 1) : 0.f;
@@ -609,16 +616,27 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
                         }
 #undef CTTS_GATEX_LOOP
                     } else {
+                        float add20[16], add21[16];
+                        if (EPI == GEMM_EPI_GATE && a.addend2) {     // uniform
+                            const float* ad = a.addend2 + (size_t)b * a.addend_bstride + a.addend_pad + n;
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) {
+                                const int c = min(cbase + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi, a.pairC - 1);
+                                add20[r] = a.addend2_sign * ad[(size_t)c * a.addend_ld];
+                                add21[r] = a.addend2_sign * ad[(size_t)(a.pairC + c) * a.addend_ld];
+                            }
+                        }
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int row = (r & 3) + 8 * (r >> 2) + 4 * lhi;
                             const int c = cbase + mt * 32 + row;
-                            const float u0 = acc[mt][nt][r] + bias[mt * 32 + row] + add0[r];
-                            const float u1 = acc[mt + 2][nt][r] + bias[64 + mt * 32 + row] + add1[r];
+                            float u0 = acc[mt][nt][r] + bias[mt * 32 + row] + add0[r];
+                            float u1 = acc[mt + 2][nt][r] + bias[64 + mt * 32 + row] + add1[r];
+                            if (EPI == GEMM_EPI_GATE && a.addend2) { u0 += add20[r]; u1 += add21[r]; }
                             float v;
                             if constexpr (EPI == GEMM_EPI_GATE) v = fast_tanh(u0) * fast_sigmoid(u1);
                             else v = sqrtf(u0 * u0 + u1 * u1);
-                            if (c < a.pairC) dst[(size_t)c * a.dst_ld + a.dst_pad + n] = v;
+                            if (c < a.pairC && ns_ok) dst[(size_t)c * a.dst_ld + a.dst_pad + ns] = v;
                         }
                     }
                 }
@@ -776,6 +794,8 @@ void load_tuning_locked() {
     g_tune.wf_queue_debug = num("CTTS_WF_QUEUE_DEBUG", 0);
     g_tune.f32_no_defer_skip = on("CTTS_F32_NO_DEFER_SKIP");
     g_tune.f32_no_wn_fold = on("CTTS_F32_NO_WN_FOLD");
+    g_tune.f32_no_winograd = on("CTTS_F32_NO_WINOGRAD");
+    g_tune.f32_winograd_min = num("CTTS_F32_WINOGRAD_MIN", -1);
     g_tune_loaded = true;
 }
 }  // namespace
@@ -822,6 +842,11 @@ int gemm_check_args(int epi, const GemmArgs& a) {
                    "gemm: interpolated addend needs the GATE epilogue (frames=%d)", a.addend_frames);
     CTTS_CHECK_ARG(a.gate >= 0 && a.gate < GATE_KINDS && (a.gate == 0 || epi == GEMM_EPI_GATE), "gemm: gate=%d with epilogue %d",
                    a.gate, epi);
+    CTTS_CHECK_ARG((a.addend2 == nullptr && a.map_d == 0) ||
+                       (epi == GEMM_EPI_GATE && a.gate == GATE_GTU && a.addend_frames == 0 && a.map_d >= 0 &&
+                        (a.addend2 == nullptr || (a.addend && (a.addend2_sign == 1.0f || a.addend2_sign == -1.0f))) &&
+                        (a.map_d == 0 || ((a.map_par == 0 || a.map_par == 1) && a.map_L > 0 && a.map_col0 >= 0))),
+                   "gemm: second addend / mapped store need the GATE epilogue (epilogue %d, map_d=%d)", epi, a.map_d);
     // the fused res/skip epilogue is validated BEFORE any shape is chosen: the small and split-K shapes (and the row queue's tile
     // bodies) take the same arguments
     CTTS_CHECK_ARG(epi != GEMM_EPI_GATE_RS ||
@@ -856,10 +881,12 @@ int launch_gemm_f32(int epi, const GemmArgs& a_in, hipStream_t stream) {
             const long long co = (long long)(a.ntiles - rem_tiles) * bn;
             const long long bo = a.batch - 1;
             for (int j = 0; j < r.nseg; ++j) r.seg[j].base += bo * r.seg[j].bstride + co;
-            if (r.dst0) r.dst0 += bo * r.dst0_bstride + co;
+            if (r.dst0) r.dst0 += bo * r.dst0_bstride + (r.map_d > 0 ? 0 : co);     // mapped store: the pair-column origin moves
+            if (r.map_d > 0) r.map_col0 += (int)co;
             if (r.dst1) r.dst1 += bo * r.dst1_bstride + co;
             if (r.src0) r.src0 += bo * r.src0_bstride + co;
             if (r.addend) r.addend += bo * r.addend_bstride + co;
+            if (r.addend2) r.addend2 += bo * r.addend_bstride + co;
             r.L = a.L - (int)co;
             r.ntiles = (int)rem_tiles;
             r.batch = 1;

@@ -481,6 +481,16 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_f32_small_kernel(const GemmA
 #pragma unroll
                 for (int r = 0; r < 16; ++r) add0[r] = add1[r] = 0.0f;
             }
+            // mapped store of the Winograd in-layer form (gemm_f32.h)
+            [[maybe_unused]] int ns = n;
+            [[maybe_unused]] bool ns_ok = true;
+            if constexpr (EPI == GEMM_EPI_GATE) {
+                if (a.map_d > 0) {                          // uniform: pair column -> natural column
+                    const int q = a.map_col0 + n;
+                    ns = (q / a.map_d) * (2 * a.map_d) + q % a.map_d + a.map_par * a.map_d;
+                    ns_ok = ns < a.map_L;
+                }
+            }
             S_STAMP_DRAIN(4);
             if constexpr (EPI == GEMM_EPI_GATEX) {
 #define S_GATEX_LOOP(K)                                                                                           \
@@ -500,6 +510,29 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_f32_small_kernel(const GemmA
                 }
 #undef S_GATEX_LOOP
             } else {
+                if constexpr (EPI == GEMM_EPI_GATE) {
+                    // second addend (gemm_f32.h): requested only now - the first one's operands, held since the kernel's entry,
+                    // are summed into the accumulators first, so that their registers are free for it
+                    if (a.addend2) {                        // uniform
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int row = (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                            acc[0][r] = acc[0][r] + lds[32 * wm + row] + add0[r];
+                            acc[1][r] = acc[1][r] + lds[64 + 32 * wm + row] + add1[r];
+                        }
+                        const float* ad = a.addend2 + (size_t)b * a.addend_bstride + a.addend_pad + n;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int row = (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                            const int c = min(cbase + row, a.pairC - 1);
+                            const float u0 = acc[0][r] + a.addend2_sign * ad[(size_t)c * a.addend_ld];
+                            const float u1 = acc[1][r] + a.addend2_sign * ad[(size_t)(a.pairC + c) * a.addend_ld];
+                            if (cbase + row < a.pairC && ns_ok)
+                                dst[(size_t)(cbase + row) * a.dst_ld + a.dst_pad + ns] = s_fast_tanh(u0) * s_fast_sigmoid(u1);
+                        }
+                        return;
+                    }
+                }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = (r & 3) + 8 * (r >> 2) + 4 * lhi;
@@ -508,7 +541,7 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_f32_small_kernel(const GemmA
                     float v;
                     if constexpr (EPI == GEMM_EPI_GATE) v = s_fast_tanh(u0) * s_fast_sigmoid(u1);
                     else v = sqrtf(u0 * u0 + u1 * u1);
-                    if (cbase + row < a.pairC) dst[(size_t)(cbase + row) * a.dst_ld + a.dst_pad + n] = v;
+                    if (cbase + row < a.pairC && ns_ok) dst[(size_t)(cbase + row) * a.dst_ld + a.dst_pad + ns] = v;
                 }
             }
         }

@@ -29,6 +29,8 @@ struct Tuning {
     bool taco_valu;        // CTTS_TACO_VALU: ctts_taco_decoder_steps_f32 at batch <= 4 on the VALU kernels of rounds 1-3 (six launches per step) instead of the batched MFMA form
     bool f32_no_defer_skip;  // CTTS_F32_NO_DEFER_SKIP: WaveGlow fp32 WN stack with one res/skip GEMM per layer (the form before round 4)
     bool f32_no_wn_fold;   // CTTS_F32_NO_WN_FOLD: WaveGlow fp32 WN stack without the start / end folds (layer 0 on x, C-row skip GEMM, C-row tail)
+    bool f32_no_winograd;  // CTTS_F32_NO_WINOGRAD: WaveGlow fp32 WN stack with the direct 3-tap in-layer GEMM at every size (no Winograd F(2,3) form)
+    int f32_winograd_min;  // CTTS_F32_WINOGRAD_MIN: take the Winograd form for utterances of at least this many columns (steps per batch item); 0 = always (default in waveglow_api.hip)
     bool wf_no_region_split; // CTTS_WF_NO_REGION_SPLIT: the fused WaveFlow layer as ONE launch per layer (no A | M | B regions on three streams)
     bool wf_no_row_queue;  // CTTS_WF_NO_ROW_QUEUE: never the one-launch-per-row work queue of the fused WaveFlow layers
     int wf_row_queue_min;  // CTTS_WF_ROW_QUEUE_MIN: take the row queue from this many 128-column items per layer on (A/B; default in waveflow_api.hip)

@@ -37,6 +37,7 @@ struct Plan {
     std::vector<FlowDims> fd;
     // packed blob offsets (floats)
     size_t up_w, up_wp, up_b, cond0_A, cond0_b, cond1_A, cond1_b;
+    size_t zero_b;                      // mb_in * GEMM_BM zeros (never written; the blob is zero-filled): bias of the Winograd T launches
     bool up_mfma;
     struct Flow {
         size_t start_w, start_b, end_w, end_b, winv, spk_tab;
@@ -47,6 +48,10 @@ struct Plan {
         // WN start / end folds (round 7): in0f_w = W_in,0[tap] . [W_start | b_start] as a dense [2C][FOLD_ROWS][ks] in_w, in0f_A its
         // packed GATE matrix (+ the cond slice; bias = in_b[0]); skend_W = W_end . W_skip,i as [n_layers][C][2 n_half], skend_b = b'
         size_t in0f_w, in0f_A, skend_W, skend_b;
+        // Winograd F(2,3) in-layer form (round 12): per layer G2 and G3 in SPLIT packing (K = C), [W0 | C_i] and [-W2 | C_i] in
+        // GATE packing (K = C + H; bias = in_b[i]); wg_dense = the dense [3][2C][C] G2, G3, -W2 of the layer being packed
+        std::vector<size_t> wg_T2_A, wg_T3_A, wg_e_A, wg_o_A;
+        size_t wg_dense;
     };
     std::vector<Flow> fl;
     size_t total;
@@ -105,6 +110,7 @@ int make_plan(const ctts_waveglow_config* cfg, Plan& p) {
     p.cond0_b = take((size_t)c.n_flows * GEMM_BM);
     p.cond1_A = take((size_t)c.n_flows * p.nch1h * A_TILE);
     p.cond1_b = take((size_t)c.n_flows * GEMM_BM);
+    p.zero_b = take((size_t)p.mb_in * GEMM_BM);
     p.fl.resize(c.n_flows);
     for (int k = 0; k < c.n_flows; ++k) {
         auto& f = p.fl[k];
@@ -130,6 +136,13 @@ int make_plan(const ctts_waveglow_config* cfg, Plan& p) {
         f.in0f_A = take((size_t)p.mb_in * p.nch_in0f * A_TILE);
         f.skend_W = take((size_t)c.n_layers * p.C * 2 * p.fd[k].n_half);
         f.skend_b = take(2 * p.fd[k].n_half);
+        for (int i = 0; i < c.n_layers; ++i) {
+            f.wg_T2_A.push_back(take((size_t)p.mb_in * p.nch_rs * A_TILE));
+            f.wg_T3_A.push_back(take((size_t)p.mb_in * p.nch_rs * A_TILE));
+            f.wg_e_A.push_back(take((size_t)p.mb_in * (p.nch_rs + p.nch1h) * A_TILE));
+            f.wg_o_A.push_back(take((size_t)p.mb_in * (p.nch_rs + p.nch1h) * A_TILE));
+        }
+        f.wg_dense = take((size_t)3 * 2 * p.C * p.C);
     }
     p.total = o;
     return CTTS_OK;
@@ -148,11 +161,40 @@ int make_geom(const Plan& p, int frames, Geom& g) {
     return CTTS_OK;
 }
 
+// Winograd F(2,3) in-layer form: pair-space geometry of layer i (dilation d = 2^i): Lp = ceil(L / 2d) d pair columns per batch
+// item, in ntiles 128-column tiles; every layer uses the row stride ldp of the widest one
+struct PairGeom { int d, Lp, ntiles; };
+PairGeom pair_geom(const Geom& g, int layer) {
+    const int d = 1 << layer;
+    const int Lp = (g.L + 2 * d - 1) / (2 * d) * d;
+    return {d, Lp, (Lp + GEMM_BN - 1) / GEMM_BN};
+}
+int pair_ld(const Plan& p, const Geom& g) {
+    int nt = 0;
+    for (int i = 0; i < p.c.n_layers; ++i) nt = std::max(nt, pair_geom(g, i).ntiles);
+    return nt * GEMM_BN;
+}
+// The form is taken only where the in-layer launch runs the fp32 MFMA loop, and for utterances of at least WINOGRAD_MIN_COLS columns
+// (steps per batch item).  The test is on the utterance, never on the batch: an utterance must come out bit for bit the same
+// whatever batch it runs in (tests/test_full_size.py), and both forms are bit-identical across the kernel shapes a batch size picks.
+// The threshold is the length the A/B was run at (900 frames, profiles/r12_02_winograd_ab.txt, r12_04_winograd_sweep.txt).
+// CTTS_F32_NO_WINOGRAD: never; CTTS_F32_WINOGRAD_MIN: another threshold (0 = always).
+constexpr long long WINOGRAD_MIN_COLS = 28800;
+bool winograd_engages(const Plan& p, const Geom& g) {
+    const Tuning t = tuning();
+    if (t.f32_no_winograd || gemm_split_level(p.c.f32_gemm_mode) != 0) return false;
+    const long long min_cols = t.f32_winograd_min >= 0 ? t.f32_winograd_min : WINOGRAD_MIN_COLS;
+    return (long long)g.L >= min_cols;
+}
+
 struct Workspace {
     float *audio, *spect, *spk, *h_tmp, *h_all, *x, *act, *out;
     float* act_all;     // deferred-skip form: the gated activations of every layer of a flow ([n_layers] x act)
     float* a16;         // WN folds: layer 0's input [B][FOLD_ROWS][ld] = [audio_0; 1 on [0, L); 0]
     float* skend;       // WN folds: the skip/end accumulator [B][2 n_half][ld] between the groups of a flow
+    // Winograd in-layer form (NULL where it does not engage): V1..V4 [4][B][C][ldp], T2 / T3 [2][B][2C][ldp], h2e / h2o [2][B][H][ldp]
+    float *wgV, *wgT, *wgH;
+    int ldp;
     size_t total;  // floats
 };
 
@@ -172,6 +214,14 @@ void carve(const Plan& p, const Geom& g, int batch, float* base, Workspace& w) {
     w.act_all = take((size_t)std::min(p.c.n_layers, (int)Plan::F32_SKIP_GROUP) * B * p.C * g.ld);
     w.a16 = take(B * FOLD_ROWS * g.ld);
     w.skend = take(B * p.c.n_group * g.ld);
+    w.wgV = w.wgT = w.wgH = nullptr;
+    w.ldp = 0;
+    if (winograd_engages(p, g)) {
+        w.ldp = pair_ld(p, g);
+        w.wgV = take((size_t)4 * B * p.C * w.ldp);
+        w.wgT = take((size_t)2 * B * 2 * p.C * w.ldp);
+        w.wgH = take((size_t)2 * B * p.H * w.ldp);
+    }
     w.total = o;
 }
 
@@ -268,10 +318,55 @@ int run_cond(const Plan& p, const Geom& g, const float* blob, const float* spect
 // [audio_0; 1; 0] instead of x, and the skip sum is never formed - a skip/end pass per group of kept activations accumulates its
 // 2 n_half-row image, and the last one of a flow is also the flow tail (coupling, inverse 1x1, un-squeeze into `wave`).
 struct WnFold { float* a16; float* skend; float* audio; float* wave; };
+// Winograd F(2,3) form of the in-layer GEMMs that read x (the whole-infer entry points, which own these buffers)
+struct WnWinograd { float* V; float* T; float* Hc; int ldp; };
+
+// One in-layer step in the Winograd form: transform, T2 = G2 V2, T3 = G3 V3, then the even and odd members of every pair
+//   act[t_e] = gate([W0 | C_i] [V1; h2e] + b + T2 + T3),   act[t_o] = gate([-W2 | C_i] [V4; h2o] + b + T2 - T3)
+// as four launches of the conv-GEMM in pair space (ld = ldp, no halo); the GATE launches store to act's natural columns.
+int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k, int i, const float* x, const float* h_all,
+                          float* act, const WnWinograd& wg, int batch, hipStream_t s) {
+    const auto& f = p.fl[k];
+    const PairGeom pg = pair_geom(g, i);
+    const int C = p.C, H = p.H, ldp = wg.ldp;
+    const long long hstride = (long long)p.c.n_flows * H * g.ld;
+    const size_t vplane = (size_t)batch * C * ldp, tplane = (size_t)batch * 2 * C * ldp, hplane = (size_t)batch * H * ldp;
+    int rc = launch_winograd_transform(x, (long long)C * g.ld, h_all + (size_t)k * H * g.ld, hstride, wg.V, wg.Hc, batch, C, H, pg.d,
+                                       g.L, pg.Lp, g.ld, g.pad, ldp, pg.ntiles * GEMM_BN, s);
+    if (rc) return rc;
+    GemmArgs a{};
+    a.gemm_mode = p.c.f32_gemm_mode;
+    a.ld = ldp; a.pad = 0; a.L = pg.Lp; a.ntiles = pg.ntiles; a.batch = batch; a.MB = p.mb_in;
+    a.bias = blob + p.zero_b;
+    a.nseg = 1; a.nch_total = p.nch_rs;
+    a.dst_ld = ldp; a.dst_pad = 0; a.dst0_bstride = (long long)2 * C * ldp;
+    a.M = 2 * C; a.split = 2 * C;
+    for (int j = 0; j < 2; ++j) {
+        a.A = blob + (j == 0 ? f.wg_T2_A[i] : f.wg_T3_A[i]);
+        a.seg[0] = {wg.V + (1 + j) * vplane, (long long)C * ldp, p.nch_rs, 0, 0, 0};
+        a.dst0 = wg.T + j * tplane;
+        if ((rc = launch_gemm_f32(GEMM_EPI_SPLIT, a, s))) return rc;
+    }
+    a.bias = blob + f.in_b[i];
+    a.nseg = 2; a.nch_total = p.nch_rs + p.nch1h;
+    a.split = 0; a.pairC = C;
+    a.dst0 = act; a.dst0_bstride = (long long)C * g.ld; a.dst_ld = g.ld; a.dst_pad = g.pad;
+    a.addend = wg.T; a.addend2 = wg.T + tplane; a.addend_bstride = (long long)2 * C * ldp;
+    a.map_d = pg.d; a.map_L = g.L;
+    for (int j = 0; j < 2; ++j) {
+        a.A = blob + (j == 0 ? f.wg_e_A[i] : f.wg_o_A[i]);
+        a.seg[0] = {wg.V + (j == 0 ? 0 : 3) * vplane, (long long)C * ldp, p.nch_rs, 0, 0, 0};
+        a.seg[1] = {wg.Hc + j * hplane, (long long)H * ldp, p.nch1h, 0, 0, 0};
+        a.addend2_sign = j == 0 ? 1.0f : -1.0f;
+        a.map_par = j;
+        if ((rc = launch_gemm_f32(GEMM_EPI_GATE, a, s))) return rc;
+    }
+    return CTTS_OK;
+}
 
 int run_wn_stack(const Plan& p, const Geom& g, const float* blob, int k, const float* audio, const float* h_all,
                  float* x, float* act, float* out, int batch, hipStream_t s, float* act_all = nullptr,
-                 const WnFold* fold = nullptr) {
+                 const WnFold* fold = nullptr, const WnWinograd* wg = nullptr) {
     const auto& f = p.fl[k];
     const auto& d = p.fd[k];
     const long long cstride = (long long)p.C * g.ld;
@@ -307,6 +402,11 @@ int run_wn_stack(const Plan& p, const Geom& g, const float* blob, int k, const f
             // slot 0 keeps bracketing EVERY in-layer launch (its contract: one entry per layer); slot 3 has this one alone
             ProfScope ps(CTTS_PROF_WN_IN, s), ps0(CTTS_PROF_WN_IN0F, s);
             rc = launch_gemm_f32(GEMM_EPI_GATE, a, s);
+            if (rc) return rc;
+        } else if (wg) {
+            // (one slot-0 entry per layer: it brackets the transform and the four launches)
+            ProfScope ps(CTTS_PROF_WN_IN, s);
+            rc = run_in_layer_winograd(p, g, blob, k, i, x, h_all, act, *wg, batch, s);
             if (rc) return rc;
         } else {
             GemmArgs a = base_args(p, g, batch);
@@ -821,6 +921,22 @@ int ctts_waveglow_pack_flow(const ctts_waveglow_config* cfg, int32_t k, const ct
                            w->rs_b[i] + (last ? 0 : C), C, p.mb_c() * GEMM_BM, gj == 0 ? 1 : 0);
         CTTS_CHECK_LAUNCH("skip_bias_f32");
     }
+    // Winograd F(2,3) in-layer form: G2, G3 (dense rows: T2 / T3 are addends in dense row order) and [W0 | C_i], [-W2 | C_i]
+    // (pair rows, like in_A); the dense scratch is reused layer by layer (one stream)
+    for (int i = 0; i < p.c.n_layers; ++i) {
+        float* dense = blob + f.wg_dense;
+        const size_t dn = (size_t)2 * C * C;
+        if ((rc = launch_winograd_g(w->in_w[i], dense, 2 * C, C, s))) return rc;
+        if ((rc = launch_pack_a(blob + f.wg_T2_A[i], dense, GEMM_BM, p.mb_in, p.nch_rs, 0, C, GEMM_EPI_SPLIT, C, 2 * C, 0, C, 1, s))) return rc;
+        if ((rc = launch_pack_a(blob + f.wg_T3_A[i], dense + dn, GEMM_BM, p.mb_in, p.nch_rs, 0, C, GEMM_EPI_SPLIT, C, 2 * C, 0, C, 1, s))) return rc;
+        if ((rc = launch_pack_a(blob + f.wg_e_A[i], w->in_w[i], GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, 0, C, GEMM_EPI_GATE, C, 2 * C, 0,
+                                (long long)C * ks, ks, s))) return rc;
+        if ((rc = launch_pack_a(blob + f.wg_o_A[i], dense + 2 * dn, GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, 0, C, GEMM_EPI_GATE, C, 2 * C, 0,
+                                C, 1, s))) return rc;
+        for (float* A : {blob + f.wg_e_A[i], blob + f.wg_o_A[i]})
+            if ((rc = launch_pack_a(A, w->cond_w[2], GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, C, H, GEMM_EPI_GATE, C, 2 * C,
+                                    (long long)2 * C * i, H, 1, s))) return rc;
+    }
     // WN start / end folds: layer 0 on [audio_0; 1] (K = [tap0, tap1, tap2] of one FOLD_ROWS chunk each, then the cond slice of
     // layer 0; bias in_b[0] as packed above) and the skip rows seen through `end`
     if ((rc = launch_fold_in0(w->in_w[0], w->start_w, w->start_b, blob + f.in0f_w, C, d.n_half, ks, s))) return rc;
@@ -913,9 +1029,11 @@ int ctts_waveglow_infer_spk_f32(const ctts_waveglow_config* cfg, const void* pac
     if (rc) return rc;
     const Tuning t = tuning();
     const bool folded = !t.f32_no_wn_fold && !t.f32_no_defer_skip;
+    const WnWinograd wg{w.wgV, w.wgT, w.wgH, w.ldp};
     for (int k = p.c.n_flows - 1; k >= 0; --k) {
         const WnFold fw{w.a16, w.skend, w.audio, k == 0 ? wave : nullptr};
-        rc = run_wn_stack(p, g, blob, k, w.audio, w.h_all, w.x, w.act, w.out, batch, s, w.act_all, folded ? &fw : nullptr);
+        rc = run_wn_stack(p, g, blob, k, w.audio, w.h_all, w.x, w.act, w.out, batch, s, w.act_all, folded ? &fw : nullptr,
+                          w.wgV ? &wg : nullptr);
         if (rc) return rc;
         if (folded) continue;        // the last skip/end pass of the flow was its tail
         rc = run_flow_tail(p, g, blob, k, w.out, w.audio, k == 0 ? wave : nullptr, batch, s);
@@ -935,7 +1053,7 @@ int ctts_tuning_flags(void) {
            (t.wf_inject_abort ? 131072 : 0) | (t.wf_queue_debug ? 262144 : 0) | (t.f32_no_round_split ? 524288 : 0) |
            (t.bf16_ps ? (1 << 20) : 0) | (t.bf16_no_ps ? (1 << 21) : 0) | (t.taco_poll_delay_set ? (1 << 23) : 0) |
            (t.taco_valu ? (1 << 24) : 0) | (t.up_no_mfma ? (1 << 25) : 0) | (t.f32_no_wn_fold ? (1 << 26) : 0) |
-           (t.taco_bg_no_pipe ? (1 << 27) : 0);
+           (t.taco_bg_no_pipe ? (1 << 27) : 0) | (t.f32_no_winograd ? (1 << 28) : 0) | (t.f32_winograd_min >= 0 ? (1 << 29) : 0);
 }
 
 int ctts_profile_create(void** handle) {

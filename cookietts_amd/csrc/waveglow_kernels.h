@@ -35,4 +35,11 @@ int launch_skip_end(const float* act, long long act_stride, int nl, const float*
                     const float* bf, const float* Winv, float* audio, float* wave, int batch, int C, int G, int ch_off,
                     int n_half, int L, int ld, int pad, hipStream_t s);
 
+// Winograd F(2,3) in-layer form (fp32 WaveGlow; the algebra is at the kernels in waveglow_kernels.hip).  Pack time: dense
+// [3][rows][C] = G2, G3, -W2 of in_w [rows][C][3].  Per layer: x and the flow's cond rows -> V1..V4 [4][B][C][ldp] and the copies
+// h2e, h2o [2][B][H][ldp] in pair order (Lp pair columns, zeros up to ncols).
+int launch_winograd_g(const float* in_w, float* dense, int rows, int C, hipStream_t s);
+int launch_winograd_transform(const float* x, long long x_bstride, const float* h2, long long h_bstride, float* V, float* Hc,
+                              int batch, int C, int H, int d, int L, int Lp, int ld, int pad, int ldp, int ncols, hipStream_t s);
+
 }  // namespace ctts

@@ -429,6 +429,76 @@ __global__ __launch_bounds__(64) void fold_skend_b_kernel(const float* __restric
     bf[e] = (float)(acc + (double)bend[e]);
 }
 
+// ----------------------------------------------------- Winograd F(2,3) in-layer form ----
+// The 3-tap dilated conv of a WN layer (dilation d) on the output pair (t, t + d):
+//   u[t]     = W0 V1 + (G2 V2 + G3 V3),   u[t + d] = (G2 V2 - G3 V3) + (-W2) V4
+//   V1 = x[t-d] - x[t+d]   V2 = x[t] + x[t+d]   V3 = x[t+d] - x[t]   V4 = x[t] - x[t+2d]
+//   G2 = (W0 + W1 + W2) / 2   G3 = (W0 - W1 + W2) / 2
+// 2 C MACs per output and row instead of 3 C.  Pair column j of a batch item stands for t_e = (j / d) 2d + j % d and
+// t_o = t_e + d; there are Lp = ceil(L / 2d) d of them.
+
+// dense[0] = G2, dense[1] = G3, dense[2] = -W2 as [rows][C] (in_w: [rows][C][3]); fp64 sums rounded once
+__global__ __launch_bounds__(256) void winograd_g_kernel(const float* __restrict__ in_w, float* __restrict__ dense, int n) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const double w0 = in_w[(size_t)idx * 3], w1 = in_w[(size_t)idx * 3 + 1], w2 = in_w[(size_t)idx * 3 + 2];
+    dense[idx] = (float)((w0 + w1 + w2) * 0.5);
+    dense[(size_t)n + idx] = (float)((w0 - w1 + w2) * 0.5);
+    dense[2 * (size_t)n + idx] = -in_w[(size_t)idx * 3 + 2];
+}
+
+// x [B][C][ld] and the flow's cond rows h2 [B][H][ld] (natural layout) -> V1..V4 [4][B][C][ldp] and the copies h2e, h2o
+// [2][B][H][ldp] in pair order.  Everything outside [0, L) reads as zero (what the conv's zero padding means; t + 2d can lie
+// beyond the halo), columns [Lp, ncols) are written as zeros.  One thread: four pair columns of one row.
+// VEC: d % 4 == 0 and L % 4 == 0 - the four columns are four consecutive time steps, 16-byte aligned, all inside or all outside
+template <bool VEC>
+__global__ __launch_bounds__(256) void winograd_transform_kernel(const float* __restrict__ x, long long x_bstride,
+                                                                 const float* __restrict__ h2, long long h_bstride,
+                                                                 float* __restrict__ V, float* __restrict__ Hc, int C, int H,
+                                                                 int d, int L, int Lp, int ld, int pad, int ldp, int ncols) {
+    const int j4 = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (j4 >= ncols) return;
+    const int row = blockIdx.y, b = blockIdx.z, B = gridDim.z;
+    const bool is_x = row < C;
+    const float* src = is_x ? x + (size_t)b * x_bstride + (size_t)row * ld + pad
+                            : h2 + (size_t)b * h_bstride + (size_t)(row - C) * ld + pad;
+    float4 vm = {0.f, 0.f, 0.f, 0.f}, v0 = vm, v1 = vm, v2 = vm;      // x[t_e - d], x[t_e], x[t_e + d], x[t_e + 2d]
+    if constexpr (VEC) {
+        if (j4 < Lp) {
+            const int te = (j4 / d) * 2 * d + j4 % d;
+            auto ld4 = [&](int t) { return (t >= 0 && t < L) ? *reinterpret_cast<const float4*>(src + t) : make_float4(0.f, 0.f, 0.f, 0.f); };
+            if (is_x) { vm = ld4(te - d); v2 = ld4(te + 2 * d); }
+            v0 = ld4(te); v1 = ld4(te + d);
+        }
+    } else {
+        float am[4], a0[4], a1[4], a2[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = j4 + e;
+            const int te = (j / d) * 2 * d + j % d;
+            const bool in = j < Lp;
+            auto ld1 = [&](int t) { return (in && t >= 0 && t < L) ? src[t] : 0.f; };
+            am[e] = is_x ? ld1(te - d) : 0.f; a2[e] = is_x ? ld1(te + 2 * d) : 0.f;
+            a0[e] = ld1(te); a1[e] = ld1(te + d);
+        }
+        vm = make_float4(am[0], am[1], am[2], am[3]); v0 = make_float4(a0[0], a0[1], a0[2], a0[3]);
+        v1 = make_float4(a1[0], a1[1], a1[2], a1[3]); v2 = make_float4(a2[0], a2[1], a2[2], a2[3]);
+    }
+    if (is_x) {
+        const size_t plane = (size_t)B * C * ldp;
+        float* o = V + ((size_t)b * C + row) * ldp + j4;
+        *reinterpret_cast<float4*>(o) = make_float4(vm.x - v1.x, vm.y - v1.y, vm.z - v1.z, vm.w - v1.w);
+        *reinterpret_cast<float4*>(o + plane) = make_float4(v0.x + v1.x, v0.y + v1.y, v0.z + v1.z, v0.w + v1.w);
+        *reinterpret_cast<float4*>(o + 2 * plane) = make_float4(v1.x - v0.x, v1.y - v0.y, v1.z - v0.z, v1.w - v0.w);
+        *reinterpret_cast<float4*>(o + 3 * plane) = make_float4(v0.x - v2.x, v0.y - v2.y, v0.z - v2.z, v0.w - v2.w);
+    } else {
+        const size_t plane = (size_t)B * H * ldp;
+        float* o = Hc + ((size_t)b * H + (row - C)) * ldp + j4;
+        *reinterpret_cast<float4*>(o) = v0;
+        *reinterpret_cast<float4*>(o + plane) = v1;
+    }
+}
+
 // a16[b][r][:] over the whole padded row: r < H: audio[b][ch_off + r][n], r == H: 1, other rows 0; 0 outside [pad, pad + L)
 template <int H>
 __global__ __launch_bounds__(256) void wn_start_ones_kernel(const float* __restrict__ audio, float* __restrict__ a16, int G,
@@ -667,6 +737,29 @@ int launch_fold_skend(const float* const* rs_w, const float* const* rs_b, const 
     }
     hipLaunchKernelGGL(fold_skend_b_kernel, dim3(1), dim3(64), 0, s, Wend, bend, sb, n_layers, bf, C, E);
     CTTS_CHECK_LAUNCH("fold_skend");
+    return CTTS_OK;
+}
+
+int launch_winograd_g(const float* in_w, float* dense, int rows, int C, hipStream_t s) {
+    const int n = rows * C;
+    hipLaunchKernelGGL(winograd_g_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in_w, dense, n);
+    CTTS_CHECK_LAUNCH("winograd_g");
+    return CTTS_OK;
+}
+
+int launch_winograd_transform(const float* x, long long x_bstride, const float* h2, long long h_bstride, float* V, float* Hc,
+                              int batch, int C, int H, int d, int L, int Lp, int ld, int pad, int ldp, int ncols, hipStream_t s) {
+    CTTS_CHECK_ARG(d >= 1 && Lp % d == 0 && (long long)Lp * 2 >= L && Lp <= ncols && ncols <= ldp && ncols % 4 == 0 && ldp % 4 == 0 &&
+                       ld % 4 == 0 && pad % 4 == 0 && pad + L <= ld,
+                   "winograd_transform: d=%d L=%d Lp=%d ncols=%d ldp=%d ld=%d pad=%d", d, L, Lp, ncols, ldp, ld, pad);
+    dim3 grid((ncols / 4 + 255) / 256, C + H, batch);
+    if (d % 4 == 0 && L % 4 == 0)
+        hipLaunchKernelGGL(winograd_transform_kernel<true>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lp,
+                           ld, pad, ldp, ncols);
+    else
+        hipLaunchKernelGGL(winograd_transform_kernel<false>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lp,
+                           ld, pad, ldp, ncols);
+    CTTS_CHECK_LAUNCH("winograd_transform");
     return CTTS_OK;
 }
 

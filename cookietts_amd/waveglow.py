@@ -357,8 +357,10 @@ class WaveGlow(_cache.PackedModule):
         mode = self._mode()
         _, _, ws_bytes, infer = _MODES[mode]
         cfg = self.c_config()
-        ws = self.workspace((device, B, F, mode), lambda: _lib.nbytes(getattr(lib, ws_bytes), C.byref(cfg), B, F,
-                                                                      what="workspace query failed"))
+        # (the size is part of the key: the fp32 library sizes the workspace by the in-layer form it will take, which a tuning
+        #  knob flipped between two calls changes)
+        nbytes = _lib.nbytes(getattr(lib, ws_bytes), C.byref(cfg), B, F, what="workspace query failed")
+        ws = self.workspace((device, B, F, mode, nbytes), lambda: nbytes)
         wave = torch.empty(B, L * self.n_group, dtype=torch.float32, device=device)
         blobs = (blob,) if bblob is None else (blob, bblob)        # the 16-bit entry points take both blobs
         with torch.cuda.device(device):

@@ -809,11 +809,16 @@ int ctts_taco_stop_rule_f32(const float* gate_logits, int32_t batch, int32_t gat
 int ctts_last_gemm_loop(void);
 
 /* Launch-shape overrides for A/B measurements (CTTS_F32_NO_GLDS, CTTS_F32_NO_SMALL, CTTS_F32_FORCE_SMALL, CTTS_GEMM_NO_XCD_PAIR, CTTS_BF16_NO_WIDE /
- * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD) never change results beyond the parity
+ * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD, CTTS_F32_NO_WINOGRAD, CTTS_F32_WINOGRAD_MIN) never change results beyond the parity
  * tolerance (CTTS_F32_NO_SPLITK changes the summation order of the fused WaveFlow layer at batch <= 2, see above; CTTS_F32_NO_WN_FOLD
  * brings back the fp32 WaveGlow WN stack without the start / end folds: WN layer 0 on the C-row x, the C-row deferred skip GEMM and the
  * C-row flow tail - the default folds W_in,0 . W_start into layer 0 and W_end . W_skip,i into a 2 n_half-row skip/end pass, which only
- * reorders sums).  The environment is read once,
+ * reorders sums; CTTS_F32_NO_WINOGRAD keeps the direct 3-tap in-layer GEMM of the fp32 WaveGlow at every size - by default
+ * ctts_waveglow_infer_*_f32 computes the in-layer conv of the layers that read x as Winograd F(2,3) on output pairs (t, t + d), four
+ * short-K launches of the same conv-GEMM behind a transform kernel, for utterances of at least CTTS_F32_WINOGRAD_MIN columns
+ * (steps per batch item; 0 = always; only under the fp32 MFMA loop).  The threshold looks at the utterance, not at the batch: an
+ * utterance keeps its bits whatever batch it runs in; one just below and one just above the threshold differ within the parity
+ * tolerance).  The environment is read once,
  * at the first launch; this re-reads it (tests and profiling scripts that flip a knob in-process). */
 int ctts_tuning_reload(void);
 /* The knobs as the library currently sees them: bit 0 CTTS_F32_NO_GLDS, 1 CTTS_GEMM_NO_XCD_PAIR,
@@ -824,7 +829,7 @@ int ctts_tuning_reload(void);
  * before the first poll of the persistent decoder's six vector exchanges; timing only), 24 CTTS_TACO_VALU
  * (ctts_taco_decoder_steps_f32 at batch <= 4 on the VALU kernels instead of the batched MFMA form), 25 CTTS_UP_NO_MFMA (the VALU upsampling kernel
  * also for the shape the MFMA one is built for: bit-identical), 26 CTTS_F32_NO_WN_FOLD, 27 CTTS_TACO_BG_NO_PIPE (the batched
- * decoder's plain schedule, the default above 64 rows, at every size).  Bits 2, 5, 6 and 22 belonged to retired knobs and stay unused.
+ * decoder's plain schedule, the default above 64 rows, at every size), 28 CTTS_F32_NO_WINOGRAD, 29 CTTS_F32_WINOGRAD_MIN set.  Bits 2, 5, 6 and 22 belonged to retired knobs and stay unused.
  * (Tests assert that a knob they set is the one in effect.) */
 int ctts_tuning_flags(void);
 
@@ -839,7 +844,8 @@ int ctts_tuning_flags(void);
 #define CTTS_PROF_WN_SKIP 2 /* deferred skip GEMM over K = (layers of the group) * C */
 /* fp32 with the WN folds (the default; CTTS_F32_NO_WN_FOLD = slots 0-2 only).  Slot 0 still brackets every in-layer launch, the
  * short folded layer-0 launch included (one entry per layer); slot 3 has that launch alone, so that a reader pricing slot 0 at the
- * full-K FLOP count can take it out.  The skip/end pass and the res GEMM of this form record in slots of their own. */
+ * full-K FLOP count can take it out.  In the Winograd form (CTTS_F32_NO_WINOGRAD turns it off) a slot-0 entry brackets a layer's
+ * transform kernel and its four launches, which execute 5/7 of the full-K FLOPs: priced at the full-K count it reads high too.  The skip/end pass and the res GEMM of this form record in slots of their own. */
 #define CTTS_PROF_WN_IN0F 3  /* layer 0's in-layer GEMM on the folded start: K = 3 x 16 + cond (also in slot 0) */
 #define CTTS_PROF_WN_SKEND 4 /* skip/end pass: 2 n_half rows of W_end . W_skip over a group's kept activations (+ the flow tail) */
 #define CTTS_PROF_WN_RES_F 5 /* res GEMM (x += W_res act) of the folded form */

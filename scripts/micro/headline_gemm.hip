@@ -23,6 +23,15 @@ int launch_gemm_f32_small(int, const GemmArgs&, hipStream_t) { return CTTS_E_ARG
 int wf_row_cus() { return 256; }
 }  // namespace ctts
 using namespace ctts;
+// stand-in for the traffic of a Winograd F(2,3) input transform: every thread reads 3 and writes 5 16-byte units
+__global__ __launch_bounds__(256) void stream_3r5w_kernel(const float4* __restrict__ src, float4* __restrict__ dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = src[i], b = src[n + i], c = src[2 * n + i];
+    dst[i] = a; dst[n + i] = b; dst[2 * n + i] = c;
+    dst[3 * n + i] = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
+    dst[4 * n + i] = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w);
+}
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 
 int main(int argc, char** argv) {
@@ -61,6 +70,65 @@ int main(int argc, char** argv) {
     };
     hipStream_t st; CK(hipStreamCreate(&st));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    if (getenv("HG_WINOGRAD")) {
+        // The four launches a Winograd F(2,3) form of this layer would make, in its pair space (half the columns per batch item,
+        // HG_WT column tiles, pad 0), and a stand-in for its transform's traffic (profiles/r12_01_winograd_launch_shapes.txt):
+        //   2 x (M = 1024, K = C = 32 chunks, SPLIT plain store)  +  2 x (M = 1024, K = C + CC = 48 chunks, GATE with an addend)
+        const int wt = getenv("HG_WT") ? atoi(getenv("HG_WT")) : 113;     // (113 x 8 = 904 tiles; 112 x 8 = 7 whole rounds)
+        const int ldp = wt * 128, Lp = getenv("HG_LP") ? atoi(getenv("HG_LP")) : L / 2;
+        float *V[4], *T[2], *H2[2], *actp;
+        for (auto& p : V) CK(hipMalloc(&p, (size_t)B * C * ldp * 4));
+        for (auto& p : T) CK(hipMalloc(&p, (size_t)B * 2 * C * ldp * 4));
+        for (auto& p : H2) CK(hipMalloc(&p, (size_t)B * CC * ldp * 4));
+        CK(hipMalloc(&actp, (size_t)B * C * ldp * 4));
+        for (auto& p : V) CK(hipMemcpy(p, x, (size_t)B * C * ldp * 4, hipMemcpyDeviceToDevice));
+        for (auto& p : H2) CK(hipMemcpy(p, h, (size_t)B * CC * ldp * 4, hipMemcpyDeviceToDevice));
+        auto wargs = [&](int layer, int which) {
+            GemmArgs a{};
+            a.ld = ldp; a.pad = 0; a.L = Lp; a.ntiles = wt; a.batch = B; a.dst_ld = ldp; a.dst_pad = 0; a.bm = 256; a.MB = 4;
+            a.A = A + (size_t)layer * 4 * nch * a_tile; a.bias = bias; a.gemm_mode = CTTS_GEMM_F32;
+            if (which < 2) {       // T = G . V
+                a.nseg = 1; a.nch_total = C / GEMM_KC; a.seg[0] = {V[1 + which], (long long)C * ldp, C / GEMM_KC, 0, 0, 0};
+                a.dst0 = T[which]; a.dst0_bstride = (long long)2 * C * ldp; a.M = 2 * C; a.split = 2 * C;
+            } else {               // even / odd
+                a.nseg = 2; a.nch_total = (C + CC) / GEMM_KC;
+                a.seg[0] = {V[which == 2 ? 0 : 3], (long long)C * ldp, C / GEMM_KC, 0, 0, 0};
+                a.seg[1] = {H2[which - 2], (long long)CC * ldp, CC / GEMM_KC, 0, 0, 0};
+                a.dst0 = actp; a.dst0_bstride = (long long)C * ldp; a.M = 2 * C; a.pairC = C;
+                a.addend = T[which - 2]; a.addend_bstride = (long long)2 * C * ldp;
+            }
+            return a;
+        };
+        const size_t sn = (size_t)B * C * ldp / 4;             // 16-byte units of one V plane: 3 read (0.71 GB), 5 written (1.18 GB)
+        float4 *ssrc, *sdst;
+        CK(hipMalloc(&ssrc, 3 * sn * 16)); CK(hipMalloc(&sdst, 5 * sn * 16)); CK(hipMemset(ssrc, 0, 3 * sn * 16));
+        const int reps = 24;
+        float sum = 0.f;
+        for (int which = 0; which < 5; ++which) {
+            auto go = [&](int i) {
+                if (which == 4) { hipLaunchKernelGGL(stream_3r5w_kernel, dim3((unsigned)((sn + 255) / 256)), dim3(256), 0, st, ssrc, sdst, sn); return 0; }
+                return launch_gemm_f32(which < 2 ? GEMM_EPI_SPLIT : GEMM_EPI_GATE, wargs(i % layers, which), st);
+            };
+            for (int i = 0; i < 4; ++i) if (go(i)) return 1;
+            CK(hipStreamSynchronize(st));
+            CK(hipEventRecord(e0, st));
+            for (int i = 0; i < reps; ++i) if (go(i)) return 1;
+            CK(hipEventRecord(e1, st));
+            CK(hipStreamSynchronize(st));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+            ms /= reps;
+            sum += ms;
+            static const char* names[5] = {"T2 = G2.V2  SPLIT K=32ch", "T3 = G3.V3  SPLIT K=32ch", "even GATE+addend K=48ch", "odd  GATE+addend K=48ch", "transform stand-in 3r5w"};
+            if (which < 4) {
+                const double flop = 2.0 * 1024 * (which < 2 ? C : C + CC) * (double)B * Lp;
+                printf("%-26s %d tiles x 4 = %.3f rounds  %.4f ms  %.4f of 157.3\n", names[which], wt * B, 4.0 * wt * B / 512.0, ms, flop / (ms * 1e-3) / 157.3e12);
+            } else {
+                printf("%-26s %.2f GB read %.2f GB written  %.4f ms  %.2f TB/s\n", names[which], 3 * sn * 16e-9, 5 * sn * 16e-9, ms, 8 * sn * 16e-12 / (ms * 1e-3));
+            }
+        }
+        printf("sum of the five: %.4f ms per layer\n", sum);
+        return 0;
+    }
     for (int i = 0; i < 4; ++i) if (launch_gemm_f32(GEMM_EPI_GATE, args(i % layers), st)) return 1;
     CK(hipStreamSynchronize(st));
     const int reps = 24;
