@@ -167,6 +167,7 @@ SIGNATURES = {
     "ctts_wn_cond_f32": (C.c_int, [_CFG, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
     "ctts_wn_stack_f32": (C.c_int, [_CFG, _FP, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
     "ctts_flow_tail_f32": (C.c_int, [_CFG, _FP, C.c_int32, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
+    "ctts_waveglow_flow_f32": (C.c_int, [_CFG, _FP, C.c_int32, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
     "ctts_waveflow_packed_bytes": (C.c_size_t, [C.POINTER(WaveFlowConfig)]),
     "ctts_waveflow_pack_flow": (C.c_int, [C.POINTER(WaveFlowConfig), C.c_int32, C.POINTER(WaveFlowFlowWeights), _FP, _FP]),
     "ctts_waveflow_workspace_bytes": (C.c_size_t, [C.POINTER(WaveFlowConfig), C.c_int32, C.c_int32]),

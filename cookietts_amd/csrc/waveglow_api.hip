@@ -485,6 +485,22 @@ int run_flow_tail(const Plan& p, const Geom& g, const float* blob, int k, const 
                             p.c.n_group, d.ch_off, d.n_half, g.L, g.ld, g.pad, s);
 }
 
+// One flow of the fp32 infer loop, in the form the tuning knobs and the workspace select: the folded, deferred stack (whose last
+// skip/end pass is also the flow's tail) or the unfolded stack followed by the flow tail; the Winograd in-layer form where carve()
+// gave it buffers.  `audio` [B][n_group][L] is updated in place (or, with `wave`, the mixed rows go there un-squeezed).  The
+// whole-infer entry and the one-flow stage entry both run exactly this.
+int run_flow(const Plan& p, const Geom& g, const float* blob, int k, const Workspace& w, float* audio, const float* h_all,
+             float* wave, int batch, hipStream_t s) {
+    const Tuning t = tuning();
+    const bool folded = !t.f32_no_wn_fold && !t.f32_no_defer_skip;
+    const WnWinograd wg{w.wgV, w.wgT, w.wgH, w.ldp};
+    const WnFold fw{w.a16, w.skend, audio, wave};
+    int rc = run_wn_stack(p, g, blob, k, audio, h_all, w.x, w.act, w.out, batch, s, w.act_all, folded ? &fw : nullptr,
+                          w.wgV ? &wg : nullptr);
+    if (rc || folded) return rc;        // folded: the last skip/end pass of the flow was its tail
+    return run_flow_tail(p, g, blob, k, w.out, audio, wave, batch, s);
+}
+
 // ======================================================================================
 // bf16 variant (BASELINE config 3): WN in-layer / res-skip GEMMs on bf16 MFMA with fp32 accumulation,
 // WN activations (x, act, skip sum, cond hidden) stored bf16 in the K8-blocked layout; upsampling, the
@@ -997,6 +1013,22 @@ int ctts_flow_tail_f32(const ctts_waveglow_config* cfg, const void* packed, int3
     return run_flow_tail(p, g, static_cast<const float*>(packed), flow, out, audio, wave, batch, as_stream(stream));
 }
 
+int ctts_waveglow_flow_f32(const ctts_waveglow_config* cfg, const void* packed, int32_t flow, float* audio,
+                           const float* h_all, float* wave, int32_t batch, int32_t frames, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    Plan p; Geom g; Workspace w;
+    int rc = make_plan(cfg, p); if (rc) return rc;
+    rc = make_geom(p, frames, g); if (rc) return rc;
+    CTTS_CHECK_ARG(flow >= 0 && flow < p.c.n_flows, "waveglow_flow: flow %d", flow);
+    CTTS_CHECK_ARG(packed && audio && h_all && workspace && batch >= 1, "waveglow_flow: bad argument");
+    carve(p, g, batch, static_cast<float*>(workspace), w);
+    if (w.total * sizeof(float) > workspace_bytes) {
+        set_error("waveglow_flow: workspace %zu bytes < required %zu", workspace_bytes, w.total * sizeof(float));
+        return CTTS_E_WORKSPACE;
+    }
+    return run_flow(p, g, static_cast<const float*>(packed), flow, w, audio, h_all, wave, batch, as_stream(stream));
+}
+
 int ctts_waveglow_infer_f32(const ctts_waveglow_config* cfg, const void* packed, const float* mel,
                             const float* z_scaled, float* wave, int32_t batch, int32_t frames, void* workspace,
                             size_t workspace_bytes, void* stream) {
@@ -1027,16 +1059,8 @@ int ctts_waveglow_infer_spk_f32(const ctts_waveglow_config* cfg, const void* pac
     if (rc) return rc;
     rc = run_cond(p, g, blob, w.spect, w.spk, w.h_tmp, w.h_all, batch, s);
     if (rc) return rc;
-    const Tuning t = tuning();
-    const bool folded = !t.f32_no_wn_fold && !t.f32_no_defer_skip;
-    const WnWinograd wg{w.wgV, w.wgT, w.wgH, w.ldp};
     for (int k = p.c.n_flows - 1; k >= 0; --k) {
-        const WnFold fw{w.a16, w.skend, w.audio, k == 0 ? wave : nullptr};
-        rc = run_wn_stack(p, g, blob, k, w.audio, w.h_all, w.x, w.act, w.out, batch, s, w.act_all, folded ? &fw : nullptr,
-                          w.wgV ? &wg : nullptr);
-        if (rc) return rc;
-        if (folded) continue;        // the last skip/end pass of the flow was its tail
-        rc = run_flow_tail(p, g, blob, k, w.out, w.audio, k == 0 ? wave : nullptr, batch, s);
+        rc = run_flow(p, g, blob, k, w, w.audio, w.h_all, k == 0 ? wave : nullptr, batch, s);
         if (rc) return rc;
     }
     return CTTS_OK;

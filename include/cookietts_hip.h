@@ -233,6 +233,17 @@ int ctts_flow_tail_f32(const ctts_waveglow_config* cfg, const void* packed, int3
                        const float* out, float* audio, float* wave, int32_t batch,
                        int32_t frames, void* stream);
 
+/* One flow exactly as ctts_waveglow_infer_spk_f32 runs it (both share one helper): the form the CTTS_F32_* knobs select at this
+ * length - WN start / end folds, deferred skip sum, Winograd F(2,3) in-layers - or the per-layer stack plus the flow tail.
+ *   audio [B][n_group][L] dense: rows [ch_off, ch_off + n_remaining) of flow `flow` are updated in place, the others are not
+ *         touched (what the infer entry keeps in its workspace between flows);
+ *   h_all [B][n_flows*256][ld] padded layout, as ctts_wn_cond_f32 writes it (only the flow's own 256 rows are read);
+ *   wave  NULL, or [B][L*n_group]: the mixed rows go there un-squeezed instead (ctts_flow_tail_f32's rule).
+ * workspace: ctts_waveglow_workspace_bytes(cfg, batch, frames) bytes, zero-filled once before its first use with this geometry. */
+int ctts_waveglow_flow_f32(const ctts_waveglow_config* cfg, const void* packed, int32_t flow, float* audio,
+                           const float* h_all, float* wave, int32_t batch, int32_t frames, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ---- WaveFlow ("ax" core, waveflow=True): _4_mtw/waveglow/efficient_model_ax.py --------- */
 
 /* Constructor arguments that shape the path (efficient_model_ax.py:19-169, glow_ax.py:427-543).

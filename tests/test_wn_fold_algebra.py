@@ -6,104 +6,17 @@
    W_skip,i / b_skip,i and b' = b_end + W_end . sum_i b_skip,i.
 
 The first and last columns are checked on their own: a bias folded without the zero padding shows only there.
+The restatement itself lives in waveglow_f64_restatement.py, shared with the per-flow stage tests.
 """
 import numpy as np
 import pytest
 
 from cookietts_amd import synthetic
-from oracle import waveglow_oracle as wo
+from waveglow_f64_restatement import FOLD_ROWS, a16 as _a16, flow_weights as _flow_weights, fold_end as _fold_end, \
+    fold_in0 as _fold_in0, shift as _shift, wn as _wn
 
-FOLD_ROWS = 16        # rows of the folded layer-0 input (waveglow_kernels.h)
 CONFIGS = ["toy", "toy_early", "toy_spk_rezero", "toy_hop512_g16"]
 TOL = 1e-11
-
-
-def _shift(x, s):
-    return wo._shift(x, s)
-
-
-def _flow_weights(sd, k, n_layers):
-    """float64 dense weights of flow k as the packer receives them: weight norm folded, ReZero alpha in the res/skip rows."""
-    p = f"WN.{k}"
-    f = wo.fold_state_dict(sd)
-    w = {"start_w": f[p + ".start.weight"][:, :, 0].astype(np.float64), "start_b": f[p + ".start.bias"].astype(np.float64),
-         "end_w": np.asarray(sd[p + ".end.weight"], np.float64)[:, :, 0], "end_b": np.asarray(sd[p + ".end.bias"], np.float64),
-         "in_w": [], "in_b": [], "rs_w": [], "rs_b": []}
-    for i in range(n_layers):
-        w["in_w"].append(f[f"{p}.in_layers.{i}.weight"].astype(np.float64))
-        w["in_b"].append(f[f"{p}.in_layers.{i}.bias"].astype(np.float64))
-        alpha = float(sd[f"{p}.alpha_i.{i}"][0]) if f"{p}.alpha_i.{i}" in sd else 1.0
-        w["rs_w"].append(f[f"{p}.res_skip_layers.{i}.weight"][:, :, 0].astype(np.float64) * alpha)
-        w["rs_b"].append(f[f"{p}.res_skip_layers.{i}.bias"].astype(np.float64) * alpha)
-    return w
-
-
-def _gate(u, C):
-    return np.tanh(u[:, :C]) / (1.0 + np.exp(-u[:, C:]))
-
-
-def _in_layer(w_in, b_in, x, cond_i, dil):
-    ks = w_in.shape[2]
-    u = b_in[None, :, None] + cond_i
-    for t in range(ks):
-        u = u + np.einsum("oc,bcl->bol", w_in[:, :, t], _shift(x, (t - ks // 2) * dil))
-    return u
-
-
-def _fold_in0(w, n_half):
-    """[2C][FOLD_ROWS][ks]: rows < n_half W_in,0[tap] . W_start, row n_half W_in,0[tap] . b_start, the rest 0."""
-    w_in = w["in_w"][0]
-    f = np.zeros((w_in.shape[0], FOLD_ROWS, w_in.shape[2]))
-    for t in range(w_in.shape[2]):
-        f[:, :n_half, t] = w_in[:, :, t] @ w["start_w"]
-        f[:, n_half, t] = w_in[:, :, t] @ w["start_b"]
-    return f
-
-
-def _a16(a):
-    B, n_half, L = a.shape
-    a16 = np.zeros((B, FOLD_ROWS, L))
-    a16[:, :n_half] = a
-    a16[:, n_half] = 1.0
-    return a16
-
-
-def _fold_end(w, C, n_layers):
-    skip_rows = [w["rs_w"][i][C:] if i < n_layers - 1 else w["rs_w"][i] for i in range(n_layers)]
-    skip_bias = [w["rs_b"][i][C:] if i < n_layers - 1 else w["rs_b"][i] for i in range(n_layers)]
-    Wf = [w["end_w"] @ s for s in skip_rows]
-    bf = w["end_b"] + w["end_w"] @ np.sum(skip_bias, axis=0)
-    return Wf, bf
-
-
-def _wn(w, a, cond, C, n_layers, fold):
-    """One WN stack in float64; fold: layer 0 on [a; 1; 0] and the skip sum seen through end. Returns (e, layer-0 input)."""
-    x = np.einsum("cj,bjl->bcl", w["start_w"], a) + w["start_b"][None, :, None]
-    out = 0.0
-    acts = []
-    u0 = None
-    for i in range(n_layers):
-        cond_i = cond[:, 2 * C * i:2 * C * (i + 1)]
-        if fold and i == 0:
-            u = _in_layer(_fold_in0(w, a.shape[1]), w["in_b"][0], _a16(a), cond_i, 1)
-        else:
-            u = _in_layer(w["in_w"][i], w["in_b"][i], x, cond_i, 2 ** i)
-        if i == 0:
-            u0 = u
-        act = _gate(u, C)
-        acts.append(act)
-        r = np.einsum("oc,bcl->bol", w["rs_w"][i], act) + w["rs_b"][i][None, :, None]
-        if i < n_layers - 1:
-            x = x + r[:, :C]
-            out = out + r[:, C:]
-        else:
-            out = out + r
-    if fold:
-        Wf, bf = _fold_end(w, C, n_layers)
-        e = sum(np.einsum("ec,bcl->bel", Wf[i], acts[i]) for i in range(n_layers)) + bf[None, :, None]
-    else:
-        e = np.einsum("ec,bcl->bel", w["end_w"], out) + w["end_b"][None, :, None]
-    return e, u0
 
 
 def _rel(a, b):
