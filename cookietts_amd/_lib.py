@@ -247,7 +247,12 @@ SIGNATURES = {
     "ctts_hifigan_workspace_f16_bytes": (C.c_size_t, [C.POINTER(HifiganConfig), C.c_int32, C.c_int32]),
     "ctts_hifigan_forward_f16": (C.c_int, [C.POINTER(HifiganConfig), _FP, _FP, C.c_int32, _FP, C.c_int32, C.c_int32, _FP,
                                            C.c_size_t, _FP]),
-    "ctts_replicate_halo_f32": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
+    "ctts_hifigan_packed_bf16x3_bytes": (C.c_size_t, [C.POINTER(HifiganConfig)]),
+    "ctts_hifigan_pack_bf16x3": (C.c_int, [C.POINTER(HifiganConfig), _FP, C.c_size_t, _FP, _FP]),
+    "ctts_hifigan_workspace_bf16x3_bytes": (C.c_size_t, [C.POINTER(HifiganConfig), C.c_int32, C.c_int32]),
+    "ctts_hifigan_forward_bf16x3": (C.c_int, [C.POINTER(HifiganConfig), _FP, _FP, C.c_int32, _FP, C.c_int32, C.c_int32, _FP,
+                                              C.c_size_t, _FP]),
+    "ctts_replicate_halo_f32":(C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "ctts_embed_rows_f32": (C.c_int, [_FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, _FP]),
     "ctts_scale_add_rows_f32": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

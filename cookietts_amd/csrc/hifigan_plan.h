@@ -3,6 +3,12 @@
 //
 // `esz` is the size of a stored activation / weight element: 4 = fp32 rows [C][ld], ld = roundup(L, 4); 2 = IEEE half in
 // the K8-blocked layout [ceil(C / 8)][ld][8], ld = L (a column of 8 channels is one 16-byte unit).
+//
+// A third format, split bf16 (hifigan_bf16x3.hip), keeps the fp32 tensors and carries each operand of a product as a hi | lo
+// pair of bf16 - 4 bytes, the fp32 element's.  It therefore IS the esz = 4 plan: the same layer list, KC (a K16 MFMA step is
+// 16 channels of one tap at KC = 16, 8 channels of two taps at KC = 8), lds_bytes(), packed_bytes, offsets, workspace geometry
+// and launch sequence; only the arrangement of a layer's packed weights ([MB][nch][ntap][KC / 8][hi, lo][BM][8] bf16) and of
+// the staged tile ([KC / 8][hi, lo][BN + (ntap - 1) * dil] units, never wider than the fp32 tile) differ.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -254,7 +260,8 @@ int hg_forward(const HgPlan& p, const HgGeom& g, const float* mel, int mel_ld, f
     return CTTS_OK;
 }
 
-// the pack kernels' arguments (T as above); A is [MB][nch][ntap][KC][BM] in fp32, [MB][nch][ntap][KC / 8][BM][8] in half
+// the pack kernels' arguments (T as above); A is [MB][nch][ntap][KC][BM] in fp32, [MB][nch][ntap][KC / 8][BM][8] in half,
+// [MB][nch][ntap][KC / 8][hi, lo][BM][8] bf16 in the split format (T = float: the same bytes)
 template <typename T>
 struct HgPackArgsT {
     const float* w;        // HG_CONV: [M][Cin][k]; HG_CONVT: [Cin][cout][ku]

@@ -14,6 +14,9 @@ dtype of the mel it was given.  Options the kernels cannot run exactly raise ``N
 ``set_compute_dtype(torch.float16)`` selects the IEEE-half storage mode (``ctts_hifigan_forward_f16``, csrc/hifigan_f16.hip):
 weights and every stored activation in half, products on the f16 MFMA, fp32 accumulation.  It is independent of the parameter
 dtype; what the reference's server gets from ``vocoder.half()`` is ``vocoder.half().set_compute_dtype(torch.float16)`` here.
+
+``set_f32_gemm_mode("bf16x3")`` keeps the fp32 tensors and runs every product as split bf16 (``ctts_hifigan_forward_bf16x3``,
+csrc/hifigan_bf16x3.hip): hi + lo bf16 operands, three bf16 MFMA products per operand pair, fp32 accumulation.
 """
 from __future__ import annotations
 
@@ -84,6 +87,15 @@ def c_config(h):
     return cfg
 
 
+# library entry points of the three arithmetic paths: packed-size query, pack, workspace-size query, forward
+_ENTRY = {
+    "f32": ("ctts_hifigan_packed_bytes", "ctts_hifigan_pack_f32", "ctts_hifigan_workspace_bytes", "ctts_hifigan_forward_f32"),
+    "f16": ("ctts_hifigan_packed_f16_bytes", "ctts_hifigan_pack_f16", "ctts_hifigan_workspace_f16_bytes", "ctts_hifigan_forward_f16"),
+    "bf16x3": ("ctts_hifigan_packed_bf16x3_bytes", "ctts_hifigan_pack_bf16x3", "ctts_hifigan_workspace_bf16x3_bytes",
+               "ctts_hifigan_forward_bf16x3"),
+}
+
+
 class _ResBlock(nn.Module):
     """Parameter tree of ResBlock1 (models.py:35-73: ``convs1`` / ``convs2``) or ResBlock2 (:75-92: ``convs``)."""
 
@@ -132,8 +144,46 @@ class Generator(_cache.PackedModule):
         if lib.ctts_hifigan_packed_bytes(C.byref(self._cfg)) == 0:
             raise NotImplementedError("cookietts_amd.HiFiGANGenerator: refused by the library: " + _lib.last_error())
         self._compute_dtype = torch.float32
+        self._f32_gemm_mode = None
 
     # ------------------------------------------------------------------ plumbing ----
+    def _path(self):
+        """Key into ``_ENTRY`` of the arithmetic the next call runs: ``"f16"``, ``"bf16x3"`` or ``"f32"``."""
+        if self._compute_dtype == torch.float16:
+            return "f16"
+        return "bf16x3" if _lib.model_gemm_mode(self._f32_gemm_mode) == _lib.MODEL_GEMM_MODES["bf16x3"] else "f32"
+
+    def set_f32_gemm_mode(self, mode):
+        """Products of the fp32 tensors, same name and meaning as on the WaveGlow classes: ``None`` / ``"default"`` / ``"f32"``
+        (exact fp32 MFMA) or ``"bf16x3"``: split bf16 - activations stay fp32 in the fp32 path's layout and workspace, weights
+        (once, at pack time) and staged activations are carried as ``hi + lo`` bf16, and every product is ``w_hi x_hi + w_lo x_hi +
+        w_hi x_lo`` on the bf16 MFMA with fp32 accumulation (16 mantissa bits per operand; the arithmetic is listed at
+        ``ctts_hifigan_forward_bf16x3``).  ``"bf16x6"`` is not built for this model (``NotImplementedError``); an unknown name
+        is a ``ValueError``.
+
+        The mode acts while the compute dtype is ``torch.float32``.  Under ``set_compute_dtype(torch.float16)`` the f16 path
+        runs; the mode is remembered but inert, and acts again once the compute dtype is back at ``torch.float32``.  ``.half()``
+        keeps its meaning: fp16 parameters, then the selected products.  Returns ``self``; the packed blob and the workspaces
+        are dropped when the selected products change and kept when they do not.  ``NotImplementedError`` - here, not at the
+        first call - if the library refuses the config."""
+        code = _lib.model_gemm_mode(mode)
+        if code == _lib.MODEL_GEMM_MODES["bf16x6"]:
+            raise NotImplementedError("cookietts_amd.HiFiGANGenerator: f32 GEMM mode 'bf16x6' is not built for this model "
+                                      "('f32' or 'bf16x3')")
+        if code == _lib.MODEL_GEMM_MODES["bf16x3"]:
+            if _lib.lib().ctts_hifigan_packed_bf16x3_bytes(C.byref(self._cfg)) == 0:
+                raise NotImplementedError("cookietts_amd.HiFiGANGenerator: split-bf16 products refused by the library: "
+                                          + _lib.last_error())
+        before = self._path()
+        self._f32_gemm_mode = mode
+        if self._path() != before:
+            self._invalidate()        # the packed blob is per format
+        return self
+
+    @property
+    def f32_gemm_mode(self):
+        return self._f32_gemm_mode
+
     def set_compute_dtype(self, dtype):
         """Storage and product format of the whole generator: ``torch.float32`` (default: fp32 tensors, exact fp32 MFMA) or
         ``torch.float16``: weights and every stored activation as IEEE half, products on the f16 matrix pipe, accumulation,
@@ -195,13 +245,12 @@ class Generator(_cache.PackedModule):
         with torch.cuda.device(device):
             flat = torch.cat([t.reshape(-1) for wb in self.folded_weights() for t in wb]).to(device).contiguous()
             n = lib.ctts_hifigan_weight_floats(C.byref(self._cfg))
-            f16 = self._compute_dtype == torch.float16
-            nbytes = (lib.ctts_hifigan_packed_f16_bytes if f16 else lib.ctts_hifigan_packed_bytes)(C.byref(self._cfg))
+            packed_bytes, name, _, _ = _ENTRY[self._path()]
+            nbytes = getattr(lib, packed_bytes)(C.byref(self._cfg))
             blob = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
             stream = _lib.stream(device)
             if flat.numel() != n:
                 raise _lib.HipLibraryError(f"HiFi-GAN: {flat.numel()} weights in the module tree, the library expects {n}")
-            name = "ctts_hifigan_pack_f16" if f16 else "ctts_hifigan_pack_f32"
             _lib.check(getattr(lib, name)(C.byref(self._cfg), _lib.ptr(flat), flat.numel(), _lib.ptr(blob), stream), name)
             torch.cuda.current_stream(device).synchronize()     # `flat` dies with this frame
         return blob
@@ -216,9 +265,8 @@ class Generator(_cache.PackedModule):
         blob = self._ensure_packed(device)
         lib = _lib.lib()
         B, _, T = x.shape
-        f16 = self._compute_dtype == torch.float16
-        ws_bytes = lib.ctts_hifigan_workspace_f16_bytes if f16 else lib.ctts_hifigan_workspace_bytes
-        fwd = "ctts_hifigan_forward_f16" if f16 else "ctts_hifigan_forward_f32"
+        _, _, ws_query, fwd = _ENTRY[self._path()]
+        ws_bytes = getattr(lib, ws_query)
         mel = x.detach().float().contiguous()
         if T % 4:                                               # rows on 16-byte boundaries: vector staging in the first conv
             mel = torch.nn.functional.pad(mel, (0, 4 - T % 4))
@@ -231,13 +279,13 @@ class Generator(_cache.PackedModule):
         return audio if x.dtype == torch.float32 else audio.to(x.dtype)
 
 
-def load_model(model_path, device='cuda', trust_checkpoint=False, compute_dtype=None):
+def load_model(model_path, device='cuda', trust_checkpoint=False, compute_dtype=None, f32_gemm_mode=None):
     """``hifigan.models.load_model`` (models.py:14-31): ``config.json`` beside the checkpoint, key ``'generator'`` with the
     weight-norm keys, weight norm removed after loading.  Returns ``(generator, h)``.
 
     The checkpoint is read with ``weights_only=True`` (no pickle code execution); one that pickles other objects needs
     ``trust_checkpoint=True`` - only for files you produced yourself.  ``compute_dtype`` (``torch.float32`` /
-    ``torch.float16``) is handed to ``Generator.set_compute_dtype``."""
+    ``torch.float16``) is handed to ``Generator.set_compute_dtype``, ``f32_gemm_mode`` to ``Generator.set_f32_gemm_mode``."""
     with open(os.path.join(os.path.split(model_path)[0], 'config.json')) as f:
         h = AttrDict(json.loads(f.read()))
     generator = Generator(h)
@@ -252,4 +300,6 @@ def load_model(model_path, device='cuda', trust_checkpoint=False, compute_dtype=
     generator.remove_weight_norm()
     if compute_dtype is not None:
         generator.set_compute_dtype(compute_dtype)
+    if f32_gemm_mode is not None:
+        generator.set_f32_gemm_mode(f32_gemm_mode)
     return generator, h

@@ -526,6 +526,25 @@ int ctts_hifigan_forward_f16(const ctts_hifigan_config* cfg, const void* packed,
                              float* audio, int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* Split-bf16 products on the fp32 tensors of the same generator (csrc/hifigan_bf16x3.hip): activations, workspace,
+ * epilogues and launch sequence are forward_f32's; every product runs as hi + lo bf16 operands on the bf16 MFMA with fp32
+ * accumulation.  Weights, once at pack time from the fp32 folded value: w_hi = bf16_rne(w), w_lo = bf16_rne(w - w_hi)
+ * (biases stay fp32; padding and dead taps are zeros in both planes).  Activations, while a tile is staged: leaky_relu in
+ * fp32 as forward_f32 does, then x_hi = bf16_rne(v), x_lo = bf16_rne(v - x_hi).  Product: acc += w_hi x_hi, + w_lo x_hi,
+ * + w_hi x_lo in that order per K16 step; no lo x lo term.  A non-finite activation gives NaN (inf - inf in the lo plane).
+ * An item of a batch equals the same item run alone bit for bit.  ctts_hifigan_packed_bf16x3_bytes ==
+ * ctts_hifigan_packed_bytes (a hi | lo pair is the 4 bytes of the fp32 weight; the blob's layout differs) and
+ * ctts_hifigan_workspace_bf16x3_bytes == ctts_hifigan_workspace_bytes.  pack_bf16x3 reads the same flat fp32 buffer as
+ * pack_f32.  Same contract as the _f16 set: every argument is validated before the first launch, the size queries return
+ * 0 (ctts_last_error names the option) for exactly the configs the fp32 queries refuse. */
+size_t ctts_hifigan_packed_bf16x3_bytes(const ctts_hifigan_config* cfg);
+int ctts_hifigan_pack_bf16x3(const ctts_hifigan_config* cfg, const float* weights, size_t weight_floats, void* packed,
+                             void* stream);
+size_t ctts_hifigan_workspace_bf16x3_bytes(const ctts_hifigan_config* cfg, int32_t batch, int32_t frames);
+int ctts_hifigan_forward_bf16x3(const ctts_hifigan_config* cfg, const void* packed, const float* mel, int32_t mel_ld,
+                                float* audio, int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
 /* ---- Tacotron2-TM decoder loop: _2_ttm/tacotron2_tm/model.py:668-767, 851-916 -------------- */
 
 /* Shapes from hparams.py (:201-258).  Built topology = the repo defaults: attention_type 0 with

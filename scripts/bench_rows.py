@@ -272,6 +272,17 @@ def _hifigan_f16_pair(key):
     return m, (lambda mel16: hr.generator(cfg, w, mel16))
 
 
+def _hifigan_bf16x3(key):
+    """A third HIP generator on the same weights with ``set_f32_gemm_mode("bf16x3")`` (its own instance: the alternated loop
+    never repacks)."""
+    from cookietts_amd import HiFiGANGenerator
+    from cookietts_amd.hifigan import AttrDict
+    cfg = synthetic.HIFIGAN_CONFIGS[key]
+    m = HiFiGANGenerator(AttrDict(cfg))
+    m.load_state_dict(synthetic.to_torch(synthetic.hifigan_state_dict(cfg, seed=1234)))
+    return m.cuda().eval().set_f32_gemm_mode("bf16x3")
+
+
 def _event_ms(fn, steps):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -292,20 +303,25 @@ def row_hifigan(args):
     Two more arms in the same alternated loop give a second row per shape, ``H/hifigan_f16``: ``hip_f16`` =
     ctts_hifigan_forward_f16 (``set_compute_dtype(torch.float16)``: IEEE-half storage, f16 MFMA) and ``torch_f16`` = the plain
     generator with ``.half()`` weights and mel through PyTorch-ROCm.  Its ``roofline`` carries both fractions - FLOP over the
-    f16 MFMA peak, algorithmic bytes (hifigan_f16_restatement.generator_bytes) over the HBM peak - and ``bound`` names the larger."""
+    f16 MFMA peak, algorithmic bytes (hifigan_f16_restatement.generator_bytes) over the HBM peak - and ``bound`` names the larger.
+
+    ``hip_bf16x3`` = ctts_hifigan_forward_bf16x3 (``set_f32_gemm_mode("bf16x3")``: fp32 tensors, split-bf16 products) in the same
+    loop gives a third row, ``H/hifigan_bf16x3``, priced against one third of the bf16 MFMA peak (three products per operand pair)
+    and against HBM by the algorithmic fp32 bytes."""
     rows = []
     frames = 900
-    arms_on = getattr(args, "arms", "hip,torch,hip_f16,torch_f16").split(",")
+    arms_on = getattr(args, "arms", "hip,torch,hip_f16,torch_f16,hip_bf16x3").split(",")
     for key, batches in (("v1", _batches(args, (1, 4, 16))), ("v1_48khz", (1,))):
         m, base, cfg, hr = _hifigan_pair(key)
         m16, base16 = _hifigan_f16_pair(key) if ("hip_f16" in arms_on or "torch_f16" in arms_on) else (None, None)
+        m3 = _hifigan_bf16x3(key) if "hip_bf16x3" in arms_on else None
         import hifigan_f16_restatement as h16
         rate = cfg["sampling_rate"]
         for B in batches:
             mel = torch.from_numpy(synthetic.synthetic_mel(B, frames, cfg["num_mels"], seed=B)).cuda()
             mel16 = mel.half()
             arms = [a for a in (("hip", lambda: m(mel)), ("torch", lambda: base(mel)), ("hip_f16", lambda: m16(mel)),
-                                ("torch_f16", lambda: base16(mel16))) if a[0] in arms_on]
+                                ("torch_f16", lambda: base16(mel16)), ("hip_bf16x3", lambda: m3(mel))) if a[0] in arms_on]
             times = {n: [] for n, _ in arms}
             with torch.no_grad():
                 outs = {}
@@ -337,8 +353,10 @@ def row_hifigan(args):
                 rows.append(row)
             if "hip_f16" in med or "torch_f16" in med:
                 rows.append(_hifigan_f16_row(key, cfg, B, frames, flop, samples, rate, times, med, outs, h16))
+            if "hip_bf16x3" in med:
+                rows.append(_hifigan_bf16x3_row(key, cfg, B, frames, flop, samples, rate, times, med, outs, h16))
             del mel, mel16, outs
-        del m, base, m16, base16
+        del m, base, m16, base16, m3
         torch.cuda.empty_cache()
     return rows
 
@@ -368,6 +386,31 @@ def _hifigan_f16_row(key, cfg, B, frames, flop, samples, rate, times, med, outs,
         if "hip" in outs:
             d = (outs["hip_f16"].double() - outs["hip"].double())
             row["hip_f16_vs_hip_f32_rel_rms"] = float(d.pow(2).mean().sqrt() / outs["hip"].double().pow(2).mean().sqrt())
+    return row
+
+
+def _hifigan_bf16x3_row(key, cfg, B, frames, flop, samples, rate, times, med, outs, h16):
+    """The split-bf16 row of one shape; the fp32 ``hip`` arm of the same loop is the ratio's denominator.  ``flop`` counts one
+    product per operand pair, so the matrix-pipe peak it is priced against is a third of the bf16 MFMA peak."""
+    nbytes = float(B * h16.generator_bytes(cfg, frames, 4))
+    peak = F16_MFMA_PEAK_TFLOPS / 3.0
+    t = times["hip_bf16x3"]
+    dt = med["hip_bf16x3"] * 1e-3
+    mfma_frac = flop / dt / 1e12 / peak
+    hbm_frac = nbytes / dt / 1e12 / HBM_PEAK_TBPS
+    row = {"row": "H/hifigan_bf16x3", "arm": "bf16x3", "metric": f"HiFi-GAN {key} generator, fp32 tensors, split-bf16 products, {B} x {cfg['num_mels']} x {frames} mel, ms per call (device events)",
+           "config": key, "batch": B, "frames": frames, "flop": flop, "algorithmic_bytes": nbytes,
+           "arms": {"hip_bf16x3": {"reps_ms": t, "median_ms": med["hip_bf16x3"], "min_ms": min(t), "max_ms": max(t),
+                                   "spread_frac": (max(t) - min(t)) / med["hip_bf16x3"]}},
+           "value": med["hip_bf16x3"], "unit": "ms", "samples_per_sec": samples / dt, "rtf": samples / dt / rate,
+           "roofline": {"kernel": "hg_conv_bf16x3_kernel (all launches of the call)", "bound": "hbm" if hbm_frac >= mfma_frac else "mfma",
+                        "mfma": {"achieved": flop / dt / 1e12, "peak": peak, "unit": "TFLOP/s", "frac": mfma_frac},
+                        "hbm": {"achieved": nbytes / dt / 1e12, "peak": HBM_PEAK_TBPS, "unit": "TB/s", "frac": hbm_frac},
+                        "frac": max(hbm_frac, mfma_frac), "traffic": "algorithmic bytes from the shapes, not counters"}}
+    if "hip" in med:
+        row["hip_f32_over_hip_bf16x3"] = med["hip"] / med["hip_bf16x3"]
+        d = (outs["hip_bf16x3"].double() - outs["hip"].double())
+        row["hip_bf16x3_vs_hip_f32_rel_rms"] = float(d.pow(2).mean().sqrt() / outs["hip"].double().pow(2).mean().sqrt())
     return row
 
 
@@ -492,8 +535,8 @@ if __name__ == "__main__":
                     help="waveglow_ax: f16 = IEEE-half storage of the WN stacks (model.set_compute_dtype(torch.float16))")
     ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab: repetitions of every arm (alternated)")
     ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts) to these batch sizes (PMC passes)")
-    ap.add_argument("--arms", default="hip,torch,hip_f16,torch_f16",
-                    help="hifigan: arms to run (hip or hip_f16 alone for a profiler pass)")
+    ap.add_argument("--arms", default="hip,torch,hip_f16,torch_f16,hip_bf16x3",
+                    help="hifigan: arms to run (hip, hip_f16 or hip_bf16x3 alone for a profiler pass)")
     args = ap.parse_args()
     fns = {"hifigan": row_hifigan, "waveflow": row_waveflow, "waveflow_table": row_waveflow_table, "waveflow_author": row_waveflow_author, "tacotron": row_tacotron, "stft": row_stft,
            "waveglow_ax": row_waveglow_ax_notebook, "waveglow_ax_ab": row_waveglow_ax_notebook_ab, "waveglow_ax_untts": row_waveglow_ax_untts}
