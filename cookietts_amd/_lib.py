@@ -347,7 +347,7 @@ TUNING_BITS = {"CTTS_F32_NO_GLDS": 0, "CTTS_GEMM_NO_XCD_PAIR": 1, "CTTS_BF16_NO_
                "CTTS_F32_NO_DEFER_SKIP": 13, "CTTS_WF_NO_REGION_SPLIT": 14, "CTTS_WF_NO_ROW_QUEUE": 15, "CTTS_WF_ROW_QUEUE_MIN": 16,
                "CTTS_WF_INJECT_ABORT": 17, "CTTS_WF_QUEUE_DEBUG": 18, "CTTS_F32_NO_ROUND_SPLIT": 19, "CTTS_BF16_PS": 20, "CTTS_BF16_NO_PS": 21,
                "CTTS_TACO_POLL_DELAY": 23, "CTTS_TACO_VALU": 24, "CTTS_UP_NO_MFMA": 25, "CTTS_F32_NO_WN_FOLD": 26, "CTTS_TACO_BG_NO_PIPE": 27,
-               "CTTS_F32_NO_WINOGRAD": 28, "CTTS_F32_WINOGRAD_MIN": 29}
+               "CTTS_F32_NO_WINOGRAD": 28, "CTTS_F32_WINOGRAD_MIN": 29, "CTTS_F32_WINOGRAD_PLAIN": 30}
 
 
 def tuning_reload():

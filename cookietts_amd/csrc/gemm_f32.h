@@ -155,6 +155,22 @@ struct GemmArgs {
                           // tiles behind it went to a separate small-shape launch: launch_gemm_f32, "round-aligned")
     long long shape_blocks;   // > 0: the launch is a PART of a larger one (a column region): choose the block shape as if the
                           // grid had this many large blocks, so that every part sums K in the order of the whole launch
+    // ---- the leaner Winograd layer (bm = 256, <= 4 segments, fp32 MFMA loop, DMA staging; SPLIT and GATE) ----
+    // parts = 2: ONE launch covers two GEMMs of the same shape on different operands.  The global column-tile index runs over
+    // parts x ntiles x batch and the part is its quotient; `batch` stays the batch of one part.  Part 1 reads A + part_A and
+    // segment j at base + part_seg[j], and stores to dst0 + part_dst0 (floats); a GATE launch takes map_par = the part and negates
+    // addend2_sign for part 1.  Bias and both addend planes are those of part 0.  SPLIT: acc0 = 0 and every row below `split`.
+    // The block shape is chosen from ONE part's block count (so no batch size changes the shape a part runs in), the round
+    // arithmetic and the peel use the merged count.  0 / 1 = one part.
+    int parts;
+    long long part_A, part_seg[4], part_dst0;
+    // mseg = 2 (GATE with map_d > 0 only): segment 1 is read THROUGH the launch's pair map - it lies in the natural layout with
+    // its own row stride / left pad (mseg_ld, mseg_pad), seg[1].base points at its row 0 (no column origin: map_col0 carries it)
+    // and the lane whose B-operand unit starts at pair column q = map_col0 + n reads the four natural columns from
+    // (q / d) 2d + q % d + map_par d on: with d % 4 == 0 and map_col0 % 4 == 0 they are consecutive and 16-byte aligned.
+    // Columns that map past the row are clamped to its last aligned unit (their outputs are dropped by the map_L / L tests).
+    int mseg, mseg_ld, mseg_pad;
+    int mseg_ch0, mseg_ch1;   // set by the launcher: the K chunks [ch0, ch1) of the launch that belong to the mapped segment
 };
 
 // Row of the dense weight matrix held by block-local row r of M-block mb, or -1 for padding
@@ -177,6 +193,8 @@ inline void gemm_apply_defaults(GemmArgs& a) {
     if (a.bm == 0) a.bm = 256;
     if (a.addend_ld == 0) { a.addend_ld = a.ld; a.addend_pad = a.pad; }
 }
+// true when a launch with this many K chunks runs the DMA-staged kernels (what GemmArgs.parts / mseg are built on)
+bool gemm_f32_dma_staged(int nch_total);
 int gemm_check_args(int epi, const GemmArgs& a);      // the shape-independent argument checks of launch_gemm_f32 (defaults applied)
 int launch_gemm_f32(int epi, const GemmArgs& a, hipStream_t stream);
 // Small-problem shape (gemm_f32_small.hip): 128 x 64 blocks / 64 x 32 wave tiles on the SAME packed operands, bit-identical

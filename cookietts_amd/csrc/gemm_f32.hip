@@ -58,13 +58,13 @@ __device__ __forceinline__ float4 load4u(gfloat_ptr p) {
 // rows < split -> dst0 (= src0 + v when acc0), rows >= split -> dst1[row - split] (+= when acc1).
 template <int EPI>
 __device__ __forceinline__ void split_epilogue(const GemmArgs& a, f32x16 (&acc)[4][2], const float* bias, int M, int row0,
-                                               int b, int ncol0, int l31, int lhi) {
+                                               int b, int ncol0, int l31, int lhi, long long part_dst0 = 0) {
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
         const int rbase = row0 + mt * 32;                        // uniform per tile
         if (rbase >= M) continue;                                // zero-padded rows of a ragged M
         const bool second = rbase >= a.split;                    // split is a multiple of 32
-        float* dst = second ? a.dst1 + (size_t)b * a.dst1_bstride : a.dst0 + (size_t)b * a.dst0_bstride;
+        float* dst = second ? a.dst1 + (size_t)b * a.dst1_bstride : a.dst0 + part_dst0 + (size_t)b * a.dst0_bstride;
         const float* src = second ? dst : (a.src0 ? a.src0 + (size_t)b * a.src0_bstride : dst);
         const int accum = second ? a.acc1 : a.acc0;
         const int rdst = second ? rbase - a.split : rbase;
@@ -153,8 +153,13 @@ __device__ __forceinline__ void split8x3(const float (&v)[8], u32x4_t& hi, u32x4
     }
 }
 
-template <int EPI, int WM, int SEGS, bool GLDS, int XS = 0>
+//
+// EXT: the launch may cover two parts (GemmArgs.parts) and read segment 1 through the pair map (GemmArgs.mseg); every other
+// instantiation ignores those fields and compiles to the code it had without them.
+template <int EPI, int WM, int SEGS, bool GLDS, int XS = 0, bool EXT = false>
 __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a) {
+    static_assert(!EXT || (GLDS && SEGS == 4 && XS == 0 && (EPI == GEMM_EPI_SPLIT || EPI == GEMM_EPI_GATE)),
+                  "parts / mapped segment: DMA-staged fp32 loop, <= 4 segments, SPLIT or GATE");
     constexpr bool X3 = XS != 0;                           // any split-bf16 main loop (XS = 3 or 6 products)
     constexpr bool X6 = XS == 6;
     static_assert(XS == 0 || XS == 3 || XS == 6, "main loop: fp32 MFMA, 3 or 6 bf16 products");
@@ -197,6 +202,13 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
         b = id / a.ntiles;
     }
     const int n0 = tile * BN;
+    // EXT: the batch index ran over parts x batch; part 1 = the second GEMM of the launch
+    [[maybe_unused]] int part = 0;
+    if constexpr (EXT) {
+        if (b >= a.batch) { part = 1; b -= a.batch; }
+    }
+#define CTTS_MAP_PAR (EXT && a.parts > 1 ? part : a.map_par)   /* (read where it is used: the other instantiations keep their code) */
+#define CTTS_A_PTR (EXT ? a.A + (long long)part * a.part_A : a.A)
 
     // segment bases: everything except the k-row of the chunk and the per-thread (row, column) offset
     gfloat_ptr sbase[4];
@@ -232,7 +244,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
     }
 
     const int nalloc = a.a_nch_alloc ? a.a_nch_alloc : a.nch_total;
-    const float* ap = a.A + ((size_t)mb * nalloc + a.a_ch_off) * A_STAGE + t * 4;
+    const float* ap = CTTS_A_PTR + ((size_t)mb * nalloc + a.a_ch_off) * A_STAGE + t * 4;
 
     // register staging: thread -> (k row t/16, columns 4(t%16) + 64j).  DMA staging: a wave instruction fills 1 KiB of
     // LDS linearly in lane order = 256/BN whole k-rows, piece (wave + 4j) of the stage.
@@ -283,7 +295,19 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
                 if (k < SEGS && sg == k)
                     base = a.seg[k].base + (size_t)b * a.seg[k].bstride + (size_t)(mb * a.seg[k].mb_rows) * a.ld +
                            (a.pad + n0 + a.seg[k].shift);
-            tab[c0] = reinterpret_cast<unsigned long long>(base + (size_t)loc * GEMM_KC * a.ld);
+            if constexpr (EXT) {
+                size_t rs = a.ld;
+#pragma unroll
+                for (int k = 0; k < SEGS; ++k)
+                    if (sg == k) base += (long long)part * a.part_seg[k];
+                if (a.mseg && sg == 1) {        // mapped segment: row 0 of the batch item, the lanes carry pad and column
+                    base = a.seg[1].base + (size_t)b * a.seg[1].bstride + (long long)part * a.part_seg[1];
+                    rs = a.mseg_ld;
+                }
+                tab[c0] = reinterpret_cast<unsigned long long>(base + (size_t)loc * GEMM_KC * rs);
+            } else {
+                tab[c0] = reinterpret_cast<unsigned long long>(base + (size_t)loc * GEMM_KC * a.ld);
+            }
         }
         __syncthreads();
     }
@@ -340,11 +364,24 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
     typedef __attribute__((address_space(3))) float* lds_fptr;
     typedef const __attribute__((address_space(1))) char* gbyte_ptr;
     // wave-uniform A base of this m-block and the 32-bit per-lane byte offsets of the two operands
-    const gbyte_ptr apu = (gbyte_ptr)(a.A + ((size_t)mb * nalloc + a.a_ch_off) * A_STAGE);
+    const gbyte_ptr apu = (gbyte_ptr)(CTTS_A_PTR + ((size_t)mb * nalloc + a.a_ch_off) * A_STAGE);
     unsigned piece_lane[6];
 #pragma unroll
     for (int p_ = 0; p_ < 6; ++p_)
         piece_lane[p_] = p_ < NA ? (unsigned)(t * 16 + 4096 * p_) : (unsigned)(thread_off * 4 + (size_t)(p_ - NA) * (piece_stride * 4));
+    // EXT, mapped segment: a second set of B-piece lane offsets - the lane's 16-byte unit starts at pair column q and is read at
+    // the natural column of q (four consecutive columns: d % 4 == 0), clamped to the row's last aligned unit
+    [[maybe_unused]] unsigned piece_lane_m[6] = {0, 0, 0, 0, 0, 0};
+    if constexpr (EXT) {
+        if (a.mseg) {
+            const int q = a.map_col0 + n0 + bcol;
+            int nat = (q / a.map_d) * (2 * a.map_d) + q % a.map_d + CTTS_MAP_PAR * a.map_d;
+            nat = min(nat, (a.mseg_ld - a.mseg_pad - 4) & ~3);
+#pragma unroll
+            for (int p_ = NA; p_ < 6; ++p_)
+                piece_lane_m[p_] = (unsigned)(((size_t)(brow + (p_ - NA) * 4 * RPP) * a.mseg_ld + a.mseg_pad + nat) * 4);
+        }
+    }
     const unsigned long long* ctab = reinterpret_cast<const unsigned long long*>(lds + CHTAB);
     // DMA piece p (0..5) of chunk c into stage buf: pieces [0, NA) = A, [NA, 6) = B.  Every address is a wave-uniform
     // 64-bit base (ac_ / bp_, SGPR pair) + a 32-bit lane offset, laundered through an empty asm so that the compiler keeps
@@ -353,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
     // profiles/r5_07_bf16_mix_ceiling_dma_forms.txt).
 #define CTTS_GLDS_PIECE(p, la_, ac_, bp_)                                                                   \
     do {                                                                                                    \
-        unsigned o_ = piece_lane[(p)];                     /* lane offset incl. the piece's own offset: nothing to reassociate */ \
+        unsigned o_ = (EXT && (p) >= NA && mp_) ? piece_lane_m[(p)] : piece_lane[(p)];   /* lane offset incl. the piece's own offset: nothing to reassociate */ \
         asm volatile("" : "+v"(o_));                                                                        \
         if constexpr ((p) < NA) __builtin_amdgcn_global_load_lds((gfloat_ptr)((ac_) + o_), (la_) + 1024 * (p), 16, 0, 0); \
         else __builtin_amdgcn_global_load_lds((gfloat_ptr)((bp_) + o_), (la_) + A_STAGE + 1024 * ((p) - NA), 16, 0, 0); \
@@ -361,6 +398,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
 #define CTTS_GLDS_ADDR_A(buf, c)                                                                            \
     lds_fptr la_ = (lds_fptr)(lds + (buf) * STAGE + wave * 256);                                            \
     const gbyte_ptr ac_ = apu + (size_t)(c) * (A_STAGE * 4);                                                \
+    [[maybe_unused]] const bool mp_ = EXT && (c) >= a.mseg_ch0 && (c) < a.mseg_ch1;   /* wave-uniform: a chunk of the mapped segment */ \
     const unsigned long long ub_ = ctab[c];
 #define CTTS_GLDS_ADDR_B()                                                                                  \
     const unsigned long long us_ =                                                                          \
@@ -540,6 +578,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
     const float* bias = lds + wm * 128;
     if constexpr (EPI == GEMM_EPI_GATE || EPI == GEMM_EPI_MAG || EPI == GEMM_EPI_GATEX) {
         float* dst = a.dst0 + (size_t)b * a.dst0_bstride;
+        if constexpr (EXT) dst += (long long)part * a.part_dst0;
         const int cbase = (mb * WM + wm) * 64;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
@@ -553,7 +592,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
                     bool ns_ok = true;
                     if (EPI == GEMM_EPI_GATE && a.map_d > 0) {   // uniform: pair column -> natural column
                         const int q = a.map_col0 + n;
-                        ns = (q / a.map_d) * (2 * a.map_d) + q % a.map_d + a.map_par * a.map_d;
+                        ns = (q / a.map_d) * (2 * a.map_d) + q % a.map_d + CTTS_MAP_PAR * a.map_d;
                         ns_ok = ns < a.map_L;
                     }
                     if ((EPI == GEMM_EPI_GATE || EPI == GEMM_EPI_GATEX) && a.addend && a.addend_frames > 0) {   // uniform: interpolated addend
@@ -622,8 +661,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
                                 const int c = min(cbase + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi, a.pairC - 1);
-                                add20[r] = a.addend2_sign * ad[(size_t)c * a.addend_ld];
-                                add21[r] = a.addend2_sign * ad[(size_t)(a.pairC + c) * a.addend_ld];
+                                add20[r] = (EXT && part ? -a.addend2_sign : a.addend2_sign) * ad[(size_t)c * a.addend_ld];
+                                add21[r] = (EXT && part ? -a.addend2_sign : a.addend2_sign) * ad[(size_t)(a.pairC + c) * a.addend_ld];
                             }
                         }
 #pragma unroll
@@ -695,8 +734,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
         // 4. residual / skip epilogue
         split_epilogue<GEMM_EPI_SPLIT>(a, acc, lds + 64 * 128, a.rs_rows, /*row0=*/0, b, n0 + wn * 64, l31, lhi);
     } else {
-        split_epilogue<EPI>(a, acc, bias, a.M, mb * BM + wm * 128, b, n0 + wn * 64, l31, lhi);
+        split_epilogue<EPI>(a, acc, bias, a.M, mb * BM + wm * 128, b, n0 + wn * 64, l31, lhi, EXT ? (long long)part * a.part_dst0 : 0);
     }
+#undef CTTS_MAP_PAR
+#undef CTTS_A_PTR
 }
 
 // CTTS_GEMM_DEFAULT in a config struct = fp32 MFMA.  (Until ABI 5 a process-wide default could be set; it is gone: the
@@ -796,6 +837,7 @@ void load_tuning_locked() {
     g_tune.f32_no_wn_fold = on("CTTS_F32_NO_WN_FOLD");
     g_tune.f32_no_winograd = on("CTTS_F32_NO_WINOGRAD");
     g_tune.f32_winograd_min = num("CTTS_F32_WINOGRAD_MIN", -1);
+    g_tune.f32_winograd_plain = on("CTTS_F32_WINOGRAD_PLAIN");
     g_tune_loaded = true;
 }
 }  // namespace
@@ -852,16 +894,64 @@ int gemm_check_args(int epi, const GemmArgs& a) {
     CTTS_CHECK_ARG(epi != GEMM_EPI_GATE_RS ||
                        (a.bm == 128 && a.pairC <= 64 && a.MB == 1 && a.rs_wT && a.rs_bias && (a.rs_rows == 64 || a.rs_rows == 128)),
                    "gemm: fused res/skip needs bm=128, <= 64 channels, rs_wT / rs_bias and 64 or 128 res/skip rows");
+    // two parts / mapped segment (the kernels' EXT form)
+    const int parts = a.parts > 1 ? a.parts : 1;
+    CTTS_CHECK_ARG(a.parts >= 0 && a.parts <= 2 && (a.mseg == 0 || a.mseg == 2), "gemm: parts=%d mseg=%d", a.parts, a.mseg);
+    if (parts > 1 || a.mseg) {
+        CTTS_CHECK_ARG((epi == GEMM_EPI_SPLIT || (epi == GEMM_EPI_GATE && a.gate == GATE_GTU)) && a.bm == 256 && a.nseg <= 4 &&
+                           a.interleave <= 1 && gemm_split_level(a.gemm_mode) == 0 && a.shape_blocks == 0 && a.addend_frames == 0,
+                       "gemm: parts / mapped segment need the fp32 SPLIT or GATE launch of the 256-row shape (epilogue %d, nseg=%d)", epi, a.nseg);
+        CTTS_CHECK_ARG(parts == 1 || epi != GEMM_EPI_SPLIT || (a.acc0 == 0 && a.src0 == nullptr && a.split >= a.M),
+                       "gemm: a two-part SPLIT launch stores every row to dst0");
+        CTTS_CHECK_ARG(parts == 1 || (long long)parts * a.ntiles * a.batch < (1ll << 31) / a.MB, "gemm: merged grid");
+    }
+    if (a.mseg) {
+        // alignment of the mapped read: a lane's four pair columns must be four consecutive, 16-byte aligned natural columns
+        const GemmSeg& g = a.seg[1];
+        CTTS_CHECK_ARG(epi == GEMM_EPI_GATE && a.nseg == 2 && a.map_d > 0 && a.map_d % 4 == 0 && a.map_col0 % 4 == 0 && a.mseg_pad >= 0 &&
+                           a.mseg_pad % 4 == 0 && a.mseg_ld % 4 == 0 && a.mseg_ld - a.mseg_pad >= 4 && g.bstride % 4 == 0 &&
+                           (parts == 1 || a.part_seg[1] % 4 == 0) && reinterpret_cast<uintptr_t>(g.base) % 16 == 0 && g.shift == 0 &&
+                           g.mb_rows == 0,
+                       "gemm: mapped segment d=%d col0=%d ld=%d pad=%d", a.map_d, a.map_col0, a.mseg_ld, a.mseg_pad);
+    }
     return CTTS_OK;
 }
+
+bool gemm_f32_dma_staged(int nch_total) { return !tuning().f32_no_glds && nch_total <= GEMM_GLDS_MAX_CHUNKS; }
+
+namespace {
+// the single-part launch of part p of a two-part one
+GemmArgs gemm_part_args(const GemmArgs& a, int p) {
+    GemmArgs r = a;
+    r.parts = 0;
+    if (p == 0) return r;
+    r.A += a.part_A;
+    for (int j = 0; j < r.nseg && j < 4; ++j) r.seg[j].base += a.part_seg[j];
+    r.dst0 += a.part_dst0;
+    r.map_par = p;
+    r.addend2_sign = -a.addend2_sign;
+    return r;
+}
+}  // namespace
 
 int launch_gemm_f32(int epi, const GemmArgs& a_in, hipStream_t stream) {
     GemmArgs a = a_in;
     gemm_apply_defaults(a);
     if (int rc = gemm_check_args(epi, a)) return rc;
     if (epi == GEMM_EPI_GATE && a.gate != GATE_GTU) epi = GEMM_EPI_GATEX;
+    const int parts = a.parts > 1 ? a.parts : 1;
+    const bool ext = parts > 1 || a.mseg;
+    a.mseg_ch0 = a.mseg_ch1 = 0;
+    if (a.mseg) { a.mseg_ch0 = a.seg[0].nch; a.mseg_ch1 = a.seg[0].nch + a.seg[1].nch; }
+    CTTS_CHECK_ARG(!a.mseg || gemm_f32_dma_staged(a.nch_total), "gemm: the mapped segment needs the DMA-staged kernels");
+    // The shape is chosen from ONE part's block count; the small shape (and the register-staged kernels) run the parts one by one
+    if (parts > 1 && (gemm_f32_small_applies(epi, a) || !gemm_f32_dma_staged(a.nch_total))) {
+        for (int p = 0; p < parts; ++p)
+            if (int rc = launch_gemm_f32(epi, gemm_part_args(a, p), stream)) return rc;
+        return CTTS_OK;
+    }
     if (gemm_f32_small_applies(epi, a)) return launch_gemm_f32_small(epi, a, stream);
-    long long tiles = (long long)a.ntiles * a.batch;         // column tiles of the launch, tile + ntiles * batch item
+    long long tiles = (long long)parts * a.ntiles * a.batch;   // column tiles of the launch, tile + ntiles * (batch item + batch * part)
     // Round-aligned launch.  Two workgroups share a CU, so a launch runs in rounds of 2 x CUs workgroups; one whose count is a
     // little above a whole number of rounds ends with a round that a few CUs run alone.  Measured on the headline's in-layer
     // launch (scripts/micro/headline_gemm.hip): 7168 workgroups = 14 rounds 5.99 ms, 7200 = 14.06 rounds 6.20 ms - 0.21 ms for
@@ -876,11 +966,12 @@ int launch_gemm_f32(int epi, const GemmArgs& a_in, hipStream_t stream) {
         // (the peeled tiles must hold valid columns: a caller may over-provision ntiles, L <= (ntiles - rem_tiles) * bn)
         if (rounds >= 2 && rem_tiles > 0 && rem_tiles * a.MB <= slots * 3 / 10 && rem_tiles < a.ntiles &&
             (long long)(a.ntiles - rem_tiles) * gemm_bn(a.bm) < a.L) {
-            GemmArgs r = a;                                    // the last rem_tiles column tiles of the last batch item
+            GemmArgs r = gemm_part_args(a, parts - 1);         // the last rem_tiles column tiles of the last part's last batch item
             const int bn = gemm_bn(a.bm);
             const long long co = (long long)(a.ntiles - rem_tiles) * bn;
             const long long bo = a.batch - 1;
-            for (int j = 0; j < r.nseg; ++j) r.seg[j].base += bo * r.seg[j].bstride + co;
+            // (a mapped segment keeps its row origin: map_col0 carries the column)
+            for (int j = 0; j < r.nseg; ++j) r.seg[j].base += bo * r.seg[j].bstride + (r.mseg && j == 1 ? 0 : co);
             if (r.dst0) r.dst0 += bo * r.dst0_bstride + (r.map_d > 0 ? 0 : co);     // mapped store: the pair-column origin moves
             if (r.map_d > 0) r.map_col0 += (int)co;
             if (r.dst1) r.dst1 += bo * r.dst1_bstride + co;
@@ -905,6 +996,12 @@ int launch_gemm_f32(int epi, const GemmArgs& a_in, hipStream_t stream) {
     CTTS_CHECK_ARG(blocks > 0 && blocks < (1ll << 31), "gemm: grid %lld", blocks);
     dim3 grid((unsigned)blocks);
     note_gemm_loop((tuning().f32_no_glds || a.nch_total > GEMM_GLDS_MAX_CHUNKS) ? 0 : gemm_split_level(a.gemm_mode));
+    if (ext) {
+        if (epi == GEMM_EPI_GATE) hipLaunchKernelGGL((conv_gemm_f32_kernel<GEMM_EPI_GATE, 2, 4, true, 0, true>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((conv_gemm_f32_kernel<GEMM_EPI_SPLIT, 2, 4, true, 0, true>), grid, dim3(256), 0, stream, a);
+        CTTS_CHECK_LAUNCH("conv_gemm_f32");
+        return CTTS_OK;
+    }
     switch (epi) {
         case GEMM_EPI_GATEX: launch_shape<GEMM_EPI_GATEX>(a.bm, grid, stream, a); break;
         case GEMM_EPI_GATE: launch_shape<GEMM_EPI_GATE>(a.bm, grid, stream, a); break;

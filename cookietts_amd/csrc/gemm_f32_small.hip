@@ -152,8 +152,10 @@ __device__ __forceinline__ void s_split8x3(const float (&v)[8], s_u32x4& hi, s_u
 }
 
 // XS: 0 = fp32 MFMA, 3 / 6 = split-bf16 products per operand pair (gemm_f32.hip, X3 / X6)
-template <int EPI, int SEGS, int XS = 0>
+// MSEG: segment 1 may be read through the pair map (GemmArgs.mseg); every other instantiation ignores the field
+template <int EPI, int SEGS, int XS = 0, bool MSEG = false>
 __global__ __launch_bounds__(256, 4) void conv_gemm_f32_small_kernel(const GemmArgs a, const int ntiles_s) {
+    static_assert(!MSEG || (EPI == GEMM_EPI_GATE && SEGS == 4 && XS == 0), "mapped segment: the fp32 GATE launch");
     constexpr bool X3 = XS != 0, X6 = XS == 6;
     __shared__ __attribute__((aligned(16))) float lds[S_LDS_FLOATS];
     constexpr bool PAIR = EPI == GEMM_EPI_GATE || EPI == GEMM_EPI_GATEX || EPI == GEMM_EPI_MAG;
@@ -256,6 +258,18 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_f32_small_kernel(const GemmA
     const unsigned dma_a_lane = (unsigned)(((lane >> 5) * a_ld + (lane & 31) * 4) * 4), dma_a_lane1 = dma_a_lane + 8 * a_ld * 4;   // piece 0 / 1
     // B: [16][64] stage, this wave's piece = k-rows 4 wave .. +4: k-row 4 wave + (lane >> 4), columns 4 (lane & 15)
     const unsigned dma_b_lane = (unsigned)(((size_t)(4 * wave + (lane >> 4)) * a.ld + (lane & 15) * 4) * 4);
+    // mapped segment: the lane's 16-byte unit starts at pair column q and is read at the natural column of q (four consecutive
+    // columns: d % 4 == 0), clamped to the row's last aligned unit
+    [[maybe_unused]] unsigned dma_b_lane_m = 0;
+    [[maybe_unused]] const bool has_m = MSEG && a.mseg != 0;
+    if constexpr (MSEG) {
+        if (has_m) {
+            const int q = a.map_col0 + n0 + (lane & 15) * 4;
+            int nat = (q / a.map_d) * (2 * a.map_d) + q % a.map_d + a.map_par * a.map_d;
+            nat = min(nat, (a.mseg_ld - a.mseg_pad - 4) & ~3);
+            dma_b_lane_m = (unsigned)(((size_t)(4 * wave + (lane >> 4)) * a.mseg_ld + a.mseg_pad + nat) * 4);
+        }
+    }
     const unsigned long long* ctab = reinterpret_cast<const unsigned long long*>(lds + S_CHTAB);
 
     f32x16 acc[2];
@@ -277,13 +291,14 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_f32_small_kernel(const GemmA
                     (lds_fptr)(lds + (buf) * S_STAGE + S_ASTAGE + wave * 256), 0);                               \
     } while (0)
 
-#define S_ISSUE_B_AT(buf, ub)                                                                                    \
+    /* (c: the chunk, wave-uniform - a chunk of the mapped segment takes the mapped lane offsets) */
+#define S_ISSUE_B_AT(buf, ub, c)                                                                                 \
     do {                                                                                                         \
         const unsigned long long ub_ = (ub);                                                                     \
         const unsigned long long us_ =                                                                           \
             ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(ub_ >> 32)) << 32) |             \
             (unsigned)__builtin_amdgcn_readfirstlane((int)ub_);                                                  \
-        CTTS_GLDS_U(reinterpret_cast<gbyte_ptr>(us_), dma_b_lane,                                                    \
+        CTTS_GLDS_U(reinterpret_cast<gbyte_ptr>(us_), (MSEG && (c) >= a.mseg_ch0 && (c) < a.mseg_ch1) ? dma_b_lane_m : dma_b_lane, \
                     (lds_fptr)(lds + (buf) * S_STAGE + S_ASTAGE + wave * 256), 0);                               \
     } while (0)
 
@@ -294,11 +309,12 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_f32_small_kernel(const GemmA
         const GemmSeg& g0 = a.seg[0];
         const GemmSeg& g1 = a.seg[1];
         const float* sb0 = g0.base + (size_t)b * g0.bstride + (size_t)(mb * g0.mb_rows) * a.ld + (a.pad + n0 + g0.shift);
-        const float* sb1 = g1.base + (size_t)b * g1.bstride + (size_t)(mb * g1.mb_rows) * a.ld + (a.pad + n0 + g1.shift);
+        const float* sb1 = has_m ? g1.base + (size_t)b * g1.bstride      // mapped: row 0, the lanes carry pad and column
+                                 : g1.base + (size_t)b * g1.bstride + (size_t)(mb * g1.mb_rows) * a.ld + (a.pad + n0 + g1.shift);
         const float* c1p = nch <= 1 ? sb0 : a.interleave > 1 ? sb1 : g0.nch > 1 ? sb0 + (size_t)GEMM_KC * a.ld : sb1;
         const int c1 = nch > 1 ? 1 : 0;
-        S_ISSUE_A(0, 0, 0); S_ISSUE_A(0, 0, 1); S_ISSUE_B_AT(0, reinterpret_cast<unsigned long long>(sb0));
-        S_ISSUE_A(1, c1, 0); S_ISSUE_A(1, c1, 1); S_ISSUE_B_AT(1, reinterpret_cast<unsigned long long>(c1p));
+        S_ISSUE_A(0, 0, 0); S_ISSUE_A(0, 0, 1); S_ISSUE_B_AT(0, reinterpret_cast<unsigned long long>(sb0), 0);
+        S_ISSUE_A(1, c1, 0); S_ISSUE_A(1, c1, 1); S_ISSUE_B_AT(1, reinterpret_cast<unsigned long long>(c1p), c1);
     }
 
     // chunk -> B address table, ONE barrier (round 5; until then: a segment table written by twelve serial branches, a barrier,
@@ -332,8 +348,11 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_f32_small_kernel(const GemmA
             const long long sbstr = *reinterpret_cast<const __attribute__((address_space(4))) long long*>(sp + offsetof(GemmSeg, bstride));
             const int sshift = *reinterpret_cast<const __attribute__((address_space(4))) int*>(sp + offsetof(GemmSeg, shift));
             const int smbr = *reinterpret_cast<const __attribute__((address_space(4))) int*>(sp + offsetof(GemmSeg, mb_rows));
-            tab[c0] = sbase + (unsigned long long)(((long long)b * sbstr + (long long)(mb * smbr) * a.ld + (a.pad + n0 + sshift) +
-                                                    (long long)loc * GEMM_KC * a.ld) * 4);
+            if (has_m && sg == 1)
+                tab[c0] = sbase + (unsigned long long)(((long long)b * sbstr + (long long)loc * GEMM_KC * a.mseg_ld) * 4);
+            else
+                tab[c0] = sbase + (unsigned long long)(((long long)b * sbstr + (long long)(mb * smbr) * a.ld + (a.pad + n0 + sshift) +
+                                                        (long long)loc * GEMM_KC * a.ld) * 4);
         }
     }
     __syncthreads();
@@ -430,7 +449,7 @@ __global__ __launch_bounds__(256, 4) void conv_gemm_f32_small_kernel(const GemmA
             __builtin_amdgcn_sched_barrier(0);
             S_READ_AT(4, aa, ba) S_WAIT(4, 2)                   // (covers the older table entry)
             asm volatile("" : "+v"(ub_next));
-            S_MFMA(2) S_ISSUE_B_AT(nb, ub_next);
+            S_MFMA(2) S_ISSUE_B_AT(nb, ub_next, cn);
             __builtin_amdgcn_sched_barrier(0);
             S_READ_AT(5, aa, ba) S_WAIT(4, 3) S_MFMA(3)
             __builtin_amdgcn_sched_barrier(0);
@@ -1766,6 +1785,12 @@ __global__ __launch_bounds__(256, 2) void wf_row_persistent_kernel(const WfRowAr
 
 template <int EPI, int XS>
 void launch_small_xs(dim3 grid, hipStream_t stream, const GemmArgs& a, int ntiles_s) {
+    if constexpr (EPI == GEMM_EPI_GATE && XS == 0) {
+        if (a.mseg) {
+            hipLaunchKernelGGL((conv_gemm_f32_small_kernel<EPI, 4, 0, true>), grid, dim3(256), 0, stream, a, ntiles_s);
+            return;
+        }
+    }
     if (a.nseg <= 4) hipLaunchKernelGGL((conv_gemm_f32_small_kernel<EPI, 4, XS>), grid, dim3(256), 0, stream, a, ntiles_s);
     else hipLaunchKernelGGL((conv_gemm_f32_small_kernel<EPI, GEMM_MAX_SEG, XS>), grid, dim3(256), 0, stream, a, ntiles_s);
 }

@@ -322,8 +322,13 @@ struct WnFold { float* a16; float* skend; float* audio; float* wave; };
 struct WnWinograd { float* V; float* T; float* Hc; int ldp; };
 
 // One in-layer step in the Winograd form: transform, T2 = G2 V2, T3 = G3 V3, then the even and odd members of every pair
-//   act[t_e] = gate([W0 | C_i] [V1; h2e] + b + T2 + T3),   act[t_o] = gate([-W2 | C_i] [V4; h2o] + b + T2 - T3)
-// as four launches of the conv-GEMM in pair space (ld = ldp, no halo); the GATE launches store to act's natural columns.
+//   act[t_e] = gate([W0 | C_i] [V1; h(t_e)] + b + T2 + T3),   act[t_o] = gate([-W2 | C_i] [V4; h(t_o)] + b + T2 - T3)
+// as launches of the conv-GEMM in pair space (ld = ldp, no halo); the GATE launches store to act's natural columns.
+// Default: T2 | T3 are the two parts of ONE launch and so are even | odd (GemmArgs.parts: one round peel per pair), and for
+// d % 4 == 0 the GATE launch reads the cond rows where they lie in h_all, through its pair map (GemmArgs.mseg) - the transform
+// then writes V only.  d = 2 (and d = 1, layer 0 without the start fold) read the copies h2e / h2o the transform makes.
+// CTTS_F32_WINOGRAD_PLAIN (or the register-staged kernels): cond copies for every layer, four launches, d = 2 transform one column
+// at a time.  Same bits either way: the same products summed in the same order.
 int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k, int i, const float* x, const float* h_all,
                           float* act, const WnWinograd& wg, int batch, hipStream_t s) {
     const auto& f = p.fl[k];
@@ -331,8 +336,11 @@ int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k
     const int C = p.C, H = p.H, ldp = wg.ldp;
     const long long hstride = (long long)p.c.n_flows * H * g.ld;
     const size_t vplane = (size_t)batch * C * ldp, tplane = (size_t)batch * 2 * C * ldp, hplane = (size_t)batch * H * ldp;
-    int rc = launch_winograd_transform(x, (long long)C * g.ld, h_all + (size_t)k * H * g.ld, hstride, wg.V, wg.Hc, batch, C, H, pg.d,
-                                       g.L, pg.Lp, g.ld, g.pad, ldp, pg.ntiles * GEMM_BN, s);
+    const bool lean = !tuning().f32_winograd_plain && gemm_f32_dma_staged(p.nch_rs + p.nch1h);
+    const bool in_place = lean && pg.d % 4 == 0;
+    const float* h2 = h_all + (size_t)k * H * g.ld;
+    int rc = launch_winograd_transform(x, (long long)C * g.ld, h2, hstride, wg.V, wg.Hc, batch, C, H, pg.d, g.L, pg.Lp, g.ld, g.pad,
+                                       ldp, pg.ntiles * GEMM_BN, !in_place, lean, s);
     if (rc) return rc;
     GemmArgs a{};
     a.gemm_mode = p.c.f32_gemm_mode;
@@ -341,7 +349,14 @@ int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k
     a.nseg = 1; a.nch_total = p.nch_rs;
     a.dst_ld = ldp; a.dst_pad = 0; a.dst0_bstride = (long long)2 * C * ldp;
     a.M = 2 * C; a.split = 2 * C;
-    for (int j = 0; j < 2; ++j) {
+    const int np = lean ? 1 : 2;          // launches per pair
+    if (lean) {
+        a.parts = 2;
+        a.part_A = (long long)f.wg_T3_A[i] - (long long)f.wg_T2_A[i];
+        a.part_seg[0] = (long long)vplane;
+        a.part_dst0 = (long long)tplane;
+    }
+    for (int j = 0; j < np; ++j) {
         a.A = blob + (j == 0 ? f.wg_T2_A[i] : f.wg_T3_A[i]);
         a.seg[0] = {wg.V + (1 + j) * vplane, (long long)C * ldp, p.nch_rs, 0, 0, 0};
         a.dst0 = wg.T + j * tplane;
@@ -353,10 +368,18 @@ int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k
     a.dst0 = act; a.dst0_bstride = (long long)C * g.ld; a.dst_ld = g.ld; a.dst_pad = g.pad;
     a.addend = wg.T; a.addend2 = wg.T + tplane; a.addend_bstride = (long long)2 * C * ldp;
     a.map_d = pg.d; a.map_L = g.L;
-    for (int j = 0; j < 2; ++j) {
+    if (lean) {
+        a.part_A = (long long)f.wg_o_A[i] - (long long)f.wg_e_A[i];
+        a.part_seg[0] = (long long)(3 * vplane);
+        a.part_seg[1] = in_place ? 0 : (long long)hplane;
+        a.part_dst0 = 0;
+    }
+    if (in_place) { a.mseg = 2; a.mseg_ld = g.ld; a.mseg_pad = g.pad; }
+    for (int j = 0; j < np; ++j) {
         a.A = blob + (j == 0 ? f.wg_e_A[i] : f.wg_o_A[i]);
         a.seg[0] = {wg.V + (j == 0 ? 0 : 3) * vplane, (long long)C * ldp, p.nch_rs, 0, 0, 0};
-        a.seg[1] = {wg.Hc + j * hplane, (long long)H * ldp, p.nch1h, 0, 0, 0};
+        if (in_place) a.seg[1] = {h2, hstride, p.nch1h, 0, 0, 0};
+        else a.seg[1] = {wg.Hc + j * hplane, (long long)H * ldp, p.nch1h, 0, 0, 0};
         a.addend2_sign = j == 0 ? 1.0f : -1.0f;
         a.map_par = j;
         if ((rc = launch_gemm_f32(GEMM_EPI_GATE, a, s))) return rc;
@@ -1077,7 +1100,8 @@ int ctts_tuning_flags(void) {
            (t.wf_inject_abort ? 131072 : 0) | (t.wf_queue_debug ? 262144 : 0) | (t.f32_no_round_split ? 524288 : 0) |
            (t.bf16_ps ? (1 << 20) : 0) | (t.bf16_no_ps ? (1 << 21) : 0) | (t.taco_poll_delay_set ? (1 << 23) : 0) |
            (t.taco_valu ? (1 << 24) : 0) | (t.up_no_mfma ? (1 << 25) : 0) | (t.f32_no_wn_fold ? (1 << 26) : 0) |
-           (t.taco_bg_no_pipe ? (1 << 27) : 0) | (t.f32_no_winograd ? (1 << 28) : 0) | (t.f32_winograd_min >= 0 ? (1 << 29) : 0);
+           (t.taco_bg_no_pipe ? (1 << 27) : 0) | (t.f32_no_winograd ? (1 << 28) : 0) | (t.f32_winograd_min >= 0 ? (1 << 29) : 0) |
+           (t.f32_winograd_plain ? (1 << 30) : 0);
 }
 
 int ctts_profile_create(void** handle) {

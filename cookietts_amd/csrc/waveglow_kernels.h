@@ -37,9 +37,11 @@ int launch_skip_end(const float* act, long long act_stride, int nl, const float*
 
 // Winograd F(2,3) in-layer form (fp32 WaveGlow; the algebra is at the kernels in waveglow_kernels.hip).  Pack time: dense
 // [3][rows][C] = G2, G3, -W2 of in_w [rows][C][3].  Per layer: x and the flow's cond rows -> V1..V4 [4][B][C][ldp] and the copies
-// h2e, h2o [2][B][H][ldp] in pair order (Lp pair columns, zeros up to ncols).
+// h2e, h2o [2][B][H][ldp] in pair order (Lp pair columns, zeros up to ncols); cond_rows = false: V only (the GATE launches read
+// the cond rows in place, GemmArgs.mseg).  vec_d2 = false: d = 2 on the one-column-at-a-time path (CTTS_F32_WINOGRAD_PLAIN).
 int launch_winograd_g(const float* in_w, float* dense, int rows, int C, hipStream_t s);
 int launch_winograd_transform(const float* x, long long x_bstride, const float* h2, long long h_bstride, float* V, float* Hc,
-                              int batch, int C, int H, int d, int L, int Lp, int ld, int pad, int ldp, int ncols, hipStream_t s);
+                              int batch, int C, int H, int d, int L, int Lp, int ld, int pad, int ldp, int ncols, bool cond_rows,
+                              bool vec_d2, hipStream_t s);
 
 }  // namespace ctts

@@ -448,10 +448,15 @@ __global__ __launch_bounds__(256) void winograd_g_kernel(const float* __restrict
 }
 
 // x [B][C][ld] and the flow's cond rows h2 [B][H][ld] (natural layout) -> V1..V4 [4][B][C][ldp] and the copies h2e, h2o
-// [2][B][H][ldp] in pair order.  Everything outside [0, L) reads as zero (what the conv's zero padding means; t + 2d can lie
-// beyond the halo), columns [Lp, ncols) are written as zeros.  One thread: four pair columns of one row.
-// VEC: d % 4 == 0 and L % 4 == 0 - the four columns are four consecutive time steps, 16-byte aligned, all inside or all outside
-template <bool VEC>
+// [2][B][H][ldp] in pair order (grid.y = C + H; grid.y = C: no cond rows - the GATE launches read h2 in place).  Everything
+// outside [0, L) reads as zero (what the conv's zero padding means; t + 2d can lie beyond the halo), columns [Lp, ncols) are
+// written as zeros.  One thread: four pair columns of one row.
+// MODE 1: d % 4 == 0 and L % 4 == 0 - the four columns are four consecutive time steps, 16-byte aligned, all inside or all outside
+// MODE 2: d == 2 and L % 4 == 0 - pair columns j4 .. j4 + 3 stand for t_e = 2 j4 + {0, 1, 4, 5}, so every tap lies in
+//         x[2 j4 - 4 .. 2 j4 + 11]: four aligned 16-byte loads, each all inside or all outside; Lp is even, so the columns
+//         j4 + 2, j4 + 3 can lie beyond it on their own
+// MODE 0: one column at a time
+template <int MODE>
 __global__ __launch_bounds__(256) void winograd_transform_kernel(const float* __restrict__ x, long long x_bstride,
                                                                  const float* __restrict__ h2, long long h_bstride,
                                                                  float* __restrict__ V, float* __restrict__ Hc, int C, int H,
@@ -463,12 +468,24 @@ __global__ __launch_bounds__(256) void winograd_transform_kernel(const float* __
     const float* src = is_x ? x + (size_t)b * x_bstride + (size_t)row * ld + pad
                             : h2 + (size_t)b * h_bstride + (size_t)(row - C) * ld + pad;
     float4 vm = {0.f, 0.f, 0.f, 0.f}, v0 = vm, v1 = vm, v2 = vm;      // x[t_e - d], x[t_e], x[t_e + d], x[t_e + 2d]
-    if constexpr (VEC) {
+    [[maybe_unused]] auto ld4 = [&](int t) { return (t >= 0 && t < L) ? *reinterpret_cast<const float4*>(src + t) : make_float4(0.f, 0.f, 0.f, 0.f); };
+    if constexpr (MODE == 1) {
         if (j4 < Lp) {
             const int te = (j4 / d) * 2 * d + j4 % d;
-            auto ld4 = [&](int t) { return (t >= 0 && t < L) ? *reinterpret_cast<const float4*>(src + t) : make_float4(0.f, 0.f, 0.f, 0.f); };
             if (is_x) { vm = ld4(te - d); v2 = ld4(te + 2 * d); }
             v0 = ld4(te); v1 = ld4(te + d);
+        }
+    } else if constexpr (MODE == 2) {
+        if (j4 < Lp) {
+            const int t0 = 2 * j4;
+            const float4 q = ld4(t0), r = ld4(t0 + 4);
+            float4 p = vm, u = vm;                                   // (cond rows: V1, V4 are not formed)
+            if (is_x) { p = ld4(t0 - 4); u = ld4(t0 + 8); }
+            const bool hi = j4 + 2 < Lp;                             // columns j4 + 2, j4 + 3 (Lp is even)
+            vm = make_float4(p.z, p.w, hi ? q.z : 0.f, hi ? q.w : 0.f);
+            v0 = make_float4(q.x, q.y, hi ? r.x : 0.f, hi ? r.y : 0.f);
+            v1 = make_float4(q.z, q.w, hi ? r.z : 0.f, hi ? r.w : 0.f);
+            v2 = make_float4(r.x, r.y, hi ? u.x : 0.f, hi ? u.y : 0.f);
         }
     } else {
         float am[4], a0[4], a1[4], a2[4];
@@ -748,16 +765,20 @@ int launch_winograd_g(const float* in_w, float* dense, int rows, int C, hipStrea
 }
 
 int launch_winograd_transform(const float* x, long long x_bstride, const float* h2, long long h_bstride, float* V, float* Hc,
-                              int batch, int C, int H, int d, int L, int Lp, int ld, int pad, int ldp, int ncols, hipStream_t s) {
+                              int batch, int C, int H, int d, int L, int Lp, int ld, int pad, int ldp, int ncols, bool cond_rows,
+                              bool vec_d2, hipStream_t s) {
     CTTS_CHECK_ARG(d >= 1 && Lp % d == 0 && (long long)Lp * 2 >= L && Lp <= ncols && ncols <= ldp && ncols % 4 == 0 && ldp % 4 == 0 &&
                        ld % 4 == 0 && pad % 4 == 0 && pad + L <= ld,
                    "winograd_transform: d=%d L=%d Lp=%d ncols=%d ldp=%d ld=%d pad=%d", d, L, Lp, ncols, ldp, ld, pad);
-    dim3 grid((ncols / 4 + 255) / 256, C + H, batch);
+    dim3 grid((ncols / 4 + 255) / 256, cond_rows ? C + H : C, batch);
     if (d % 4 == 0 && L % 4 == 0)
-        hipLaunchKernelGGL(winograd_transform_kernel<true>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lp,
+        hipLaunchKernelGGL(winograd_transform_kernel<1>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lp,
+                           ld, pad, ldp, ncols);
+    else if (d == 2 && L % 4 == 0 && vec_d2)
+        hipLaunchKernelGGL(winograd_transform_kernel<2>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lp,
                            ld, pad, ldp, ncols);
     else
-        hipLaunchKernelGGL(winograd_transform_kernel<false>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lp,
+        hipLaunchKernelGGL(winograd_transform_kernel<0>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lp,
                            ld, pad, ldp, ncols);
     CTTS_CHECK_LAUNCH("winograd_transform");
     return CTTS_OK;

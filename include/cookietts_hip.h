@@ -839,7 +839,7 @@ int ctts_taco_stop_rule_f32(const float* gate_logits, int32_t batch, int32_t gat
 int ctts_last_gemm_loop(void);
 
 /* Launch-shape overrides for A/B measurements (CTTS_F32_NO_GLDS, CTTS_F32_NO_SMALL, CTTS_F32_FORCE_SMALL, CTTS_GEMM_NO_XCD_PAIR, CTTS_BF16_NO_WIDE /
- * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD, CTTS_F32_NO_WINOGRAD, CTTS_F32_WINOGRAD_MIN) never change results beyond the parity
+ * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD, CTTS_F32_NO_WINOGRAD, CTTS_F32_WINOGRAD_MIN, CTTS_F32_WINOGRAD_PLAIN) never change results beyond the parity
  * tolerance (CTTS_F32_NO_SPLITK changes the summation order of the fused WaveFlow layer at batch <= 2, see above; CTTS_F32_NO_WN_FOLD
  * brings back the fp32 WaveGlow WN stack without the start / end folds: WN layer 0 on the C-row x, the C-row deferred skip GEMM and the
  * C-row flow tail - the default folds W_in,0 . W_start into layer 0 and W_end . W_skip,i into a 2 n_half-row skip/end pass, which only
@@ -848,7 +848,9 @@ int ctts_last_gemm_loop(void);
  * short-K launches of the same conv-GEMM behind a transform kernel, for utterances of at least CTTS_F32_WINOGRAD_MIN columns
  * (steps per batch item; 0 = always; only under the fp32 MFMA loop).  The threshold looks at the utterance, not at the batch: an
  * utterance keeps its bits whatever batch it runs in; one just below and one just above the threshold differ within the parity
- * tolerance).  The environment is read once,
+ * tolerance.  CTTS_F32_WINOGRAD_PLAIN runs that form as the five launches per layer it was first built as - cond rows copied into
+ * pair order for every layer, T2 / T3 and even / odd as four launches - where the default reads the cond rows in place and pairs
+ * the launches: bit-identical, the A/B arm).  The environment is read once,
  * at the first launch; this re-reads it (tests and profiling scripts that flip a knob in-process). */
 int ctts_tuning_reload(void);
 /* The knobs as the library currently sees them: bit 0 CTTS_F32_NO_GLDS, 1 CTTS_GEMM_NO_XCD_PAIR,
@@ -859,7 +861,7 @@ int ctts_tuning_reload(void);
  * before the first poll of the persistent decoder's six vector exchanges; timing only), 24 CTTS_TACO_VALU
  * (ctts_taco_decoder_steps_f32 at batch <= 4 on the VALU kernels instead of the batched MFMA form), 25 CTTS_UP_NO_MFMA (the VALU upsampling kernel
  * also for the shape the MFMA one is built for: bit-identical), 26 CTTS_F32_NO_WN_FOLD, 27 CTTS_TACO_BG_NO_PIPE (the batched
- * decoder's plain schedule, the default above 64 rows, at every size), 28 CTTS_F32_NO_WINOGRAD, 29 CTTS_F32_WINOGRAD_MIN set.  Bits 2, 5, 6 and 22 belonged to retired knobs and stay unused.
+ * decoder's plain schedule, the default above 64 rows, at every size), 28 CTTS_F32_NO_WINOGRAD, 29 CTTS_F32_WINOGRAD_MIN set, 30 CTTS_F32_WINOGRAD_PLAIN.  Bits 2, 5, 6 and 22 belonged to retired knobs and stay unused.
  * (Tests assert that a knob they set is the one in effect.) */
 int ctts_tuning_flags(void);
 
