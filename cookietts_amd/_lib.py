@@ -236,6 +236,13 @@ SIGNATURES = {
     "ctts_wgax_workspace_f16_bytes": (C.c_size_t, [C.POINTER(WgaxConfig), C.c_int32, C.c_int64]),
     "ctts_wgax_inverse_f16": (C.c_int, [C.POINTER(WgaxConfig), _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP,
                                         C.c_int32, C.c_int64, _FP, C.c_size_t, _FP]),
+    "ctts_wgax_sep_packed_bytes": (C.c_size_t, [C.POINTER(WgaxConfig)]),
+    "ctts_wgax_sep_pack_flow": (C.c_int, [C.POINTER(WgaxConfig), C.c_int32, C.POINTER(WgaxFlowWeights), C.POINTER(_FP),
+                                          C.POINTER(_FP), _FP, _FP]),
+    "ctts_wgax_sep_workspace_bytes": (C.c_size_t, [C.POINTER(WgaxConfig), C.c_int32, C.c_int64]),
+    "ctts_wgax_sep_inverse_f32": (C.c_int, [C.POINTER(WgaxConfig), _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP,
+                                            C.c_int32, C.c_int64, _FP, C.c_size_t, _FP]),
+    "ctts_depthwise_conv1d_f32": (C.c_int, [_FP, _FP, _FP, _FP] + [C.c_int32] * 7 + [_FP]),
     "ctts_hifigan_weight_floats": (C.c_size_t, [C.POINTER(HifiganConfig)]),
     "ctts_hifigan_packed_bytes": (C.c_size_t, [C.POINTER(HifiganConfig)]),
     "ctts_hifigan_pack_f32": (C.c_int, [C.POINTER(HifiganConfig), _FP, C.c_size_t, _FP, _FP]),

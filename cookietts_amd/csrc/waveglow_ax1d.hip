@@ -29,6 +29,12 @@
 // as the fp32 addend of the 16-bit GATE epilogue with the fp32 path's own interpolation arithmetic.  Rounding points (each a
 // round-to-nearest-even to half): the packed weights once; x after `start` and after every x + res; the gated activations;
 // the skip sum after every layer's accumulation.  GTU only: the plan refuses the other thirteen gated units.
+//
+// Separable in-layers (the ctts_wgax_sep_* entry points; glow_ax.py:337-348: depthwise Conv1d(C, C, ks, groups=C, dilation=d)
+// then pointwise Conv1d(C, 2C, 1)): one more launch per layer in front of the unchanged GEMMs.  ax_depthwise_kernel writes
+// dw = bd + sum_t wd[t] * x[. + (t - ks/2) d] (fp32 fma chain, taps ascending) into a fourth C-row tensor, the GATE launch then
+// reads dw as ONE segment at shift 0 with the pointwise [2C][C] weights (K = C instead of ks * C), SPLIT is unchanged.  The
+// GEMM's 11-segment limit does not apply behind the depthwise stage: ks is any odd value from 3 to 31.  fp32 storage only.
 #include <algorithm>
 #include <vector>
 
@@ -51,11 +57,14 @@ struct AxFlowDims { int n_rem, n_half, ch_off; };
 struct AxPlan {
     ctts_wgax_config c;
     bool half;                  // IEEE-half storage form: the A entries of `fl` are packed halves (offsets stay in floats)
+    bool sep;                   // separable in-layers: c.kernel_size is the depthwise width, the in-layer GEMM is the pointwise 1x1
+    int ks_g;                   // taps of the in-layer GEMM: kernel_size, or 1 behind a depthwise stage
     int C, nch_in, nch_c, mb_in;   // K chunks: of GEMM_KC channels, of BGEMM_KC in the half form
     std::vector<AxFlowDims> fd;
     struct Flow {
         size_t start_w, start_b, end_w, end_b, winv;
         std::vector<size_t> in_A, in_b, rs_A, rs_b;
+        std::vector<size_t> dw_w, dw_b;     // sep: dense [C][ks], [C]
     };
     std::vector<Flow> fl;
     size_t total;
@@ -63,15 +72,23 @@ struct AxPlan {
     int rs_mb(int layer) const { return (rs_rows(layer) + GEMM_BM - 1) / GEMM_BM; }
 };
 
-int make_ax_plan(const ctts_wgax_config* cfg, AxPlan& p, bool half = false) {
+constexpr int AX_SEP_MAX_KS = 31;
+
+int make_ax_plan(const ctts_wgax_config* cfg, AxPlan& p, bool half = false, bool sep = false) {
     CTTS_CHECK_ARG(cfg != nullptr, "wgax: config is NULL");
     p.c = *cfg;
     const auto& c = p.c;
     CTTS_CHECK_ARG(c.n_flows >= 1 && c.n_layers >= 1 && c.n_layers <= 12, "wgax: n_flows=%d n_layers=%d", c.n_flows, c.n_layers);
     CTTS_CHECK_ARG(gemm_mode_valid(c.f32_gemm_mode), "f32_gemm_mode=%d (CTTS_GEMM_DEFAULT / _F32 / _BF16X3 / _BF16X6)", c.f32_gemm_mode);
     CTTS_CHECK_ARG(c.n_group >= 2 && c.n_group % 2 == 0 && c.n_group <= AX_MAX_GROUP, "wgax: n_group=%d (even, <= 32)", c.n_group);
-    CTTS_CHECK_ARG(c.kernel_size % 2 == 1 && c.kernel_size >= 1 && c.kernel_size <= GEMM_MAX_SEG - 1,
-                   "wgax: kernel_size=%d (odd, <= 11)", c.kernel_size);
+    if (sep) {
+        CTTS_CHECK_ARG(c.kernel_size % 2 == 1 && c.kernel_size >= 3 && c.kernel_size <= AX_SEP_MAX_KS,
+                       "wgax sep: kernel_size=%d (depthwise width: odd, 3 .. 31)", c.kernel_size);
+        CTTS_CHECK_ARG(!half, "wgax sep: half storage is not built for separable in-layers");
+    } else {
+        CTTS_CHECK_ARG(c.kernel_size % 2 == 1 && c.kernel_size >= 1 && c.kernel_size <= GEMM_MAX_SEG - 1,
+                       "wgax: kernel_size=%d (odd, <= 11)", c.kernel_size);
+    }
     // 32: the res / skip split row of the SPLIT epilogue is a multiple of 32; a ragged last M-block (channels that are
     // not a multiple of 128) is zero-padded in the packed weights and masked in the epilogues
     CTTS_CHECK_ARG(c.n_channels >= 32 && c.n_channels % 32 == 0, "wgax: n_channels=%d (multiple of 32)", c.n_channels);
@@ -81,6 +98,8 @@ int make_ax_plan(const ctts_wgax_config* cfg, AxPlan& p, bool half = false) {
     CTTS_CHECK_ARG(c.gated_unit >= 0 && c.gated_unit < GATE_KINDS && (c.merge_res_skip == 0 || c.merge_res_skip == 1),
                    "wgax: gated_unit=%d merge_res_skip=%d", c.gated_unit, c.merge_res_skip);
     p.half = half;
+    p.sep = sep;
+    p.ks_g = sep ? 1 : c.kernel_size;
     if (half) {
         // the 16-bit GATE epilogue is tanh * sigmoid and has no run-time unit switch; of the other thirteen units the four
         // sin(16 x) ones leave the 1e-3 waveform bound with half activations, the rest no known checkpoint uses
@@ -92,7 +111,7 @@ int make_ax_plan(const ctts_wgax_config* cfg, AxPlan& p, bool half = false) {
     }
     p.C = c.n_channels;
     p.nch_c = p.C / (half ? BGEMM_KC : GEMM_KC);
-    p.nch_in = c.kernel_size * p.nch_c;
+    p.nch_in = p.ks_g * p.nch_c;
     p.mb_in = (2 * p.C + GEMM_BM - 1) / GEMM_BM;
     int n_rem = c.n_group;
     p.fd.resize(c.n_flows);
@@ -118,6 +137,10 @@ int make_ax_plan(const ctts_wgax_config* cfg, AxPlan& p, bool half = false) {
             f.in_b.push_back(take((size_t)p.mb_in * GEMM_BM));
             f.rs_A.push_back(take((size_t)p.rs_mb(i) * p.nch_c * a_tile));
             f.rs_b.push_back(take((size_t)p.rs_mb(i) * GEMM_BM));
+            if (sep) {
+                f.dw_w.push_back(take((size_t)p.C * c.kernel_size));
+                f.dw_b.push_back(take(p.C));
+            }
         }
     }
     p.total = o;
@@ -139,7 +162,7 @@ int make_ax_geom(const AxPlan& p, long long samples, AxGeom& g) {
 }
 
 // x, act, out: fp32 [B][C][ld], or (half form) K8-blocked halves [B][C/8][ld][8] in half the floats
-struct AxWs { float *audio, *x, *act, *out; size_t total; };
+struct AxWs { float *audio, *x, *act, *out, *dw; size_t total; };
 
 void ax_carve(const AxPlan& p, const AxGeom& g, int batch, float* base, AxWs& w) {
     const size_t per = p.half ? 2 : 1;                          // elements of a C-row tensor per float
@@ -150,6 +173,7 @@ void ax_carve(const AxPlan& p, const AxGeom& g, int batch, float* base, AxWs& w)
     w.x = take(B * p.C * g.ld / per);                           // (ld is a multiple of 32)
     w.act = take(B * p.C * g.ld / per);
     w.out = take(B * p.C * g.ld / per);
+    w.dw = p.sep ? take(B * p.C * g.ld) : nullptr;              // depthwise output: the in-layer GEMM's only segment
     w.total = o;
 }
 
@@ -436,6 +460,67 @@ __global__ __launch_bounds__(64) void replicate_halo_kernel(float* __restrict__ 
     if (i < halo) { row[-1 - i] = row[0]; row[T + i] = row[T - 1]; }
 }
 
+// ---- depthwise stage of a separable in-layer (glow_ax.py:342-344) ---------------------------------------------------------
+// y[b][c][pad + l] = bd[c] + sum_t wd[c][t] * x[b][c][pad + l + (t - ks/2) dil], as ONE fma chain per element: acc = bd[c],
+// then acc = fmaf(wd[c][t], x[..], acc) for t = 0 .. ks - 1 ascending - in both load forms.  A lane owns 4 consecutive
+// columns of one channel (pad and ld are multiples of 4: its 16 bytes are aligned); a workgroup owns 1024 columns of ONE
+// channel, so the ks weights and the bias are uniform.  ALIGNED (dil % 4 == 0): every tap is one aligned 16-byte load;
+// otherwise four dword loads per tap.  Reads stay inside the row: columns [pad - (ks/2) dil, pad + round_up(L, 4) + (ks/2) dil)
+// with (ks/2) dil <= pad and pad + round_up(L, 4) + (ks/2) dil <= ld (the launcher checks).  Only columns l < L are written:
+// the tail of a ragged last quad goes out as dword stores, halo and tail columns keep what they hold (zero in the model).
+template <bool ALIGNED>
+__global__ __launch_bounds__(256) void ax_depthwise_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                           const float* __restrict__ bias, float* __restrict__ y, int C, int L,
+                                                           int ld, int pad, int ks, int dil) {
+    const int l = (blockIdx.x * 256 + threadIdx.x) * 4;
+    const int c = blockIdx.y, b = blockIdx.z;
+    if (l >= L) return;
+    const size_t row = ((size_t)b * C + c) * ld + pad + l;
+    const float* wc = w + (size_t)c * ks;
+    const float bc = bias[c];
+    float acc[4] = {bc, bc, bc, bc};
+    const float* xt = x + row - (size_t)(ks / 2) * dil;
+    for (int t = 0; t < ks; ++t, xt += dil) {
+        const float wt = wc[t];
+        float v[4];
+        if constexpr (ALIGNED) {
+            const float4 q = *reinterpret_cast<const float4*>(xt);
+            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = xt[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = fmaf(wt, v[e], acc[e]);
+    }
+    if (l + 3 < L) {
+        *reinterpret_cast<float4*>(y + row) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (l + e < L) y[row + e] = acc[e];
+    }
+}
+
+int launch_ax_depthwise(const float* x, const float* w, const float* b, float* y, int batch, int C, int L, int ld, int pad,
+                        int ks, int dil, hipStream_t s) {
+    CTTS_CHECK_ARG(x && w && b && y, "depthwise_conv1d: NULL pointer");
+    CTTS_CHECK_ARG(x != y, "depthwise_conv1d: x == y (the taps read neighbouring columns: not an in-place operator)");
+    CTTS_CHECK_ARG(batch >= 1 && batch <= 65535 && C >= 1 && C <= 65535 && L >= 1 && L < (1 << 30),
+                   "depthwise_conv1d: batch=%d C=%d L=%d", batch, C, L);
+    CTTS_CHECK_ARG(ks % 2 == 1 && ks >= 1 && ks <= AX_SEP_MAX_KS && dil >= 1, "depthwise_conv1d: ks=%d (odd, <= 31) dil=%d", ks, dil);
+    CTTS_CHECK_ARG(pad >= 0 && pad % 4 == 0 && ld % 4 == 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0,
+                   "depthwise_conv1d: pad=%d, ld=%d and both tensors must be 16-byte aligned", pad, ld);
+    const long long reach = (long long)(ks / 2) * dil;
+    CTTS_CHECK_ARG(reach <= pad, "depthwise_conv1d: (ks/2)*dil = %lld > pad = %d", reach, pad);
+    CTTS_CHECK_ARG((long long)pad + round_up(L, 4) + reach <= ld, "depthwise_conv1d: pad + L + (ks/2)*dil beyond ld=%d", ld);
+    const dim3 grid((L + 1023) / 1024, C, batch);
+    if (dil % 4 == 0) hipLaunchKernelGGL(ax_depthwise_kernel<true>, grid, dim3(256), 0, s, x, w, b, y, C, L, ld, pad, ks, dil);
+    else hipLaunchKernelGGL(ax_depthwise_kernel<false>, grid, dim3(256), 0, s, x, w, b, y, C, L, ld, pad, ks, dil);
+    CTTS_CHECK_LAUNCH("ax_depthwise");
+    return CTTS_OK;
+}
+
 }  // namespace
 }  // namespace ctts
 
@@ -455,16 +540,24 @@ size_t ctts_wgax_packed_f16_bytes(const ctts_wgax_config* cfg) {
     return p.total * sizeof(float);
 }
 
-static int wgax_pack_flow(const ctts_wgax_config* cfg, int32_t k, const ctts_wgax_flow_weights* w, void* packed,
-                          void* stream, bool half) {
+size_t ctts_wgax_sep_packed_bytes(const ctts_wgax_config* cfg) {
     AxPlan p;
-    int rc = make_ax_plan(cfg, p, half); if (rc) return rc;
+    if (make_ax_plan(cfg, p, false, true)) return 0;
+    return p.total * sizeof(float);
+}
+
+static int wgax_pack_flow(const ctts_wgax_config* cfg, int32_t k, const ctts_wgax_flow_weights* w, void* packed,
+                          void* stream, bool half, bool sep = false, const float* const* dw_w = nullptr,
+                          const float* const* dw_b = nullptr) {
+    AxPlan p;
+    int rc = make_ax_plan(cfg, p, half, sep); if (rc) return rc;
     CTTS_CHECK_ARG(k >= 0 && k < p.c.n_flows && w && packed, "wgax pack_flow: bad argument (flow %d)", k);
+    CTTS_CHECK_ARG(!sep || (dw_w && dw_b), "wgax sep pack_flow: NULL depthwise weights");
     hipStream_t s = as_stream(stream);
     float* blob = static_cast<float*>(packed);
     const auto& f = p.fl[k];
     const auto& d = p.fd[k];
-    const int C = p.C, ks = p.c.kernel_size;
+    const int C = p.C, ks = p.ks_g;                              // sep: in_w[i] is the pointwise [2C][C]
     auto d2d = [&](size_t off, const float* src, size_t n) -> int {
         CTTS_CHECK_ARG(src != nullptr, "wgax pack_flow: NULL weight pointer");
         CTTS_CHECK_HIP(hipMemcpyAsync(blob + off, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -490,6 +583,10 @@ static int wgax_pack_flow(const ctts_wgax_config* cfg, int32_t k, const ctts_wga
         }
         if ((rc = launch_pack_bias(blob + f.in_b[i], GEMM_BM, p.mb_in, w->in_b[i], 0, nullptr, 0, GEMM_EPI_GATE, C, 2 * C,
                                    s))) return rc;
+        if (sep) {
+            if ((rc = d2d(f.dw_w[i], dw_w[i], (size_t)C * p.c.kernel_size))) return rc;     // dense [C][ks] as it is
+            if ((rc = d2d(f.dw_b[i], dw_b[i], C))) return rc;
+        }
         const int rows = p.rs_rows(i);
         if (half) rc = launch_pack_a_bf16(reinterpret_cast<bf16_t*>(blob + f.rs_A[i]), w->rs_w[i], p.rs_mb(i), p.nch_c, 0, C,
                                           BGEMM_EPI_SPLIT, C, rows, 0, C, 1, s, 1, 0, 0, 1);
@@ -512,9 +609,14 @@ int ctts_wgax_pack_flow_f16(const ctts_wgax_config* cfg, int32_t k, const ctts_w
     return wgax_pack_flow(cfg, k, w, packed, stream, true);
 }
 
-static size_t wgax_workspace_bytes(const ctts_wgax_config* cfg, int32_t batch, int64_t samples, bool half) {
+int ctts_wgax_sep_pack_flow(const ctts_wgax_config* cfg, int32_t k, const ctts_wgax_flow_weights* w,
+                            const float* const* dw_w, const float* const* dw_b, void* packed, void* stream) {
+    return wgax_pack_flow(cfg, k, w, packed, stream, false, true, dw_w, dw_b);
+}
+
+static size_t wgax_workspace_bytes(const ctts_wgax_config* cfg, int32_t batch, int64_t samples, bool half, bool sep = false) {
     AxPlan p; AxGeom g; AxWs w;
-    if (make_ax_plan(cfg, p, half) || make_ax_geom(p, samples, g) || batch < 1) return 0;
+    if (make_ax_plan(cfg, p, half, sep) || make_ax_geom(p, samples, g) || batch < 1) return 0;
     ax_carve(p, g, batch, nullptr, w);
     return w.total * sizeof(float);
 }
@@ -525,6 +627,15 @@ size_t ctts_wgax_workspace_bytes(const ctts_wgax_config* cfg, int32_t batch, int
 
 size_t ctts_wgax_workspace_f16_bytes(const ctts_wgax_config* cfg, int32_t batch, int64_t samples) {
     return wgax_workspace_bytes(cfg, batch, samples, true);
+}
+
+size_t ctts_wgax_sep_workspace_bytes(const ctts_wgax_config* cfg, int32_t batch, int64_t samples) {
+    return wgax_workspace_bytes(cfg, batch, samples, false, true);
+}
+
+int ctts_depthwise_conv1d_f32(const float* x, const float* w, const float* b, float* y, int32_t batch, int32_t C, int32_t L,
+                              int32_t ld, int32_t pad, int32_t ks, int32_t dil, void* stream) {
+    return launch_ax_depthwise(x, w, b, y, batch, C, L, ld, pad, ks, dil, as_stream(stream));
 }
 
 int ctts_replicate_halo_f32(float* x, int32_t batch, int32_t C, int32_t T, int32_t ld, int32_t pad, int32_t halo,
@@ -540,9 +651,9 @@ int ctts_replicate_halo_f32(float* x, int32_t batch, int32_t C, int32_t T, int32
 
 static int wgax_inverse(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,
                         int32_t cond_ld, int32_t cond_pad, int32_t frames, float* audio, int32_t batch,
-                        int64_t samples, void* workspace, size_t workspace_bytes, void* stream, bool half) {
+                        int64_t samples, void* workspace, size_t workspace_bytes, void* stream, bool half, bool sep = false) {
     AxPlan p; AxGeom g; AxWs w;
-    int rc = make_ax_plan(cfg, p, half); if (rc) return rc;
+    int rc = make_ax_plan(cfg, p, half, sep); if (rc) return rc;
     rc = make_ax_geom(p, samples, g); if (rc) return rc;
     CTTS_CHECK_ARG(packed && z && cond && audio && workspace && batch >= 1 && frames >= 1 && cond_ld >= frames + cond_pad,
                    "wgax inverse: bad argument");
@@ -553,7 +664,7 @@ static int wgax_inverse(const ctts_wgax_config* cfg, const void* packed, const f
     }
     hipStream_t s = as_stream(stream);
     const float* blob = static_cast<const float*>(packed);
-    const int G = p.c.n_group, C = p.C, L = g.L, ks = p.c.kernel_size, nl = p.c.n_layers;
+    const int G = p.c.n_group, C = p.C, L = g.L, ks = p.ks_g, nl = p.c.n_layers;
     const long long cstride = (long long)C * g.ld;
     const dim3 lgrid((L + 255) / 256, batch);
 
@@ -631,11 +742,14 @@ static int wgax_inverse(const ctts_wgax_config* cfg, const void* packed, const f
                 if ((rc = launch_gemm_bf16(BGEMM_EPI_SPLIT, r, s))) return rc;
                 continue;
             }
+            // separable: the dilated taps are the depthwise launch's, the GEMM reads its output at shift 0 (ks == 1 here)
+            if (p.sep && (rc = launch_ax_depthwise(w.x, blob + f.dw_w[i], blob + f.dw_b[i], w.dw, batch, C, L, g.ld, g.pad,
+                                                   p.c.kernel_size, dil, s))) return rc;
             {
                 GemmArgs a = base_args();
                 a.A = blob + f.in_A[i]; a.bias = blob + f.in_b[i];
                 a.nseg = ks; a.interleave = ks; a.nch_total = p.nch_in; a.MB = p.mb_in;
-                for (int t = 0; t < ks; ++t) a.seg[t] = {w.x, cstride, p.nch_c, (t - ks / 2) * dil, 0, 0};
+                for (int t = 0; t < ks; ++t) a.seg[t] = {p.sep ? w.dw : w.x, cstride, p.nch_c, (t - ks / 2) * dil, 0, 0};
                 a.dst0 = w.act; a.dst0_bstride = cstride;
                 a.M = 2 * C; a.pairC = C;
                 // frame-rate conditioning rows of this layer, interpolated to sample rate inside the GATE epilogue
@@ -671,6 +785,13 @@ int ctts_wgax_inverse_f32(const ctts_wgax_config* cfg, const void* packed, const
                           int64_t samples, void* workspace, size_t workspace_bytes, void* stream) {
     return wgax_inverse(cfg, packed, z, cond, cond_ld, cond_pad, frames, audio, batch, samples, workspace, workspace_bytes,
                         stream, false);
+}
+
+int ctts_wgax_sep_inverse_f32(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,
+                              int32_t cond_ld, int32_t cond_pad, int32_t frames, float* audio, int32_t batch,
+                              int64_t samples, void* workspace, size_t workspace_bytes, void* stream) {
+    return wgax_inverse(cfg, packed, z, cond, cond_ld, cond_pad, frames, audio, batch, samples, workspace, workspace_bytes,
+                        stream, false, true);
 }
 
 int ctts_wgax_inverse_f16(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,

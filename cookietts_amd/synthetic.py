@@ -367,6 +367,66 @@ WAVEGLOW_AX_CONFIGS = {
 }
 
 
+def _ax_sep_notebook_toy():
+    import copy
+    cfg = copy.deepcopy(WAVEGLOW_AX_CONFIGS["notebook_toy"])
+    cfg["WN_config"]["seperable_conv"] = 1
+    return cfg
+
+
+# separable (depthwise + pointwise) in-layers on the 1-D core (glow_ax.py:337-348); kept apart from WAVEGLOW_AX_CONFIGS
+WAVEGLOW_AX_SEP_CONFIGS = {
+    # L = 325: odd, three 128-column GEMM tiles, a ragged last 4-column unit in the depthwise stage
+    "sep_toy": waveglow_ax_config(n_flows=4, n_group=8, n_early_every=2, hop_length=200, win_length=800,
+                                  WN=dict(seperable_conv=True)),
+    # odd dilations (dword loads), 7 taps, a ragged last M-block
+    "sep_k7_dil_c96": waveglow_ax_config(n_flows=4, n_group=8, n_channels=96, kernel_size_w=7, hop_length=200, win_length=800,
+                                         channel_mixing='permute', mix_first=False,
+                                         WN=dict(seperable_conv=True, n_layers_dilations_w=[3, 1, 7])),
+    # more taps than the dense in-layer GEMM has segments
+    "sep_k13_merge_c160": waveglow_ax_config(n_flows=2, n_group=12, n_channels=160, n_layers=2, kernel_size_w=13,
+                                             hop_length=240, win_length=960,
+                                             WN=dict(seperable_conv=True, merge_res_skip=True, gated_unit='GLU')),
+    # dilation 128 against L = 325: taps reach the zero halo from both edges
+    "sep_deep": waveglow_ax_config(n_flows=2, n_group=8, n_layers=8, hop_length=200, win_length=800,
+                                   WN=dict(seperable_conv=True)),
+    # kernel_size 1: the reference builds the dense layer (glow_ax.py:337)
+    "sep_k1": waveglow_ax_config(n_flows=2, n_group=8, kernel_size_w=1, WN=dict(seperable_conv=True)),
+    # the notebook's option set (speaker ids, cond stack, early outputs)
+    "sep_notebook_toy": _ax_sep_notebook_toy(),
+}
+
+
+def fold_separable(sd, cfg):
+    """-> (dense_sd, dense_cfg): the dense in-layers that compute what the separable ones of ``sd`` compute,
+    W[o][c][t] = Wp[o][c] * wd[c][t] and bias = bp + Wp . bd, evaluated in float64 from the weight-norm-folded factors and
+    re-expressed as ``weight_v`` = W, ``weight_g`` = its per-row norm.  Exact in real arithmetic; every other entry is
+    passed through.  A config without separable layers (or with kernel size 1) comes back as it is."""
+    import copy
+    dense_cfg = copy.deepcopy(cfg)
+    dense_cfg["WN_config"]["seperable_conv"] = False
+    out = {}
+
+    def folded(prefix):
+        v = np.asarray(sd[prefix + ".weight_v"], np.float64)
+        g = np.asarray(sd[prefix + ".weight_g"], np.float64)
+        return g * v / np.sqrt((v ** 2).sum(axis=(1, 2), keepdims=True))
+    for key, val in sd.items():
+        parts = key.split(".")
+        if "in_layers" in parts and len(parts) >= 3 and parts[-2] in ("0", "1") and parts[-3].isdigit():
+            if key.endswith(".0.weight_v"):
+                p = key[:-len(".0.weight_v")]
+                wd, wp = folded(p + ".0")[:, 0, :], folded(p + ".1")[:, :, 0]      # [C, ks], [2C, C]
+                w = (wp[:, :, None] * wd[None, :, :]).astype(np.float32)
+                out[p + ".weight_v"] = w
+                out[p + ".weight_g"] = np.sqrt((w.astype(np.float64) ** 2).sum(axis=(1, 2), keepdims=True)).astype(np.float32)
+                out[p + ".bias"] = (np.asarray(sd[p + ".1.bias"], np.float64)
+                                    + wp @ np.asarray(sd[p + ".0.bias"], np.float64)).astype(np.float32)
+            continue
+        out[key] = val
+    return out, dense_cfg
+
+
 def waveglow_ax_flow_channels(cfg):
     """n_remaining_channels per flow (efficient_model_ax.py:170-189)."""
     n_rem, out = cfg["n_group"], []
@@ -381,7 +441,8 @@ def waveglow_ax_state_dict(cfg, seed=1234, end_std=None):
     """Random-init state dict with the reference's keys for ``waveflow=False``: ``WN.k.WN.{start,in_layers.i,
     res_skip_layers.i,cond_layers.l}.{bias,weight_g,weight_v}`` (3-D conv weights), ``WN.k.WN.end.{weight,bias}``,
     ``WN.k.WN.speaker_embed.weight``, ``convinv.k.weight`` (1x1conv mixing only), ``speaker_embed.weight``, ``alpha``,
-    ``cond_layers.l.*``."""
+    ``cond_layers.l.*``; with ``seperable_conv`` and a kernel wider than 1, ``WN.k.WN.in_layers.i.{0,1}.*`` (depthwise
+    [C, 1, ks], pointwise [2C, C, 1]) instead of ``in_layers.i.*``."""
     rng = np.random.default_rng(seed)
     wn = cfg["WN_config"]
     C, n_layers = wn["n_channels"], wn["n_layers"]
@@ -439,7 +500,11 @@ def waveglow_ax_state_dict(cfg, seed=1234, end_std=None):
             _tconv_params(rng, sd, p + ".upsample_net", cond_out, 2 * C * n_layers, cond_out,
                           wn.get("transposed_conv_kernel_size", 4), wn["transposed_conv_scales"])
         for i in range(n_layers):
-            _wn_conv(rng, sd, f"{p}.in_layers.{i}", 2 * C, C, ks)
+            if wn.get("seperable_conv") and ks != 1:                             # glow_ax.py:341-348: depthwise, pointwise
+                _wn_conv(rng, sd, f"{p}.in_layers.{i}.0", C, 1, ks)
+                _wn_conv(rng, sd, f"{p}.in_layers.{i}.1", 2 * C, C, 1)
+            else:
+                _wn_conv(rng, sd, f"{p}.in_layers.{i}", 2 * C, C, ks)
             if wn.get("res_skip", True):
                 _wn_conv(rng, sd, f"{p}.res_skip_layers.{i}", 2 * C if (i < n_layers - 1 and not wn.get("merge_res_skip")) else C, C, 1)
         if conv_mix:

@@ -14,7 +14,8 @@ Host-side mirror of ``/root/reference/CookieTTS/_4_mtw/waveglow/efficient_model_
   WN level, the model-level conditioning stack (plain / residual / 1x1-conv residual, rezero), multi-layer WN
   conditioning stacks with activations, the grouped per-flow cond conv, model- and WN-level
   ``TransposedUpsampleNet``, spect shift / scale, log-variance mel channels, perceived-volume companding,
-  de-emphasis; separable (depthwise + pointwise) in-layers on the 2-D core.
+  de-emphasis; separable (depthwise + pointwise) in-layers on both cores (the 1-D core: up to 31 taps, fp32 storage,
+  ``ctts_wgax_sep_inverse_f32``).
 
 Same constructor kwargs, same ``state_dict`` keys (``WN.k.WN.{start,cond_layers.l,in_layers.i,res_skip_layers.i}.
 {weight_g,weight_v,bias}``, ``WN.k.WN.end.{weight,bias}``, ``convinv.k.weight``, ``upsample_net.*``, ...), same
@@ -104,7 +105,11 @@ class _WN1d(nn.Module):
             cond_out = hid
         dims = [cond_in + sdim] + [wn['cond_hidden_channels']] * (wn['cond_layers'] - 1) + [cond_out]
         self.cond_layers = nn.ModuleList([WNConv((dims[l + 1], dims[l], k)) for l in range(wn['cond_layers'])])
-        self.in_layers = nn.ModuleList([WNConv((2 * C_, C_, ks)) for _ in range(n_layers)])
+        if wn.get('seperable_conv', False) and ks != 1:                          # glow_ax.py:337-348
+            self.in_layers = nn.ModuleList([nn.ModuleList([WNConv((C_, 1, ks)), WNConv((2 * C_, C_, 1))])
+                                            for _ in range(n_layers)])
+        else:
+            self.in_layers = nn.ModuleList([WNConv((2 * C_, C_, ks)) for _ in range(n_layers)])
         merge = bool(wn.get('merge_res_skip', False))                            # glow_ax.py:352-355
         self.res_skip_layers = nn.ModuleList([
             WNConv((2 * C_ if (i < n_layers - 1 and not merge) else C_, C_, 1)) for i in range(n_layers)]
@@ -294,7 +299,6 @@ class WaveGlow(_cache.PackedModule):
         if waveflow:
             need(n_group <= 64, "waveflow=True with n_group > 64")
         else:
-            need(not wn.get('seperable_conv', False), "waveflow=False with seperable_conv")
             need(wn['n_channels'] % 32 == 0, "waveflow=False with n_channels not a multiple of 32")
             need(n_group <= 32, "waveflow=False with n_group > 32")
         need(cond_residual in (False, True, 0, 1, '1x1conv'), f"cond_residual={cond_residual!r}")
@@ -335,7 +339,11 @@ class WaveGlow(_cache.PackedModule):
             need(wn.get('seperable_conv', False) or wn['kernel_size_h'] * wn['kernel_size_w'] <= 11,
                  "dense in-layer kernels with more than 11 taps (use seperable_conv)")
         else:
-            need((wn.get('kernel_size_w') or wn.get('kernel_size')) <= 11, "1-D in-layer kernels wider than 11")
+            ks1 = wn.get('kernel_size_w') or wn.get('kernel_size')
+            if wn.get('seperable_conv', False) and ks1 != 1:
+                need(ks1 <= 31, "separable 1-D in-layer kernels wider than 31")
+            else:
+                need(ks1 <= 11, "dense 1-D in-layer kernels wider than 11 (use seperable_conv)")
         need(2 * cond_kernel_size - 1 <= 11 and 2 * wn.get('cond_kernel_size', 1) - 1 <= 11, "cond kernels wider than 11")
         assert mixing != 'permuteheight' or n_flows % 2 == 0, "PermuteHeight requires even n_flows"
 
@@ -426,6 +434,8 @@ class WaveGlow(_cache.PackedModule):
                         and self.shift_spect == 0. and self.scale_spect == 1.
                         and wn.get('cond_layers', 1) == 1 and wn.get('cond_kernel_size', 1) == 1
                         and self._act_wn[0] == 0)
+        # separable (depthwise + pointwise) in-layers of the 1-D core: the ctts_wgax_sep_* entry points
+        self._sep1d = (not waveflow) and isinstance(self.WN[0].WN.in_layers[0], nn.ModuleList)
         self._f32_gemm_mode = None
         self._compute_dtype = torch.float32
 
@@ -465,13 +475,17 @@ class WaveGlow(_cache.PackedModule):
         ``NotImplementedError`` - here, not at the first ``infer`` - for what half storage is not built for:
         ``waveflow=True`` (the 2-D core's <= 128-channel row queue is latency-bound: narrower tensors buy nothing there,
         ``set_f32_gemm_mode("bf16x3")`` is its reduced-precision mode), a gated unit other than GTU (the 16-bit gate
-        epilogue is tanh * sigmoid only; the sin(16 x) units would leave the 1e-3 waveform bound), or a plan the library
-        refuses (kernel_size * n_channels / 32 beyond the 16-bit GEMM's chunk table)."""
+        epilogue is tanh * sigmoid only; the sin(16 x) units would leave the 1e-3 waveform bound), ``seperable_conv``
+        in-layers (the depthwise stage is built on fp32 rows only), or a plan the library refuses (kernel_size *
+        n_channels / 32 beyond the 16-bit GEMM's chunk table)."""
         if dtype not in (torch.float32, torch.float16):
             raise ValueError(f"compute dtype must be torch.float32 or torch.float16, not {dtype!r}")
         if dtype == torch.float16:
             if self.waveflow:
                 raise NotImplementedError("half storage is not built for waveflow=True (latency-bound row queue); "
+                                          "use set_f32_gemm_mode('bf16x3')")
+            if self._sep1d:
+                raise NotImplementedError("half storage is not built for seperable_conv in-layers (fp32 depthwise stage); "
                                           "use set_f32_gemm_mode('bf16x3')")
             unit = str(self.WN_config.get('gated_unit', 'GTU')).upper()
             if unit != 'GTU':
@@ -524,10 +538,13 @@ class WaveGlow(_cache.PackedModule):
             size, pack_flow, name = lib.ctts_waveflow_packed_bytes, lib.ctts_waveflow_pack_flow, "ctts_waveflow_pack_flow"
         else:
             cfg = self.c_config_1d()
-            size = lib.ctts_wgax_packed_f16_bytes if half else lib.ctts_wgax_packed_bytes
-            pack_flow, name = (lib.ctts_wgax_pack_flow_f16 if half else lib.ctts_wgax_pack_flow), "ctts_wgax_pack_flow"
+            if self._sep1d:
+                size, pack_flow, name = lib.ctts_wgax_sep_packed_bytes, lib.ctts_wgax_sep_pack_flow, "ctts_wgax_sep_pack_flow"
+            else:
+                size = lib.ctts_wgax_packed_f16_bytes if half else lib.ctts_wgax_packed_bytes
+                pack_flow, name = (lib.ctts_wgax_pack_flow_f16 if half else lib.ctts_wgax_pack_flow), "ctts_wgax_pack_flow"
         nbytes = _lib.nbytes(size, C.byref(cfg), what="unsupported ax-core config")
-        sep = self.waveflow and isinstance(self.WN[0].WN.in_layers[0], nn.ModuleList)
+        sep = isinstance(self.WN[0].WN.in_layers[0], nn.ModuleList)
         with torch.cuda.device(device):
             stream = _lib.stream(device)
             blob = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
@@ -558,8 +575,10 @@ class WaveGlow(_cache.PackedModule):
                 fw.in_w = arr(lambda i: folded_weight(gemm(i), stream, keep).data_ptr())
                 fw.in_b = arr(lambda i: _cache.dev(gemm(i).bias, keep))
                 if sep:
-                    fw.dw_w = arr(lambda i: folded_weight(wn.in_layers[i][0], stream, keep).data_ptr())
-                    fw.dw_b = arr(lambda i: _cache.dev(wn.in_layers[i][0].bias, keep))
+                    dw_w = arr(lambda i: folded_weight(wn.in_layers[i][0], stream, keep).data_ptr())
+                    dw_b = arr(lambda i: _cache.dev(wn.in_layers[i][0].bias, keep))
+                    if self.waveflow:
+                        fw.dw_w, fw.dw_b = dw_w, dw_b
                 fw.rs_w = arr(lambda i: eye.data_ptr() if no_rs else folded_weight(wn.res_skip_layers[i], stream, keep).data_ptr())
                 fw.rs_b = arr(lambda i: zero_b.data_ptr() if no_rs else _cache.dev(wn.res_skip_layers[i].bias, keep))
                 fw.end_w = _cache.dev(wn.end.weight, keep)
@@ -571,7 +590,10 @@ class WaveGlow(_cache.PackedModule):
                     self.convinv[k].W_inverse = W_inverse[..., None]
                     keep.append(W_inverse)
                     fw.w_inverse = W_inverse.data_ptr()
-                _lib.check(pack_flow(C.byref(cfg), k, C.byref(fw), _lib.ptr(blob), stream), f"{name}({k})")
+                if self._sep1d:       # the 1-D struct has no depthwise fields: they travel as arguments
+                    _lib.check(pack_flow(C.byref(cfg), k, C.byref(fw), dw_w, dw_b, _lib.ptr(blob), stream), f"{name}({k})")
+                else:
+                    _lib.check(pack_flow(C.byref(cfg), k, C.byref(fw), _lib.ptr(blob), stream), f"{name}({k})")
             ops = None
             gm = _lib.model_gemm_mode(self._f32_gemm_mode)
             if not self._folded:
@@ -743,7 +765,8 @@ class WaveGlow(_cache.PackedModule):
     def inverse(self, z, cond, speaker_ids=None, return_CPU=True):
         """efficient_model_ax.py:279-357: z [B, T] (noise, sigma applied), cond [B, n_mel(*2), frames].  ``waveflow=True``:
         WaveFlowCoupling + WN_2d (ctts_waveflow_inverse_f32 / _cond_f32); ``waveflow=False``: AffineCouplingBlock + the 1-D WN
-        (ctts_wgax_inverse_f32, or ctts_wgax_inverse_f16 after ``set_compute_dtype(torch.float16)``)."""
+        (ctts_wgax_inverse_f32, ctts_wgax_sep_inverse_f32 with separable in-layers, or ctts_wgax_inverse_f16 after
+        ``set_compute_dtype(torch.float16)``)."""
         device = cond.device
         blob, ops = self._ensure_packed(device)
         lib = _lib.lib()
@@ -752,7 +775,8 @@ class WaveGlow(_cache.PackedModule):
             cfg, ws_bytes, what = self.c_config(), lib.ctts_waveflow_workspace_bytes, "WaveFlow workspace query failed"
         else:
             cfg, what = self.c_config_1d(), "ax WaveGlow workspace query failed"
-            ws_bytes = lib.ctts_wgax_workspace_f16_bytes if half else lib.ctts_wgax_workspace_bytes
+            ws_bytes = (lib.ctts_wgax_sep_workspace_bytes if self._sep1d else
+                        lib.ctts_wgax_workspace_f16_bytes if half else lib.ctts_wgax_workspace_bytes)
         mel = cond.detach().float().contiguous()
         zz = z.detach().to(device=device, dtype=torch.float32).contiguous()
         B, T = zz.shape
@@ -773,7 +797,8 @@ class WaveGlow(_cache.PackedModule):
                                                                  ld, PAD, _lib.ptr(audio), B, T, n_cond, _lib.ptr(ws),
                                                                  ws.numel() * 4, stream), "ctts_waveflow_inverse_cond_f32")
                 else:
-                    name = "ctts_wgax_inverse_f16" if half else "ctts_wgax_inverse_f32"
+                    name = ("ctts_wgax_sep_inverse_f32" if self._sep1d else
+                            "ctts_wgax_inverse_f16" if half else "ctts_wgax_inverse_f32")
                     _lib.check(getattr(lib, name)(C.byref(cfg), _lib.ptr(blob), _lib.ptr(zz), _lib.ptr(frames), ld, PAD, n_cond,
                                                   _lib.ptr(audio), B, T, _lib.ptr(ws), ws.numel() * 4, stream), name)
             if self.vol_scaling:       # ax:342-344

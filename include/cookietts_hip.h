@@ -400,7 +400,8 @@ int ctts_deemphasis_f32(const float* x, float* y, int32_t batch, int32_t T, doub
  *   PermuteHeight.inverse         efficient_modules.py:376-403
  *   early outputs                 efficient_model_ax.py:312-316, 340-341;   ignore_nan  :13-16, 333-334
  *   mix_first ordering            efficient_model_ax.py:324-325, 337-338
- * Built: all fourteen gated units, res_skip=True, merge_res_skip, dense in-layers with width dilation 2^i,
+ * Built: all fourteen gated units, res_skip=True, merge_res_skip, dense in-layers (<= 11 taps) and separable (depthwise +
+ * pointwise, glow_ax.py:341-348) in-layers up to 31 taps (the ctts_wgax_sep_* entry points), width dilation 2^i or per layer,
  * the per-flow WN conditioning stack is evaluated by the caller (composed from ctts_conv1d_f32 / ctts_embed_rows_f32 /
  * ctts_scale_add_rows_f32 / ctts_replicate_halo_f32) and handed over, like ctts_waveflow_inverse_cond_f32: at FRAME
  * rate (upsample_first=False; `frames` columns, interpolated to the latent's rate inside the gate epilogue) or already
@@ -461,6 +462,27 @@ size_t ctts_wgax_workspace_f16_bytes(const ctts_wgax_config* cfg, int32_t batch,
 int ctts_wgax_inverse_f16(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,
                           int32_t cond_ld, int32_t cond_pad, int32_t frames, float* audio, int32_t batch,
                           int64_t samples, void* workspace, size_t workspace_bytes, void* stream);
+/* Separable in-layers (WN_config['seperable_conv'] with kernel_size > 1, glow_ax.py:341-348: weight-normed depthwise
+ * Conv1d(C, C, ks, groups=C, dilation=d) then pointwise Conv1d(C, 2C, 1)).  Same config struct - `kernel_size` is the
+ * DEPTHWISE width, odd, 3 .. 31 (the dense form's 11-tap limit does not apply) - and the same arguments as the functions
+ * above, with an own packed blob and an own workspace (one more C-row tensor).  In ctts_wgax_sep_pack_flow, w->in_w[i] is the
+ * pointwise [2C][C], w->in_b[i] its [2C] bias, dw_w[i] the depthwise [C][ks] and dw_b[i] its [C] bias, all weight-norm
+ * folded.  Per layer: ctts_depthwise_conv1d_f32's kernel, then the dense form's two GEMMs with K = C in the first;
+ * f32_gemm_mode acts on the GEMMs only, the depthwise stage is always an fp32 fma chain.  fp32 storage only. */
+size_t ctts_wgax_sep_packed_bytes(const ctts_wgax_config* cfg);
+int ctts_wgax_sep_pack_flow(const ctts_wgax_config* cfg, int32_t flow, const ctts_wgax_flow_weights* w,
+                            const float* const* dw_w, const float* const* dw_b, void* packed, void* stream);
+size_t ctts_wgax_sep_workspace_bytes(const ctts_wgax_config* cfg, int32_t batch, int64_t samples);
+int ctts_wgax_sep_inverse_f32(const ctts_wgax_config* cfg, const void* packed, const float* z, const float* cond,
+                              int32_t cond_ld, int32_t cond_pad, int32_t frames, float* audio, int32_t batch,
+                              int64_t samples, void* workspace, size_t workspace_bytes, void* stream);
+/* Depthwise 1-D convolution on padded rows: y[b][c][pad + l] = b[c] + sum_t w[c][t] * x[b][c][pad + l + (t - ks/2) * dil] for
+ * l < L, evaluated as acc = b[c]; acc = fmaf(w[c][t], x[..], acc) for t = 0 .. ks-1 in ascending order.  x, y fp32
+ * [batch][C][ld] (16-byte aligned, ld and pad multiples of 4), w [C][ks], ks odd <= 31, dil >= 1.  Only columns
+ * [pad, pad + L) of y are written.  CTTS_E_ARG for a NULL pointer, x == y (not an in-place operator), an even ks or one above
+ * 31, (ks/2) * dil > pad, or a row too short for the taps of its last column (pad + round_up(L, 4) + (ks/2) * dil > ld). */
+int ctts_depthwise_conv1d_f32(const float* x, const float* w, const float* b, float* y, int32_t batch, int32_t C, int32_t L,
+                              int32_t ld, int32_t pad, int32_t ks, int32_t dil, void* stream);
 /* padding_mode='replicate' of the conditioning convs (efficient_model_ax.py:90, glow_ax.py:311): fill the `halo`
  * columns either side of the valid range of x [B][C][ld] with the edge values, before a ctts_conv1d_f32 reads them. */
 int ctts_replicate_halo_f32(float* x, int32_t batch, int32_t C, int32_t T, int32_t ld, int32_t pad, int32_t halo,

@@ -240,6 +240,67 @@ def row_waveglow_ax_notebook_ab(args):
     return rows
 
 
+def row_waveglow_ax_sep_ab(args):
+    """Separable in-layers on the 1-D ax core against the same network folded into dense in-layers: the notebook config
+    (48 flows x 8 x 256, n_group 24) with ``seperable_conv`` at kernel size 3 and 7 (``--ks``), batch 1 and 8 on the notebook
+    row's 5.84 s clip.  Arm ``sep`` = depthwise launch + K = C GEMM (ctts_wgax_sep_inverse_f32); arm ``fold`` = the same weights
+    through ``synthetic.fold_separable`` on the dense path (K = ks * C).  Same latent for both arms, the arms alternated
+    ``--reps`` times in one process after a warm-up of each, timed by device events; ``--arms sep`` for a profiler pass."""
+    import copy
+    import gc
+    from cookietts_amd.waveglow_ax import WaveGlow
+    arms_on = [a for a in getattr(args, "arms", "").split(",") if a in ("sep", "fold")] or ["sep", "fold"]
+    rows = []
+    for ks in (int(k) for k in getattr(args, "ks", "3,7").split(",")):
+        cfg = copy.deepcopy(synthetic.WAVEGLOW_AX_CONFIGS["notebook"])
+        cfg["WN_config"].update(seperable_conv=True, kernel_size_w=ks)
+        sd = synthetic.waveglow_ax_state_dict(cfg, seed=1234)
+        models = {}
+        for name in arms_on:
+            c, w = (cfg, sd) if name == "sep" else synthetic.fold_separable(sd, cfg)[::-1]
+            m = WaveGlow(**c)
+            m.load_state_dict(synthetic.to_torch(w))
+            models[name] = _mode(m.cuda().eval(), args)
+        wn = cfg["WN_config"]
+        C, nl, G = wn["n_channels"], wn["n_layers"], cfg["n_group"]
+        for B in _batches(args, (1, 8)):
+            mel, ids = _ax_notebook_input(cfg, B)
+            T = AX_NOTEBOOK_FRAMES * cfg["hop_length"]
+            z = torch.randn(B, T - T % G, device="cuda")
+            arms = [(n, (lambda m=m: m.infer_from_noise(mel, z, speaker_ids=ids, return_CPU=False))) for n, m in models.items()]
+            times, outs = {n: [] for n, _ in arms}, {}
+            for n, fn in arms:
+                for _ in range(max(1, args.warmup)):
+                    outs[n] = fn()
+                torch.cuda.synchronize()
+            for _ in range(getattr(args, "reps", 5)):
+                for n, fn in arms:
+                    times[n].append(_event_ms(fn, args.steps))
+            med = {n: sorted(t)[len(t) // 2] for n, t in times.items()}
+            L = z.shape[1] // G
+            row = {"row": "W5/notebook_sep_ab", "metric": f"ax WaveGlow waveflow=False, 48 flows x 8 x 256, n_group 24, seperable_conv, "
+                                                          f"kernel {ks}, 160x468 mel (5.84 s clip), ms per call (device events)",
+                   "kernel_size": ks, "batch": B, "unit": "ms", "dtype": "f32",
+                   "arms": {n: {"reps_ms": t, "median_ms": med[n], "min_ms": min(t), "max_ms": max(t),
+                                "spread_frac": (max(t) - min(t)) / med[n]} for n, t in times.items()},
+                   # counted from the layer shapes, per call: in-layer + res/skip GEMMs of each arm, and the depthwise stage's traffic
+                   "gemm_flop": {"sep": 2.0 * cfg["n_flows"] * nl * (2 * C * C + 2 * C * C) * B * L,
+                                 "fold": 2.0 * cfg["n_flows"] * nl * (ks * 2 * C * C + 2 * C * C) * B * L},
+                   "depthwise_launches": cfg["n_flows"] * nl, "depthwise_bytes_per_launch": 2 * B * C * L * 4}
+            if "sep" in med:
+                row.update({"value": med["sep"], "rtf_48k": B * (AX_NOTEBOOK_FRAMES - 1) * cfg["hop_length"] / (med["sep"] * 1e-3) / 48000.0})
+            if len(med) == 2:
+                row["fold_over_sep"] = med["fold"] / med["sep"]
+                d = outs["sep"].double() - outs["fold"].double()
+                row["sep_vs_fold_rel_rms"] = float(d.pow(2).mean().sqrt() / outs["fold"].double().pow(2).mean().sqrt())
+            rows.append(row)
+            del outs, z, mel
+        del models
+        gc.collect()
+        torch.cuda.empty_cache()
+    return rows
+
+
 def _hifigan_pair(key):
     """(HIP generator, baseline closure, cfg): the same synthetic weights behind ``cookietts_amd.HiFiGANGenerator`` and behind
     the plain ``torch.nn.functional`` restatement (tests/hifigan_restatement.py, folded weights, fp32 on the same GPU)."""
@@ -536,10 +597,12 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab: repetitions of every arm (alternated)")
     ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts) to these batch sizes (PMC passes)")
     ap.add_argument("--arms", default="hip,torch,hip_f16,torch_f16,hip_bf16x3",
-                    help="hifigan: arms to run (hip, hip_f16 or hip_bf16x3 alone for a profiler pass)")
+                    help="hifigan: arms to run (hip, hip_f16 or hip_bf16x3 alone for a profiler pass); waveglow_ax_sep_ab: sep, fold")
+    ap.add_argument("--ks", default="3,7", help="waveglow_ax_sep_ab: comma list of depthwise kernel sizes")
     args = ap.parse_args()
     fns = {"hifigan": row_hifigan, "waveflow": row_waveflow, "waveflow_table": row_waveflow_table, "waveflow_author": row_waveflow_author, "tacotron": row_tacotron, "stft": row_stft,
-           "waveglow_ax": row_waveglow_ax_notebook, "waveglow_ax_ab": row_waveglow_ax_notebook_ab, "waveglow_ax_untts": row_waveglow_ax_untts}
+           "waveglow_ax": row_waveglow_ax_notebook, "waveglow_ax_ab": row_waveglow_ax_notebook_ab, "waveglow_ax_untts": row_waveglow_ax_untts,
+           "waveglow_ax_sep_ab": row_waveglow_ax_sep_ab}
     for r in args.rows.split(","):
         out = fns[r](args)
         for line in (out if isinstance(out, list) else [out]):
