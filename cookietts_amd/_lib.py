@@ -183,6 +183,12 @@ SIGNATURES = {
                                               C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
     "ctts_taco_decoder_steps_hidden_f32": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, _FP, _FP, C.c_int32,
                                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
+    "ctts_taco_prenet_frames_bytes": (C.c_size_t, [C.POINTER(TacoDecoderConfig), C.c_int32, C.c_int32]),
+    "ctts_taco_prenet_frames_f32": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, _FP, C.c_size_t, C.c_int32,
+                                              C.c_int32, _FP]),
+    "ctts_taco_decoder_steps_forced_f32": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, C.c_int32, C.c_int32,
+                                                     C.c_int32, C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
+    "ctts_taco_project_frames_f32": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
     "ctts_taco_decoder_persistent_bytes": (C.c_size_t, [C.POINTER(TacoDecoderConfig), C.c_int32, C.c_int32]),
     "ctts_taco_decoder_steps_persistent_f32": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, _FP, C.c_int32,
                                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_size_t,

@@ -54,6 +54,8 @@ struct BgArgs {
     // BG_EPI_CELL: LSTMCell, gate order i, f, g, o; bias and state in the checkpoint / workspace layouts.  hsum (second decoder RNN):
     // also hsum[ix] = h' + hres[ix], the residual sum dec_h + d2_h that the gate / mel projection reads (model.py:755-759)
     const float *bih, *bhh; float *c, *h_new; int H; float* hsum; const float* hres;
+    // ... teacher-forced loop: hsum also goes to hid[item][unit][step] of hidden_out [B][hid_D][max_steps] (NULL = off)
+    float* hid; int hid_D;
     // BG_EPI_SEQ: one time step of a packed-sequence LSTM direction (the encoder's BiLSTM): the input projection of every
     // step is precomputed (sq.gadd, biases included), item b is active while sq.step < lengths[b] (see LstmSeq)
     LstmSeq sq; const float* h_old;
@@ -297,7 +299,11 @@ __device__ __forceinline__ void bg_body(const BgArgs& a, bg_u4* lds, int blk, in
             const float hy = og * tanhf(cy);
             a.c[ix] = cy;
             a.h_new[ix] = hy;
-            if (a.hsum) a.hsum[ix] = hy + a.hres[ix];
+            if (a.hsum) {
+                const float hs = hy + a.hres[ix];
+                a.hsum[ix] = hs;
+                if (a.hid) a.hid[((size_t)it * a.hid_D + unit) * a.max_steps + a.step] = hs;
+            }
         } else if constexpr (EPI == BG_EPI_SEQ) {
             const int unit = 4 * tile + j, H = a.H;
             const LstmSeq& sq = a.sq;
@@ -506,7 +512,12 @@ __device__ __forceinline__ void attn_post_body(const AttnArgs& a, const float* _
             if (tt & 1) { c1[0] = fmaf(wv_, mv.x, c1[0]); c1[1] = fmaf(wv_, mv.y, c1[1]); }
             else { c0[0] = fmaf(wv_, mv.x, c0[0]); c0[1] = fmaf(wv_, mv.y, c0[1]); }
         }
-        *reinterpret_cast<float2*>(&a.ctx[(size_t)b * a.Dm + d]) = make_float2(c0[0] + c1[0], c0[1] + c1[1]);
+        const float2 cv = make_float2(c0[0] + c1[0], c0[1] + c1[1]);
+        *reinterpret_cast<float2*>(&a.ctx[(size_t)b * a.Dm + d]) = cv;
+        if (a.hid) {                                       // teacher-forced loop: the context rows of hidden_out
+            float* hp = a.hid + ((size_t)b * a.hid_D + a.hid_off + d) * a.max_steps + a.step;
+            hp[0] = cv.x; hp[a.max_steps] = cv.y;
+        }
     }
     for (int p = t; p < a.T; p += 256) {
         const float wgt = (p >= s && p < s + W) ? wts[p - s] : 0.f;
@@ -569,9 +580,11 @@ inline void bg_cell_shape(int nb_pad, bool att, int& mtw, int& nt, int& st, int&
     mtw = nb_pad <= 16 ? 1 : 2; nt = nb_pad <= 16 ? 1 : nb_pad <= 32 ? 2 : 4; st = nb_pad <= 16 ? 8 : nb_pad <= 32 ? 5 : 4; wvs = 4;
     if (att && nb_pad <= 16) mtw = 2;
 }
-inline int bg_launch_cell(const BgArgs& a, int nb_pad, const AttnArgs* attn, float* apre, int* astart, int batch, hipStream_t s) {
+// att_shape: take the attention RNN's launch shape (default: where the attention's part 1 rides along, which is that cell's launch)
+inline int bg_launch_cell(const BgArgs& a, int nb_pad, const AttnArgs* attn, float* apre, int* astart, int batch, hipStream_t s,
+                          int att_shape = -1) {
     int mtw, nt, st, wvs;
-    bg_cell_shape(nb_pad, attn != nullptr, mtw, nt, st, wvs);
+    bg_cell_shape(nb_pad, att_shape < 0 ? attn != nullptr : att_shape != 0, mtw, nt, st, wvs);
     const int ny = nb_pad <= 32 ? 1 : nb_pad / 64;
     int rc = CTTS_E_ARG;
     bool found = false;

@@ -343,6 +343,7 @@ struct AttnArgs {
     float *w, *cum, *ctx, *pos, *align_out;
     const int* lengths;
     int T, A, Ra, Dm, F, K, R, step, max_steps;
+    float* hid; int hid_D, hid_off;        // batched form, teacher-forced loop: ctx also goes to rows [hid_off, hid_off + Dm) of hidden_out
 };
 
 template <int FMAX>
@@ -807,19 +808,33 @@ __global__ __launch_bounds__(256) void hidden_state_kernel(const float* __restri
 //   4  decoder RNN FINAL: context columns + both sums          5  second decoder RNN FINAL: dec_h(step) columns + its sum
 //   6  projection row set         + next step's attention RNN EARLY on [ctx(step) | dec_h(step)]
 //   7  second prenet layer        + next step's attention RNN EARLY on att_h(step)
+// Teacher-forced loop (prenet_all != NULL; Decoder.forward, model.py:829-844 with p_teacher_forcing = 1): the prenet of every step
+// was computed before the loop (prenet_all [max_steps][NB][P], ctts_taco_prenet_frames_f32) and the projection runs once after it
+// over the recorded hidden_out (ctts_taco_project_frames_f32), so launches 6 and 7 are gone: five launches per step.  Launch 1
+// carries the attention's part 1 in both schedules; launches 3 and 5 also record [dec_h + d2_h | ctx] into hidden_out.  In the
+// pipelined schedule the EARLY sums that launches 6 / 7 hosted move: the attention RNN's [ctx | dec_h] columns are summed by its
+// own launch (FINAL over [prenet | ctx | dec_h]), its att_h columns ride in launch 2 of the step before (slot 0).  Above 16 rows
+// the next step's attention RNN is a role of launch 5 and its attention part 1 rides in launch 4: four launches per step (`merge`).
 int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uint8_t* keep_masks, float* mel_out, float* gate_out,
-                  float* align_out, float* hidden_out, int batch, int text_len, int step0, int n_steps, int max_steps, hipStream_t s) {
+                  float* align_out, float* hidden_out, int batch, int text_len, int step0, int n_steps, int max_steps, hipStream_t s,
+                  const float* prenet_all = nullptr) {
     const auto& c = p.c;
     const int NB = ws_rows(p, batch);
+    const bool forced = prenet_all != nullptr;
+    // above 16 rows the second decoder RNN of step t and the attention RNN of step t + 1 - independent of each other - are two roles of
+    // ONE launch (four launches per step): 53.5 against 58.4, 69.9 / 84.5, 130.9 / 134.0, 206.8 / 213.3 us per step at 32 / 64 / 128 / 256
+    // rows; at 16 rows, where the role has the attention RNN's narrower launch shape, 50.4 against 50.2 (profiles/r16_02)
+    const bool merge = forced && NB > 16;
     const int Pn = c.prenet_dim, Ra = c.attention_rnn_dim, Rd = c.decoder_rnn_dim, Rd2 = c.second_decoder_rnn_dim, Dm = c.memory_dim;
     const bool pipe = NB <= 64 && !tuning().taco_bg_no_pipe;
     const int nyb = NB / 16;
     int rc;
     // the three cells' GEMMs for a given step parity (cur = step & 1): X pieces and state, K range / partial mode set by the caller
-    auto att_args = [&](int cur) {
+    auto att_args = [&](int step) {
+        const int cur = step & 1;
         BgArgs a{};
         a.W = blob + p.bg_att.off; a.rows = p.bg_att.rows; a.batch = batch;
-        bg_set_x(a, p.bg_att, w.prenet, Pn, w.ctx, Dm, w.dec_h[cur], Rd, w.att_h[cur], Ra);
+        bg_set_x(a, p.bg_att, forced ? prenet_all + (size_t)step * NB * Pn : w.prenet, Pn, w.ctx, Dm, w.dec_h[cur], Rd, w.att_h[cur], Ra);
         a.bih = blob + p.att[2]; a.bhh = blob + p.att[3]; a.c = w.att_c; a.h_new = w.att_h[cur ^ 1]; a.H = Ra;
         a.part = w.part_att; a.nt_total = nyb;
         return a;
@@ -832,12 +847,14 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
         a.part = w.part_dec; a.nt_total = nyb;
         return a;
     };
-    auto d2_args = [&](int cur) {
+    auto d2_args = [&](int step) {
+        const int cur = step & 1;
         BgArgs a{};
         a.W = blob + p.bg_d2.off; a.rows = p.bg_d2.rows; a.batch = batch;
         bg_set_x(a, p.bg_d2, w.dec_h[cur ^ 1], Rd, w.d2_h[cur], Rd2, nullptr, 0, nullptr, 0);
         a.bih = blob + p.d2[2]; a.bhh = blob + p.d2[3]; a.c = w.d2_c; a.h_new = w.d2_h[cur ^ 1]; a.H = Rd2;
         a.hsum = w.hsum; a.hres = w.dec_h[cur ^ 1];
+        if (forced) { a.hid = hidden_out; a.hid_D = Rd2 + Dm; a.step = step; a.max_steps = max_steps; }
         a.part = w.part_d2; a.nt_total = nyb;
         return a;
     };
@@ -857,13 +874,18 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
         at.T = text_len; at.A = c.attention_dim; at.Ra = Ra; at.Dm = Dm;
         at.F = c.location_n_filters; at.K = c.location_kernel_size; at.R = c.window_range;
         at.step = step; at.max_steps = max_steps;
+        if (forced) { at.hid = hidden_out; at.hid_D = Rd2 + Dm; at.hid_off = Rd2; }
         return at;
     };
-    if (pipe && n_steps > 0) {      // what the previous call's last step did not leave: the EARLY sums of step0's attention RNN and
+    if (pipe && forced && n_steps > 0) {      // the att_h sum of step0's attention RNN, as launch 2 of the step before would leave it
+        BgRoles m{};
+        m.cell[0] = early(att_args(step0), aD, aK, 0); m.n_cell[0] = 1;
+        if ((rc = bg_launch_multi8(m, NB, s))) return rc;
+    } else if (pipe && n_steps > 0) {      // what the previous call's last step did not leave: the EARLY sums of step0's attention RNN and
         const AttnArgs at0 = attn_args(step0);                  // its attention part 1
         BgRoles m{};
-        m.cell[0] = early(att_args(step0 & 1), aP, aD, 0); m.n_cell[0] = 1;
-        m.cell[1] = early(att_args(step0 & 1), aD, aK, 1); m.n_cell[1] = 1;
+        m.cell[0] = early(att_args(step0), aP, aD, 0); m.n_cell[0] = 1;
+        m.cell[1] = early(att_args(step0), aD, aK, 1); m.n_cell[1] = 1;
         m.pre = &at0; m.apre = w.apre; m.astart = w.astart; m.n_pre = batch;
         if ((rc = bg_launch_multi8(m, NB, s))) return rc;
     }
@@ -873,7 +895,12 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
         const AttnArgs at = attn_args(step), at_next = attn_args(step + 1);
         // 1: attention RNN on [prenet | context | decoder hidden], recurrent on its own hidden state (model.py:707-717); in the plain
         // schedule the attention's part 1 rides along, in the pipelined one it ran in the previous step's launch 7
-        if ((rc = bg_launch_cell(pipe ? final_(att_args(cur), 0, aP, 2) : att_args(cur), NB, pipe ? nullptr : &at, w.apre, w.astart, batch, s))) return rc;
+        // (teacher-forced loop: only a call's first step launches it - see launch 5)
+        auto att_launch = [&](int st) { return pipe ? final_(att_args(st), 0, forced ? aD : aP, forced ? 1 : 2) : att_args(st); };
+        if (!(merge && step > step0) &&
+            (rc = bg_launch_cell(att_launch(step), NB, pipe && !forced ? nullptr : &at, w.apre, w.astart, batch, s))) return rc;
+        // teacher-forced loop: the NEXT step's attention part 1 rides in launch 4, its attention RNN is a role of launch 5
+        const AttnArgs* ride = merge && more ? &at_next : nullptr;
         BgArgs q{};     // 2: query rows (model.py:126)
         q.W = blob + p.bg_q.off; q.rows = p.bg_q.rows; q.batch = batch;
         bg_set_x(q, p.bg_q, w.att_h[nxt], Ra, nullptr, 0, nullptr, 0, nullptr, 0);
@@ -882,21 +909,27 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
             BgRoles m{};
             m.small = q; m.n_small = p.bg_q.tiles * nyb; m.small_epi = BG_EPI_LINEAR;
             m.cell[0] = early(dec_args(cur), 0, dA, 0); m.n_cell[0] = 1;
+            if (forced && more) { m.cell[1] = early(att_args(step + 1), aD, aK, 0); m.n_cell[1] = 1; }
             if ((rc = bg_launch_multi8(m, NB, s))) return rc;
             // 3: attention part 2 + the EARLY sums on last step's dec_h / d2_h
             if ((rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, batch, early(dec_args(cur), dC, dK, 1),
-                                            early(d2_args(cur), sD, sK, 0), NB, s))) return rc;
+                                            early(d2_args(step), sD, sK, 0), NB, s))) return rc;
             // 4, 5: decoder RNN on [attention hidden | context] (model.py:741-747), second decoder RNN on its output (:749-755)
-            if ((rc = bg_launch_cell(final_(dec_args(cur), dA, dC, 2), NB, nullptr, nullptr, nullptr, batch, s))) return rc;
-            if ((rc = bg_launch_cell(final_(d2_args(cur), 0, sD, 1), NB, nullptr, nullptr, nullptr, batch, s))) return rc;
+            if ((rc = bg_launch_cell(final_(dec_args(cur), dA, dC, 2), NB, ride, w.apre, w.astart, batch, s, 0))) return rc;
+            if (ride) rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, 0, final_(d2_args(step), 0, sD, 1), att_launch(step + 1), NB, s);
+            else rc = bg_launch_cell(final_(d2_args(step), 0, sD, 1), NB, nullptr, nullptr, nullptr, batch, s);
+            if (rc) return rc;
         } else {
             if ((rc = bg_launch_small<BG_EPI_LINEAR>(q, NB, s))) return rc;
             if ((rc = BG_ALLOW_LDS(attn_post_kernel, BGA_POST_LDS_BYTES))) return rc;
             hipLaunchKernelGGL(attn_post_kernel, dim3(batch), dim3(256), BGA_POST_LDS_BYTES, s, at, w.qbuf, w.apre, w.astart);
             CTTS_CHECK_LAUNCH("attn_post");
-            if ((rc = bg_launch_cell(dec_args(cur), NB, nullptr, nullptr, nullptr, batch, s))) return rc;
-            if ((rc = bg_launch_cell(d2_args(cur), NB, nullptr, nullptr, nullptr, batch, s))) return rc;
+            if ((rc = bg_launch_cell(dec_args(cur), NB, ride, w.apre, w.astart, batch, s, 0))) return rc;
+            if (ride) rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, 0, d2_args(step), att_launch(step + 1), NB, s);
+            else rc = bg_launch_cell(d2_args(step), NB, nullptr, nullptr, nullptr, batch, s);
+            if (rc) return rc;
         }
+        if (forced) continue;                              // no projection, no prenet: five launches
         const unsigned char* keep = step + 1 < max_steps ? keep_masks + (size_t)(step + 1) * 2 * batch * Pn : nullptr;
         BgArgs pr{}, w2{};
         // 6: projection row set on [dec_h + d2_h | ctx] (model.py:755-765) + first prenet layer of the next step (:187-190)
@@ -911,12 +944,12 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
         if (pipe) {
             BgRoles m{};
             m.small = pr; m.n_small = p.bg_proj.tiles * nyb; m.small_epi = BG_EPI_PROJ;
-            if (more) { m.cell[0] = early(att_args(nxt), aP, aD, 0); m.n_cell[0] = 1; }
+            if (more) { m.cell[0] = early(att_args(step + 1), aP, aD, 0); m.n_cell[0] = 1; }
             if ((rc = bg_launch_multi8(m, NB, s))) return rc;
             BgRoles m2{};
             if (keep) { m2.small = w2; m2.n_small = p.bg_w2.tiles * nyb; m2.small_epi = BG_EPI_PRENET2; }
             if (more) {
-                m2.cell[0] = early(att_args(nxt), aD, aK, 1); m2.n_cell[0] = 1;
+                m2.cell[0] = early(att_args(step + 1), aD, aK, 1); m2.n_cell[0] = 1;
                 m2.pre = &at_next; m2.apre = w.apre; m2.astart = w.astart; m2.n_pre = batch;     // (reads what launch 3 left: weights, position)
             }
             if ((rc = bg_launch_multi8(m2, NB, s))) return rc;
@@ -930,6 +963,144 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
         }
     }
     return CTTS_OK;
+}
+
+// ---- teacher-forced decoding: the prenet of every frame before the loop, the projection of every step after it ----------------
+// prenet_all[step][item][:] = relu(W2 . (relu(W1 . x) * keep1 * 2)) * keep2 * 2 (model.py:187-190), x = frame step - 1 of `frames`
+// [B][n_mel][T] (the layout of gt_mel), the go frame for step 0 (model.py:805-813: zeros, or init [B][n_mel]).  One workgroup =
+// one step x 16 items: both layers as v_mfma_f32_16x16x4_f32 products (A = 16 weight rows x 4 k from the transposed copies
+// [k][row], B = 4 k x 16 items from LDS; D: lane (j = lane / 16, item = lane % 16) holds rows 4 j .. 4 j + 3), the four waves take
+// the m-tiles round robin, the first layer's masked activations go through LDS.  Items [B, NB) are written as zeros.
+struct PrenetFramesArgs {
+    const float *W1T, *W2T, *frames, *init;
+    const unsigned char* keep;       // [T][2][B][P]
+    float* out;                      // [T][NB][P]
+    int n_mel, P, B, NB, T;
+};
+constexpr int PF_LD = 257;           // LDS row of one item: n_mel, P <= 256; odd, so the 16 items of a B operand hit 16 banks
+
+__device__ __forceinline__ bg_f4 pf_tile(const float* __restrict__ WT, int P, int K, int tile, const float* xs, int lane) {
+    bg_f4 acc = bg_f4{0.f, 0.f, 0.f, 0.f};
+    const float* wp = WT + (size_t)(lane >> 4) * P + 16 * tile + (lane & 15);
+    const float* xp = xs + (lane & 15) * PF_LD + (lane >> 4);
+    int k = 0;
+    for (; k + 16 <= K; k += 16) {                         // four products' operands requested together
+        float wv[4], xv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { wv[u] = wp[(size_t)(k + 4 * u) * P]; xv[u] = xp[k + 4 * u]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u], xv[u], acc, 0, 0, 0);
+    }
+    for (; k < K; k += 4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(size_t)k * P], xp[k], acc, 0, 0, 0);
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void prenet_frames_kernel(const PrenetFramesArgs a) {
+    __shared__ float xs[16 * PF_LD], a1[16 * PF_LD];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int n0 = blockIdx.x * 16, step = blockIdx.y;
+    for (int i = t; i < 16 * a.n_mel; i += 256) {
+        const int it = i / a.n_mel, k = i % a.n_mel, b = n0 + it;
+        float v = 0.f;
+        if (b < a.B) {
+            if (step > 0) v = a.frames[((size_t)b * a.n_mel + k) * a.T + step - 1];
+            else if (a.init) v = a.init[(size_t)b * a.n_mel + k];
+        }
+        xs[it * PF_LD + k] = v;
+    }
+    __syncthreads();
+    const int it = lane & 15, j = lane >> 4, b = n0 + it;
+    const unsigned char* keep = a.keep + ((size_t)step * 2 * a.B + min(b, a.B - 1)) * a.P;     // layer 0; layer 1 is B * P further
+    for (int tile = wave; tile < a.P / 16; tile += 4) {
+        const bg_f4 acc = pf_tile(a.W1T, a.P, a.n_mel, tile, xs, lane);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int r = 16 * tile + 4 * j + v;
+            a1[it * PF_LD + r] = (b < a.B && keep[r]) ? fmaxf(acc[v], 0.f) * 2.0f : 0.0f;
+        }
+    }
+    __syncthreads();
+    for (int tile = wave; tile < a.P / 16; tile += 4) {
+        const bg_f4 acc = pf_tile(a.W2T, a.P, a.P, tile, a1, lane);
+        float4 o;
+        float* ov = &o.x;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int r = 16 * tile + 4 * j + v;
+            ov[v] = (b < a.B && keep[(size_t)a.B * a.P + r]) ? fmaxf(acc[v], 0.f) * 2.0f : 0.0f;
+        }
+        *reinterpret_cast<float4*>(a.out + ((size_t)step * a.NB + b) * a.P + 16 * tile + 4 * j) = o;
+    }
+}
+
+// mel_out[b][r][t] / gate_out[b][t] = bias[r] + sum_k W[r][k] hidden[b][k][t] (model.py:763-765; W = the packed projection rows
+// [n_mel mel rows | gate row][D]) for every step at once.  One workgroup = one item x 32 steps x up to 6 m-tiles; its four waves
+// split K and are summed through LDS in a fixed order.  A lane (row, kq) reads the 16 bytes W[row][16 c + 4 kq ..] of a chunk and
+// uses element s in the chunk's MFMA s; the B operand of that MFMA is hidden[b][16 c + 4 kq + s][t] (16 consecutive steps per k).
+struct ProjFramesArgs {
+    const float *W, *bias, *hidden;
+    float *mel, *gate;
+    int rows, n_mel, D, T, ttiles;
+};
+constexpr int PJ_MT = 6, PJ_NT = 2;
+
+__global__ __launch_bounds__(256) void project_frames_kernel(const ProjFramesArgs a) {
+    __shared__ bg_f4 red[4 * PJ_MT * PJ_NT * 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int b = blockIdx.x / a.ttiles, t0 = (blockIdx.x % a.ttiles) * (16 * PJ_NT), tile0 = blockIdx.y * PJ_MT;
+    const int nch = a.D / 16, per = (nch + 3) / 4;
+    const int c0 = min(wave * per, nch), c1 = min(c0 + per, nch);
+    const int kq4 = 4 * (lane >> 4);
+    bg_f4 acc[PJ_MT][PJ_NT];
+#pragma unroll
+    for (int m = 0; m < PJ_MT; ++m)
+#pragma unroll
+        for (int nt = 0; nt < PJ_NT; ++nt) acc[m][nt] = bg_f4{0.f, 0.f, 0.f, 0.f};
+    const float* wrow[PJ_MT];
+#pragma unroll
+    for (int m = 0; m < PJ_MT; ++m) wrow[m] = a.W + (size_t)min(16 * (tile0 + m) + (lane & 15), a.rows - 1) * a.D + kq4;
+    const float* hcol[PJ_NT];
+#pragma unroll
+    for (int nt = 0; nt < PJ_NT; ++nt) hcol[nt] = a.hidden + ((size_t)b * a.D + kq4) * a.T + min(t0 + 16 * nt + (lane & 15), a.T - 1);
+    for (int c = c0; c < c1; ++c) {
+        float4 wv[PJ_MT];
+        float hv[PJ_NT][4];
+#pragma unroll
+        for (int m = 0; m < PJ_MT; ++m) wv[m] = *reinterpret_cast<const float4*>(wrow[m] + 16 * c);
+#pragma unroll
+        for (int nt = 0; nt < PJ_NT; ++nt)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) hv[nt][s] = hcol[nt][(size_t)(16 * c + s) * a.T];
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int m = 0; m < PJ_MT; ++m)
+#pragma unroll
+                for (int nt = 0; nt < PJ_NT; ++nt)
+                    acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32((&wv[m].x)[s], hv[nt][s], acc[m][nt], 0, 0, 0);
+    }
+#pragma unroll
+    for (int m = 0; m < PJ_MT; ++m)
+#pragma unroll
+        for (int nt = 0; nt < PJ_NT; ++nt) red[((wave * PJ_MT + m) * PJ_NT + nt) * 64 + lane] = acc[m][nt];
+    __syncthreads();
+    for (int idx = wave; idx < PJ_MT * PJ_NT; idx += 4) {
+        const int m = idx / PJ_NT, nt = idx % PJ_NT;
+        bg_f4 pw[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) pw[w] = red[((w * PJ_MT + m) * PJ_NT + nt) * 64 + lane];
+        const bg_f4 sum = (pw[0] + pw[1]) + (pw[2] + pw[3]);
+        const int tt = t0 + 16 * nt + (lane & 15);
+        if (tt >= a.T) continue;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int r = 16 * (tile0 + m) + 4 * (lane >> 4) + v;
+            if (r >= a.rows) continue;
+            const float val = sum[v] + a.bias[r];
+            if (r < a.n_mel) a.mel[((size_t)b * a.n_mel + r) * a.T + tt] = val;
+            else a.gate[(size_t)b * a.T + tt] = val;
+        }
+    }
 }
 
 // G[c][j][a] = sum_f Wd[f][a] * Wloc[f][c][j]: the location conv (model.py:56-60) folded into the location-dense layer (:61-62)
@@ -1211,6 +1382,70 @@ int ctts_taco_decoder_steps_hidden_f32(const ctts_taco_decoder_config* cfg, cons
             CTTS_CHECK_LAUNCH("hidden_state");
         }
     }
+    return CTTS_OK;
+}
+
+// ---- teacher-forced decoding (Decoder.forward, model.py:769-849) -------------------------------------------------------------
+size_t ctts_taco_prenet_frames_bytes(const ctts_taco_decoder_config* cfg, int32_t batch, int32_t n_frames) {
+    DecPlan p;
+    if (make_dec_plan(cfg, p)) return 0;
+    if (!bg_supported(p)) { set_error("prenet frames: this decoder shape has no batched form"); return 0; }
+    if (batch < 1 || batch > MAX_BATCH || n_frames < 1) { set_error("prenet frames: batch=%d (1..%d) n_frames=%d", batch, MAX_BATCH, n_frames); return 0; }
+    return (size_t)n_frames * ws_rows(p, batch) * p.c.prenet_dim * sizeof(float);
+}
+
+int ctts_taco_prenet_frames_f32(const ctts_taco_decoder_config* cfg, const void* packed, const float* frames,
+                                const float* init_frame, const uint8_t* keep_masks, float* prenet_all, size_t prenet_all_bytes,
+                                int32_t batch, int32_t n_frames, void* stream) {
+    DecPlan p;
+    int rc = make_dec_plan(cfg, p); if (rc) return rc;
+    CTTS_CHECK_ARG(packed && frames && keep_masks && prenet_all, "prenet frames: NULL pointer");
+    CTTS_CHECK_ARG(bg_supported(p), "prenet frames: this decoder shape has no batched form (ctts_taco_decoder_max_batch is %d)", MAX_NB);
+    CTTS_CHECK_ARG(batch >= 1 && batch <= MAX_BATCH && n_frames >= 1, "prenet frames: batch=%d (1..%d) n_frames=%d", batch, MAX_BATCH, n_frames);
+    const auto& c = p.c;
+    const int NB = ws_rows(p, batch);
+    const size_t need = (size_t)n_frames * NB * c.prenet_dim * sizeof(float);
+    CTTS_CHECK_ARG(prenet_all_bytes >= need, "prenet frames: prenet_all %zu bytes < required %zu", prenet_all_bytes, need);
+    CTTS_CHECK_ARG(n_frames <= 65535, "prenet frames: n_frames=%d (<= 65535 per call)", n_frames);
+    const float* blob = static_cast<const float*>(packed);
+    const PrenetFramesArgs a{blob + p.prenet_w1, blob + p.prenet_w2, frames, init_frame, keep_masks, prenet_all,
+                             c.n_mel_channels, c.prenet_dim, batch, NB, n_frames};
+    hipLaunchKernelGGL(prenet_frames_kernel, dim3(NB / 16, n_frames), dim3(256), 0, as_stream(stream), a);
+    CTTS_CHECK_LAUNCH("prenet_frames");
+    return CTTS_OK;
+}
+
+int ctts_taco_decoder_steps_forced_f32(const ctts_taco_decoder_config* cfg, const void* packed, const float* prenet_all,
+                                       float* align_out, float* hidden_out, int32_t batch, int32_t text_len, int32_t step0,
+                                       int32_t n_steps, int32_t max_steps, void* workspace, size_t workspace_bytes, void* stream) {
+    DecPlan p; DecWs w;
+    int rc = make_dec_plan(cfg, p); if (rc) return rc;
+    CTTS_CHECK_ARG(packed && prenet_all && align_out && hidden_out && workspace, "forced decoder steps: NULL pointer");
+    CTTS_CHECK_ARG(bg_supported(p), "forced decoder steps: this decoder shape has no batched form (ctts_taco_decoder_max_batch is %d)", MAX_NB);
+    CTTS_CHECK_ARG(batch >= 1 && batch <= MAX_BATCH && step0 >= 0 && n_steps >= 0 && step0 + n_steps <= max_steps,
+                   "forced decoder steps: batch=%d (1..%d) step0=%d n_steps=%d max_steps=%d", batch, MAX_BATCH, step0, n_steps, max_steps);
+    CTTS_CHECK_ARG(text_len >= 1, "forced decoder steps: text_len=%d", text_len);
+    dec_carve(p, batch, text_len, static_cast<float*>(workspace), w);
+    CTTS_CHECK_ARG(w.total * sizeof(float) <= workspace_bytes, "forced decoder steps: workspace %zu bytes < required %zu",
+                   workspace_bytes, w.total * sizeof(float));
+    return batched_steps(p, w, static_cast<const float*>(packed), nullptr, nullptr, nullptr, align_out, hidden_out, batch, text_len,
+                         step0, n_steps, max_steps, as_stream(stream), prenet_all);
+}
+
+int ctts_taco_project_frames_f32(const ctts_taco_decoder_config* cfg, const void* packed, const float* hidden, float* mel_out,
+                                 float* gate_out, int32_t batch, int32_t n_frames, void* stream) {
+    DecPlan p;
+    int rc = make_dec_plan(cfg, p); if (rc) return rc;
+    CTTS_CHECK_ARG(packed && hidden && mel_out && gate_out, "project frames: NULL pointer");
+    CTTS_CHECK_ARG(p.Dproj % 16 == 0, "project frames: second_decoder_rnn_dim + memory_dim = %d (a multiple of 16)", p.Dproj);
+    CTTS_CHECK_ARG(batch >= 1 && n_frames >= 1, "project frames: batch=%d n_frames=%d", batch, n_frames);
+    const auto& c = p.c;
+    const float* blob = static_cast<const float*>(packed);
+    const int ttiles = (n_frames + 16 * PJ_NT - 1) / (16 * PJ_NT), rows = c.n_mel_channels + 1;
+    CTTS_CHECK_ARG((long long)batch * ttiles <= 0x7fffffffLL, "project frames: batch=%d n_frames=%d exceed one grid", batch, n_frames);
+    const ProjFramesArgs a{blob + p.proj_w, blob + p.proj_b, hidden, mel_out, gate_out, rows, c.n_mel_channels, p.Dproj, n_frames, ttiles};
+    hipLaunchKernelGGL(project_frames_kernel, dim3(batch * ttiles, ((rows + 15) / 16 + PJ_MT - 1) / PJ_MT), dim3(256), 0, as_stream(stream), a);
+    CTTS_CHECK_LAUNCH("project_frames");
     return CTTS_OK;
 }
 

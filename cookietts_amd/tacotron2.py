@@ -1,7 +1,8 @@
 """Tacotron2-TM (text -> mel) with the decoder loop on the MI355X HIP path (BASELINE config 5).
 
 Host-side mirror of ``/root/reference/CookieTTS/_2_ttm/tacotron2_tm/model.py``: ``Tacotron2(hparams)``
-(:920-957), ``Tacotron2.inference`` (:1044-1080), ``Decoder.inference`` (:851-916), ``load_model`` (:22-33),
+(:920-957), ``Tacotron2.inference`` (:1044-1080), ``Decoder.inference`` (:851-916), the teacher-forced ``Tacotron2.forward``
+(:976-1028) / ``Decoder.forward`` (:769-849) in eval mode (what GTA.py runs), ``load_model`` (:22-33),
 with the reference's module tree so ``state_dict`` keys/shapes are identical and reference checkpoints
 (``checkpoint['state_dict']``, train.py:255-279) load unchanged.
 
@@ -185,6 +186,8 @@ class Decoder(_cache.PackedModule):
         # "disabled" (a probe found the 256 workgroups not co-resident; re-probed after PERSIST_REPROBE_AFTER calls)
         self._persist = "unprobed"
         self._persist_fallback_calls = 0
+        self.dump_attention_weights = False                  # model.py:402 (a debugging switch of forward(); refused there)
+        self.forced_chunk = _CHUNK or None                   # forward(): steps per library call (None: all of them in one)
 
     @property
     def persistent_state(self):
@@ -410,6 +413,102 @@ class Decoder(_cache.PackedModule):
         return (mel[:, :, :n_total].contiguous(), torch.sigmoid(gate[:, :n_total]), align[:, :n_total].contiguous(),
                 None if hidden is None else hidden[:, :, :n_total].contiguous())
 
+    def check_forced(self, n_frames, preserve_decoder, teacher_force_till, p_teacher_forcing):
+        """What ``forward`` refuses, before anything is launched (NotImplementedError names the option)."""
+        def refuse(what):
+            raise NotImplementedError(f"Tacotron2 teacher-forced forward on the HIP path does not build: {what}")
+        if self.training:
+            refuse("self.training (train() mode: GTA.py --use_training_mode, prenet_noise, zoneout); call .eval()")
+        if self.dump_attention_weights:
+            refuse("dump_attention_weights")
+        if preserve_decoder is not None and bool(torch.as_tensor(preserve_decoder).any()):
+            refuse("preserve_decoder / pres_prev_state with a True entry (decoder state carried over from the previous call)")
+        # model.py:830: step i is teacher-forced when ``teacher_force_till >= i or p_teacher_forcing >= torch.rand(1)``
+        if teacher_force_till is None:
+            raise TypeError("teacher_force_till is None (the reference compares it with the step index, model.py:830)")
+        if teacher_force_till < n_frames - 1:
+            if p_teacher_forcing is None:
+                raise TypeError("p_teacher_forcing is None (the reference compares it with torch.rand(1), model.py:830)")
+            if p_teacher_forcing < 1.0:
+                refuse(f"p_teacher_forcing={p_teacher_forcing} < 1.0 with teacher_force_till={teacher_force_till} < T - 1 "
+                       f"(stochastic mixing of predicted frames)")
+
+    @torch.no_grad()
+    def forward(self, memory, decoder_inputs, memory_lengths, preserve_decoder=None, decoder_input=None, teacher_force_till=0,
+                p_teacher_forcing=1.0, return_hidden_state=False, keep_masks=None):
+        """model.py:769-849 in eval mode under full teacher forcing (what GTA.py asks for: ``teacher_force_till=0,
+        p_teacher_forcing=1.0``).  memory [B, txt_T, memory_in_dim], decoder_inputs [B, n_mel, T] (gt_mel), memory_lengths [B],
+        decoder_input [B, n_mel, 1] = the step-0 frame (None: the zero go frame).
+        Returns (mel [B, n_mel, T], gate LOGITS [B, T], alignments [B, T, txt_T], hidden_att_contexts [B, Rd2 + Dm, T] or None,
+        memory [B, txt_T, memory_dim]: the bottlenecked memory, copied out of the head of the decoder workspace).
+        Three library stages: the prenet of every frame (``ctts_taco_prenet_frames_f32``), the loop without prenet and
+        projection (``ctts_taco_decoder_steps_forced_f32``, five launches per step, four above 16 rows), the projection of every step
+        (``ctts_taco_project_frames_f32``).  ``keep_masks`` [>=T, 2, B, prenet_dim] uint8 overrides the random prenet dropout
+        (mask t = step t's prenet input).  What the HIP path does not build raises NotImplementedError, by name."""
+        self.check_forced(decoder_inputs.shape[2], preserve_decoder, teacher_force_till, p_teacher_forcing)
+        B, n_mel, n_frames = decoder_inputs.shape
+        if n_mel != self.n_mel_channels or n_frames < 1:
+            raise ValueError(f"decoder_inputs {tuple(decoder_inputs.shape)}: expected [B, {self.n_mel_channels}, T >= 1]")
+        device = memory.device
+        blob = self._ensure_packed(device)
+        lib = _lib.lib()
+        cfg = self.c_config()
+        if tuple(memory.shape[::2]) != (B, self._memory_in_dim):
+            raise ValueError(f"memory {tuple(memory.shape)}: expected [{B}, txt_T, {self._memory_in_dim}]")
+        T = memory.shape[1]
+        P, D = self.prenet_dim, self.second_decoder_rnn_dim + self.memory_dim
+        mem = memory.detach().float().contiguous()
+        lens = memory_lengths.detach().to(device=device, dtype=torch.int32).contiguous()
+        frames = decoder_inputs.detach().to(device=device, dtype=torch.float32).contiguous()
+        init = None
+        if decoder_input is not None:
+            if tuple(decoder_input.shape) != (B, n_mel, 1):
+                raise ValueError(f"decoder_input {tuple(decoder_input.shape)}: expected [{B}, {n_mel}, 1]")
+            init = decoder_input.detach().to(device=device, dtype=torch.float32).reshape(B, n_mel).contiguous()
+        if keep_masks is None:
+            keep_masks = (torch.rand(n_frames, 2, B, P, device=device) < 0.5).to(torch.uint8)
+        else:
+            keep_masks = torch.as_tensor(keep_masks).to(device=device, dtype=torch.uint8).contiguous()
+            assert keep_masks.shape[0] >= n_frames and tuple(keep_masks.shape[1:]) == (2, B, P)
+            keep_masks = keep_masks[:n_frames].contiguous()
+        # batches above the library's limit run as groups (one workspace each), the way inference groups them
+        per_ws = int(lib.ctts_taco_decoder_max_batch(C.byref(cfg)))
+        groups = tuple((g0, min(g0 + per_ws, B)) for g0 in range(0, B, max(per_ws, 1)))
+        key = (device, B, T, groups)
+        wss = self.workspace(key, lambda: [_lib.nbytes(lib.ctts_taco_decoder_workspace_bytes, C.byref(cfg), g1 - g0, T,
+                                                       what="decoder workspace query failed") for g0, g1 in groups], zero=False)
+        mel = torch.empty(B, n_mel, n_frames, dtype=torch.float32, device=device)
+        gate = torch.empty(B, n_frames, dtype=torch.float32, device=device)
+        align = torch.zeros(B, n_frames, T, dtype=torch.float32, device=device)
+        hidden = torch.zeros(B, D, n_frames, dtype=torch.float32, device=device)
+        memory_out = torch.empty(B, T, self.memory_dim, dtype=torch.float32, device=device)
+        chunk = int(self.forced_chunk or n_frames)
+        with torch.cuda.device(device):
+            stream = _lib.stream(device)
+            for (g0, g1), ws in zip(groups, wss):
+                nb = g1 - g0
+                km = keep_masks if len(groups) == 1 else keep_masks[:, :, g0:g1].contiguous()
+                pre_bytes = _lib.nbytes(lib.ctts_taco_prenet_frames_bytes, C.byref(cfg), nb, n_frames,
+                                        what="teacher-forced decoding is not built for this decoder shape")
+                prenet_all = torch.empty(pre_bytes // 4, dtype=torch.float32, device=device)
+                _lib.check(lib.ctts_taco_prenet_frames_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(frames[g0:g1]),
+                                                          None if init is None else _lib.ptr(init[g0:g1]), _lib.ptr(km),
+                                                          _lib.ptr(prenet_all), pre_bytes, nb, n_frames, stream),
+                           "ctts_taco_prenet_frames_f32")
+                _lib.check(lib.ctts_taco_decoder_init_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(mem[g0:g1]), _lib.ptr(lens[g0:g1]),
+                                                         nb, T, _lib.ptr(ws), ws.numel() * 4, stream), "ctts_taco_decoder_init_f32")
+                # the bottlenecked memory (model.py:796-797, returned at :849) is the first array of the workspace, [rows][T][Dm]
+                memory_out[g0:g1] = ws[:nb * T * self.memory_dim].view(nb, T, self.memory_dim)
+                for s0 in range(0, n_frames, chunk):
+                    _lib.check(lib.ctts_taco_decoder_steps_forced_f32(
+                        C.byref(cfg), _lib.ptr(blob), _lib.ptr(prenet_all), _lib.ptr(align[g0:g1]), _lib.ptr(hidden[g0:g1]), nb, T,
+                        s0, min(chunk, n_frames - s0), n_frames, _lib.ptr(ws), ws.numel() * 4, stream),
+                        "ctts_taco_decoder_steps_forced_f32")
+                _lib.check(lib.ctts_taco_project_frames_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(hidden[g0:g1]), _lib.ptr(mel[g0:g1]),
+                                                           _lib.ptr(gate[g0:g1]), nb, n_frames, stream),
+                           "ctts_taco_project_frames_f32")
+        return mel, gate, align, hidden if return_hidden_state else None, memory_out
+
 
 MAX_GROUP = 4      # utterances per persistent-decoder / packed-LSTM workspace (ctts_taco_decoder_steps_persistent_f32, ctts_lstm_seq_*: batch <= 4)
 # batches from this size on decode in ONE workspace on the batched MFMA form (ctts_taco_decoder_max_batch rows at most); below it,
@@ -629,6 +728,9 @@ class Tacotron2(nn.Module):
         self.fp16_run = hp.fp16_run
         self.n_mel_channels = hp.n_mel_channels
         self.n_frames_per_step = hp.n_frames_per_step
+        self.p_teacher_forcing = getattr(hp, 'p_teacher_forcing', 1.0)      # model.py:926-927, 936: forward()'s defaults
+        self.teacher_force_till = getattr(hp, 'teacher_force_till', 0)
+        self.drop_frame_rate = getattr(hp, 'drop_frame_rate', 0.0)
         self.embedding = nn.Embedding(hp.n_symbols, hp.symbols_embedding_dim)
         val = np.sqrt(3.0) * np.sqrt(2.0 / (hp.n_symbols + hp.symbols_embedding_dim))
         self.embedding.weight.data.uniform_(-val, val)
@@ -650,6 +752,19 @@ class Tacotron2(nn.Module):
         """model.py:1044-1080.  Returns the reference's dict (pred_mel_postnet, pred_gate, alignments, pred_sylps)."""
         if self.training:
             raise RuntimeError("call .eval() first: inference uses eval-mode batch norm / no dropout but the prenet's")
+        memory, pred_sylps, enc_dim = self._assemble_memory(text_seq, text_lengths, speaker_id, torchmoji_hdn, gt_sylps)
+        pred_mel, pred_gate, alignments, hidden = self.decoder.inference(memory, memory_lengths=text_lengths, keep_masks=keep_masks,
+                                                                         fixed_steps=fixed_steps, return_hidden_state=return_hidden_state)
+        pred_mel_postnet = self.postnet(pred_mel) if hasattr(self, 'postnet') else pred_mel
+        out = {"pred_mel_postnet": pred_mel_postnet, "pred_gate": pred_gate, "alignments": alignments,
+               "pred_sylps": pred_sylps, "pred_mel": pred_mel, "encoder_outputs": memory[:, :, :enc_dim]}
+        if return_hidden_state:      # (the reference computes them and drops them from its dict, model.py:1069-1079; kept here)
+            out["hidden_att_contexts"] = hidden
+        return out
+
+    def _assemble_memory(self, text_seq, text_lengths, speaker_id, torchmoji_hdn, gt_sylps):
+        """model.py:989-1009 / 1046-1068: encoder, speaker embedding, SylpsNet (eval: sylzu = mu), torchMoji -> the decoder's
+        memory [B, txt_T, memory_in_dim].  Returns (memory, pred_sylps [B, 1], encoder width)."""
         device = text_seq.device
         if device.type != 'cuda':
             raise _lib.HipLibraryError("Tacotron2 HIP path needs GPU tensors (no CPU fallback)")
@@ -690,14 +805,50 @@ class Tacotron2(nn.Module):
                                                      _lib.ptr(memory), _lib.ptr(pred_sylps), B, txt_T, enc_dim,
                                                      self.speaker_embedding_dim, sn[0].linear_layer.out_features, tmh.shape[1],
                                                      self.tm_linear.out_features, _lib.stream(device)), "ctts_taco_memory_sylps_f32")
-        pred_mel, pred_gate, alignments, hidden = self.decoder.inference(memory, memory_lengths=text_lengths, keep_masks=keep_masks,
-                                                                         fixed_steps=fixed_steps, return_hidden_state=return_hidden_state)
-        pred_mel_postnet = self.postnet(pred_mel) if hasattr(self, 'postnet') else pred_mel
-        out = {"pred_mel_postnet": pred_mel_postnet, "pred_gate": pred_gate, "alignments": alignments,
-               "pred_sylps": pred_sylps, "pred_mel": pred_mel, "encoder_outputs": memory[:, :, :enc_dim]}
-        if return_hidden_state:      # (the reference computes them and drops them from its dict, model.py:1069-1079; kept here)
-            out["hidden_att_contexts"] = hidden
-        return out
+        return memory, pred_sylps, enc_dim
+
+    @staticmethod
+    def resolve_teacher_forcing(own_p_teacher_forcing, own_teacher_force_till, teacher_force_till, p_teacher_forcing):
+        """model.py:980-981 as written, quirk included: the SECOND line tests the value the first one just assigned, so
+        ``teacher_force_till=None`` stays None whenever the model's own p_teacher_forcing is set.
+        Returns (p_teacher_forcing, teacher_force_till)."""
+        p_teacher_forcing = own_p_teacher_forcing if teacher_force_till is None else p_teacher_forcing
+        teacher_force_till = own_teacher_force_till if p_teacher_forcing is None else teacher_force_till
+        return p_teacher_forcing, teacher_force_till
+
+    @torch.no_grad()
+    def forward(self, gt_mel, mel_lengths, text, text_lengths, speaker_id, gt_sylps, torchmoji_hdn, pres_prev_state=None,
+                cont_next_iter=None, init_mel=None, teacher_force_till=None, p_teacher_forcing=None, drop_frame_rate=None,
+                return_hidden_state=False, keep_masks=None):
+        """model.py:976-1028 in eval mode, no gradients: the teacher-forced pass GTA.py runs over a dataset
+        (_2_ttm/tacotron2_tm/GTA.py:117, _3_generate_postnets/GTA.py:192).  Returns the reference's nine-key dict; nothing
+        is masked beyond ``mel_lengths`` and every row runs ``gt_mel.shape[2]`` steps, as in the reference.
+        ``drop_frame_rate`` only acts in train() mode (model.py:984), which is refused; ``cont_next_iter`` is unused there too."""
+        if self.training:
+            raise NotImplementedError("Tacotron2 teacher-forced forward on the HIP path does not build: self.training (train() mode: "
+                                      "GTA.py --use_training_mode, drop_frame_rate, prenet_noise, sampled sylzu); call .eval()")
+        if pres_prev_state is not None and bool(torch.as_tensor(pres_prev_state).any()):
+            raise NotImplementedError("Tacotron2 teacher-forced forward on the HIP path does not build: pres_prev_state with a True "
+                                      "entry (decoder state carried over from the previous call)")
+        p_teacher_forcing, teacher_force_till = self.resolve_teacher_forcing(self.p_teacher_forcing, self.teacher_force_till,
+                                                                             teacher_force_till, p_teacher_forcing)
+        self.decoder.check_forced(gt_mel.shape[2], pres_prev_state, teacher_force_till, p_teacher_forcing)
+        if gt_sylps is None:
+            raise ValueError("forward needs gt_sylps [B] (model.py:999)")
+        memory, pred_sylps, enc_dim = self._assemble_memory(text, text_lengths, speaker_id, torchmoji_hdn, gt_sylps)
+        # SylpsNet.forward (SylpsNet.py:33-42) on gt_sylps: mu and logvar; the memory's column is mu (eval-mode reparameterize),
+        # which _assemble_memory computed on the device.  These two [B] outputs are a 2-column affine map of B numbers.
+        syl = torch.as_tensor(gt_sylps).detach().to(device=memory.device, dtype=torch.float32).reshape(-1)
+        syl_cat = torch.stack((syl, syl.log()), dim=1)
+        syl_params = syl_cat + self.sylps_net.res_weight * self.sylps_net.seq_layers(syl_cat.clone())
+        pred_mel, pred_gate_logits, alignments, hidden, _ = self.decoder(
+            memory, gt_mel, memory_lengths=text_lengths, preserve_decoder=pres_prev_state, decoder_input=init_mel,
+            teacher_force_till=teacher_force_till, p_teacher_forcing=p_teacher_forcing, return_hidden_state=return_hidden_state,
+            keep_masks=keep_masks)
+        pred_mel_postnet = self.postnet(pred_mel) if hasattr(self, 'postnet') else None
+        return {"pred_mel": pred_mel, "pred_mel_postnet": pred_mel_postnet, "pred_gate_logits": pred_gate_logits,
+                "pred_sylps": pred_sylps, "pred_sylps_mu": syl_params[:, 0], "pred_sylps_logvar": syl_params[:, 1],
+                "alignments": alignments, "hidden_att_contexts": hidden, "encoder_outputs": memory[:, :, :enc_dim]}
 
 
 def load_model(hparams):

@@ -651,6 +651,40 @@ int ctts_taco_decoder_steps_hidden_f32(const ctts_taco_decoder_config* cfg, cons
                                        int32_t step0, int32_t n_steps, int32_t max_steps, void* workspace,
                                        void* stream);
 
+/* ---- Teacher-forced decoding: Decoder.forward (model.py:769-849) with p_teacher_forcing = 1, what GTA.py runs in eval() mode
+ * (_2_ttm/tacotron2_tm/GTA.py:77-117, 264; _3_generate_postnets/GTA.py:192).  Three stages around the workspace, state layout,
+ * ctts_taco_decoder_init_f32 prologue and align_out of the free-running steps above.  Built where
+ * ctts_taco_decoder_max_batch(cfg) is 256 (the batched form); other shapes are refused with CTTS_E_ARG. */
+
+/* Bytes of prenet_all for `batch` items and n_frames steps: [n_frames][NB][prenet_dim] floats, NB = the padded row count of the
+ * workspace (16, 32, then multiples of 64).  0 (and a message) for a shape or batch the batched form does not take. */
+size_t ctts_taco_prenet_frames_bytes(const ctts_taco_decoder_config* cfg, int32_t batch, int32_t n_frames);
+/* The prenet of EVERY step before the loop (model.py:823 on the frames of :803-813; Prenet.forward :187-190):
+ *   prenet_all[t][b][:] = relu(W2 . (relu(W1 . x_t) * keep[t][0][b] * 2)) * keep[t][1][b] * 2,
+ *   x_t = frames[b][:][t - 1] for t >= 1 (frames [B][n_mel][n_frames]: the layout of gt_mel), x_0 = the go frame: init_frame
+ *   [B][n_mel], or zeros where it is NULL (model.py:805-810)
+ *   keep_masks [n_frames][2][B][P] uint8 as in ctts_taco_decoder_steps_f32: index t is the mask of step t's prenet input.
+ * Rows [B, NB) of every step are written as zeros.  One launch, both layers on v_mfma_f32_16x16x4_f32. */
+int ctts_taco_prenet_frames_f32(const ctts_taco_decoder_config* cfg, const void* packed, const float* frames,
+                                const float* init_frame, const uint8_t* keep_masks, float* prenet_all,
+                                size_t prenet_all_bytes, int32_t batch, int32_t n_frames, void* stream);
+/* Steps [step0, step0 + n_steps) of Decoder.forward's loop (model.py:829-844) under full teacher forcing: step t's prenet input
+ * is prenet_all[t] (max_steps steps of the layout above), nothing is projected inside the loop.  Five stream-ordered launches
+ * per step: attention RNN (+ the attention's part 1) -> query rows -> attention part 2 -> decoder RNN -> second decoder RNN;
+ * above 16 rows four: the second decoder RNN and the NEXT step's attention RNN are two roles of one launch.
+ *   align_out  [B][max_steps][text_len]
+ *   hidden_out [B][second_decoder_rnn_dim + memory_dim][max_steps] = [dec_h + d2_h | attention context] per step (required:
+ *              it is the input of ctts_taco_project_frames_f32 and Decoder.forward's hidden_att_contexts, model.py:761, 843-844)
+ * Blocks of steps can be chained like the free-running entry points'. */
+int ctts_taco_decoder_steps_forced_f32(const ctts_taco_decoder_config* cfg, const void* packed, const float* prenet_all,
+                                       float* align_out, float* hidden_out, int32_t batch, int32_t text_len,
+                                       int32_t step0, int32_t n_steps, int32_t max_steps, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+/* The gate and mel projections of every step after the loop (model.py:763-765), one launch over all B x n_frames columns:
+ *   hidden [B][second_decoder_rnn_dim + memory_dim][n_frames] -> mel_out [B][n_mel][n_frames], gate_out [B][n_frames] (logits). */
+int ctts_taco_project_frames_f32(const ctts_taco_decoder_config* cfg, const void* packed, const float* hidden,
+                                 float* mel_out, float* gate_out, int32_t batch, int32_t n_frames, void* stream);
+
 /* Persistent form of ctts_taco_decoder_steps_f32: ONE launch of 256 resident workgroups (256 threads each, one wave per
  * SIMD) runs all n_steps steps with EVERY LSTM weight resident on the compute units for the whole launch (registers + LDS;
  * the 108 MB of weights are read once, at entry: ask for blocks of >= 32 steps), products on v_mfma_f32_4x4x1, and vectors

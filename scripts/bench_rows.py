@@ -548,6 +548,106 @@ def row_tacotron(args, vocoder=None):
             "text_to_wave_rtf_f16_vocoder": None if dv16 is None else samples / (dt + dv16) / 22050.0}
 
 
+def row_taco_forced(args):
+    """Teacher-forced ``Tacotron2.forward`` (the GTA pass) against the free-running ``inference(fixed_steps=400)`` of the same build:
+    200 symbols, 400 steps, 16 / 64 / 256 rows, the same prenet masks in both arms.  Per row count two pairs of arms, each pair
+    alternated ``--reps`` times in one process after a warm-up of each and timed by device events:
+      loop   the decoder loop alone, through the library: ``ctts_taco_decoder_steps_forced_f32`` (five launches per step at 16 rows,
+             four above, on a prenet_all computed before) against ``ctts_taco_decoder_steps_f32`` (seven), both on an initialised
+             workspace
+      call   the whole call: ``forward`` (encoder + prenet-frames + loop + projection + postnet) against ``inference``
+    The free-running arms are code this row's commit did not touch: they are the yardstick.  ``clears_10x_spread``: the per-step
+    difference of the loop arms is more than ten times the larger of their spreads (max - min over the repetitions).
+    ``--arms forced`` (or ``free``) runs one arm alone, for a profiler pass."""
+    import ctypes as C
+    from cookietts_amd import _lib
+    from cookietts_amd.tacotron2 import Tacotron2
+    hp = synthetic.tacotron_hparams()
+    m = Tacotron2(hp)
+    m.load_state_dict(synthetic.to_torch(synthetic.tacotron_state_dict(hp, seed=1234)))
+    m = m.cuda().eval()
+    dec, lib = m.decoder, _lib.lib()
+    TXT, T = 200, 400
+    reps = getattr(args, "reps", 5)
+    arms_on = [a for a in getattr(args, "arms", "").split(",") if a in ("forced", "free")] or ["forced", "free"]
+    rng = np.random.default_rng(1234)
+    rows = []
+    for B in _batches(args, (16, 64, 256)):
+        text = torch.from_numpy(rng.integers(1, hp.n_symbols, size=(B, TXT))).cuda()
+        lens = torch.full((B,), TXT, dtype=torch.int64).cuda()
+        spk = (torch.arange(B) % hp.n_speakers).cuda()
+        tm = torch.from_numpy(rng.standard_normal((B, hp.torchMoji_attDim)).astype(np.float32)).cuda()
+        syl = torch.from_numpy(rng.uniform(2.5, 6.5, B).astype(np.float32)).cuda()
+        gt = torch.from_numpy(synthetic.synthetic_mel(B, T, hp.n_mel_channels)).cuda()
+        masks = torch.from_numpy(synthetic.prenet_dropout_masks(T, B, hp.prenet_dim)).cuda()
+        # ---- the loop alone
+        dev = text.device
+        blob, cfg, st = dec._ensure_packed(dev), dec.c_config(), _lib.stream(dev)
+        mem = torch.from_numpy((rng.standard_normal((B, TXT, dec._memory_in_dim)) * 0.5).astype(np.float32)).cuda()
+        lens32 = lens.to(torch.int32)
+        ws = torch.empty(lib.ctts_taco_decoder_workspace_bytes(C.byref(cfg), B, TXT) // 4, dtype=torch.float32, device=dev)
+        pre_bytes = lib.ctts_taco_prenet_frames_bytes(C.byref(cfg), B, T)
+        prenet_all = torch.empty(pre_bytes // 4, dtype=torch.float32, device=dev)
+        mel = torch.empty(B, hp.n_mel_channels, T, device=dev)
+        gate, align = torch.empty(B, T, device=dev), torch.empty(B, T, TXT, device=dev)
+        hidden = torch.empty(B, hp.second_decoder_rnn_dim + hp.memory_bottleneck_dim, T, device=dev)
+        _lib.check(lib.ctts_taco_prenet_frames_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(gt), None, _lib.ptr(masks), _lib.ptr(prenet_all),
+                                                  pre_bytes, B, T, st), "ctts_taco_prenet_frames_f32")
+
+        def init():
+            _lib.check(lib.ctts_taco_decoder_init_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(mem), _lib.ptr(lens32), B, TXT, _lib.ptr(ws),
+                                                     ws.numel() * 4, st), "ctts_taco_decoder_init_f32")
+
+        def loop_forced():
+            _lib.check(lib.ctts_taco_decoder_steps_forced_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(prenet_all), _lib.ptr(align),
+                                                              _lib.ptr(hidden), B, TXT, 0, T, T, _lib.ptr(ws), ws.numel() * 4, st),
+                       "ctts_taco_decoder_steps_forced_f32")
+
+        def loop_free():
+            _lib.check(lib.ctts_taco_decoder_steps_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(masks), _lib.ptr(mel), _lib.ptr(gate),
+                                                       _lib.ptr(align), B, TXT, 0, T, T, _lib.ptr(ws), st), "ctts_taco_decoder_steps_f32")
+
+        def one(fn):                                       # ms of fn() alone: the workspace is initialised outside the events
+            init()
+            return _event_ms(fn, 1)
+        pairs = {"loop": (("forced", lambda: one(loop_forced)), ("free", lambda: one(loop_free))),
+                 "call": (("forced", lambda: _event_ms(lambda: m(gt, lens, text, lens, spk, syl, tm, teacher_force_till=0,
+                                                                  p_teacher_forcing=1.0, keep_masks=masks), 1)),
+                          ("free", lambda: _event_ms(lambda: m.inference(text, lens, spk, tm, gt_sylps=syl, keep_masks=masks,
+                                                                         fixed_steps=T), 1)))}
+        row = {"row": "C/taco_forced", "metric": "teacher-forced Tacotron2.forward vs free-running inference(fixed_steps), 200 symbols, "
+                                                 "400 steps (device events, arms alternated)", "batch": B, "steps": T, "dtype": "f32",
+               "launches_per_step": {"forced": 5 if B <= 16 else 4, "free": 7}, "schedule": "pipelined" if B <= 64 else "plain"}
+        for pname, arms in pairs.items():
+            arms = [a for a in arms if a[0] in arms_on]
+            times = {n: [] for n, _ in arms}
+            for n, fn in arms:
+                for _ in range(max(1, args.warmup)):
+                    fn()
+            for _ in range(reps):
+                for n, fn in arms:
+                    times[n].append(fn())
+            stat = {}
+            for n, t in times.items():
+                med = sorted(t)[len(t) // 2]
+                stat[n] = {"reps_ms": t, "median_ms": med, "min_ms": min(t), "max_ms": max(t), "spread_ms": max(t) - min(t),
+                           "spread_frac": (max(t) - min(t)) / med}
+                if pname == "loop":
+                    stat[n]["us_per_step"] = med / T * 1e3
+            row[pname] = stat
+            if len(stat) == 2:
+                diff = stat["free"]["median_ms"] - stat["forced"]["median_ms"]
+                spread = max(stat["free"]["spread_ms"], stat["forced"]["spread_ms"])
+                row[pname] = dict(stat, free_minus_forced_ms=diff, free_over_forced=stat["free"]["median_ms"] / stat["forced"]["median_ms"],
+                                  max_spread_ms=spread, clears_10x_spread=bool(diff > 10 * spread))
+        row.update({"value": row["loop"][arms_on[0]]["us_per_step"], "unit": "us/step", "higher_is_better": False})
+        rows.append(row)
+        del ws, prenet_all, hidden, align, mem, gt, masks
+        dec._ws, dec._xchg = {}, {}
+        torch.cuda.empty_cache()
+    return rows
+
+
 def row_stft(args):
     from cookietts_amd import TacotronSTFT
     taco = TacotronSTFT().cuda()
@@ -594,15 +694,15 @@ if __name__ == "__main__":
                     help="main loop of the rows' fp32 conv-GEMMs, set on each model (model.set_f32_gemm_mode)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16"],
                     help="waveglow_ax: f16 = IEEE-half storage of the WN stacks (model.set_compute_dtype(torch.float16))")
-    ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab: repetitions of every arm (alternated)")
-    ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts) to these batch sizes (PMC passes)")
+    ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab, waveglow_ax_sep_ab, taco_forced: repetitions of every arm (alternated)")
+    ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts, taco_forced) to these batch sizes (PMC passes)")
     ap.add_argument("--arms", default="hip,torch,hip_f16,torch_f16,hip_bf16x3",
-                    help="hifigan: arms to run (hip, hip_f16 or hip_bf16x3 alone for a profiler pass); waveglow_ax_sep_ab: sep, fold")
+                    help="hifigan: arms to run (hip, hip_f16 or hip_bf16x3 alone for a profiler pass); waveglow_ax_sep_ab: sep, fold; taco_forced: forced, free")
     ap.add_argument("--ks", default="3,7", help="waveglow_ax_sep_ab: comma list of depthwise kernel sizes")
     args = ap.parse_args()
     fns = {"hifigan": row_hifigan, "waveflow": row_waveflow, "waveflow_table": row_waveflow_table, "waveflow_author": row_waveflow_author, "tacotron": row_tacotron, "stft": row_stft,
            "waveglow_ax": row_waveglow_ax_notebook, "waveglow_ax_ab": row_waveglow_ax_notebook_ab, "waveglow_ax_untts": row_waveglow_ax_untts,
-           "waveglow_ax_sep_ab": row_waveglow_ax_sep_ab}
+           "waveglow_ax_sep_ab": row_waveglow_ax_sep_ab, "taco_forced": row_taco_forced}
     for r in args.rows.split(","):
         out = fns[r](args)
         for line in (out if isinstance(out, list) else [out]):
