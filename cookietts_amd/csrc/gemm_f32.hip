@@ -838,6 +838,8 @@ void load_tuning_locked() {
     g_tune.f32_no_winograd = on("CTTS_F32_NO_WINOGRAD");
     g_tune.f32_winograd_min = num("CTTS_F32_WINOGRAD_MIN", -1);
     g_tune.f32_winograd_plain = on("CTTS_F32_WINOGRAD_PLAIN");
+    g_tune.f32_winograd_fused_min = num("CTTS_F32_WINOGRAD_FUSED_MIN", -1);
+    g_tune.f32_winograd_no_fused = on("CTTS_F32_WINOGRAD_NO_FUSED");
     g_tune_loaded = true;
 }
 }  // namespace

@@ -32,6 +32,8 @@ struct Tuning {
     bool f32_no_winograd;  // CTTS_F32_NO_WINOGRAD: WaveGlow fp32 WN stack with the direct 3-tap in-layer GEMM at every size (no Winograd F(2,3) form)
     int f32_winograd_min;  // CTTS_F32_WINOGRAD_MIN: take the Winograd form for utterances of at least this many columns (steps per batch item); 0 = always (default in waveglow_api.hip)
     bool f32_winograd_plain;  // CTTS_F32_WINOGRAD_PLAIN: the Winograd form as five launches per layer (cond rows copied into pair order for every layer, T2 / T3 and even / odd as separate launches, d = 2 transform one column at a time): the A/B arm and the tests' reference of the merged form, bit-identical
+    int f32_winograd_fused_min;  // CTTS_F32_WINOGRAD_FUSED_MIN: take the one-launch Winograd layer (wn_winograd_layer.hip) for utterances of at least this many columns; 0 = always (default in waveglow_api.hip).  Below it the Winograd form, where it engages, runs as the paired launches
+    bool f32_winograd_no_fused;  // CTTS_F32_WINOGRAD_NO_FUSED: never the one-launch Winograd layer: T2 | T3 and even | odd as two launches of the conv-GEMM with the T planes in HBM (the A/B arm)
     bool wf_no_region_split; // CTTS_WF_NO_REGION_SPLIT: the fused WaveFlow layer as ONE launch per layer (no A | M | B regions on three streams)
     bool wf_no_row_queue;  // CTTS_WF_NO_ROW_QUEUE: never the one-launch-per-row work queue of the fused WaveFlow layers
     int wf_row_queue_min;  // CTTS_WF_ROW_QUEUE_MIN: take the row queue from this many 128-column items per layer on (A/B; default in waveflow_api.hip)

@@ -7,6 +7,7 @@
 #include "gemm_f32.h"
 #include "tuning.h"
 #include "waveglow_kernels.h"
+#include "wn_winograd_layer.h"
 
 namespace ctts {
 
@@ -187,6 +188,19 @@ bool winograd_engages(const Plan& p, const Geom& g) {
     return (long long)g.L >= min_cols;
 }
 
+// The one-launch Winograd layer (wn_winograd_layer.hip: T2 / T3 stay in registers) where the Winograd form engages, for utterances of
+// at least WINOGRAD_FUSED_MIN_COLS columns - the length its A/B was run at (900 frames, profiles/r17_01_winograd_fused_ab.txt); the
+// test is on the utterance alone, like the form's own.  Shorter ones keep the paired launches.  CTTS_F32_WINOGRAD_FUSED_MIN: another
+// threshold (0 = always); CTTS_F32_WINOGRAD_NO_FUSED or CTTS_F32_WINOGRAD_PLAIN: never.  Not bit-equal to the paired launches:
+// ((S2 +- S3) + products) + b against ((products + b) + T2) +- T3.
+constexpr long long WINOGRAD_FUSED_MIN_COLS = 28800;
+bool winograd_fused_engages(const Plan& p, const Geom& g) {
+    const Tuning t = tuning();
+    if (t.f32_winograd_no_fused || t.f32_winograd_plain || t.f32_no_glds || !wn_winograd_layer_supported(p.C, p.H)) return false;
+    const long long min_cols = t.f32_winograd_fused_min >= 0 ? t.f32_winograd_fused_min : WINOGRAD_FUSED_MIN_COLS;
+    return winograd_engages(p, g) && (long long)g.L >= min_cols;
+}
+
 struct Workspace {
     float *audio, *spect, *spk, *h_tmp, *h_all, *x, *act, *out;
     float* act_all;     // deferred-skip form: the gated activations of every layer of a flow ([n_layers] x act)
@@ -329,6 +343,8 @@ struct WnWinograd { float* V; float* T; float* Hc; int ldp; };
 // then writes V only.  d = 2 (and d = 1, layer 0 without the start fold) read the copies h2e / h2o the transform makes.
 // CTTS_F32_WINOGRAD_PLAIN (or the register-staged kernels): cond copies for every layer, four launches, d = 2 transform one column
 // at a time.  Same bits either way: the same products summed in the same order.
+// Long utterances (winograd_fused_engages): the transform, then ONE launch of wn_winograd_layer.hip that keeps T2 / T3 in registers -
+// the same products, ((S2 +- S3) + products) + b: not the same bits.  The T planes stay in the workspace for the knob arm.
 int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k, int i, const float* x, const float* h_all,
                           float* act, const WnWinograd& wg, int batch, hipStream_t s) {
     const auto& f = p.fl[k];
@@ -338,10 +354,26 @@ int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k
     const size_t vplane = (size_t)batch * C * ldp, tplane = (size_t)batch * 2 * C * ldp, hplane = (size_t)batch * H * ldp;
     const bool lean = !tuning().f32_winograd_plain && gemm_f32_dma_staged(p.nch_rs + p.nch1h);
     const bool in_place = lean && pg.d % 4 == 0;
+    const bool fused = lean && winograd_fused_engages(p, g);
     const float* h2 = h_all + (size_t)k * H * g.ld;
     int rc = launch_winograd_transform(x, (long long)C * g.ld, h2, hstride, wg.V, wg.Hc, batch, C, H, pg.d, g.L, pg.Lp, g.ld, g.pad,
                                        ldp, pg.ntiles * GEMM_BN, !in_place, lean, s);
     if (rc) return rc;
+    if (fused) {
+        // ONE launch behind the transform: the four products of a pair block through one chunk stream, T2 / T3 in registers
+        WnWinogradLayerArgs w{};
+        w.A_T2 = blob + f.wg_T2_A[i]; w.A_T3 = blob + f.wg_T3_A[i]; w.A_e = blob + f.wg_e_A[i]; w.A_o = blob + f.wg_o_A[i];
+        w.bias = blob + f.in_b[i];
+        w.V = wg.V; w.vplane = (long long)vplane;
+        w.Hc = wg.Hc; w.hplane = (long long)hplane;
+        w.h2 = h2; w.h_bstride = hstride;
+        w.act = act; w.act_bstride = (long long)C * g.ld;
+        w.C = C; w.H = H; w.batch = batch;
+        w.ldp = ldp; w.Lp = pg.Lp; w.ntiles = pg.ntiles;
+        w.d = pg.d; w.L = g.L; w.ld = g.ld; w.pad = g.pad;
+        w.in_place = in_place;
+        return launch_wn_winograd_layer(w, s);
+    }
     GemmArgs a{};
     a.gemm_mode = p.c.f32_gemm_mode;
     a.ld = ldp; a.pad = 0; a.L = pg.Lp; a.ntiles = pg.ntiles; a.batch = batch; a.MB = p.mb_in;
@@ -1101,7 +1133,7 @@ int ctts_tuning_flags(void) {
            (t.bf16_ps ? (1 << 20) : 0) | (t.bf16_no_ps ? (1 << 21) : 0) | (t.taco_poll_delay_set ? (1 << 23) : 0) |
            (t.taco_valu ? (1 << 24) : 0) | (t.up_no_mfma ? (1 << 25) : 0) | (t.f32_no_wn_fold ? (1 << 26) : 0) |
            (t.taco_bg_no_pipe ? (1 << 27) : 0) | (t.f32_no_winograd ? (1 << 28) : 0) | (t.f32_winograd_min >= 0 ? (1 << 29) : 0) |
-           (t.f32_winograd_plain ? (1 << 30) : 0);
+           (t.f32_winograd_plain ? (1 << 30) : 0) | (t.f32_winograd_fused_min >= 0 ? 4 : 0) | (t.f32_winograd_no_fused ? 32 : 0);
 }
 
 int ctts_profile_create(void** handle) {

@@ -1,0 +1,316 @@
+// One launch per Winograd F(2,3) in-layer step of the fp32 WaveGlow (see wn_winograd_layer.h for the contract).
+//
+// Workgroup = 256 threads = 4 waves (2 x 2) on 128 packed rows x BN = 64 NT pair columns of one batch item; a wave holds the 32 tanh
+// and the 32 sigmoid rows of 32 channels x 32 NT columns in TWO accumulator sets S and D (2 x 32 NT VGPRs).  The main loop is the
+// conv-GEMM's (gemm_f32.hip): three LDS stages filled by global_load_lds two chunks ahead, one DMA piece per k-step behind that
+// k-step's MFMAs, counted vmcnt + raw s_barrier, fragments of k-step ks + 1 read while ks runs - run over ONE stream of
+// 2 n1 + 2 n2 chunks (n1 = C / 16, n2 = (C + H) / 16):
+//   [0, n1)            S += G2 . V2
+//   [n1, 2 n1)         D += G3 . V3             then (S, D) <- (S + D, S - D)
+//   [2 n1, 2 n1 + n2)  S += [W0 | C_i] . [V1; h(t_e)]    then act[t_e] = gate(S + b)
+//   [.., 2 n1 + 2 n2)  D += [-W2 | C_i] . [V4; h(t_o)]   then act[t_o] = gate(D + b)
+// The DMA cursor runs through the even phase's epilogue (gfx9 counts stores on vmcnt too: the wait behind the next chunk then also
+// drains them, which is merely conservative - loads return in order among themselves).
+// A chunk -> (A address, B address) table is built once per workgroup.  The weights are read where the lean form's launches read
+// them: a GATE-packed panel holds this workgroup's 128 rows as one half of every 256-row k-row, a SPLIT-packed one (dense row order)
+// as two 64-row runs of two M-blocks - the lanes carry that, no second copy of the weights exists.
+// NT = 2 (128 columns) and NT = 1 (64 columns, for small grids and the tiles beyond the last whole round) sum every column's
+// products in the same order with the same instruction: bit-identical.
+#include "wn_winograd_layer.h"
+#include "tuning.h"
+
+namespace ctts {
+
+typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
+
+namespace {
+
+// the GATE epilogue's gate math (gemm_f32.hip): exp via v_exp_f32, reciprocal via v_rcp_f32
+__device__ __forceinline__ float wg_sigmoid(float u) {
+    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u * -1.4426950408889634f));
+}
+__device__ __forceinline__ float wg_tanh(float u) {
+    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u * 2.8853900817779268f));
+}
+
+}  // namespace
+
+template <int NT>
+__global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnWinogradLayerArgs a) {
+    constexpr int BN = 64 * NT;
+    constexpr int A_ST = GEMM_KC * 128;                   // floats of a stage's A part
+    constexpr int STG = A_ST + GEMM_KC * BN;              // floats per stage
+    constexpr int TAB = 3 * STG;                          // chunk table: {A address, B address} = 4 dwords per chunk
+    constexpr int BIAS = TAB + 4 * WNWG_MAX_CHUNKS;
+    constexpr int UPR = BN / 4;                           // 16-byte units per k-row of the B stage
+    constexpr int RPP = 64 / UPR;                         // k-rows per B piece (2 or 4)
+    __shared__ __attribute__((aligned(16))) float lds[BIAS + 128];
+
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int l31 = lane & 31, lhi = lane >> 5;
+
+    // block -> (channel block, column tile, batch item).  Dispatch places block id on XCD id % 8: an XCD runs all the channel
+    // blocks of a column tile back to back, so the tile's B rows are fetched into one L2 and every XCD streams the same weights
+    const int ncb = a.C >> 6;
+    const int jx = blockIdx.x >> 3;
+    const int cb = jx % ncb;
+    const int gt = (jx / ncb) * 8 + (blockIdx.x & 7);
+    if (gt >= a.kt_total) return;                         // whole workgroup: the grid is rounded up to 8 tiles
+    const int b = a.b0 + gt / a.kt;
+    const int n0 = a.col0 + (gt % a.kt) * BN;             // first pair column (of the batch item)
+
+    const int n1 = a.C / GEMM_KC, n2 = (a.C + a.H) / GEMM_KC;
+    const int c_e = 2 * n1, c_o = 2 * n1 + n2, nch = 2 * n1 + 2 * n2;
+
+    // SPLIT-packed panels: this block's tanh rows are dense rows 64 cb .., its sigmoid rows dense rows C + 64 cb ..
+    const int mb_t = (64 * cb) >> 8, loc_t = (64 * cb) & 255;
+    const int mb_s = (a.C + 64 * cb) >> 8, loc_s = (a.C + 64 * cb) & 255;
+    {
+        uint4* tab = reinterpret_cast<uint4*>(lds + TAB);
+        for (int c = t; c < nch; c += 256) {
+            const float *ap, *bp;
+            if (c < c_e) {
+                const int ph = c >= n1, loc = c - ph * n1;
+                ap = (ph ? a.A_T3 : a.A_T2) + ((size_t)mb_t * n1 + loc) * (GEMM_KC * 256) + loc_t;
+                bp = a.V + (1 + ph) * a.vplane + ((size_t)b * a.C + (size_t)loc * GEMM_KC) * a.ldp + n0;
+            } else {
+                const int ph = c >= c_o, loc = c - c_e - ph * n2;
+                ap = (ph ? a.A_o : a.A_e) + ((size_t)(cb >> 1) * n2 + loc) * (GEMM_KC * 256) + (cb & 1) * 128;
+                if (loc < n1) bp = a.V + (ph ? 3 : 0) * a.vplane + ((size_t)b * a.C + (size_t)loc * GEMM_KC) * a.ldp + n0;
+                else if (a.in_place) bp = a.h2 + (size_t)b * a.h_bstride + (size_t)(loc - n1) * GEMM_KC * a.ld;   // the lanes carry pad and column
+                else bp = a.Hc + ph * a.hplane + ((size_t)b * a.H + (size_t)(loc - n1) * GEMM_KC) * a.ldp + n0;
+            }
+            const unsigned long long ua = reinterpret_cast<unsigned long long>(ap), ub = reinterpret_cast<unsigned long long>(bp);
+            tab[c] = make_uint4((unsigned)ua, (unsigned)(ua >> 32), (unsigned)ub, (unsigned)(ub >> 32));
+        }
+        if (t < 128) lds[BIAS + t] = a.bias[cb * 128 + t];
+    }
+
+    // 32-bit lane byte offsets of the DMA pieces.  A piece j of wave w = k-rows 2 (w + 4 j), + 1 of the stage (256 floats, lane order)
+    unsigned offa_g[2], offa_s[2], offb[NT], offb_e[NT], offb_o[NT];
+    {
+        const int col = (lane & 31) * 4;
+        const long long delta = ((long long)(mb_s - mb_t) * n1) * (GEMM_KC * 256) + (loc_s - loc_t);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int krow = 2 * (wave + 4 * j) + (lane >> 5);
+            offa_g[j] = (unsigned)((krow * 256 + col) * 4);
+            offa_s[j] = (unsigned)((krow * 256 + (col < 64 ? (long long)col : col - 64 + delta)) * 4);
+        }
+        const int bcol = (lane % UPR) * 4;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int krow = (wave + 4 * j) * RPP + lane / UPR;
+            offb[j] = (unsigned)(((size_t)krow * a.ldp + bcol) * 4);
+            offb_e[j] = offb_o[j] = 0;
+            if (a.in_place) {
+                // the lane's unit starts at pair column q and is read at the natural column of q: four consecutive, 16-byte aligned
+                // columns (d % 4 == 0), clamped to the row's last aligned unit (those outputs are dropped by the L / Lp tests)
+                const int q = n0 + bcol;
+                const int te = (q / a.d) * (2 * a.d) + q % a.d;
+                const int lim = (a.ld - a.pad - 4) & ~3;
+                offb_e[j] = (unsigned)(((size_t)krow * a.ld + a.pad + min(te, lim)) * 4);
+                offb_o[j] = (unsigned)(((size_t)krow * a.ld + a.pad + min(te + a.d, lim)) * 4);
+            }
+        }
+    }
+    const int m_e0 = a.in_place ? c_e + n1 : 0x7fffffff, m_e1 = c_o;      // mapped cond chunks of the even / odd phase
+    const int m_o0 = a.in_place ? c_o + n1 : 0x7fffffff;
+
+    wg_f32x16 S[2][NT], D[2][NT];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { S[i][j][r] = 0.0f; D[i][j][r] = 0.0f; }
+    __syncthreads();                                      // table and bias visible
+
+    typedef __attribute__((address_space(3))) float* lds_fptr;
+    typedef const __attribute__((address_space(1))) float* gfloat_ptr;
+    typedef const __attribute__((address_space(1))) char* gbyte_ptr;
+    const uint4* ctab = reinterpret_cast<const uint4*>(lds + TAB);
+    // Every DMA address is a wave-uniform 64-bit base (SGPR pair) + a 32-bit lane offset laundered through an empty asm, so that
+    // the compiler keeps the global_load_lds_dwordx4 v, s[a:b] form (gemm_f32.hip, CTTS_GLDS_PIECE)
+#define WNWG_ADDR(buf, c)                                                                                   \
+    lds_fptr la_ = (lds_fptr)(lds + (buf) * STG + wave * 256);                                              \
+    const uint4 e_ = ctab[c];                                                                               \
+    const bool as_ = (c) < c_e;                                      /* wave-uniform: SPLIT-packed panel */ \
+    const bool me_ = (c) >= m_e0 && (c) < m_e1, mo_ = (c) >= m_o0;   /* wave-uniform: mapped cond chunk */
+#define WNWG_BASES()                                                                                        \
+    const gbyte_ptr ac_ = reinterpret_cast<gbyte_ptr>(                                                      \
+        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)e_.y) << 32) |                   \
+        (unsigned)__builtin_amdgcn_readfirstlane((int)e_.x));                                               \
+    const gbyte_ptr bp_ = reinterpret_cast<gbyte_ptr>(                                                      \
+        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)e_.w) << 32) |                   \
+        (unsigned)__builtin_amdgcn_readfirstlane((int)e_.z));
+#define WNWG_PIECE(p)                                                                                       \
+    do {                                                                                                    \
+        if constexpr ((p) < 2) {                                                                            \
+            unsigned o_ = as_ ? offa_s[(p)] : offa_g[(p)];                                                  \
+            asm volatile("" : "+v"(o_));                                                                    \
+            __builtin_amdgcn_global_load_lds((gfloat_ptr)(ac_ + o_), la_ + 1024 * (p), 16, 0, 0);           \
+        } else if constexpr ((p) < 2 + NT) {                                                                \
+            unsigned o_ = me_ ? offb_e[(p) - 2] : mo_ ? offb_o[(p) - 2] : offb[(p) - 2];                     \
+            asm volatile("" : "+v"(o_));                                                                    \
+            __builtin_amdgcn_global_load_lds((gfloat_ptr)(bp_ + o_), la_ + A_ST + 1024 * ((p) - 2), 16, 0, 0); \
+        }                                                                                                   \
+    } while (0)
+#define WNWG_WAIT()                                                                                         \
+    do {                                                                                                    \
+        if constexpr (NT == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                             \
+        else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");                                               \
+    } while (0)
+
+    // 2 + NT DMAs per thread per chunk, in order: vmcnt(2 + NT) = "everything but the newest chunk has landed" (the last two
+    // iterations re-issue the final chunk into a stage nobody reads any more: the DMA count per iteration stays constant)
+    {
+        { WNWG_ADDR(0, 0) WNWG_BASES() WNWG_PIECE(0); WNWG_PIECE(1); WNWG_PIECE(2); WNWG_PIECE(3); }
+        { WNWG_ADDR(1, 1) WNWG_BASES() WNWG_PIECE(0); WNWG_PIECE(1); WNWG_PIECE(2); WNWG_PIECE(3); }
+        WNWG_WAIT();
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
+    int cur = 0;
+    // one chunk into accumulator set X: per k-step one fenced region [fragments of k-step ks + 1 | 2 NT MFMAs of ks | one DMA piece]
+#define WNWG_READ_FRAGS(ks)                                                                                 \
+    _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) av[ks][mt] = As[(2 * (ks) + lhi) * 128 + mt * 64];     \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) bv[ks][nt] = Bs[(2 * (ks) + lhi) * BN + nt * 32];
+#define WNWG_MFMA(X, ks)                                                                                    \
+    _Pragma("unroll") for (int mt = 0; mt < 2; ++mt)                                                        \
+        _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                                   \
+            X[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks][mt], bv[ks][nt], X[mt][nt], 0, 0, 0);
+#define WNWG_REGION(X, ks, p)                                                                               \
+    __builtin_amdgcn_sched_barrier(0);                                                                      \
+    if constexpr ((ks) + 1 < GEMM_KC / 2) { WNWG_READ_FRAGS((ks) + 1) }                                     \
+    WNWG_MFMA(X, ks)                                                                                        \
+    WNWG_PIECE(p);
+#define WNWG_CHUNK(X)                                                                                       \
+    {                                                                                                       \
+        const float* As = lds + cur * STG + wm * 32 + l31;                                                  \
+        const float* Bs = lds + cur * STG + A_ST + wn * (32 * NT) + l31;                                    \
+        float av[GEMM_KC / 2][2], bv[GEMM_KC / 2][NT];                                                      \
+        const int nb = cur >= 1 ? cur - 1 : 2;              /* (cur + 2) % 3: the stage of chunk ch - 1 */  \
+        const int cn = ch + 2 < nch ? ch + 2 : nch - 1;                                                     \
+        WNWG_ADDR(nb, cn)                                                                                   \
+        WNWG_READ_FRAGS(0)                                                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        WNWG_BASES()                                                                                        \
+        WNWG_REGION(X, 0, 0) WNWG_REGION(X, 1, 1) WNWG_REGION(X, 2, 2) WNWG_REGION(X, 3, 3)                 \
+        WNWG_REGION(X, 4, 4) WNWG_REGION(X, 5, 4) WNWG_REGION(X, 6, 4) WNWG_REGION(X, 7, 4)                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        WNWG_WAIT();                                        /* chunk ch + 1 landed, the newest in flight */ \
+        __builtin_amdgcn_s_barrier();                                                                       \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        cur = cur == 2 ? 0 : cur + 1;                                                                       \
+    }
+
+    // gate and store one accumulator set: pair column n of the batch item -> natural column (n / d) 2d + n % d + par d
+    float* dst = a.act + (size_t)b * a.act_bstride + (size_t)(cb * 64 + wm * 32) * a.ld + a.pad;
+    const float* bias = lds + BIAS + wm * 32;
+#define WNWG_GATE(X, par)                                                                                   \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                                     \
+        const int n = n0 + wn * (32 * NT) + nt * 32 + l31;                                                  \
+        const int ns = (n / a.d) * (2 * a.d) + n % a.d + (par) * a.d;                                       \
+        if (n < a.Lp && ns < a.L) {                                                                         \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                \
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * lhi;                                           \
+                const float u0 = X[0][nt][r] + bias[row];                                                   \
+                const float u1 = X[1][nt][r] + bias[64 + row];                                              \
+                dst[(size_t)row * a.ld + ns] = wg_tanh(u0) * wg_sigmoid(u1);                                \
+            }                                                                                               \
+        }                                                                                                   \
+    }
+
+    int ch = 0;
+    for (; ch < n1; ++ch) WNWG_CHUNK(S)
+    for (; ch < c_e; ++ch) WNWG_CHUNK(D)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float s = S[i][j][r], dd = D[i][j][r];
+                S[i][j][r] = s + dd;
+                D[i][j][r] = s - dd;
+            }
+    for (; ch < c_o; ++ch) WNWG_CHUNK(S)
+    WNWG_GATE(S, 0)
+    for (; ch < nch; ++ch) WNWG_CHUNK(D)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the re-issued tail DMAs still target LDS
+    __builtin_amdgcn_s_barrier();
+    WNWG_GATE(D, 1)
+#undef WNWG_GATE
+#undef WNWG_CHUNK
+#undef WNWG_REGION
+#undef WNWG_MFMA
+#undef WNWG_READ_FRAGS
+#undef WNWG_WAIT
+#undef WNWG_PIECE
+#undef WNWG_BASES
+#undef WNWG_ADDR
+}
+
+bool wn_winograd_layer_supported(int C, int H) {
+    return C >= 128 && C % 128 == 0 && H > 0 && H % GEMM_KC == 0 && 2 * (C / GEMM_KC) + 2 * ((C + H) / GEMM_KC) <= WNWG_MAX_CHUNKS;
+}
+
+namespace {
+template <int NT>
+int launch_wnwg_shape(WnWinogradLayerArgs a, int kt, long long kt_total, hipStream_t stream) {
+    a.kt = kt;
+    a.kt_total = (int)kt_total;
+    const long long blocks = 8ll * (a.C / 64) * ((kt_total + 7) / 8);
+    CTTS_CHECK_ARG(blocks > 0 && blocks < (1ll << 31) && kt_total < (1ll << 31), "wn_winograd_layer: grid %lld", blocks);
+    hipLaunchKernelGGL((wn_winograd_layer_f32_kernel<NT>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    CTTS_CHECK_LAUNCH("wn_winograd_layer");
+    return CTTS_OK;
+}
+}  // namespace
+
+int launch_wn_winograd_layer(const WnWinogradLayerArgs& a_in, hipStream_t stream) {
+    WnWinogradLayerArgs a = a_in;
+    CTTS_CHECK_ARG(wn_winograd_layer_supported(a.C, a.H), "wn_winograd_layer: C=%d H=%d", a.C, a.H);
+    CTTS_CHECK_ARG(a.A_T2 && a.A_T3 && a.A_e && a.A_o && a.bias && a.V && a.act && a.batch >= 1, "wn_winograd_layer: operand not set");
+    CTTS_CHECK_ARG(a.d >= 1 && a.L >= 1 && a.Lp >= 1 && a.ntiles >= 1 && a.Lp <= a.ntiles * 128 && a.ntiles * 128 <= a.ldp && a.ldp % 4 == 0 &&
+                       a.ld % 4 == 0 && a.pad >= 0 && a.pad % 4 == 0 && a.L + a.pad <= a.ld,
+                   "wn_winograd_layer: geometry d=%d L=%d Lp=%d ntiles=%d ldp=%d ld=%d pad=%d", a.d, a.L, a.Lp, a.ntiles, a.ldp, a.ld, a.pad);
+    // in place: a lane's four pair columns must be four consecutive, 16-byte aligned natural columns
+    CTTS_CHECK_ARG(a.in_place ? (a.h2 && a.d % 4 == 0 && a.ld - a.pad >= 4 && a.h_bstride % 4 == 0 && reinterpret_cast<uintptr_t>(a.h2) % 16 == 0)
+                              : a.Hc != nullptr,
+                   "wn_winograd_layer: cond rows (in_place=%d d=%d)", a.in_place, a.d);
+    a.b0 = 0;
+    a.col0 = 0;
+    const Tuning tn = tuning();
+    const int ncb = a.C / 64;
+    const long long slots = 2ll * wf_row_cus();
+    const int kt_narrow = (a.Lp + 63) / 64;
+    long long tiles = (long long)a.ntiles * a.batch;
+    // the narrow shape where the wide one would run fewer than two whole rounds (the role of gemm_f32_small_applies): no peel exists
+    // there, and three narrow workgroups fit a CU.  Measured at one 900-frame utterance (904 wide workgroups): 72.2 against 73.2 ms
+    // per step (profiles/r17_01_winograd_fused_ab.txt); from four utterances on the wide shape with its peel is level or ahead
+    if (!tn.f32_no_small && (tn.f32_force_small || ncb * tiles < 2 * slots)) return launch_wnwg_shape<1>(a, kt_narrow, (long long)kt_narrow * a.batch, stream);
+    // Round-aligned launch (gemm_f32.hip, launch_gemm_f32): the tiles beyond the last whole round of 2 x CUs workgroups - they lie at
+    // the end of the last batch item - go to a launch of the narrow shape FIRST, and the wide launch covers the rest
+    if (!tn.f32_no_round_split && !tn.f32_no_small) {
+        const long long rounds = ncb * tiles / slots;
+        const long long rem_tiles = (ncb * tiles - rounds * slots + ncb - 1) / ncb;
+        if (rounds >= 2 && rem_tiles > 0 && rem_tiles * ncb <= slots * 3 / 10 && rem_tiles < a.ntiles &&
+            (long long)(a.ntiles - rem_tiles) * 128 < a.Lp) {
+            WnWinogradLayerArgs r = a;
+            r.b0 = a.batch - 1;
+            r.col0 = (int)(a.ntiles - rem_tiles) * 128;
+            const int kt = (a.Lp - r.col0 + 63) / 64;
+            if (int rc = launch_wnwg_shape<1>(r, kt, kt, stream)) return rc;
+            tiles -= rem_tiles;
+        }
+    }
+    return launch_wnwg_shape<2>(a, a.ntiles, tiles, stream);
+}
+
+}  // namespace ctts

@@ -895,7 +895,7 @@ int ctts_taco_stop_rule_f32(const float* gate_logits, int32_t batch, int32_t gat
 int ctts_last_gemm_loop(void);
 
 /* Launch-shape overrides for A/B measurements (CTTS_F32_NO_GLDS, CTTS_F32_NO_SMALL, CTTS_F32_FORCE_SMALL, CTTS_GEMM_NO_XCD_PAIR, CTTS_BF16_NO_WIDE /
- * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD, CTTS_F32_NO_WINOGRAD, CTTS_F32_WINOGRAD_MIN, CTTS_F32_WINOGRAD_PLAIN) never change results beyond the parity
+ * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD, CTTS_F32_NO_WINOGRAD, CTTS_F32_WINOGRAD_MIN, CTTS_F32_WINOGRAD_PLAIN, CTTS_F32_WINOGRAD_FUSED_MIN, CTTS_F32_WINOGRAD_NO_FUSED) never change results beyond the parity
  * tolerance (CTTS_F32_NO_SPLITK changes the summation order of the fused WaveFlow layer at batch <= 2, see above; CTTS_F32_NO_WN_FOLD
  * brings back the fp32 WaveGlow WN stack without the start / end folds: WN layer 0 on the C-row x, the C-row deferred skip GEMM and the
  * C-row flow tail - the default folds W_in,0 . W_start into layer 0 and W_end . W_skip,i into a 2 n_half-row skip/end pass, which only
@@ -906,10 +906,15 @@ int ctts_last_gemm_loop(void);
  * utterance keeps its bits whatever batch it runs in; one just below and one just above the threshold differ within the parity
  * tolerance.  CTTS_F32_WINOGRAD_PLAIN runs that form as the five launches per layer it was first built as - cond rows copied into
  * pair order for every layer, T2 / T3 and even / odd as four launches - where the default reads the cond rows in place and pairs
- * the launches: bit-identical, the A/B arm).  The environment is read once,
+ * the launches: bit-identical, the A/B arm.  For utterances of at least CTTS_F32_WINOGRAD_FUSED_MIN columns (default: the Winograd
+ * form's own default threshold; 0 = always; again the utterance alone decides) a Winograd layer is ONE launch behind the transform
+ * kernel: a workgroup runs the four products of a pair block through one chunk stream and T2 / T3 stay in registers -
+ * ((S2 +- S3) + products) + b where the paired launches round ((products + b) + T2) +- T3, a re-ordered sum.
+ * CTTS_F32_WINOGRAD_NO_FUSED keeps the paired launches at every size: the A/B arm).  The environment is read once,
  * at the first launch; this re-reads it (tests and profiling scripts that flip a knob in-process). */
 int ctts_tuning_reload(void);
-/* The knobs as the library currently sees them: bit 0 CTTS_F32_NO_GLDS, 1 CTTS_GEMM_NO_XCD_PAIR,
+/* The knobs as the library currently sees them: bit 0 CTTS_F32_NO_GLDS, 1 CTTS_GEMM_NO_XCD_PAIR, 2 CTTS_F32_WINOGRAD_FUSED_MIN set,
+ * 5 CTTS_F32_WINOGRAD_NO_FUSED,
  * 3 CTTS_BF16_NO_WIDE, 4 CTTS_BF16_NO_PP, 7 CTTS_WF_NO_FUSE, 8 CTTS_TACO_NO_FUSE,
  * 9 CTTS_F32_NO_SMALL, 10 CTTS_F32_FORCE_SMALL, 11 CTTS_F32_NO_SPLITK, 12 CTTS_WF_NO_VEC_INTERP, 13 CTTS_F32_NO_DEFER_SKIP, 14 CTTS_WF_NO_REGION_SPLIT,
  * 15 CTTS_WF_NO_ROW_QUEUE, 16 CTTS_WF_ROW_QUEUE_MIN set, 17 CTTS_WF_INJECT_ABORT, 18 CTTS_WF_QUEUE_DEBUG != 0, 19 CTTS_F32_NO_ROUND_SPLIT,
@@ -917,7 +922,7 @@ int ctts_tuning_reload(void);
  * before the first poll of the persistent decoder's six vector exchanges; timing only), 24 CTTS_TACO_VALU
  * (ctts_taco_decoder_steps_f32 at batch <= 4 on the VALU kernels instead of the batched MFMA form), 25 CTTS_UP_NO_MFMA (the VALU upsampling kernel
  * also for the shape the MFMA one is built for: bit-identical), 26 CTTS_F32_NO_WN_FOLD, 27 CTTS_TACO_BG_NO_PIPE (the batched
- * decoder's plain schedule, the default above 64 rows, at every size), 28 CTTS_F32_NO_WINOGRAD, 29 CTTS_F32_WINOGRAD_MIN set, 30 CTTS_F32_WINOGRAD_PLAIN.  Bits 2, 5, 6 and 22 belonged to retired knobs and stay unused.
+ * decoder's plain schedule, the default above 64 rows, at every size), 28 CTTS_F32_NO_WINOGRAD, 29 CTTS_F32_WINOGRAD_MIN set, 30 CTTS_F32_WINOGRAD_PLAIN.  Bits 6 and 22 belonged to retired knobs and stay unused (2 and 5 did too, until the one-launch Winograd layer took them).
  * (Tests assert that a knob they set is the one in effect.) */
 int ctts_tuning_flags(void);
 
@@ -933,7 +938,7 @@ int ctts_tuning_flags(void);
 /* fp32 with the WN folds (the default; CTTS_F32_NO_WN_FOLD = slots 0-2 only).  Slot 0 still brackets every in-layer launch, the
  * short folded layer-0 launch included (one entry per layer); slot 3 has that launch alone, so that a reader pricing slot 0 at the
  * full-K FLOP count can take it out.  In the Winograd form (CTTS_F32_NO_WINOGRAD turns it off) a slot-0 entry brackets a layer's
- * transform kernel and its four launches, which execute 5/7 of the full-K FLOPs: priced at the full-K count it reads high too.  The skip/end pass and the res GEMM of this form record in slots of their own. */
+ * transform kernel and its launches (one, two or four), which execute 5/7 of the full-K FLOPs: priced at the full-K count it reads high too.  The skip/end pass and the res GEMM of this form record in slots of their own. */
 #define CTTS_PROF_WN_IN0F 3  /* layer 0's in-layer GEMM on the folded start: K = 3 x 16 + cond (also in slot 0) */
 #define CTTS_PROF_WN_SKEND 4 /* skip/end pass: 2 n_half rows of W_end . W_skip over a group's kept activations (+ the flow tail) */
 #define CTTS_PROF_WN_RES_F 5 /* res GEMM (x += W_res act) of the folded form */

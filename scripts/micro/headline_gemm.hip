@@ -12,9 +12,11 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../../cookietts_amd/csrc/gemm_f32.hip"
+#include "../../cookietts_amd/csrc/wn_winograd_layer.hip"
 
 namespace ctts {
 void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
@@ -31,6 +33,16 @@ __global__ __launch_bounds__(256) void stream_3r5w_kernel(const float4* __restri
     dst[i] = a; dst[n + i] = b; dst[2 * n + i] = c;
     dst[3 * n + i] = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
     dst[4 * n + i] = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w);
+}
+// out[0] = max |a - b|, out[1] = max |a| (as the bits of non-negative floats)
+__global__ __launch_bounds__(256) void max_diff_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n, unsigned* out) {
+    float d = 0.f, m = 0.f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        d = fmaxf(d, fabsf(a[i] - b[i]));
+        m = fmaxf(m, fabsf(a[i]));
+    }
+    atomicMax(out, __float_as_uint(d));
+    atomicMax(out + 1, __float_as_uint(m));
 }
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 
@@ -99,6 +111,94 @@ int main(int argc, char** argv) {
             }
             return a;
         };
+        if (getenv("HG_FUSED")) {
+            // The one-launch Winograd layer (wn_winograd_layer.hip) against the two launches it replaces - T2 | T3 and even | odd as
+            // the lean form issues them (two parts each, T planes in HBM, second addend, mapped store, cond rows in place) - on the
+            // same operands, in this process, alternated HG_ROUNDS times; first the two forms' outputs are compared.
+            //   HG_WINOGRAD=1 HG_FUSED=1 [HG_WT=112 HG_LP=14336]  (whole rounds; the default 113 / 14 400 has the 64-workgroup tail;
+            //   HG_PEEL=1 lets the fused launcher peel it, the conv-GEMM's peel needs the small shape, which is not linked in here)
+            const int slots = 5, n1 = C / GEMM_KC, n2 = (C + CC) / GEMM_KC;
+            const int Ln = 2 * Lp;                               // natural columns (ld holds them: Lp <= L / 2)
+            const size_t vplane = (size_t)B * C * ldp, tplane = (size_t)B * 2 * C * ldp;
+            const size_t slot_f = (size_t)4 * (2 * n1 + 2 * n2) * a_tile;
+            float *Vb, *Tb, *act2, *bias2;
+            unsigned* dmax;
+            CK(hipMalloc(&Vb, 4 * vplane * 4)); CK(hipMalloc(&Tb, 2 * tplane * 4)); CK(hipMalloc(&act2, (size_t)B * C * ld * 4));
+            CK(hipMalloc(&bias2, 1024 * 4)); CK(hipMalloc(&dmax, 8));
+            for (int p = 0; p < 4; ++p) CK(hipMemcpy(Vb + p * vplane, x + p * 1000, vplane * 4, hipMemcpyDeviceToDevice));
+            CK(hipMemcpy(bias2, x + 4096, 1024 * 4, hipMemcpyDeviceToDevice));
+            if ((size_t)slots * slot_f > (size_t)layers * 4 * nch * a_tile) return 1;
+            auto wslot = [&](int i) { return A + (size_t)(i % slots) * slot_f; };
+            auto dil = [&](int i) { return 8 << (i % slots); };                    // d = 8 .. 128: cond rows in place
+            auto lean = [&](int i) {
+                const float* w = wslot(i);
+                GemmArgs a{};
+                a.gemm_mode = CTTS_GEMM_F32; a.bm = 256;
+                a.ld = ldp; a.pad = 0; a.L = Lp; a.ntiles = wt; a.batch = B; a.MB = 4;
+                a.bias = bias; a.nseg = 1; a.nch_total = n1;
+                a.dst_ld = ldp; a.dst_pad = 0; a.dst0_bstride = (long long)2 * C * ldp; a.M = 2 * C; a.split = 2 * C;
+                a.parts = 2; a.part_A = (long long)4 * n1 * a_tile; a.part_seg[0] = (long long)vplane; a.part_dst0 = (long long)tplane;
+                a.A = w; a.seg[0] = {Vb + vplane, (long long)C * ldp, n1, 0, 0, 0}; a.dst0 = Tb;
+                if (int rc = launch_gemm_f32(GEMM_EPI_SPLIT, a, st)) return rc;
+                a.bias = bias2; a.nseg = 2; a.nch_total = n2; a.split = 0; a.pairC = C;
+                a.dst0 = act; a.dst0_bstride = (long long)C * ld; a.dst_ld = ld; a.dst_pad = PADC;
+                a.addend = Tb; a.addend2 = Tb + tplane; a.addend_bstride = (long long)2 * C * ldp; a.addend2_sign = 1.0f;
+                a.map_d = dil(i); a.map_L = Ln; a.map_par = 0;
+                a.part_A = (long long)4 * n2 * a_tile; a.part_seg[0] = (long long)(3 * vplane); a.part_seg[1] = 0; a.part_dst0 = 0;
+                a.mseg = 2; a.mseg_ld = ld; a.mseg_pad = PADC;
+                a.A = w + (size_t)8 * n1 * a_tile;
+                a.seg[0] = {Vb, (long long)C * ldp, n1, 0, 0, 0};
+                a.seg[1] = {h, (long long)CC * ld, CC / GEMM_KC, 0, 0, 0};
+                return launch_gemm_f32(GEMM_EPI_GATE, a, st);
+            };
+            auto fused = [&](int i, float* dst) {
+                const float* w = wslot(i);
+                WnWinogradLayerArgs f{};
+                f.A_T2 = w; f.A_T3 = w + (size_t)4 * n1 * a_tile; f.A_e = w + (size_t)8 * n1 * a_tile; f.A_o = f.A_e + (size_t)4 * n2 * a_tile;
+                f.bias = bias2; f.V = Vb; f.vplane = (long long)vplane; f.h2 = h; f.h_bstride = (long long)CC * ld;
+                f.act = dst; f.act_bstride = (long long)C * ld; f.C = C; f.H = CC; f.batch = B;
+                f.ldp = ldp; f.Lp = Lp; f.ntiles = wt; f.d = dil(i); f.L = Ln; f.ld = ld; f.pad = PADC; f.in_place = 1;
+                return launch_wn_winograd_layer(f, st);
+            };
+            for (int i = 0; i < slots; ++i) {                    // the same bits up to the re-ordered sum
+                CK(hipMemsetAsync(act, 0, (size_t)B * C * ld * 4, st)); CK(hipMemsetAsync(act2, 0, (size_t)B * C * ld * 4, st));
+                CK(hipMemsetAsync(dmax, 0, 8, st));
+                setenv("CTTS_F32_NO_ROUND_SPLIT", "1", 1); reload_tuning();
+                if (lean(i)) return 1;
+                if (getenv("HG_PEEL")) { unsetenv("CTTS_F32_NO_ROUND_SPLIT"); reload_tuning(); }
+                if (fused(i, act2)) return 1;
+                const size_t n = (size_t)B * C * ld;
+                hipLaunchKernelGGL(max_diff_kernel, dim3(4096), dim3(256), 0, st, act, act2, n, dmax);
+                unsigned hd[2];
+                CK(hipMemcpyAsync(hd, dmax, 8, hipMemcpyDeviceToHost, st)); CK(hipStreamSynchronize(st));
+                float fd[2]; memcpy(fd, hd, 8);
+                printf("d = %3d: max |fused - lean| = %.3e, max |lean| = %.3e\n", dil(i), fd[0], fd[1]);
+                if (!(fd[0] <= 2e-5f) || !(fd[1] > 0.01f)) { printf("MISMATCH\n"); return 2; }
+            }
+            const int rounds = getenv("HG_ROUNDS") ? atoi(getenv("HG_ROUNDS")) : 5, reps = 12;
+            float lo[2] = {1e9f, 1e9f}, hi[2] = {0.f, 0.f}, sum[2] = {0.f, 0.f};
+            for (int r = 0; r < rounds; ++r)
+                for (int arm = 0; arm < 2; ++arm) {
+                    if (arm == 0 || !getenv("HG_PEEL")) setenv("CTTS_F32_NO_ROUND_SPLIT", "1", 1);
+                    else unsetenv("CTTS_F32_NO_ROUND_SPLIT");
+                    reload_tuning();
+                    for (int i = 0; i < 3; ++i) if (arm ? fused(i, act2) : lean(i)) return 1;
+                    CK(hipStreamSynchronize(st));
+                    CK(hipEventRecord(e0, st));
+                    for (int i = 0; i < reps; ++i) if (arm ? fused(i, act2) : lean(i)) return 1;
+                    CK(hipEventRecord(e1, st));
+                    CK(hipStreamSynchronize(st));
+                    float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                    ms /= reps;
+                    printf("round %d  %-28s %.4f ms per layer\n", r, arm ? "fused (one launch)" : "T2 | T3 + even | odd", ms);
+                    lo[arm] = ms < lo[arm] ? ms : lo[arm]; hi[arm] = ms > hi[arm] ? ms : hi[arm]; sum[arm] += ms;
+                }
+            const float spread = (hi[0] - lo[0]) > (hi[1] - lo[1]) ? hi[0] - lo[0] : hi[1] - lo[1];
+            printf("%d tiles x %d, Lp = %d%s: two launches %.4f ms (spread %.4f), fused %.4f ms (spread %.4f): gain %.4f ms = %.1f x the larger spread\n",
+                   wt, B, Lp, getenv("HG_PEEL") ? ", fused tail peeled" : "", sum[0] / rounds, hi[0] - lo[0], sum[1] / rounds, hi[1] - lo[1],
+                   (sum[0] - sum[1]) / rounds, (sum[0] - sum[1]) / rounds / (spread > 0.f ? spread : 1e-9f));
+            return 0;
+        }
         const size_t sn = (size_t)B * C * ldp / 4;             // 16-byte units of one V plane: 3 read (0.71 GB), 5 written (1.18 GB)
         float4 *ssrc, *sdst;
         CK(hipMalloc(&ssrc, 3 * sn * 16)); CK(hipMalloc(&sdst, 5 * sn * 16)); CK(hipMemset(ssrc, 0, 3 * sn * 16));
