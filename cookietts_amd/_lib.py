@@ -183,6 +183,10 @@ SIGNATURES = {
                                               C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
     "ctts_taco_decoder_steps_hidden_f32": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, _FP, _FP, C.c_int32,
                                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
+    "ctts_taco_decoder_packed_bf16x3_bytes": (C.c_size_t, [C.POINTER(TacoDecoderConfig)]),
+    "ctts_taco_decoder_pack_bf16x3": (C.c_int, [C.POINTER(TacoDecoderConfig), C.POINTER(TacoDecoderWeights), _FP, _FP]),
+    "ctts_taco_decoder_steps_bf16x3": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, _FP, _FP, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
     "ctts_taco_prenet_frames_bytes": (C.c_size_t, [C.POINTER(TacoDecoderConfig), C.c_int32, C.c_int32]),
     "ctts_taco_prenet_frames_f32": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, _FP, C.c_size_t, C.c_int32,
                                               C.c_int32, _FP]),

@@ -793,6 +793,17 @@ __global__ __launch_bounds__(256) void hidden_state_kernel(const float* __restri
 }
 
 #include "tacotron_batched.h"
+#include "tacotron_batched_bf16x3.h"
+
+// the split-bf16 cell launch of the plain schedule: one shape for every batch above 64 rows (NT and the K split fix an item's bits).
+// Four m-tiles x 32 items per workgroup, 3-deep ring (144 KiB), four waves: of the shapes that fit the LDS and the vmcnt budget it
+// is the fastest on all three cells at 128 and 256 rows - attention RNN at 256 rows 59.4 us against 79.3 as <2, 4, 3, 4> (the fp32
+// launch's tile), 89.9 as <4, 4, 4, 2>, and 94.8 for the fp32 launch (scripts/micro/taco_cell_bf16x3.hip,
+// profiles/r18_00_taco_cell_bf16x3_ab.txt)
+inline int bgx_launch_cell(const BgArgs& a, const float* planes, int nb_pad, const AttnArgs* attn, float* apre, int* astart, int batch,
+                           hipStream_t s) {
+    return bgx_launch_shape<4, 2, 3, 4>(bgx_args(a, planes), nb_pad, attn, apre, astart, batch, s);
+}
 
 // One decoder step of the batched form (4 < batch <= MAX_BATCH, and batch <= 4 where the persistent kernel is not used): seven
 // dependent launches.  Plain schedule (more than 64 items, or CTTS_TACO_BG_NO_PIPE):
@@ -817,10 +828,12 @@ __global__ __launch_bounds__(256) void hidden_state_kernel(const float* __restri
 // the next step's attention RNN is a role of launch 5 and its attention part 1 rides in launch 4: four launches per step (`merge`).
 int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uint8_t* keep_masks, float* mel_out, float* gate_out,
                   float* align_out, float* hidden_out, int batch, int text_len, int step0, int n_steps, int max_steps, hipStream_t s,
-                  const float* prenet_all = nullptr) {
+                  const float* prenet_all = nullptr, bool bf16x3 = false) {
     const auto& c = p.c;
     const int NB = ws_rows(p, batch);
     const bool forced = prenet_all != nullptr;
+    // split-bf16 cells: the plain schedule's three cell launches (more than 64 rows), free-running loop; `blob` then ends in the planes
+    const bool x3 = bf16x3 && NB > 64 && !forced;
     // above 16 rows the second decoder RNN of step t and the attention RNN of step t + 1 - independent of each other - are two roles of
     // ONE launch (four launches per step): 53.5 against 58.4, 69.9 / 84.5, 130.9 / 134.0, 206.8 / 213.3 us per step at 32 / 64 / 128 / 256
     // rows; at 16 rows, where the role has the attention RNN's narrower launch shape, 50.4 against 50.2 (profiles/r16_02)
@@ -897,8 +910,10 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
         // schedule the attention's part 1 rides along, in the pipelined one it ran in the previous step's launch 7
         // (teacher-forced loop: only a call's first step launches it - see launch 5)
         auto att_launch = [&](int st) { return pipe ? final_(att_args(st), 0, forced ? aD : aP, forced ? 1 : 2) : att_args(st); };
-        if (!(merge && step > step0) &&
-            (rc = bg_launch_cell(att_launch(step), NB, pipe && !forced ? nullptr : &at, w.apre, w.astart, batch, s))) return rc;
+        if (x3) {
+            if ((rc = bgx_launch_cell(att_args(step), blob + p.x3_att, NB, &at, w.apre, w.astart, batch, s))) return rc;
+        } else if (!(merge && step > step0) &&
+                   (rc = bg_launch_cell(att_launch(step), NB, pipe && !forced ? nullptr : &at, w.apre, w.astart, batch, s))) return rc;
         // teacher-forced loop: the NEXT step's attention part 1 rides in launch 4, its attention RNN is a role of launch 5
         const AttnArgs* ride = merge && more ? &at_next : nullptr;
         BgArgs q{};     // 2: query rows (model.py:126)
@@ -924,8 +939,11 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
             if ((rc = BG_ALLOW_LDS(attn_post_kernel, BGA_POST_LDS_BYTES))) return rc;
             hipLaunchKernelGGL(attn_post_kernel, dim3(batch), dim3(256), BGA_POST_LDS_BYTES, s, at, w.qbuf, w.apre, w.astart);
             CTTS_CHECK_LAUNCH("attn_post");
-            if ((rc = bg_launch_cell(dec_args(cur), NB, ride, w.apre, w.astart, batch, s, 0))) return rc;
-            if (ride) rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, 0, d2_args(step), att_launch(step + 1), NB, s);
+            if (x3) {
+                if ((rc = bgx_launch_cell(dec_args(cur), blob + p.x3_dec, NB, nullptr, nullptr, nullptr, batch, s))) return rc;
+                rc = bgx_launch_cell(d2_args(step), blob + p.x3_d2, NB, nullptr, nullptr, nullptr, batch, s);
+            } else if ((rc = bg_launch_cell(dec_args(cur), NB, ride, w.apre, w.astart, batch, s, 0))) return rc;
+            else if (ride) rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, 0, d2_args(step), att_launch(step + 1), NB, s);
             else rc = bg_launch_cell(d2_args(step), NB, nullptr, nullptr, nullptr, batch, s);
             if (rc) return rc;
         }
@@ -1383,6 +1401,70 @@ int ctts_taco_decoder_steps_hidden_f32(const ctts_taco_decoder_config* cfg, cons
         }
     }
     return CTTS_OK;
+}
+
+// ---- split-bf16 (bf16x3) cells above 64 rows ---------------------------------------------------------------------------------
+namespace {
+// the shapes the mode is not built for, before any launch
+int x3_refuse(const DecPlan& p, const char* what) {
+    CTTS_CHECK_ARG(p.x3_bad == nullptr, "%s: %s is not a multiple of 32 (the split planes' K chunk)", what, p.x3_bad);
+    CTTS_CHECK_ARG(bg_supported(p), "%s: this decoder shape has no batched form (ctts_taco_decoder_max_batch is %d, bf16x3 needs %d)", what,
+                   MAX_NB, MAX_BATCH);
+    return CTTS_OK;
+}
+int bgx_pack(float* blob, size_t off, const BgMat& m, const BgSeg* segs, int nseg, int interleave_H, hipStream_t s) {
+    BgxPackArgs a{};
+    for (int i = 0; i < nseg; ++i) a.seg[i] = segs[i];
+    a.nseg = nseg; a.rows = m.rows; a.tiles = m.tiles; a.nchunks = m.nchunks / 2; a.interleave_H = interleave_H;
+    a.dst = reinterpret_cast<unsigned*>(blob + off);
+    const size_t total = (size_t)a.tiles * a.nchunks * 256;
+    hipLaunchKernelGGL(bgx_pack_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0, s, a);
+    CTTS_CHECK_LAUNCH("bgx_pack");
+    return CTTS_OK;
+}
+}  // namespace
+
+size_t ctts_taco_decoder_packed_bf16x3_bytes(const ctts_taco_decoder_config* cfg) {
+    DecPlan p;
+    if (make_dec_plan(cfg, p) || x3_refuse(p, "decoder bf16x3 size")) return 0;
+    return (p.total + p.x3_total) * sizeof(float);
+}
+
+int ctts_taco_decoder_pack_bf16x3(const ctts_taco_decoder_config* cfg, const ctts_taco_decoder_weights* w, void* packed, void* stream) {
+    DecPlan p;
+    int rc = make_dec_plan(cfg, p); if (rc) return rc;
+    if ((rc = x3_refuse(p, "decoder bf16x3 pack"))) return rc;
+    if ((rc = ctts_taco_decoder_pack(cfg, w, packed, stream))) return rc;      // the fp32 blob, byte for byte
+    const auto& c = p.c;
+    hipStream_t s = as_stream(stream);
+    float* blob = static_cast<float*>(packed);
+    const int Ra = c.attention_rnn_dim, Rd = c.decoder_rnn_dim, Rd2 = c.second_decoder_rnn_dim;
+    const BgSeg att[2] = {{blob + p.att[0], p.I_att, 0, p.I_att}, {blob + p.att[1], Ra, 0, Ra}};
+    const BgSeg dec[2] = {{blob + p.dec[0], p.I_dec, 0, p.I_dec}, {blob + p.dec[1], Rd, 0, Rd}};
+    const BgSeg d2[2] = {{blob + p.d2[0], p.I_d2, 0, p.I_d2}, {blob + p.d2[1], Rd2, 0, Rd2}};
+    if ((rc = bgx_pack(blob, p.x3_att, p.bg_att, att, 2, Ra, s))) return rc;
+    if ((rc = bgx_pack(blob, p.x3_dec, p.bg_dec, dec, 2, Rd, s))) return rc;
+    if ((rc = bgx_pack(blob, p.x3_d2, p.bg_d2, d2, 2, Rd2, s))) return rc;
+    CTTS_CHECK_HIP(hipStreamSynchronize(s));     // as ctts_taco_decoder_pack: the blob is ready on return
+    return CTTS_OK;
+}
+
+int ctts_taco_decoder_steps_bf16x3(const ctts_taco_decoder_config* cfg, const void* packed, const uint8_t* keep_masks, float* mel_out,
+                                   float* gate_out, float* align_out, float* hidden_out, int32_t batch, int32_t text_len, int32_t step0,
+                                   int32_t n_steps, int32_t max_steps, void* workspace, void* stream) {
+    DecPlan p; DecWs w;
+    int rc = make_dec_plan(cfg, p); if (rc) return rc;
+    if ((rc = x3_refuse(p, "decoder bf16x3 steps"))) return rc;
+    // at or below 64 rows the step is bound by the weight stream and keeps its pipelined fp32 schedule, bit for bit
+    if (batch <= 64)
+        return ctts_taco_decoder_steps_hidden_f32(cfg, packed, keep_masks, mel_out, gate_out, align_out, hidden_out, batch, text_len, step0,
+                                                  n_steps, max_steps, workspace, stream);
+    CTTS_CHECK_ARG(packed && keep_masks && mel_out && gate_out && align_out && workspace, "decoder bf16x3 steps: NULL pointer");
+    CTTS_CHECK_ARG(batch <= MAX_BATCH && step0 >= 0 && n_steps >= 0 && step0 + n_steps <= max_steps,
+                   "decoder bf16x3 steps: batch=%d (1..%d) step0=%d n_steps=%d max_steps=%d", batch, MAX_BATCH, step0, n_steps, max_steps);
+    dec_carve(p, batch, text_len, static_cast<float*>(workspace), w);
+    return batched_steps(p, w, static_cast<const float*>(packed), keep_masks, mel_out, gate_out, align_out, hidden_out, batch, text_len,
+                         step0, n_steps, max_steps, as_stream(stream), nullptr, true);
 }
 
 // ---- teacher-forced decoding (Decoder.forward, model.py:769-849) -------------------------------------------------------------

@@ -33,6 +33,12 @@ struct DecPlan {
     BgMat bg_att, bg_dec, bg_d2, bg_q, bg_proj, bg_w2;
     bool bg_ok;
     size_t total;
+    // split-bf16 (bf16x3) blob = the fp32 blob (`total` floats, byte for byte) + the hi | lo planes of the three cells
+    // (tacotron_batched_bf16x3.h), each as large as the cell's fp32 tiles: offsets from the blob's start, x3_total = floats added.
+    // x3_ok = bg_ok and every X piece of a cell a multiple of 32 wide (the planes' chunk); x3_bad = the config field that is not
+    size_t x3_att, x3_dec, x3_d2, x3_total;
+    bool x3_ok;
+    const char* x3_bad;
 };
 
 inline int make_dec_plan(const ctts_taco_decoder_config* cfg, DecPlan& p) {
@@ -101,6 +107,15 @@ inline int make_dec_plan(const ctts_taco_decoder_config* cfg, DecPlan& p) {
         p.bg_att = p.bg_dec = p.bg_d2 = p.bg_q = p.bg_proj = p.bg_w2 = BgMat{0, 0, 0, 0};
     }
     p.total = o;
+    p.x3_att = p.x3_dec = p.x3_d2 = p.x3_total = 0;
+    p.x3_bad = c.prenet_dim % 32 ? "prenet_dim" : c.memory_dim % 32 ? "memory_dim" : c.decoder_rnn_dim % 32 ? "decoder_rnn_dim" :
+               c.attention_rnn_dim % 32 ? "attention_rnn_dim" : nullptr;
+    p.x3_ok = p.bg_ok && p.x3_bad == nullptr;
+    if (p.x3_ok) {
+        auto planes = [&](const BgMat& m) { return take((size_t)m.tiles * m.nchunks * 64 * 4); };
+        p.x3_att = planes(p.bg_att); p.x3_dec = planes(p.bg_dec); p.x3_d2 = planes(p.bg_d2);
+        p.x3_total = o - p.total;
+    }
     return CTTS_OK;
 }
 

@@ -188,6 +188,7 @@ class Decoder(_cache.PackedModule):
         self._persist_fallback_calls = 0
         self.dump_attention_weights = False                  # model.py:402 (a debugging switch of forward(); refused there)
         self.forced_chunk = _CHUNK or None                   # forward(): steps per library call (None: all of them in one)
+        self._f32_gemm_mode, self._bf16x3 = None, False      # set_f32_gemm_mode
 
     @property
     def persistent_state(self):
@@ -200,6 +201,35 @@ class Decoder(_cache.PackedModule):
         the persistent kernel again and checks it synchronously."""
         self._persist, self._persist_fallback_calls = "unprobed", 0
         self._xchg = {}
+
+    def set_f32_gemm_mode(self, mode):
+        """Products of the fp32 tensors, same name and meaning as on the vocoder classes: ``None`` / ``"default"`` / ``"f32"``
+        (exact fp32 MFMA) or ``"bf16x3"``: split bf16 for the three LSTM cell GEMMs of the free-running loop (``inference``) in
+        calls of 65 rows and more - weights (once, at pack time) and the cells' inputs (as they are read) are carried as ``hi + lo``
+        bf16 and every product is ``w_hi x_hi + w_lo x_hi + w_hi x_lo`` on the bf16 MFMA with fp32 accumulation (the arithmetic
+        is listed at ``ctts_taco_decoder_steps_bf16x3``).  Everything else stays fp32 and unchanged: the other stages of the
+        step, calls of 64 rows and fewer (their pipelined schedule, bit for bit), the persistent form (<= 8 rows) and the
+        teacher-forced ``forward`` - they read the fp32 part of the same blob.  ``"bf16x6"`` is not built for this model
+        (``NotImplementedError``); an unknown name is a ``ValueError``.  Works on a model that is still on the CPU.  Returns
+        ``self``; the packed blob (108 MB larger in this mode at the default shape) and the workspaces are dropped when the mode
+        changes and kept when it does not.  ``NotImplementedError`` - here, not at the first call - if the library refuses
+        the shape."""
+        code = _lib.model_gemm_mode(mode)
+        if code == _lib.MODEL_GEMM_MODES["bf16x6"]:
+            raise NotImplementedError("cookietts_amd.Tacotron2 decoder: f32 GEMM mode 'bf16x6' is not built for this model "
+                                      "('f32' or 'bf16x3')")
+        on = code == _lib.MODEL_GEMM_MODES["bf16x3"]
+        if on and _lib.lib().ctts_taco_decoder_packed_bf16x3_bytes(C.byref(self.c_config())) == 0:
+            raise NotImplementedError("cookietts_amd.Tacotron2 decoder: split-bf16 products refused by the library: "
+                                      + _lib.last_error())
+        if on != self._bf16x3:
+            self._invalidate()        # the packed blob is per mode
+        self._f32_gemm_mode, self._bf16x3 = mode, on
+        return self
+
+    @property
+    def f32_gemm_mode(self):
+        return self._f32_gemm_mode
 
     # ------------------------------------------------------------------ plumbing ----
     def c_config(self):
@@ -220,7 +250,12 @@ class Decoder(_cache.PackedModule):
     def _pack(self, device):
         lib = _lib.lib()
         cfg = self.c_config()
-        nbytes = _lib.nbytes(lib.ctts_taco_decoder_packed_bytes, C.byref(cfg), what="unsupported decoder config")
+        # split-bf16 mode: the fp32 blob followed by the cells' hi | lo planes (every fp32 entry point takes it as the fp32 blob)
+        size_fn, pack_fn, pack_name = lib.ctts_taco_decoder_packed_bytes, lib.ctts_taco_decoder_pack, "ctts_taco_decoder_pack"
+        if self._bf16x3:
+            size_fn, pack_fn, pack_name = (lib.ctts_taco_decoder_packed_bf16x3_bytes, lib.ctts_taco_decoder_pack_bf16x3,
+                                           "ctts_taco_decoder_pack_bf16x3")
+        nbytes = _lib.nbytes(size_fn, C.byref(cfg), what="unsupported decoder config")
         keep = []
 
         def dev(t):
@@ -250,8 +285,7 @@ class Decoder(_cache.PackedModule):
         w.exp_smoothing_factor = float(self.exp_smoothing_factor.detach().reshape(-1)[0])
         with torch.cuda.device(device):
             blob = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-            _lib.check(lib.ctts_taco_decoder_pack(C.byref(cfg), C.byref(w), _lib.ptr(blob), _lib.stream(device)),
-                       "ctts_taco_decoder_pack")
+            _lib.check(pack_fn(C.byref(cfg), C.byref(w), _lib.ptr(blob), _lib.stream(device)), pack_name)
             torch.cuda.current_stream(device).synchronize()
         return blob
 
@@ -309,6 +343,10 @@ class Decoder(_cache.PackedModule):
             self._xchg = {key: xchg}
         assert len(xchg) == len(groups), (len(xchg), groups)
         xchg = list(xchg)
+        # the per-launch form: split-bf16 cells above 64 rows where the mode is on (the entry point runs the fp32 steps below that)
+        steps_fn, steps_name = lib.ctts_taco_decoder_steps_hidden_f32, "ctts_taco_decoder_steps_hidden_f32"
+        if self._bf16x3:
+            steps_fn, steps_name = lib.ctts_taco_decoder_steps_bf16x3, "ctts_taco_decoder_steps_bf16x3"
 
         def ctl_words(xb):
             return xb[-PERSIST_CTL_WORDS:].view(torch.int32)[:4]
@@ -377,10 +415,10 @@ class Decoder(_cache.PackedModule):
                                 self._xchg = {}
                                 xb = None
                     if xb is None:
-                        _lib.check(lib.ctts_taco_decoder_steps_hidden_f32(
+                        _lib.check(steps_fn(
                             C.byref(cfg), _lib.ptr(blob), _lib.ptr(km), _lib.ptr(mel[g0:g1]), _lib.ptr(gate[g0:g1]),
                             _lib.ptr(align[g0:g1]), None if hidden is None else _lib.ptr(hidden[g0:g1]), g1 - g0, T, done, n,
-                            max_steps, _lib.ptr(ws), stream), "ctts_taco_decoder_steps_hidden_f32")
+                            max_steps, _lib.ptr(ws), stream), steps_name)
                 done += n
                 if fixed_steps is None:
                     _lib.check(lib.ctts_taco_stop_rule_f32(_lib.ptr(gate), B, max_steps, done - n, n,
@@ -745,6 +783,16 @@ class Tacotron2(nn.Module):
         self.tm_linear = nn.Linear(hp.torchMoji_attDim, hp.torchMoji_crushedDim)
         if hp.torchMoji_BatchNorm:
             self.tm_bn = nn.BatchNorm1d(hp.torchMoji_attDim, momentum=0.05)
+
+    def set_f32_gemm_mode(self, mode):
+        """``Decoder.set_f32_gemm_mode`` on this model's decoder (``"bf16x3"``: split-bf16 LSTM cell products in ``inference``
+        calls of 65 rows and more; encoder, postnet and the teacher-forced ``forward`` stay fp32).  Returns ``self``."""
+        self.decoder.set_f32_gemm_mode(mode)
+        return self
+
+    @property
+    def f32_gemm_mode(self):
+        return self.decoder.f32_gemm_mode
 
     @torch.no_grad()
     def inference(self, text_seq, text_lengths, speaker_id, torchmoji_hdn, gt_sylps=None, return_hidden_state=False,

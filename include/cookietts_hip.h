@@ -651,6 +651,41 @@ int ctts_taco_decoder_steps_hidden_f32(const ctts_taco_decoder_config* cfg, cons
                                        int32_t step0, int32_t n_steps, int32_t max_steps, void* workspace,
                                        void* stream);
 
+/* Split-bf16 (bf16x3) products for the three LSTM cell GEMMs of the free-running loop above 64 rows (batch >= 65: the plain
+ * schedule of the batched form; csrc/tacotron_batched_bf16x3.h).  Tensors, workspace layout and size, launch sequence and every
+ * other stage are the fp32 path's.
+ *   Weights, once at pack time from the fp32 value: w_hi = bf16_rne(w), w_lo = bf16_rne(w - w_hi).
+ *   Activations: the X operand of a cell ([prenet | context | hidden states], fp32 in the workspace) is split as it is read for
+ *   the product: x_hi = bf16_rne(x), x_lo = bf16_rne(x - x_hi).
+ *   Product, per step of 32 K columns on v_mfma_f32_16x16x32_bf16: acc += w_hi x_hi, then + w_lo x_hi, then + w_hi x_lo, fp32
+ *   accumulation; no lo x lo term.  The K slices of a workgroup's waves are summed in a fixed order; biases, gates, cell update,
+ *   the residual sum dec_h + d2_h and the hidden record are the fp32 cell epilogue unchanged.
+ *   Everything that is not a cell GEMM - query rows, projection row set, second prenet layer, both attention parts, init, the
+ *   stop rule (the caller's) - is unchanged and fp32.
+ *   An item's result does not depend on the other rows of the batch (one item-tile shape and one K split for every batch above
+ *   64 rows); a run is bit-identical to a repeat.
+ * Blob: ctts_taco_decoder_pack_bf16x3 writes the fp32 blob of ctts_taco_decoder_pack, byte for byte, followed by the hi | lo planes
+ * of the three cells ([m-tile][chunk of 32 K][hi | lo][lane][8 bf16]; a hi | lo pair is the 4 bytes of the fp32 weight), so
+ *   ctts_taco_decoder_packed_bf16x3_bytes == ctts_taco_decoder_packed_bytes + 4 * (4 Ra (P + Dm + Rd + Ra) + 4 Rd (Ra + Dm + Rd)
+ *                                            + 4 Rd2 (Rd + Rd2))      (+ 108 MB at the default shape)
+ * and EVERY other entry point (init, steps_f32 / steps_hidden_f32 / steps_persistent_f32 / steps_forced_f32, prenet_frames,
+ * project_frames) accepts the blob and gives the fp32 blob's bits.
+ * ctts_taco_decoder_steps_bf16x3 takes the arguments of ctts_taco_decoder_steps_hidden_f32.  At or below 64 rows it runs exactly
+ * what that entry point runs, bit for bit: those sizes are bound by the weight stream, not by the matrix pipe, and keep their
+ * pipelined schedule.  The teacher-forced loop and the persistent form have no split-bf16 variant.
+ * Refused before any launch (the size query returns 0, the others CTTS_E_ARG; ctts_last_error names the reason): shapes without
+ * the batched form (ctts_taco_decoder_max_batch(cfg) != 256), and shapes in which a K piece of a cell (prenet_dim, memory_dim,
+ * decoder_rnn_dim, attention_rnn_dim) is not a multiple of 32 wide - the message names the field.  (Today's conditions of the
+ * batched form imply the second: every K a multiple of 64 leaves no piece that is not a multiple of 32.) */
+size_t ctts_taco_decoder_packed_bf16x3_bytes(const ctts_taco_decoder_config* cfg);
+int ctts_taco_decoder_pack_bf16x3(const ctts_taco_decoder_config* cfg, const ctts_taco_decoder_weights* w,
+                                  void* packed, void* stream);
+int ctts_taco_decoder_steps_bf16x3(const ctts_taco_decoder_config* cfg, const void* packed,
+                                   const uint8_t* keep_masks, float* mel_out, float* gate_out,
+                                   float* align_out, float* hidden_out, int32_t batch, int32_t text_len,
+                                   int32_t step0, int32_t n_steps, int32_t max_steps, void* workspace,
+                                   void* stream);
+
 /* ---- Teacher-forced decoding: Decoder.forward (model.py:769-849) with p_teacher_forcing = 1, what GTA.py runs in eval() mode
  * (_2_ttm/tacotron2_tm/GTA.py:77-117, 264; _3_generate_postnets/GTA.py:192).  Three stages around the workspace, state layout,
  * ctts_taco_decoder_init_f32 prologue and align_out of the free-running steps above.  Built where

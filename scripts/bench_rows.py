@@ -648,6 +648,67 @@ def row_taco_forced(args):
     return rows
 
 
+def row_taco_bf16x3(args):
+    """``Decoder.inference(fixed_steps=256)`` above 64 rows with ``set_f32_gemm_mode("bf16x3")`` off / on on the same model: 65, 128
+    and 256 rows of 200 symbols, arms alternated ``--reps`` times in one process (device events around the whole call; a change of
+    mode repacks the blob, so every timed call follows an untimed one in the same mode).  The fp32 arm is the parent's code path:
+    it is the yardstick.  ``clears_10x_spread``: the per-step difference exceeds ten times the larger arm's spread (max - min over
+    the repetitions).  ``roofline`` per arm: the cells' FLOPs of a step (three products per operand pair in the split mode) against
+    the peak of the MFMA they run on, and the cells' weight bytes of a step against HBM; ``bound`` names the larger fraction."""
+    from cookietts_amd.tacotron2 import Tacotron2
+    hp = synthetic.tacotron_hparams()
+    m = Tacotron2(hp)
+    m.load_state_dict(synthetic.to_torch(synthetic.tacotron_state_dict(hp, seed=1234)))
+    m = m.cuda().eval()
+    dec = m.decoder
+    TXT, steps = 200, 256
+    reps = getattr(args, "reps", 5)
+    rng = np.random.default_rng(1234)
+    cell_weights = sum(p.numel() for n, p in dec.named_parameters() if "rnn" in n and "weight" in n)
+    peaks = {"f32": ("v_mfma_f32_16x16x4_f32", FP32_MFMA_PEAK_TFLOPS, 1), "bf16x3": ("v_mfma_f32_16x16x32_bf16", F16_MFMA_PEAK_TFLOPS, 3)}
+    rows = []
+    for B in _batches(args, (65, 128, 256)):
+        mem = torch.from_numpy((rng.standard_normal((B, TXT, dec._memory_in_dim)) * 0.5).astype(np.float32)).cuda()
+        lens = torch.full((B,), TXT, dtype=torch.int64).cuda()
+        masks = torch.from_numpy(synthetic.prenet_dropout_masks(steps, B, hp.prenet_dim)).cuda()
+
+        def call(mode):
+            dec.set_f32_gemm_mode(mode)
+            dec.inference(mem, lens, keep_masks=masks, fixed_steps=steps)            # (re)packs where the mode changed; untimed
+            return _event_ms(lambda: dec.inference(mem, lens, keep_masks=masks, fixed_steps=steps), 1)
+        times = {"f32": [], "bf16x3": []}
+        for mode in times:
+            for _ in range(max(1, args.warmup)):
+                call(mode)
+        for _ in range(reps):
+            for mode in times:
+                times[mode].append(call(mode))
+        stat = {}
+        for mode, t in times.items():
+            med = sorted(t)[len(t) // 2]
+            us = med / steps * 1e3
+            kernel, peak, products = peaks[mode]
+            tflops = 2.0 * products * B * cell_weights / (us * 1e-6) / 1e12
+            gbs = cell_weights * 4 / 1e9 / (us * 1e-6)
+            mfma_frac, hbm_frac = tflops / peak, gbs / 8000.0
+            stat[mode] = {"reps_ms": t, "median_ms": med, "us_per_step": us, "spread_us_per_step": (max(t) - min(t)) / steps * 1e3,
+                          "roofline": {"kernel": "three cell launches of the step (" + kernel + ")", "bound": "mfma" if mfma_frac >= hbm_frac else "hbm",
+                                       "mfma": {"achieved": tflops, "peak": peak, "unit": "TFLOP/s", "frac": mfma_frac},
+                                       "hbm": {"achieved": gbs, "peak": 8000.0, "unit": "GB/s", "frac": hbm_frac}}}
+        diff = stat["f32"]["us_per_step"] - stat["bf16x3"]["us_per_step"]
+        spread = max(stat["f32"]["spread_us_per_step"], stat["bf16x3"]["spread_us_per_step"])
+        rows.append({"row": "C/taco_bf16x3", "metric": "Decoder.inference(fixed_steps=256), 200 symbols, f32 GEMM mode off / on (device events, "
+                                                       "arms alternated)", "batch": B, "steps": steps, "dtype": "f32", "schedule": "plain",
+                     "value": stat["bf16x3"]["us_per_step"], "unit": "us/step", "higher_is_better": False, "f32": stat["f32"],
+                     "bf16x3": stat["bf16x3"], "f32_minus_bf16x3_us_per_step": diff, "f32_over_bf16x3": stat["f32"]["us_per_step"] / stat["bf16x3"]["us_per_step"],
+                     "max_spread_us_per_step": spread, "clears_10x_spread": bool(diff > 10 * spread), "f32_gemm_mode": "f32 | bf16x3 (the two arms)"})
+        del mem, masks
+        dec._ws, dec._xchg = {}, {}
+        torch.cuda.empty_cache()
+    dec.set_f32_gemm_mode(None)
+    return rows
+
+
 def row_stft(args):
     from cookietts_amd import TacotronSTFT
     taco = TacotronSTFT().cuda()
@@ -694,17 +755,18 @@ if __name__ == "__main__":
                     help="main loop of the rows' fp32 conv-GEMMs, set on each model (model.set_f32_gemm_mode)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16"],
                     help="waveglow_ax: f16 = IEEE-half storage of the WN stacks (model.set_compute_dtype(torch.float16))")
-    ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab, waveglow_ax_sep_ab, taco_forced: repetitions of every arm (alternated)")
-    ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts, taco_forced) to these batch sizes (PMC passes)")
+    ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab, waveglow_ax_sep_ab, taco_forced, taco_bf16x3: repetitions of every arm (alternated)")
+    ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts, taco_forced, taco_bf16x3) to these batch sizes (PMC passes)")
     ap.add_argument("--arms", default="hip,torch,hip_f16,torch_f16,hip_bf16x3",
                     help="hifigan: arms to run (hip, hip_f16 or hip_bf16x3 alone for a profiler pass); waveglow_ax_sep_ab: sep, fold; taco_forced: forced, free")
     ap.add_argument("--ks", default="3,7", help="waveglow_ax_sep_ab: comma list of depthwise kernel sizes")
     args = ap.parse_args()
     fns = {"hifigan": row_hifigan, "waveflow": row_waveflow, "waveflow_table": row_waveflow_table, "waveflow_author": row_waveflow_author, "tacotron": row_tacotron, "stft": row_stft,
            "waveglow_ax": row_waveglow_ax_notebook, "waveglow_ax_ab": row_waveglow_ax_notebook_ab, "waveglow_ax_untts": row_waveglow_ax_untts,
-           "waveglow_ax_sep_ab": row_waveglow_ax_sep_ab, "taco_forced": row_taco_forced}
+           "waveglow_ax_sep_ab": row_waveglow_ax_sep_ab, "taco_forced": row_taco_forced, "taco_bf16x3": row_taco_bf16x3}
     for r in args.rows.split(","):
         out = fns[r](args)
         for line in (out if isinstance(out, list) else [out]):
-            line["f32_gemm_mode"] = line.get("arm") if line.get("arm") in ("f32", "bf16x3") else args.gemm_mode    # set on every model of the row (model.set_f32_gemm_mode)
+            if "f32_gemm_mode" not in line:                      # (taco_bf16x3 names its two arms itself)
+                line["f32_gemm_mode"] = line.get("arm") if line.get("arm") in ("f32", "bf16x3") else args.gemm_mode    # set on every model of the row (model.set_f32_gemm_mode)
             print(json.dumps(line), flush=True)
