@@ -192,6 +192,8 @@ SIGNATURES = {
                                               C.c_int32, _FP]),
     "ctts_taco_decoder_steps_forced_f32": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, C.c_int32, C.c_int32,
                                                      C.c_int32, C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
+    "ctts_taco_decoder_steps_forced_bf16x3": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, C.c_int32, C.c_int32,
+                                                        C.c_int32, C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
     "ctts_taco_project_frames_f32": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
     "ctts_taco_decoder_persistent_bytes": (C.c_size_t, [C.POINTER(TacoDecoderConfig), C.c_int32, C.c_int32]),
     "ctts_taco_decoder_steps_persistent_f32": (C.c_int, [C.POINTER(TacoDecoderConfig), _FP, _FP, _FP, _FP, _FP, C.c_int32,

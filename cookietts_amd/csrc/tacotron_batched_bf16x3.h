@@ -241,6 +241,30 @@ __global__ __launch_bounds__(WAVES * 64) void bgx_cell_attn_kernel(const BgArgs 
     else if (blockIdx.y == 0) attn_pre_body(at, apre, astart, *reinterpret_cast<BgAttnLds*>(bg_lds), blockIdx.x - nblk);
 }
 
+// two independent cells in one launch (teacher-forced loop: the attention RNN of step t + 1 and the second decoder RNN of step t):
+// workgroups [0, nblk0) of every grid row are a0's, [nblk0, gridDim.x) a1's.  The body is the one of the launches above, so a
+// cell's bits are the same alone and as a role.  (Two kernel parameters, not an array of roles: see bg_multi8_kernel.)
+template <int MTW, int NT, int S, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void bgx_cell2_kernel(const BgArgs a0, int nblk0, const BgArgs a1) {
+    extern __shared__ __attribute__((aligned(16))) bg_u4 bg_lds[];
+    if ((int)blockIdx.x < nblk0) bgx_cell_body<MTW, NT, S, WAVES>(a0, bg_lds, blockIdx.x, blockIdx.y);
+    else bgx_cell_body<MTW, NT, S, WAVES>(a1, bg_lds, blockIdx.x - nblk0, blockIdx.y);
+}
+
+template <int MTW, int NT, int S, int WAVES>
+int bgx_launch_shape2(const BgArgs& a0, const BgArgs& a1, int nb_pad, hipStream_t s) {
+    constexpr int LDS = bgx_lds_bytes<MTW, NT, S, WAVES>();
+    static_assert(LDS <= 160 * 1024, "LDS of a CU");
+    CTTS_CHECK_ARG(nb_pad % (16 * NT) == 0 && a0.pmode == 0 && a0.c_end == 0 && a1.pmode == 0 && a1.c_end == 0,
+                   "bf16x3 cell pair: %d rows are not whole item groups of %d", nb_pad, 16 * NT);
+    const int nblk0 = (a0.tiles + MTW - 1) / MTW, nblk1 = (a1.tiles + MTW - 1) / MTW, ny = nb_pad / (16 * NT);
+    int rc;
+    if ((rc = BG_ALLOW_LDS((bgx_cell2_kernel<MTW, NT, S, WAVES>), LDS))) return rc;
+    hipLaunchKernelGGL((bgx_cell2_kernel<MTW, NT, S, WAVES>), dim3(nblk0 + nblk1, ny), dim3(64 * WAVES), LDS, s, a0, nblk0, a1);
+    CTTS_CHECK_LAUNCH("bgx_cell2");
+    return CTTS_OK;
+}
+
 // nb_pad: a multiple of 16 NT; attn != NULL: the attention's part 1 rides along
 template <int MTW, int NT, int S, int WAVES>
 int bgx_launch_shape(const BgArgs& a, int nb_pad, const AttnArgs* attn, float* apre, int* astart, int batch, hipStream_t s) {

@@ -804,6 +804,10 @@ inline int bgx_launch_cell(const BgArgs& a, const float* planes, int nb_pad, con
                            hipStream_t s) {
     return bgx_launch_shape<4, 2, 3, 4>(bgx_args(a, planes), nb_pad, attn, apre, astart, batch, s);
 }
+// two independent cells as the two roles of one launch of that shape; a0's workgroups are the first of every grid row
+inline int bgx_launch_cell2(const BgArgs& a0, const float* planes0, const BgArgs& a1, const float* planes1, int nb_pad, hipStream_t s) {
+    return bgx_launch_shape2<4, 2, 3, 4>(bgx_args(a0, planes0), bgx_args(a1, planes1), nb_pad, s);
+}
 
 // One decoder step of the batched form (4 < batch <= MAX_BATCH, and batch <= 4 where the persistent kernel is not used): seven
 // dependent launches.  Plain schedule (more than 64 items, or CTTS_TACO_BG_NO_PIPE):
@@ -826,14 +830,16 @@ inline int bgx_launch_cell(const BgArgs& a, const float* planes, int nb_pad, con
 // pipelined schedule the EARLY sums that launches 6 / 7 hosted move: the attention RNN's [ctx | dec_h] columns are summed by its
 // own launch (FINAL over [prenet | ctx | dec_h]), its att_h columns ride in launch 2 of the step before (slot 0).  Above 16 rows
 // the next step's attention RNN is a role of launch 5 and its attention part 1 rides in launch 4: four launches per step (`merge`).
+// Split-bf16 cells (bf16x3, more than 64 rows): the plain schedule of either loop with its cell launches on the split planes
+// (bgx_launch_cell; the teacher-forced loop's two-role launch 5 is bgx_launch_cell2); every other launch is the fp32 one.
 int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uint8_t* keep_masks, float* mel_out, float* gate_out,
                   float* align_out, float* hidden_out, int batch, int text_len, int step0, int n_steps, int max_steps, hipStream_t s,
                   const float* prenet_all = nullptr, bool bf16x3 = false) {
     const auto& c = p.c;
     const int NB = ws_rows(p, batch);
     const bool forced = prenet_all != nullptr;
-    // split-bf16 cells: the plain schedule's three cell launches (more than 64 rows), free-running loop; `blob` then ends in the planes
-    const bool x3 = bf16x3 && NB > 64 && !forced;
+    // split-bf16 cells: the plain schedule's three cell launches (more than 64 rows), both loops; `blob` then ends in the planes
+    const bool x3 = bf16x3 && NB > 64;
     // above 16 rows the second decoder RNN of step t and the attention RNN of step t + 1 - independent of each other - are two roles of
     // ONE launch (four launches per step): 53.5 against 58.4, 69.9 / 84.5, 130.9 / 134.0, 206.8 / 213.3 us per step at 32 / 64 / 128 / 256
     // rows; at 16 rows, where the role has the attention RNN's narrower launch shape, 50.4 against 50.2 (profiles/r16_02)
@@ -911,7 +917,7 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
         // (teacher-forced loop: only a call's first step launches it - see launch 5)
         auto att_launch = [&](int st) { return pipe ? final_(att_args(st), 0, forced ? aD : aP, forced ? 1 : 2) : att_args(st); };
         if (x3) {
-            if ((rc = bgx_launch_cell(att_args(step), blob + p.x3_att, NB, &at, w.apre, w.astart, batch, s))) return rc;
+            if (!(merge && step > step0) && (rc = bgx_launch_cell(att_args(step), blob + p.x3_att, NB, &at, w.apre, w.astart, batch, s))) return rc;
         } else if (!(merge && step > step0) &&
                    (rc = bg_launch_cell(att_launch(step), NB, pipe && !forced ? nullptr : &at, w.apre, w.astart, batch, s))) return rc;
         // teacher-forced loop: the NEXT step's attention part 1 rides in launch 4, its attention RNN is a role of launch 5
@@ -939,9 +945,13 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
             if ((rc = BG_ALLOW_LDS(attn_post_kernel, BGA_POST_LDS_BYTES))) return rc;
             hipLaunchKernelGGL(attn_post_kernel, dim3(batch), dim3(256), BGA_POST_LDS_BYTES, s, at, w.qbuf, w.apre, w.astart);
             CTTS_CHECK_LAUNCH("attn_post");
-            if (x3) {
-                if ((rc = bgx_launch_cell(dec_args(cur), blob + p.x3_dec, NB, nullptr, nullptr, nullptr, batch, s))) return rc;
-                rc = bgx_launch_cell(d2_args(step), blob + p.x3_d2, NB, nullptr, nullptr, nullptr, batch, s);
+            if (x3) {      // (`ride` is NULL in the free-running loop: the three cells as three launches)
+                if ((rc = bgx_launch_cell(dec_args(cur), blob + p.x3_dec, NB, ride, w.apre, w.astart, batch, s))) return rc;
+                // teacher-forced loop: the second decoder RNN and the next step's attention RNN as two roles of one launch - 89.7 against
+                // 101.9 us per step as two launches at 128 rows, 151.6 / 153.4 at 256; with the attention RNN's workgroups first
+                // 90.3 and 156.6 (profiles/r19_00)
+                if (ride) rc = bgx_launch_cell2(d2_args(step), blob + p.x3_d2, att_args(step + 1), blob + p.x3_att, NB, s);
+                else rc = bgx_launch_cell(d2_args(step), blob + p.x3_d2, NB, nullptr, nullptr, nullptr, batch, s);
             } else if ((rc = bg_launch_cell(dec_args(cur), NB, ride, w.apre, w.astart, batch, s, 0))) return rc;
             else if (ride) rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, 0, d2_args(step), att_launch(step + 1), NB, s);
             else rc = bg_launch_cell(d2_args(step), NB, nullptr, nullptr, nullptr, batch, s);
@@ -1512,6 +1522,27 @@ int ctts_taco_decoder_steps_forced_f32(const ctts_taco_decoder_config* cfg, cons
                    workspace_bytes, w.total * sizeof(float));
     return batched_steps(p, w, static_cast<const float*>(packed), nullptr, nullptr, nullptr, align_out, hidden_out, batch, text_len,
                          step0, n_steps, max_steps, as_stream(stream), prenet_all);
+}
+
+int ctts_taco_decoder_steps_forced_bf16x3(const ctts_taco_decoder_config* cfg, const void* packed, const float* prenet_all,
+                                          float* align_out, float* hidden_out, int32_t batch, int32_t text_len, int32_t step0,
+                                          int32_t n_steps, int32_t max_steps, void* workspace, size_t workspace_bytes, void* stream) {
+    DecPlan p; DecWs w;
+    int rc = make_dec_plan(cfg, p); if (rc) return rc;
+    if ((rc = x3_refuse(p, "forced decoder bf16x3 steps"))) return rc;
+    // at or below 64 rows the loop keeps its fp32 schedules, bit for bit
+    if (batch <= 64)
+        return ctts_taco_decoder_steps_forced_f32(cfg, packed, prenet_all, align_out, hidden_out, batch, text_len, step0, n_steps, max_steps,
+                                                  workspace, workspace_bytes, stream);
+    CTTS_CHECK_ARG(packed && prenet_all && align_out && hidden_out && workspace, "forced decoder steps: NULL pointer");
+    CTTS_CHECK_ARG(batch <= MAX_BATCH && step0 >= 0 && n_steps >= 0 && step0 + n_steps <= max_steps,
+                   "forced decoder steps: batch=%d (1..%d) step0=%d n_steps=%d max_steps=%d", batch, MAX_BATCH, step0, n_steps, max_steps);
+    CTTS_CHECK_ARG(text_len >= 1, "forced decoder steps: text_len=%d", text_len);
+    dec_carve(p, batch, text_len, static_cast<float*>(workspace), w);
+    CTTS_CHECK_ARG(w.total * sizeof(float) <= workspace_bytes, "forced decoder steps: workspace %zu bytes < required %zu",
+                   workspace_bytes, w.total * sizeof(float));
+    return batched_steps(p, w, static_cast<const float*>(packed), nullptr, nullptr, nullptr, align_out, hidden_out, batch, text_len,
+                         step0, n_steps, max_steps, as_stream(stream), prenet_all, true);
 }
 
 int ctts_taco_project_frames_f32(const ctts_taco_decoder_config* cfg, const void* packed, const float* hidden, float* mel_out,

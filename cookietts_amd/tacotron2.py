@@ -204,12 +204,14 @@ class Decoder(_cache.PackedModule):
 
     def set_f32_gemm_mode(self, mode):
         """Products of the fp32 tensors, same name and meaning as on the vocoder classes: ``None`` / ``"default"`` / ``"f32"``
-        (exact fp32 MFMA) or ``"bf16x3"``: split bf16 for the three LSTM cell GEMMs of the free-running loop (``inference``) in
-        calls of 65 rows and more - weights (once, at pack time) and the cells' inputs (as they are read) are carried as ``hi + lo``
-        bf16 and every product is ``w_hi x_hi + w_lo x_hi + w_hi x_lo`` on the bf16 MFMA with fp32 accumulation (the arithmetic
-        is listed at ``ctts_taco_decoder_steps_bf16x3``).  Everything else stays fp32 and unchanged: the other stages of the
-        step, calls of 64 rows and fewer (their pipelined schedule, bit for bit), the persistent form (<= 8 rows) and the
-        teacher-forced ``forward`` - they read the fp32 part of the same blob.  ``"bf16x6"`` is not built for this model
+        (exact fp32 MFMA) or ``"bf16x3"``: split bf16 for the three LSTM cell GEMMs of the free-running loop (``inference``) and
+        of the teacher-forced loop (``forward``) in calls - in ``forward``, groups - of 65 rows and more: weights (once, at pack
+        time) and the cells' inputs (as they are read) are carried as ``hi + lo`` bf16 and every product is
+        ``w_hi x_hi + w_lo x_hi + w_hi x_lo`` on the bf16 MFMA with fp32 accumulation (the arithmetic is listed at
+        ``ctts_taco_decoder_steps_bf16x3``; ``ctts_taco_decoder_steps_forced_bf16x3`` is the teacher-forced loop under the same
+        contract).  Everything else stays fp32 and unchanged: the other stages of the step, the prenet and projection frame
+        operators of ``forward``, calls of 64 rows and fewer (their fp32 schedules, bit for bit) and the persistent form
+        (<= 8 rows) - they read the fp32 part of the same blob.  ``"bf16x6"`` is not built for this model
         (``NotImplementedError``); an unknown name is a ``ValueError``.  Works on a model that is still on the CPU.  Returns
         ``self``; the packed blob (108 MB larger in this mode at the default shape) and the workspaces are dropped when the mode
         changes and kept when it does not.  ``NotImplementedError`` - here, not at the first call - if the library refuses
@@ -481,7 +483,9 @@ class Decoder(_cache.PackedModule):
         memory [B, txt_T, memory_dim]: the bottlenecked memory, copied out of the head of the decoder workspace).
         Three library stages: the prenet of every frame (``ctts_taco_prenet_frames_f32``), the loop without prenet and
         projection (``ctts_taco_decoder_steps_forced_f32``, five launches per step, four above 16 rows), the projection of every step
-        (``ctts_taco_project_frames_f32``).  ``keep_masks`` [>=T, 2, B, prenet_dim] uint8 overrides the random prenet dropout
+        (``ctts_taco_project_frames_f32``).  With ``set_f32_gemm_mode("bf16x3")`` a group of more than 64 rows runs the loop as
+        ``ctts_taco_decoder_steps_forced_bf16x3`` (split-bf16 products in the three LSTM cell GEMMs, same four launches per step);
+        groups of 64 rows and fewer, the prenet and the projection stay fp32.  ``keep_masks`` [>=T, 2, B, prenet_dim] uint8 overrides the random prenet dropout
         (mask t = step t's prenet input).  What the HIP path does not build raises NotImplementedError, by name."""
         self.check_forced(decoder_inputs.shape[2], preserve_decoder, teacher_force_till, p_teacher_forcing)
         B, n_mel, n_frames = decoder_inputs.shape
@@ -537,11 +541,15 @@ class Decoder(_cache.PackedModule):
                                                          nb, T, _lib.ptr(ws), ws.numel() * 4, stream), "ctts_taco_decoder_init_f32")
                 # the bottlenecked memory (model.py:796-797, returned at :849) is the first array of the workspace, [rows][T][Dm]
                 memory_out[g0:g1] = ws[:nb * T * self.memory_dim].view(nb, T, self.memory_dim)
+                # split-bf16 cells where the mode is on and the group has more than 64 rows; every other group - the trailing group
+                # of a batch above the library's limit too - takes the fp32 entry point on the same blob
+                steps_fn, steps_name = lib.ctts_taco_decoder_steps_forced_f32, "ctts_taco_decoder_steps_forced_f32"
+                if self._bf16x3 and nb > 64:
+                    steps_fn, steps_name = lib.ctts_taco_decoder_steps_forced_bf16x3, "ctts_taco_decoder_steps_forced_bf16x3"
                 for s0 in range(0, n_frames, chunk):
-                    _lib.check(lib.ctts_taco_decoder_steps_forced_f32(
+                    _lib.check(steps_fn(
                         C.byref(cfg), _lib.ptr(blob), _lib.ptr(prenet_all), _lib.ptr(align[g0:g1]), _lib.ptr(hidden[g0:g1]), nb, T,
-                        s0, min(chunk, n_frames - s0), n_frames, _lib.ptr(ws), ws.numel() * 4, stream),
-                        "ctts_taco_decoder_steps_forced_f32")
+                        s0, min(chunk, n_frames - s0), n_frames, _lib.ptr(ws), ws.numel() * 4, stream), steps_name)
                 _lib.check(lib.ctts_taco_project_frames_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(hidden[g0:g1]), _lib.ptr(mel[g0:g1]),
                                                            _lib.ptr(gate[g0:g1]), nb, n_frames, stream),
                            "ctts_taco_project_frames_f32")
@@ -785,8 +793,9 @@ class Tacotron2(nn.Module):
             self.tm_bn = nn.BatchNorm1d(hp.torchMoji_attDim, momentum=0.05)
 
     def set_f32_gemm_mode(self, mode):
-        """``Decoder.set_f32_gemm_mode`` on this model's decoder (``"bf16x3"``: split-bf16 LSTM cell products in ``inference``
-        calls of 65 rows and more; encoder, postnet and the teacher-forced ``forward`` stay fp32).  Returns ``self``."""
+        """``Decoder.set_f32_gemm_mode`` on this model's decoder (``"bf16x3"``: split-bf16 LSTM cell products in the decoder loop
+        of ``inference`` and of the teacher-forced ``forward`` at 65 rows and more; encoder, postnet and the prenet / projection
+        frame operators of ``forward`` stay fp32).  Returns ``self``."""
         self.decoder.set_f32_gemm_mode(mode)
         return self
 

@@ -672,7 +672,8 @@ int ctts_taco_decoder_steps_hidden_f32(const ctts_taco_decoder_config* cfg, cons
  * project_frames) accepts the blob and gives the fp32 blob's bits.
  * ctts_taco_decoder_steps_bf16x3 takes the arguments of ctts_taco_decoder_steps_hidden_f32.  At or below 64 rows it runs exactly
  * what that entry point runs, bit for bit: those sizes are bound by the weight stream, not by the matrix pipe, and keep their
- * pipelined schedule.  The teacher-forced loop and the persistent form have no split-bf16 variant.
+ * pipelined schedule.  The persistent form has no split-bf16 variant; the teacher-forced loop's is
+ * ctts_taco_decoder_steps_forced_bf16x3, below, under this same contract.
  * Refused before any launch (the size query returns 0, the others CTTS_E_ARG; ctts_last_error names the reason): shapes without
  * the batched form (ctts_taco_decoder_max_batch(cfg) != 256), and shapes in which a K piece of a cell (prenet_dim, memory_dim,
  * decoder_rnn_dim, attention_rnn_dim) is not a multiple of 32 wide - the message names the field.  (Today's conditions of the
@@ -715,6 +716,24 @@ int ctts_taco_decoder_steps_forced_f32(const ctts_taco_decoder_config* cfg, cons
                                        float* align_out, float* hidden_out, int32_t batch, int32_t text_len,
                                        int32_t step0, int32_t n_steps, int32_t max_steps, void* workspace,
                                        size_t workspace_bytes, void* stream);
+/* The same loop with split-bf16 (bf16x3) products for the three LSTM cell GEMMs above 64 rows (batch >= 65): the arithmetic
+ * contract of ctts_taco_decoder_steps_bf16x3, word for word - weights split once at pack time, X split as it is read, per 32 K
+ * columns acc += w_hi x_hi, + w_lo x_hi, + w_hi x_lo with fp32 accumulation, no lo x lo term, the fp32 cell epilogue (biases,
+ * gates, cell update, dec_h + d2_h and its hidden_out record) unchanged.  Same arguments and checks as
+ * ctts_taco_decoder_steps_forced_f32; `packed` is the blob of ctts_taco_decoder_pack_bf16x3.  The launch sequence is that entry
+ * point's four launches per step with the three cell launches on the split planes (the second decoder RNN of step t and the
+ * attention RNN of step t + 1 stay two roles of one launch); prenet_all, query rows, both attention parts, the context rows of
+ * hidden_out and the two one-shot operators around the loop are fp32 and unchanged.
+ *   A cell's bits are the same whether it runs in a launch of its own or as a role, so blocks of steps chain bit for bit; an
+ *   item's result does not depend on the other rows of the batch; a run is bit-identical to a repeat.
+ *   At or below 64 rows it runs exactly what ctts_taco_decoder_steps_forced_f32 runs, bit for bit.
+ *   ctts_taco_decoder_steps_forced_f32 on the bf16x3 blob keeps giving the fp32 bits.
+ * Refused before any pointer is touched, with the refusals of the other bf16x3 entry points (no batched form; a K piece of a cell
+ * that is not a multiple of 32 wide, named by field). */
+int ctts_taco_decoder_steps_forced_bf16x3(const ctts_taco_decoder_config* cfg, const void* packed, const float* prenet_all,
+                                          float* align_out, float* hidden_out, int32_t batch, int32_t text_len,
+                                          int32_t step0, int32_t n_steps, int32_t max_steps, void* workspace,
+                                          size_t workspace_bytes, void* stream);
 /* The gate and mel projections of every step after the loop (model.py:763-765), one launch over all B x n_frames columns:
  *   hidden [B][second_decoder_rnn_dim + memory_dim][n_frames] -> mel_out [B][n_mel][n_frames], gate_out [B][n_frames] (logits). */
 int ctts_taco_project_frames_f32(const ctts_taco_decoder_config* cfg, const void* packed, const float* hidden,

@@ -709,6 +709,97 @@ def row_taco_bf16x3(args):
     return rows
 
 
+def row_taco_forced_bf16x3(args):
+    """The teacher-forced loop above 64 rows with ``set_f32_gemm_mode("bf16x3")`` off / on on the same model: 65, 128, 192 and 256
+    rows (192 = what GTA.py runs: batch_size 32 x 6), 200 symbols, 400 steps.  Per row count two pairs of arms, each pair alternated
+    ``--reps`` times in one process after a warm-up of each and timed by device events:
+      loop   the decoder loop alone, through the library, on an initialised workspace and a prenet_all computed before:
+             ``ctts_taco_decoder_steps_forced_f32`` on the fp32 blob against ``ctts_taco_decoder_steps_forced_bf16x3`` on the bf16x3
+             blob (four launches per step in both)
+      call   the whole ``Tacotron2.forward`` (encoder + prenet frames + loop + projection + postnet) in either mode; a change of
+             mode repacks the blob, so every timed call follows an untimed one in the same mode
+    The fp32 arms are the parent's code path: they are the yardstick.  ``clears_10x_spread``: the difference of the two arms exceeds
+    ten times the larger arm's spread (max - min over the repetitions); where it does not, the difference is not claimed."""
+    import ctypes as C
+    from cookietts_amd import _lib
+    from cookietts_amd.tacotron2 import Tacotron2
+    hp = synthetic.tacotron_hparams()
+    m = Tacotron2(hp)
+    m.load_state_dict(synthetic.to_torch(synthetic.tacotron_state_dict(hp, seed=1234)))
+    m = m.cuda().eval()
+    dec, lib = m.decoder, _lib.lib()
+    TXT, T = 200, 400
+    reps = getattr(args, "reps", 5)
+    rng = np.random.default_rng(1234)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    cfg, st = dec.c_config(), _lib.stream(dev)
+    blobs = {}
+    for mode in ("f32", "bf16x3"):                           # both blobs of the one model, kept for the loop arms
+        dec.set_f32_gemm_mode(mode)
+        blobs[mode] = dec._ensure_packed(dev)
+    entry = {"f32": ("ctts_taco_decoder_steps_forced_f32", lib.ctts_taco_decoder_steps_forced_f32),
+             "bf16x3": ("ctts_taco_decoder_steps_forced_bf16x3", lib.ctts_taco_decoder_steps_forced_bf16x3)}
+    rows = []
+    for B in _batches(args, (65, 128, 192, 256)):
+        text = torch.from_numpy(rng.integers(1, hp.n_symbols, size=(B, TXT))).cuda()
+        lens = torch.full((B,), TXT, dtype=torch.int64).cuda()
+        spk = (torch.arange(B) % hp.n_speakers).cuda()
+        tm = torch.from_numpy(rng.standard_normal((B, hp.torchMoji_attDim)).astype(np.float32)).cuda()
+        syl = torch.from_numpy(rng.uniform(2.5, 6.5, B).astype(np.float32)).cuda()
+        gt = torch.from_numpy(synthetic.synthetic_mel(B, T, hp.n_mel_channels)).cuda()
+        masks = torch.from_numpy(synthetic.prenet_dropout_masks(T, B, hp.prenet_dim)).cuda()
+        mem = torch.from_numpy((rng.standard_normal((B, TXT, dec._memory_in_dim)) * 0.5).astype(np.float32)).cuda()
+        lens32 = lens.to(torch.int32)
+        ws = torch.empty(lib.ctts_taco_decoder_workspace_bytes(C.byref(cfg), B, TXT) // 4, dtype=torch.float32, device=dev)
+        pre_bytes = lib.ctts_taco_prenet_frames_bytes(C.byref(cfg), B, T)
+        prenet_all = torch.empty(pre_bytes // 4, dtype=torch.float32, device=dev)
+        align = torch.empty(B, T, TXT, device=dev)
+        hidden = torch.empty(B, hp.second_decoder_rnn_dim + hp.memory_bottleneck_dim, T, device=dev)
+        _lib.check(lib.ctts_taco_prenet_frames_f32(C.byref(cfg), _lib.ptr(blobs["f32"]), _lib.ptr(gt), None, _lib.ptr(masks),
+                                                  _lib.ptr(prenet_all), pre_bytes, B, T, st), "ctts_taco_prenet_frames_f32")
+
+        def loop(mode):                                    # ms of the loop alone: the workspace is initialised outside the events
+            blob, (name, fn) = blobs[mode], entry[mode]
+            _lib.check(lib.ctts_taco_decoder_init_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(mem), _lib.ptr(lens32), B, TXT, _lib.ptr(ws),
+                                                     ws.numel() * 4, st), "ctts_taco_decoder_init_f32")
+            return _event_ms(lambda: _lib.check(fn(C.byref(cfg), _lib.ptr(blob), _lib.ptr(prenet_all), _lib.ptr(align), _lib.ptr(hidden),
+                                                   B, TXT, 0, T, T, _lib.ptr(ws), ws.numel() * 4, st), name), 1)
+
+        def call(mode):
+            fwd = lambda: m(gt, lens, text, lens, spk, syl, tm, teacher_force_till=0, p_teacher_forcing=1.0, keep_masks=masks)   # noqa: E731
+            m.set_f32_gemm_mode(mode)
+            fwd()                                              # (re)packs where the mode changed; untimed
+            return _event_ms(fwd, 1)
+        row = {"row": "C/taco_forced_bf16x3", "metric": "teacher-forced decoder loop and Tacotron2.forward, 200 symbols, 400 steps, f32 GEMM "
+                                                        "mode off / on (device events, arms alternated)", "batch": B, "steps": T,
+               "dtype": "f32", "schedule": "plain", "launches_per_step": 4, "f32_gemm_mode": "f32 | bf16x3 (the two arms)"}
+        for pname, fn in (("loop", loop), ("call", call)):
+            times = {"f32": [], "bf16x3": []}
+            for mode in times:
+                for _ in range(max(1, args.warmup)):
+                    fn(mode)
+            for _ in range(reps):
+                for mode in times:
+                    times[mode].append(fn(mode))
+            stat = {}
+            for mode, t in times.items():
+                med = sorted(t)[len(t) // 2]
+                stat[mode] = {"reps_ms": t, "median_ms": med, "spread_ms": max(t) - min(t)}
+                if pname == "loop":
+                    stat[mode].update(us_per_step=med / T * 1e3, spread_us_per_step=(max(t) - min(t)) / T * 1e3)
+            diff = stat["f32"]["median_ms"] - stat["bf16x3"]["median_ms"]
+            spread = max(stat["f32"]["spread_ms"], stat["bf16x3"]["spread_ms"])
+            row[pname] = dict(stat, f32_minus_bf16x3_ms=diff, f32_over_bf16x3=stat["f32"]["median_ms"] / stat["bf16x3"]["median_ms"],
+                              max_spread_ms=spread, clears_10x_spread=bool(abs(diff) > 10 * spread))
+        row.update({"value": row["loop"]["bf16x3"]["us_per_step"], "unit": "us/step", "higher_is_better": False})
+        rows.append(row)
+        del ws, prenet_all, hidden, align, mem, gt, masks
+        dec._ws, dec._xchg = {}, {}
+        torch.cuda.empty_cache()
+    m.set_f32_gemm_mode(None)
+    return rows
+
+
 def row_stft(args):
     from cookietts_amd import TacotronSTFT
     taco = TacotronSTFT().cuda()
@@ -755,18 +846,19 @@ if __name__ == "__main__":
                     help="main loop of the rows' fp32 conv-GEMMs, set on each model (model.set_f32_gemm_mode)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16"],
                     help="waveglow_ax: f16 = IEEE-half storage of the WN stacks (model.set_compute_dtype(torch.float16))")
-    ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab, waveglow_ax_sep_ab, taco_forced, taco_bf16x3: repetitions of every arm (alternated)")
-    ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts, taco_forced, taco_bf16x3) to these batch sizes (PMC passes)")
+    ap.add_argument("--reps", type=int, default=5, help="waveglow_ax_ab, waveglow_ax_sep_ab, taco_forced, taco_bf16x3, taco_forced_bf16x3: repetitions of every arm (alternated)")
+    ap.add_argument("--batches", default="", help="comma list: restrict the multi-batch rows (waveglow_ax, waveglow_ax_untts, taco_forced, taco_bf16x3, taco_forced_bf16x3) to these batch sizes (PMC passes)")
     ap.add_argument("--arms", default="hip,torch,hip_f16,torch_f16,hip_bf16x3",
                     help="hifigan: arms to run (hip, hip_f16 or hip_bf16x3 alone for a profiler pass); waveglow_ax_sep_ab: sep, fold; taco_forced: forced, free")
     ap.add_argument("--ks", default="3,7", help="waveglow_ax_sep_ab: comma list of depthwise kernel sizes")
     args = ap.parse_args()
     fns = {"hifigan": row_hifigan, "waveflow": row_waveflow, "waveflow_table": row_waveflow_table, "waveflow_author": row_waveflow_author, "tacotron": row_tacotron, "stft": row_stft,
            "waveglow_ax": row_waveglow_ax_notebook, "waveglow_ax_ab": row_waveglow_ax_notebook_ab, "waveglow_ax_untts": row_waveglow_ax_untts,
-           "waveglow_ax_sep_ab": row_waveglow_ax_sep_ab, "taco_forced": row_taco_forced, "taco_bf16x3": row_taco_bf16x3}
+           "waveglow_ax_sep_ab": row_waveglow_ax_sep_ab, "taco_forced": row_taco_forced, "taco_bf16x3": row_taco_bf16x3,
+           "taco_forced_bf16x3": row_taco_forced_bf16x3}
     for r in args.rows.split(","):
         out = fns[r](args)
         for line in (out if isinstance(out, list) else [out]):
-            if "f32_gemm_mode" not in line:                      # (taco_bf16x3 names its two arms itself)
+            if "f32_gemm_mode" not in line:                      # (taco_bf16x3 and taco_forced_bf16x3 name their two arms themselves)
                 line["f32_gemm_mode"] = line.get("arm") if line.get("arm") in ("f32", "bf16x3") else args.gemm_mode    # set on every model of the row (model.set_f32_gemm_mode)
             print(json.dumps(line), flush=True)
