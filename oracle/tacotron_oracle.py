@@ -169,7 +169,8 @@ def _conv1d_same(x, w, b):
     T = x.shape[2]
     y = np.zeros((x.shape[0], w.shape[0], T), dtype=FT)
     for j in range(K):
-        y += np.einsum("oc,bct->bot", w[:, :, j], xp[:, :, j:j + T]).astype(FT)
+        # optimize=True: the contraction goes through BLAS (50x faster at encoder sizes; same equation, pairwise-blocked sums)
+        y += np.einsum("oc,bct->bot", w[:, :, j], xp[:, :, j:j + T], optimize=True).astype(FT)
     return (y + b[None, :, None]).astype(FT)
 
 
