@@ -135,6 +135,19 @@ class TacoMemoryWeights(C.Structure):
                                    "syl_res_weight", "tm_gamma", "tm_beta", "tm_mean", "tm_var", "tm_w", "tm_b")]
 
 
+class RetryConfig(C.Structure):
+    """``ctts_retry_config``."""
+    _fields_ = [(n, C.c_double) for n in ("diagonality_weighting", "max_focus_weighting", "min_focus_weighting",
+                                          "avg_focus_weighting", "target_score", "absolutely_required_score")] + [
+        (n, C.c_int32) for n in ("max_attempts", "absolute_maximum_tries", "n_texts", "per_text", "n_mel", "t_cap", "enc_cap")]
+
+
+class RetryStatus(C.Structure):
+    """``ctts_retry_status``: the first 32 bytes of a retry state."""
+    _fields_ = [("done", C.c_int32), ("n_passes", C.c_int32), ("min_best_score", C.c_double), ("min_tries", C.c_int32),
+                ("n_without_winner", C.c_int32), ("max_best_length", C.c_int32), ("max_best_T", C.c_int32)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check every symbol the
 # header declares is exported.
 _CFG = C.POINTER(WaveGlowConfig)
@@ -284,6 +297,14 @@ SIGNATURES = {
     "ctts_taco_stop_state_bytes": (C.c_size_t, [C.c_int32]),
     "ctts_taco_stop_reset": (C.c_int, [_FP, C.c_int32, C.c_int32, _FP]),
     "ctts_taco_stop_rule_f32": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _FP, _FP]),
+    "ctts_retry_state_bytes": (C.c_size_t, [C.POINTER(RetryConfig)]),
+    "ctts_retry_state_layout": (C.c_int, [C.POINTER(RetryConfig), C.POINTER(C.c_size_t)]),
+    "ctts_retry_reset": (C.c_int, [C.POINTER(RetryConfig), _FP, _FP]),
+    "ctts_retry_update_f32": (C.c_int, [C.POINTER(RetryConfig), _FP, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP,
+                                        _FP]),
+    "ctts_retry_vocoder_batch_f32": (C.c_int, [C.POINTER(RetryConfig), _FP, _FP, C.c_int32, C.c_float, _FP]),
+    "ctts_pcm16_concat": (C.c_int, [_FP, C.c_int32, _FP, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _FP, C.c_int64, _FP,
+                                    _FP]),
     "ctts_affine_rows_f32": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                        C.c_float, _FP]),
     "ctts_vol_unscale_f32": (C.c_int, [_FP, C.c_int64, _FP]),

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["alignment_metric", "get_first_over_thresh"]
+__all__ = ["alignment_metric", "get_first_over_thresh", "metric_table"]
 
 _KEYS = ("diagonalitys", "avg_prob", "encoder_max_focus", "encoder_min_focus", "encoder_avg_focus", "p_missing_enc")
 
@@ -38,6 +38,16 @@ def alignment_metric(alignments, input_lengths=None, output_lengths=None, enc_mi
                      average_across_batch=False):
     """alignments [B, dec, enc] -> dict of per-item scores (utils.py:59-120), same keys and dtypes
     (``diagonalitys`` float64, the rest float32).  Unlike the reference (:81) the argument is left untouched."""
+    out = metric_table(alignments, input_lengths, output_lengths, enc_min_thresh)
+    res = {k: (out[:, i] if i == 0 else out[:, i].to(torch.float32)) for i, k in enumerate(_KEYS)}
+    if average_across_batch:                                   # utils.py:105-111
+        res = {k: v.mean() for k, v in res.items()}
+    return res
+
+
+def metric_table(alignments, input_lengths=None, output_lengths=None, enc_min_thresh=0.7):
+    """The six scores of :func:`alignment_metric` as the library writes them: float64 [B, 6], columns in the order of the
+    dict's keys (the table ``ctts_retry_update_f32`` reads)."""
     al = _device_f32(alignments, "alignment_metric")
     if al.dim() != 3:
         raise ValueError(f"alignment_metric expects [B, dec, enc], got {tuple(al.shape)}")
@@ -54,7 +64,4 @@ def alignment_metric(alignments, input_lengths=None, output_lengths=None, enc_mi
         _lib.check(lib.ctts_alignment_metric_f32(_lib.ptr(al), _lib.ptr(il), _lib.ptr(ol), B, dec, enc,
                                                  float(enc_min_thresh), _lib.ptr(out), _lib.ptr(ws), nbytes, stream),
                    "ctts_alignment_metric_f32")
-    res = {k: (out[:, i] if i == 0 else out[:, i].to(torch.float32)) for i, k in enumerate(_KEYS)}
-    if average_across_batch:                                   # utils.py:105-111
-        res = {k: v.mean() for k, v in res.items()}
-    return res
+    return out

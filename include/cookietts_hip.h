@@ -919,6 +919,85 @@ int ctts_taco_stop_reset(void* state, int32_t batch, int32_t max_decoder_steps, 
 int ctts_taco_stop_rule_f32(const float* gate_logits, int32_t batch, int32_t gate_ld, int32_t step0, int32_t n_steps,
                             float gate_threshold, int32_t gate_delay, void* state, void* stream);
 
+/* ---- the T2S retry loop: best-of-N selection, vocoder batch, int16 PCM ------------------------------------------
+ * _5_infer/t2s_server/text2speech.py:548-651 runs Tacotron passes over rows = n_texts * per_text candidates (row =
+ * j * per_text + k is candidate k of text j) until every text has a candidate scoring at least target_score or a stop rule
+ * fires, reading every candidate back to the host to score it.  These entry points keep that loop's state on the device;
+ * the host reads one 32-byte status block per pass.  Caller-owned device memory, nothing allocated or synchronised
+ * inside, no kernel waits on another workgroup.  (ABI 7: additions do not bump the version.) */
+typedef struct ctts_retry_config {
+    double diagonality_weighting, max_focus_weighting, min_focus_weighting, avg_focus_weighting; /* :378-381: 0.5 1.0 0.5 1.0 */
+    double target_score, absolutely_required_score;   /* :334: t2s_config.json's 0.75; -1e3 */
+    int32_t max_attempts, absolute_maximum_tries;     /* :334: 64; 2048 */
+    int32_t n_texts, per_text;                        /* simultaneous_texts, batch_size_per_text; each and their product <= 4096 */
+    int32_t n_mel, t_cap, enc_cap;                    /* capacity of the kept winners: [n_mel][t_cap] mel and, when
+                                                       * enc_cap > 0, [t_cap][enc_cap] alignments per text */
+} ctts_retry_config;
+
+/* The first 32 bytes of the state: what the host reads after a pass. */
+typedef struct ctts_retry_status {
+    int32_t done;              /* 0 go on; 1 min(best_score) >= target_score (:552); 2 the max_attempts rule (:621);
+                                * 3 the absolute_maximum_tries rule (:623).  Sticky: once non-zero, updates are no-ops */
+    int32_t n_passes;          /* updates counted (:560), the one a rule fired in included */
+    double min_best_score;     /* np.amin(best_score) */
+    int32_t min_tries;         /* np.amin(tries) */
+    int32_t n_without_winner;  /* texts no candidate has won yet: the reference's assertion at :636 when not 0 */
+    int32_t max_best_length;   /* max over texts of the winners' output_length (:650); 0 without winners */
+    int32_t max_best_T;        /* max over texts of the winners' pass length */
+} ctts_retry_status;
+
+/* State layout: sections in this order, each starting on a 16-byte boundary (N = n_texts, R = rows):
+ *   ctts_retry_status status
+ *   double  best_score[N]            reset to -1e5 (:548)
+ *   double  detail[N][6]             the winner's { weighted_score as score_str prints it (:606, before the 1e-7 of :615),
+ *                                    diagonality, max_dur, min_dur, avg_dur, mis_dur punishment }
+ *   int32_t tries[N], best_length[N] (the winner's output_length), best_T[N] (its pass's T), best_pass[N] (0-based pass,
+ *           -1 = no winner), best_row[N] (row in that pass), changed[N] (row that won in the LAST update, else -1)
+ *   float   best_mel[N][n_mel][t_cap]        columns [0, best_T) hold the winner's whole pass-length mel
+ *   float   best_alignments[N][t_cap][enc_cap]   rows [0, best_T), columns [0, enc of that pass)
+ *   scratch of the last update: double row_score[R] (the score each row entered the replay with), double row_detail[R][6],
+ *           int32_t row_flags[R][8]
+ * ctts_retry_state_bytes: the size, or 0 (ctts_last_error names the reason) for a config outside the limits above. */
+size_t ctts_retry_state_bytes(const ctts_retry_config* cfg);
+/* Byte offsets of the CTTS_RETRY_SECTIONS sections above, in that order (status, best_score, detail, tries, best_length,
+ * best_T, best_pass, best_row, changed, best_mel, best_alignments, row_score, row_detail, row_flags): host code, no GPU. */
+#define CTTS_RETRY_SECTIONS 14
+int ctts_retry_state_layout(const ctts_retry_config* cfg, size_t* offsets);
+/* :548-551: best_score = -1e5, tries = 0, no winners, status cleared. */
+int ctts_retry_reset(const ctts_retry_config* cfg, void* state, void* stream);
+/* One pass of :563-625 (and the loop condition of :552), three launches:
+ *   (a) one flag per row: any NaN in that row of mel [rows][n_mel][T], gate [rows][T] or alignments [rows][T][enc] (:614);
+ *   (b) one workgroup scores every row in IEEE double with the operation order of :598-605 from metrics [rows][6]
+ *       (ctts_alignment_metric_f32's out; columns 1-5 are rounded to float32 first, which is what .item() of the reference's
+ *       float32 tensors yields), max(a, b) as Python's (a unless b > a: a NaN first argument stays), no fused multiply-add;
+ *       the mis_dur punishment only where text_lengths[j] > 12; a flagged row scores 1e-7 (:615; the `== float('nan')` beside
+ *       it is always false).  Then :590-625 are replayed in the reference's order, texts ascending, candidates ascending:
+ *       score > best_score[j] (strict: the first of equal scores wins, NaN never wins) makes the row text j's winner,
+ *       tries[j] += 1, and after every candidate the stop rules of :621-625 look at min(tries) and min(best_score) over all
+ *       texts; when one fires the remaining candidates of the pass are not considered (raise StopIteration).  The status
+ *       block is written last;
+ *   (c) every text whose winner changed copies that row's mel (and alignments when enc_cap > 0) into the state.
+ * detail [rows][6] (or NULL) receives every row's six detail doubles.  output_lengths int32 [rows], text_lengths int32
+ * [n_texts], both on the device.  CTTS_E_ARG before any launch for T > t_cap or enc > enc_cap > 0. */
+int ctts_retry_update_f32(const ctts_retry_config* cfg, const float* mel, const float* gate, const float* alignments,
+                          const double* metrics, const int32_t* output_lengths, const int32_t* text_lengths, int32_t T,
+                          int32_t enc, double* detail, void* state, void* stream);
+/* :645-651: mel_out [n_texts][n_mel][t_out]; element [j][m][c] = best_mel[j][m][c] for c < best_T[j], pad_value beyond (the
+ * reference: -11.52).  The reference pads the winners' whole pass-length mels, so frames between a winner's output_length and
+ * its pass's T keep the decoder's values.  t_out is the status block's max_best_length.  A text without a winner
+ * (n_without_winner > 0) is the caller's error; its rows are all pad_value. */
+int ctts_retry_vocoder_batch_f32(const ctts_retry_config* cfg, const void* state, float* mel_out, int32_t t_out,
+                                 float pad_value, void* stream);
+/* :675-695 for a vocoder batch audio [batch][ld] (fp32, or IEEE half with is_half != 0): of row b the first
+ * min(frames[b] * hop, ld) samples (:677-678), then silence_samples zeros (:690-692: behind EVERY clip, the last one too),
+ * each sample widened to fp32, multiplied by 32768 in fp32 and truncated toward zero to int16 (:695).  Two deliberate
+ * differences: a product outside [-32768, 32767] saturates and NaN gives 0 (numpy's astype('int16') is platform-defined for
+ * both).  Rows are written back to back in order (what the sox merge behind :707 produces); offsets [batch + 1] (device
+ * int64) receives each row's first sample and the total.  A total above pcm_capacity: nothing is written beyond the
+ * capacity and offsets[batch] is minus the total; batch * (ld + silence_samples) always suffices. */
+int ctts_pcm16_concat(const void* audio, int32_t is_half, const int32_t* frames, int32_t batch, int64_t ld, int32_t hop,
+                      int32_t silence_samples, int16_t* pcm, int64_t pcm_capacity, int64_t* offsets, void* stream);
+
 /* ---- main loop of the fp32 conv-GEMM ------------------------------------------------------------------------
  * Every fp32 path of the library (WaveGlow fp32, WaveFlow, the ax WaveGlow, conv1d / LSTM input projections, STFT)
  * goes through one conv-GEMM.  mode 0 (default): v_mfma_f32_32x32x2_f32, exact fp32 products.  mode 1 ("split bf16"):
