@@ -620,24 +620,28 @@ class WaveGlow(_cache.PackedModule):
             torch.cuda.current_stream(device).synchronize()
         return blob, ops
 
-    def _to_latent_length(self, h, B, rows_n, hT, hld, T, ld, dst, interpolate, stream):
+    def _to_latent_length(self, h, B, rows_n, hT, hld, T, ld, dst, interpolate, stream, two_d):
         """``_upsample_mels`` after the transposed convs (ax:177-185, glow_ax.py:365-372 / 548-553): linear interpolation
         (align_corners=True) to the latent's length when the net's factor is not hop // n_group, else a centre crop -
-        the 1-D rule ``[pad_l : -pad_r]`` or the 2-D WN's ``[pad : -(pad + pad % 2)]``."""
-        lib = _lib.lib()
+        the 1-D rule ``[pad_l : -pad_r]`` (the model's own net on both cores, and the 1-D WN's) or, ``two_d``, the 2-D WN's
+        ``[pad : -(pad + pad % 2)]``."""
         if interpolate:
+            lib = _lib.lib()
             for b in range(B):
                 _lib.check(lib.ctts_resample_rows_f32(_lib.ptr(h[b]), _lib.ptr(dst[b]), 1, rows_n, hT, hld, PAD, T, ld, PAD, 0,
                                                       0.0, stream), "ctts_resample_rows_f32")
             return
-        if self.waveflow:
+        if two_d:
             pad = (hT - T) // 2
             lo, hi = pad, pad + pad % 2
         else:
-            lo, hi = (hT - T) // 2, -((T - hT) // 2)
+            # ``pad_r = -(audio_len-cond_len)//2`` is (cond_len - audio_len) // 2 (the minus binds first): floor on both sides,
+            # so an odd difference leaves one column too many in the reference and its WN fails - refused below
+            lo = hi = (hT - T) // 2
         if hT - lo - hi != T or lo < 0:
             raise RuntimeError(f"upsampled conditioning of length {hT} cannot be cropped to the latent's {T} columns "
                                f"(the reference fails on the same shapes)")
+        lib = _lib.lib()
         for b in range(B):      # shifted copy: 'nearest' at scale 1 from the source advanced by `lo` columns
             _lib.check(lib.ctts_resample_rows_f32(h[b].data_ptr() + 4 * lo, _lib.ptr(dst[b]), 1, rows_n, hT - lo, hld, PAD, T,
                                                   ld, PAD, 2, 1.0, stream), "ctts_resample_rows_f32")
@@ -733,7 +737,8 @@ class WaveGlow(_cache.PackedModule):
             T = out_steps
             ld = _ld_for(T)
             xw = rows(c_wn_in + (0 if grp else sdim) + (16 if grp else 0))
-            self._to_latent_length(h, B, c_wn_in, hT, hld, T, ld, xw, factor != self.hop_length // self.n_group, stream)
+            self._to_latent_length(h, B, c_wn_in, hT, hld, T, ld, xw, factor != self.hop_length // self.n_group, stream,
+                                   two_d=False)                              # efficient_model_ax._upsample_mels: the 1-D rule
         # per flow: WN speaker embedding, conv stack -> 2C*n_layers rows
         C2L = 2 * self.WN_config['n_channels'] * self.WN_config['n_layers']
         wn_up = ops.get('wn_tconv')                 # per-flow TransposedUpsampleNet behind the WN cond stack
@@ -758,7 +763,7 @@ class WaveGlow(_cache.PackedModule):
                 for tc in wn_up[k]:
                     h, hT, hld = tc(h, B, hT, hld, stream)
                 self._to_latent_length(h, B, C2L, hT, hld, T_out, ld_out, frames[k],
-                                       self._wn_tconv_factor != self.hop_length // self.n_group, stream)
+                                       self._wn_tconv_factor != self.hop_length // self.n_group, stream, two_d=self.waveflow)
         return frames, ld_out, T_out
 
     # --------------------------------------------------------------------- the path ----

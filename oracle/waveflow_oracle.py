@@ -158,7 +158,7 @@ def to_latent_length(cond, L, interpolation_required, two_d):
         pad = (n - L) // 2
         out = cond[:, :, pad:n - (pad + pad % 2)]
     else:
-        pad_l, pad_r = (n - L) // 2, -((L - n) // 2)
+        pad_l, pad_r = (n - L) // 2, (-(L - n)) // 2            # ax:179-180 as Python reads it: the unary minus binds first
         out = cond[:, :, pad_l:n - pad_r]
     assert out.shape[2] == L, f"crop of {n} columns to {L} fails in the reference as well"
     return np.ascontiguousarray(out)
