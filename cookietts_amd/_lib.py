@@ -108,6 +108,16 @@ class LstmWeights(C.Structure):
     _fields_ = [("w_ih", _FP), ("w_hh", _FP), ("b_ih", _FP), ("b_hh", _FP)]
 
 
+class TorchMojiConfig(C.Structure):
+    """``ctts_torchmoji_config``."""
+    _fields_ = [(n, C.c_int32) for n in ("nb_tokens", "embedding_dim", "hidden_size")]
+
+
+class TorchMojiWeights(C.Structure):
+    """``ctts_torchmoji_weights``: ``lstm[layer][direction]``."""
+    _fields_ = [("embed", _FP), ("lstm", (LstmWeights * 2) * 2), ("attention_vector", _FP)]
+
+
 class TacoDecoderWeights(C.Structure):
     _fields_ = [("bottleneck_w", _FP), ("memory_layer_w", _FP), ("query_w", _FP), ("v_w", _FP), ("loc_conv_w", _FP),
                 ("loc_dense_w", _FP), ("prenet_w1", _FP), ("prenet_w2", _FP),
@@ -226,6 +236,16 @@ SIGNATURES = {
     "ctts_lstm_biseq_f32": (C.c_int, [_FP, _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       _FP, _FP, C.c_size_t, _FP]),
+    "ctts_lstm_biseq_hardsig_f32": (C.c_int, [_FP, _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, _FP, _FP, C.c_size_t, _FP]),
+    "ctts_torchmoji_packed_bytes": (C.c_size_t, [C.POINTER(TorchMojiConfig)]),
+    "ctts_torchmoji_pack_f32": (C.c_int, [C.POINTER(TorchMojiConfig), C.POINTER(TorchMojiWeights), _FP, _FP]),
+    "ctts_torchmoji_workspace_bytes": (C.c_size_t, [C.POINTER(TorchMojiConfig), C.c_int32, C.c_int32]),
+    "ctts_torchmoji_lengths": (C.c_int, [_FP, _FP, C.c_int32, C.c_int32, _FP]),
+    "ctts_torchmoji_features_f32": (C.c_int, [C.POINTER(TorchMojiConfig), _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP,
+                                              C.c_size_t, _FP]),
+    "ctts_attention_pool_f32": (C.c_int, [_FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "ctts_taco_embed_f32": (C.c_int, [_FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, _FP]),
     "ctts_taco_memory_f32": (C.c_int, [C.POINTER(TacoMemoryWeights), _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32,

@@ -315,7 +315,10 @@ __device__ __forceinline__ void bg_body(const BgArgs& a, bg_u4* lds, int blk, in
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
                     pre[g] = sum[g] + sq.gadd[(size_t)it * sq.ga_bstride + (size_t)(g * H + unit) * sq.ga_ld + sq.ga_pad + tb];
-                const float ig = bg_sigmoid(pre[0]), fg = bg_sigmoid(pre[1]), gg = tanhf(pre[2]), og = bg_sigmoid(pre[3]);
+                float ig, fg, og;
+                if (sq.hardsig) { ig = hard_sigmoidf_(pre[0]); fg = hard_sigmoidf_(pre[1]); og = hard_sigmoidf_(pre[3]); }
+                else { ig = bg_sigmoid(pre[0]); fg = bg_sigmoid(pre[1]); og = bg_sigmoid(pre[3]); }
+                const float gg = tanhf(pre[2]);
                 const float cy = fg * a.c[ix] + ig * gg;
                 const float hy = og * tanhf(cy);
                 a.c[ix] = cy;

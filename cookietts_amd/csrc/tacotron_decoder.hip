@@ -30,6 +30,8 @@ __device__ __forceinline__ float4 load4_nt(const float* p) {
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+// torchMoji's gate (utils/torchmoji/lstm.py:352-357): clamp(0.2 x + 0.5, 0, 1), plain fp32
+__device__ __forceinline__ float hard_sigmoidf_(float x) { return fminf(fmaxf(fmaf(0.2f, x, 0.5f), 0.0f), 1.0f); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -138,6 +140,7 @@ struct LstmSeq {
     const int* lengths; int step, reverse;
     float* out; long long out_bstride; int out_tstride, out_col;
     float* hn; int hn_stride, hn_col;
+    int hardsig;              // gates i, f, o through hard_sigmoidf_ instead of the logistic (uniform over the launch; 0 everywhere but torchMoji)
 };
 
 // Column window of one launch.  The decoder splits every cell's matvec in two: the columns whose inputs are known
@@ -305,7 +308,10 @@ __device__ __forceinline__ void lstm_body(const LstmCall& q, float* __restrict__
             }
         }
         if (active) {
-            const float ig = sigmoidf_(pre[0]), fg = sigmoidf_(pre[1]), gg = tanhf(pre[2]), og = sigmoidf_(pre[3]);
+            float ig, fg, og;
+            if (sq.hardsig) { ig = hard_sigmoidf_(pre[0]); fg = hard_sigmoidf_(pre[1]); og = hard_sigmoidf_(pre[3]); }
+            else { ig = sigmoidf_(pre[0]); fg = sigmoidf_(pre[1]); og = sigmoidf_(pre[3]); }
+            const float gg = tanhf(pre[2]);
             const float cy = fg * c[idx] + ig * gg;
             const float hy = og * tanhf(cy);
             c[idx] = cy;
@@ -1697,11 +1703,12 @@ int ctts_lstm_seq_f32(const void* packed, const float* x, const int32_t* lengths
     return CTTS_OK;
 }
 
-int ctts_lstm_biseq_f32(const void* packed_fwd, const void* packed_bwd, const float* x, const int32_t* lengths, float* out,
-                        int64_t out_bstride, int32_t out_tstride, int32_t out_col_fwd, int32_t out_col_bwd, float* hn,
-                        int32_t hn_stride, int32_t hn_col_fwd, int32_t hn_col_bwd, int32_t batch, int32_t T, int32_t input_size,
-                        int32_t hidden_size, int32_t ld, int32_t pad, void* workspace_fwd, void* workspace_bwd,
-                        size_t workspace_bytes, void* stream) {
+namespace {
+int biseq_run(int hardsig, const void* packed_fwd, const void* packed_bwd, const float* x, const int32_t* lengths, float* out,
+              int64_t out_bstride, int32_t out_tstride, int32_t out_col_fwd, int32_t out_col_bwd, float* hn,
+              int32_t hn_stride, int32_t hn_col_fwd, int32_t hn_col_bwd, int32_t batch, int32_t T, int32_t input_size,
+              int32_t hidden_size, int32_t ld, int32_t pad, void* workspace_fwd, void* workspace_bwd,
+              size_t workspace_bytes, void* stream) {
     hipStream_t s = as_stream(stream);
     CTTS_CHECK_ARG(workspace_fwd != workspace_bwd, "lstm_biseq: the two directions need their own workspaces");
     SeqDir d[2];
@@ -1711,6 +1718,7 @@ int ctts_lstm_biseq_f32(const void* packed_fwd, const void* packed_bwd, const fl
     rc = seq_prepare(packed_bwd, x, lengths, 1, out, out_bstride, out_tstride, out_col_bwd, hn, hn_stride, hn_col_bwd, batch, T,
                      input_size, hidden_size, ld, pad, workspace_bwd, workspace_bytes, s, d[1]);
     if (rc) return rc;
+    d[0].sq.hardsig = d[1].sq.hardsig = hardsig;
     const LstmPart whole{nullptr, nullptr, 0, 0, 1};
     for (int step = 0; step < T && batch > MAX_NB; ++step) {      // batched form: the recurrent product as an MFMA GEMM over the batch
         BgArgs a[2];
@@ -1737,6 +1745,27 @@ int ctts_lstm_biseq_f32(const void* packed_fwd, const void* packed_bwd, const fl
         if (rc) return rc;
     }
     return CTTS_OK;
+}
+}  // namespace
+
+int ctts_lstm_biseq_f32(const void* packed_fwd, const void* packed_bwd, const float* x, const int32_t* lengths, float* out,
+                        int64_t out_bstride, int32_t out_tstride, int32_t out_col_fwd, int32_t out_col_bwd, float* hn,
+                        int32_t hn_stride, int32_t hn_col_fwd, int32_t hn_col_bwd, int32_t batch, int32_t T, int32_t input_size,
+                        int32_t hidden_size, int32_t ld, int32_t pad, void* workspace_fwd, void* workspace_bwd,
+                        size_t workspace_bytes, void* stream) {
+    return biseq_run(0, packed_fwd, packed_bwd, x, lengths, out, out_bstride, out_tstride, out_col_fwd, out_col_bwd, hn, hn_stride,
+                     hn_col_fwd, hn_col_bwd, batch, T, input_size, hidden_size, ld, pad, workspace_fwd, workspace_bwd,
+                     workspace_bytes, stream);
+}
+
+int ctts_lstm_biseq_hardsig_f32(const void* packed_fwd, const void* packed_bwd, const float* x, const int32_t* lengths, float* out,
+                                int64_t out_bstride, int32_t out_tstride, int32_t out_col_fwd, int32_t out_col_bwd, float* hn,
+                                int32_t hn_stride, int32_t hn_col_fwd, int32_t hn_col_bwd, int32_t batch, int32_t T,
+                                int32_t input_size, int32_t hidden_size, int32_t ld, int32_t pad, void* workspace_fwd,
+                                void* workspace_bwd, size_t workspace_bytes, void* stream) {
+    return biseq_run(1, packed_fwd, packed_bwd, x, lengths, out, out_bstride, out_tstride, out_col_fwd, out_col_bwd, hn, hn_stride,
+                     hn_col_fwd, hn_col_bwd, batch, T, input_size, hidden_size, ld, pad, workspace_fwd, workspace_bwd,
+                     workspace_bytes, stream);
 }
 
 }  // extern "C"

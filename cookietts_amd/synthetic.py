@@ -896,3 +896,26 @@ def hifigan_state_dict(cfg, seed=1234):
         sd[prefix + ".weight_g"] = g.astype(np.float32)
         sd[prefix + ".weight_v"] = rng.standard_normal(shape, dtype=np.float32)
     return sd
+
+
+def torchmoji_state_dict(nb_tokens, seed=1234, embedding_dim=256, hidden_size=512):
+    """State dict of the reference ``TorchMoji(nb_classes=None, nb_tokens, feature_output=True)``
+    (utils/torchmoji/model_def.py:134-140): its keys and shapes.  The reference's own init (biases 0, attention vector
+    N(0, 0.05^2)) would hide a dropped ``b_hh`` and leaves the hard sigmoid's clamps nearly unused; here LSTM weights are
+    N(0, (2.5 / sqrt(fan_in))^2), biases N(0, 0.3^2), the embedding U(-1.5, 1.5) and the attention vector N(0, 0.3^2), which puts
+    several per cent of the i / f / o pre-activations beyond each clamp (asserted in tests/test_torchmoji.py)."""
+    rng = np.random.default_rng(seed)
+    E, H = embedding_dim, hidden_size
+    sd = {"embed.weight": ((rng.random((nb_tokens, E), dtype=np.float32) * np.float32(2.0) - np.float32(1.0)) * np.float32(1.5))}
+    for layer, fan_in in ((0, E), (1, 2 * H)):
+        for sfx in ("", "_reverse"):
+            p = f"lstm_{layer}."
+            sd[p + "weight_ih_l0" + sfx] = np.float32(2.5 / np.sqrt(fan_in)) * rng.standard_normal((4 * H, fan_in), dtype=np.float32)
+            sd[p + "weight_hh_l0" + sfx] = np.float32(2.5 / np.sqrt(H)) * rng.standard_normal((4 * H, H), dtype=np.float32)
+            sd[p + "bias_ih_l0" + sfx] = np.float32(0.3) * rng.standard_normal((4 * H,), dtype=np.float32)
+            sd[p + "bias_hh_l0" + sfx] = np.float32(0.3) * rng.standard_normal((4 * H,), dtype=np.float32)
+    sd["attention_layer.attention_vector"] = np.float32(0.3) * rng.standard_normal((4 * H + E,), dtype=np.float32)
+    return sd
+
+
+__all__.append("torchmoji_state_dict")

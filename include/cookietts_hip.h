@@ -810,6 +810,59 @@ int ctts_lstm_biseq_f32(const void* packed_fwd, const void* packed_bwd, const fl
                         int32_t hn_stride, int32_t hn_col_fwd, int32_t hn_col_bwd, int32_t batch, int32_t T, int32_t input_size,
                         int32_t hidden_size, int32_t ld, int32_t pad, void* workspace_fwd, void* workspace_bwd,
                         size_t workspace_bytes, void* stream);
+/* The same layer with torchMoji's gates (utils/torchmoji/lstm.py:330-357): i, f, o through
+ * hard_sigmoid(v) = clamp(0.2 v + 0.5, 0, 1) - one fmaf and a fmaxf / fminf clamp, plain fp32 - and g through tanh;
+ * c' = f c + i g, h' = o tanh(c').  Same arguments, packed blobs (ctts_lstm_seq_packed_bytes / _pack_f32), workspaces
+ * (ctts_lstm_seq_workspace_bytes), batch forms and packed-sequence semantics as ctts_lstm_biseq_f32; a row of length 0 is idle. */
+int ctts_lstm_biseq_hardsig_f32(const void* packed_fwd, const void* packed_bwd, const float* x, const int32_t* lengths, float* out,
+                                int64_t out_bstride, int32_t out_tstride, int32_t out_col_fwd, int32_t out_col_bwd, float* hn,
+                                int32_t hn_stride, int32_t hn_col_fwd, int32_t hn_col_bwd, int32_t batch, int32_t T,
+                                int32_t input_size, int32_t hidden_size, int32_t ld, int32_t pad, void* workspace_fwd,
+                                void* workspace_bwd, size_t workspace_bytes, void* stream);
+
+/* ---- torchMoji feature encoder (utils/torchmoji/model_def.py:100-253, feature_output=True) -------------------------------
+ * The T2S server's default style input (text2speech.py:497-509).  For tokens [B][T] (int64, device):
+ *   len[b]     = index of the last non-zero token of row b, plus one (model_def.py:193); zeros inside a sentence are tokens
+ *   x[b][t]    = tanh(embed[tok[b][t]])                                              E wide      (model_def.py:209-210)
+ *   lstm_0     packed bidirectional hard-sigmoid LSTM, E -> H per direction, zero initial states (model_def.py:189-190, 220)
+ *   lstm_1     the same, 2H -> H per direction, fed with lstm_0's [fwd | bwd]        (model_def.py:221)
+ *   feat[b][t] = [lstm_1 out (2H) | lstm_0 out (2H) | x (E)], F = 4H + E wide, zero for t >= len[b]   (model_def.py:224-229)
+ *   attention pooling (attlayer.py:48-66): logit = feat . attention_vector; w = exp(logit - M) for t < len[b], else 0;
+ *   a = w / sum_t w; out[b] = sum_t a[b][t] feat[b][t].  The reference takes M over the whole padded batch; here M is the
+ *   row's own maximum over its valid steps (the same quotient up to rounding, and no row can underflow to 0 / 0).
+ * Outputs are in INPUT order: the reference sorts by length for packing, un-sorts the features and returns the attention
+ * weights still sorted (model_def.py:194-195, 241-251); the rows here are independent, nothing is sorted.
+ * The dropouts are identity in eval(); the classifier head (output_layer) is not part of this.  Products are fp32 MFMA
+ * (CTTS_GEMM_DEFAULT); no reduced-precision mode: the call is a chain of 2 T + 12 dependent launches, launch-latency-bound.
+ * Limits: embedding_dim % 16 == 0, hidden_size % 64 == 0, batch <= 256 (what ctts_taco_decoder_max_batch answers for the
+ * batched form), T <= 8192.  Size queries answer 0 with a ctts_last_error message for a refused shape. */
+typedef struct ctts_torchmoji_config {
+    int32_t nb_tokens;       /* rows of the embedding table (50000) */
+    int32_t embedding_dim;   /* 256 */
+    int32_t hidden_size;     /* 512, per direction */
+} ctts_torchmoji_config;
+typedef struct ctts_torchmoji_weights {   /* device pointers, the checkpoint's own layouts */
+    const float* embed;                   /* embed.weight [nb_tokens][E] */
+    ctts_lstm_weights lstm[2][2];         /* lstm_{0,1}.{weight_ih,weight_hh,bias_ih,bias_hh}_l0 ([l][0]) and ..._l0_reverse ([l][1]) */
+    const float* attention_vector;        /* attention_layer.attention_vector [4H + E] */
+} ctts_torchmoji_weights;
+size_t ctts_torchmoji_packed_bytes(const ctts_torchmoji_config* cfg);
+int ctts_torchmoji_pack_f32(const ctts_torchmoji_config* cfg, const ctts_torchmoji_weights* w, void* packed, void* stream);
+size_t ctts_torchmoji_workspace_bytes(const ctts_torchmoji_config* cfg, int32_t batch, int32_t T);
+/* lengths[b] (int32, device) = last non-zero index of tokens[b][:] plus one, 0 for an all-zero row */
+int ctts_torchmoji_lengths(const int64_t* tokens, int32_t* lengths, int32_t batch, int32_t T, void* stream);
+/* features [B][4H + E]; attention [B][T] (zero beyond len[b]) or NULL.  lengths[b] in [0, T]: a row of length 0 yields a zero
+ * feature row and zero attention.  A token outside [0, nb_tokens) is clamped into the table on the device (the gather never
+ * reads outside it); reporting the range error is the host's business.  Every step of all T columns is issued; rows past
+ * their length idle.  Workspace contents: x0 [B][E][ld], x1 [B][2H][ld] (the channel-major padded inputs of the two input
+ * projections, zero outside [pad, pad + len[b])), feat [B][T][F], and the two directions' LSTM workspaces. */
+int ctts_torchmoji_features_f32(const ctts_torchmoji_config* cfg, const void* packed, const int64_t* tokens,
+                                const int32_t* lengths, float* features, float* attention, int32_t batch, int32_t T,
+                                void* workspace, size_t workspace_bytes, void* stream);
+/* The pooling alone (attlayer.py:48-66 as above): feat [B][T][D], vector [D], lengths int32 [B] in [0, T];
+ * out [B][D], att [B][T] or NULL.  T <= 8192 (one row's logits live in LDS). */
+int ctts_attention_pool_f32(const float* feat, const float* vector, const int32_t* lengths, float* out, float* att,
+                            int32_t batch, int32_t T, int32_t D, void* stream);
 
 /* x0[b][c][pad+t] = c < E ? embedding[text[b][t]][c] : spk_table[speaker[b]][c - E]   (model.py:1049, 284-288) */
 int ctts_taco_embed_f32(const float* embedding, const float* spk_table, const int64_t* text,
