@@ -191,6 +191,13 @@ SIGNATURES = {
     "ctts_wn_stack_f32": (C.c_int, [_CFG, _FP, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
     "ctts_flow_tail_f32": (C.c_int, [_CFG, _FP, C.c_int32, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
     "ctts_waveglow_flow_f32": (C.c_int, [_CFG, _FP, C.c_int32, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
+    "ctts_waveglow_forward_packed_bytes": (C.c_size_t, [_CFG]),
+    "ctts_waveglow_pack_forward_mix": (C.c_int, [_CFG, C.c_int32, _FP, _FP, _FP]),
+    "ctts_waveglow_forward_workspace_bytes": (C.c_size_t, [_CFG, C.c_int32, C.c_int32]),
+    "ctts_waveglow_forward_spk_f32": (C.c_int, [_CFG, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP,
+                                               C.c_size_t, _FP]),
+    "ctts_waveglow_flow_forward_f32": (C.c_int, [_CFG, _FP, _FP, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP,
+                                                C.c_size_t, _FP]),
     "ctts_waveflow_packed_bytes": (C.c_size_t, [C.POINTER(WaveFlowConfig)]),
     "ctts_waveflow_pack_flow": (C.c_int, [C.POINTER(WaveFlowConfig), C.c_int32, C.POINTER(WaveFlowFlowWeights), _FP, _FP]),
     "ctts_waveflow_workspace_bytes": (C.c_size_t, [C.POINTER(WaveFlowConfig), C.c_int32, C.c_int32]),

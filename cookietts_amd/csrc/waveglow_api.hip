@@ -421,7 +421,7 @@ int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k
 
 int run_wn_stack(const Plan& p, const Geom& g, const float* blob, int k, const float* audio, const float* h_all,
                  float* x, float* act, float* out, int batch, hipStream_t s, float* act_all = nullptr,
-                 const WnFold* fold = nullptr, const WnWinograd* wg = nullptr) {
+                 const WnFold* fold = nullptr, const WnWinograd* wg = nullptr, const CouplingForward* fwd = nullptr) {
     const auto& f = p.fl[k];
     const auto& d = p.fd[k];
     const long long cstride = (long long)p.C * g.ld;
@@ -498,7 +498,7 @@ int run_wn_stack(const Plan& p, const Geom& g, const float* blob, int k, const f
                 rc = launch_skip_end(act_all, (long long)act_stride, p.group_layers(gi),
                                      blob + f.skend_W + (size_t)gi * Plan::F32_SKIP_GROUP * p.C * E, fold->skend, gi == 0, last,
                                      blob + f.skend_b, blob + f.winv, fold->audio, fold->wave, batch, p.C, p.c.n_group, d.ch_off,
-                                     d.n_half, g.L, g.ld, g.pad, s);
+                                     d.n_half, g.L, g.ld, g.pad, s, last ? fwd : nullptr);
                 if (rc) return rc;
             } else if (last || (i + 1) % Plan::F32_SKIP_GROUP == 0) {
                 const int nl = p.group_layers(gi);
@@ -533,27 +533,69 @@ int run_wn_stack(const Plan& p, const Geom& g, const float* blob, int k, const f
 }
 
 int run_flow_tail(const Plan& p, const Geom& g, const float* blob, int k, const float* out, float* audio,
-                  float* wave, int batch, hipStream_t s) {
+                  float* wave, int batch, hipStream_t s, const CouplingForward* fwd = nullptr) {
     const auto& f = p.fl[k];
     const auto& d = p.fd[k];
     return launch_flow_tail(out, audio, wave, blob + f.end_w, blob + f.end_b, blob + f.winv, batch, p.C,
-                            p.c.n_group, d.ch_off, d.n_half, g.L, g.ld, g.pad, s);
+                            p.c.n_group, d.ch_off, d.n_half, g.L, g.ld, g.pad, s, fwd);
 }
 
 // One flow of the fp32 infer loop, in the form the tuning knobs and the workspace select: the folded, deferred stack (whose last
 // skip/end pass is also the flow's tail) or the unfolded stack followed by the flow tail; the Winograd in-layer form where carve()
 // gave it buffers.  `audio` [B][n_group][L] is updated in place (or, with `wave`, the mixed rows go there un-squeezed).  The
-// whole-infer entry and the one-flow stage entry both run exactly this.
+// whole-infer entry and the one-flow stage entry both run exactly this.  `fwd`: the forward direction (run_flow_forward) - the same
+// stack on rows a_0, and the tail, whichever kernel it is, does the forward coupling instead.
 int run_flow(const Plan& p, const Geom& g, const float* blob, int k, const Workspace& w, float* audio, const float* h_all,
-             float* wave, int batch, hipStream_t s) {
+             float* wave, int batch, hipStream_t s, const CouplingForward* fwd = nullptr) {
     const Tuning t = tuning();
     const bool folded = !t.f32_no_wn_fold && !t.f32_no_defer_skip;
     const WnWinograd wg{w.wgV, w.wgT, w.wgH, w.ldp};
     const WnFold fw{w.a16, w.skend, audio, wave};
     int rc = run_wn_stack(p, g, blob, k, audio, h_all, w.x, w.act, w.out, batch, s, w.act_all, folded ? &fw : nullptr,
-                          w.wgV ? &wg : nullptr);
+                          w.wgV ? &wg : nullptr, fwd);
     if (rc || folded) return rc;        // folded: the last skip/end pass of the flow was its tail
-    return run_flow_tail(p, g, blob, k, w.out, audio, wave, batch, s);
+    return run_flow_tail(p, g, blob, k, w.out, audio, wave, batch, s, fwd);
+}
+
+// ---- forward (analysis) direction, glow.py:267-312 --------------------------------------------------------------------------
+// The forward mix matrices W_k [n_rem][n_rem] live in a blob of their own (the infer blob holds their inverses only).
+size_t fwd_mix_off(const Plan& p, int k) {
+    size_t o = 0;
+    for (int j = 0; j < k; ++j) o += align_up((size_t)p.fd[j].n_rem * p.fd[j].n_rem);
+    return o;
+}
+int fwd_log_s_rows(const Plan& p, int k) {
+    int r = 0;
+    for (int j = 0; j < k; ++j) r += p.fd[j].n_half;
+    return r;
+}
+
+// Behind the infer workspace: the fp64 slots of the two-stage sums - ls_part [B][n_flows][nblk_ls] (one per tail workgroup) and
+// z_part [B][nblk_z]
+struct FwdWorkspace { Workspace w; double *ls_part, *z_part; int nblk_ls, nblk_z; size_t total; };
+
+void carve_fwd(const Plan& p, const Geom& g, int batch, float* base, FwdWorkspace& fw) {
+    carve(p, g, batch, base, fw.w);
+    fw.nblk_ls = (g.L + 255) / 256;
+    fw.nblk_z = (int)(((long long)p.c.n_group * g.L + FWD_SUMSQ_CHUNK - 1) / FWD_SUMSQ_CHUNK);
+    size_t o = fw.w.total;                              // a multiple of ALIGN_F floats = 256 bytes
+    auto take = [&](size_t doubles) { size_t r = o; o = align_up(o + 2 * doubles); return base ? reinterpret_cast<double*>(base + r) : nullptr; };
+    fw.ls_part = take((size_t)batch * p.c.n_flows * fw.nblk_ls);
+    fw.z_part = take((size_t)batch * fw.nblk_z);
+    fw.total = o;
+}
+
+// One flow of the forward loop: the head (forward 1x1 mix of the rows still in play; flow 0 reads the waveform un-squeezed),
+// then run_flow with the forward tail.  z [B][n_group][L] is updated in place; rows above ch_off are early outputs and stay.
+// log_s_flow: NULL or this flow's rows (item stride ls_bstride).  The whole-model entry and the stage entry both run exactly this.
+int run_flow_forward(const Plan& p, const Geom& g, const float* blob, const float* fwd_blob, int k, const FwdWorkspace& fw,
+                     float* z, const float* wave, const float* h_all, float* log_s_flow, long long ls_bstride, int batch,
+                     hipStream_t s) {
+    const auto& d = p.fd[k];
+    int rc = launch_flow_head_forward(fwd_blob + fwd_mix_off(p, k), wave, z, batch, p.c.n_group, d.ch_off, d.n_rem, g.L, s);
+    if (rc) return rc;
+    const CouplingForward cf{log_s_flow, ls_bstride, fw.ls_part + (size_t)k * fw.nblk_ls, (long long)p.c.n_flows * fw.nblk_ls};
+    return run_flow(p, g, blob, k, fw.w, z, h_all, nullptr, batch, s, &cf);
 }
 
 // ======================================================================================
@@ -1082,6 +1124,95 @@ int ctts_waveglow_flow_f32(const ctts_waveglow_config* cfg, const void* packed, 
         return CTTS_E_WORKSPACE;
     }
     return run_flow(p, g, static_cast<const float*>(packed), flow, w, audio, h_all, wave, batch, as_stream(stream));
+}
+
+size_t ctts_waveglow_forward_packed_bytes(const ctts_waveglow_config* cfg) {
+    Plan p;
+    if (make_plan(cfg, p)) return 0;
+    return fwd_mix_off(p, p.c.n_flows) * sizeof(float);
+}
+
+int ctts_waveglow_pack_forward_mix(const ctts_waveglow_config* cfg, int32_t flow, const float* w, void* packed_fwd,
+                                   void* stream) {
+    Plan p;
+    int rc = make_plan(cfg, p); if (rc) return rc;
+    CTTS_CHECK_ARG(flow >= 0 && flow < p.c.n_flows, "pack_forward_mix: flow %d", flow);
+    CTTS_CHECK_ARG(w && packed_fwd, "pack_forward_mix: NULL pointer");
+    const size_t n = (size_t)p.fd[flow].n_rem * p.fd[flow].n_rem;
+    CTTS_CHECK_HIP(hipMemcpyAsync(static_cast<float*>(packed_fwd) + fwd_mix_off(p, flow), w, n * sizeof(float),
+                                  hipMemcpyDeviceToDevice, as_stream(stream)));
+    return CTTS_OK;
+}
+
+size_t ctts_waveglow_forward_workspace_bytes(const ctts_waveglow_config* cfg, int32_t batch, int32_t frames) {
+    Plan p; Geom g; FwdWorkspace fw;
+    if (make_plan(cfg, p) || make_geom(p, frames, g)) return 0;
+    if (batch < 1) { set_error("forward_workspace_bytes: batch=%d", batch); return 0; }
+    carve_fwd(p, g, batch, nullptr, fw);
+    return fw.total * sizeof(float);
+}
+
+int ctts_waveglow_flow_forward_f32(const ctts_waveglow_config* cfg, const void* packed, const void* packed_fwd, int32_t flow,
+                                   float* z, const float* wave, const float* h_all, float* log_s, double* sum_log_s,
+                                   int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes, void* stream) {
+    Plan p; Geom g; FwdWorkspace fw;
+    int rc = make_plan(cfg, p); if (rc) return rc;
+    rc = make_geom(p, frames, g); if (rc) return rc;
+    CTTS_CHECK_ARG(flow >= 0 && flow < p.c.n_flows, "waveglow_flow_forward: flow %d", flow);
+    CTTS_CHECK_ARG(packed && packed_fwd && z && h_all && workspace && batch >= 1, "waveglow_flow_forward: bad argument");
+    CTTS_CHECK_ARG(wave == nullptr || flow == 0, "waveglow_flow_forward: only flow 0 reads the waveform (flow %d)", flow);
+    carve_fwd(p, g, batch, static_cast<float*>(workspace), fw);
+    if (fw.total * sizeof(float) > workspace_bytes) {
+        set_error("waveglow_flow_forward: workspace %zu bytes < required %zu", workspace_bytes, fw.total * sizeof(float));
+        return CTTS_E_WORKSPACE;
+    }
+    hipStream_t s = as_stream(stream);
+    rc = run_flow_forward(p, g, static_cast<const float*>(packed), static_cast<const float*>(packed_fwd), flow, fw, z, wave, h_all,
+                          log_s, (long long)p.fd[flow].n_half * g.L, batch, s);
+    if (rc || !sum_log_s) return rc;
+    return launch_sum_partials(fw.ls_part + (size_t)flow * fw.nblk_ls, (long long)p.c.n_flows * fw.nblk_ls, 0, fw.nblk_ls, sum_log_s,
+                               1, 1, batch, s);
+}
+
+int ctts_waveglow_forward_spk_f32(const ctts_waveglow_config* cfg, const void* packed, const void* packed_fwd, const float* mel,
+                                  const float* audio, const int64_t* speaker_ids, float* z, float* log_s, double* sums,
+                                  int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes, void* stream) {
+    Plan p; Geom g; FwdWorkspace fw;
+    int rc = make_plan(cfg, p); if (rc) return rc;
+    rc = make_geom(p, frames, g); if (rc) return rc;
+    CTTS_CHECK_ARG(packed && packed_fwd && mel && audio && z && workspace && batch >= 1, "forward: bad argument");
+    CTTS_CHECK_ARG(p.S == 0 || speaker_ids != nullptr, "multispeaker model (speaker_embed_dim=%d) needs speaker ids (glow.py:193)",
+                   p.c.speaker_embed_dim);
+    carve_fwd(p, g, batch, static_cast<float*>(workspace), fw);
+    if (fw.total * sizeof(float) > workspace_bytes) {
+        set_error("forward: workspace %zu bytes < required %zu", workspace_bytes, fw.total * sizeof(float));
+        return CTTS_E_WORKSPACE;
+    }
+    hipStream_t s = as_stream(stream);
+    const float* blob = static_cast<const float*>(packed);
+    const Workspace& w = fw.w;
+    // glow.py:276-282 with audio.size(1) == frames * hop keeps the columns infer's trim keeps: the same conditioning
+    rc = launch_upsample_squeeze(mel, blob + p.up_w, p.up_mfma ? blob + p.up_wp : nullptr, blob + p.up_b, w.spect, batch, p.c.n_mel_channels, frames,
+                                 p.c.win_length, p.c.hop_length, p.c.n_group, g.ld, g.pad, s);
+    if (rc) return rc;
+    rc = fill_speaker_rows(p, g, blob, speaker_ids, w.spk, batch, s);
+    if (rc) return rc;
+    rc = run_cond(p, g, blob, w.spect, w.spk, w.h_tmp, w.h_all, batch, s);
+    if (rc) return rc;
+    const int S = fwd_log_s_rows(p, p.c.n_flows);
+    for (int k = 0; k < p.c.n_flows; ++k) {
+        float* ls = log_s ? log_s + (size_t)fwd_log_s_rows(p, k) * g.L : nullptr;
+        rc = run_flow_forward(p, g, blob, static_cast<const float*>(packed_fwd), k, fw, z, k == 0 ? audio : nullptr, w.h_all, ls,
+                              (long long)S * g.L, batch, s);
+        if (rc) return rc;
+    }
+    if (!sums) return CTTS_OK;
+    rc = launch_sum_partials(fw.ls_part, (long long)p.c.n_flows * fw.nblk_ls, fw.nblk_ls, fw.nblk_ls, sums, p.c.n_flows + 1,
+                             p.c.n_flows, batch, s);
+    if (rc) return rc;
+    rc = launch_sumsq_partials(z, fw.z_part, batch, (long long)p.c.n_group * g.L, fw.nblk_z, s);
+    if (rc) return rc;
+    return launch_sum_partials(fw.z_part, fw.nblk_z, 0, fw.nblk_z, sums + p.c.n_flows, p.c.n_flows + 1, 1, batch, s);
 }
 
 int ctts_waveglow_infer_f32(const ctts_waveglow_config* cfg, const void* packed, const float* mel,

@@ -19,9 +19,27 @@ int launch_upsample_squeeze(const float* mel, const float* W, const float* Wp, c
                             int n_mel, int F, int win, int hop, int G, int ld, int pad, hipStream_t s);
 int launch_wn_start(const float* audio, const float* Ws, const float* bs, float* x, int batch, int C, int G,
                     int ch_off, int n_half, int L, int ld, int pad, hipStream_t s);
+// Forward (analysis) direction of a flow boundary, glow.py:305-307: where the tail kernels get one of these they compute
+// a_1 = exp(log_s) a_1 + b in place instead of the inverse coupling and mix nothing (the forward mix is the flow's head).
+struct CouplingForward {
+    float* log_s;             // NULL, or the flow's log_s rows: item b, row j at log_s + b * ls_bstride + j * L
+    long long ls_bstride;
+    double* part;             // per-workgroup sums of log_s, fp64: item b, 256-column block i at part + b * part_bstride + i
+    long long part_bstride;
+};
+constexpr int FWD_SUMSQ_CHUNK = 4096;     // floats of one item per workgroup of launch_sumsq_partials
 int launch_flow_tail(const float* out, float* audio, float* wave, const float* Wend, const float* bend,
                      const float* Winv, int batch, int C, int G, int ch_off, int n_half, int L, int ld, int pad,
-                     hipStream_t s);
+                     hipStream_t s, const CouplingForward* fwd = nullptr);
+// Head of a forward flow: rows [ch_off, ch_off + n_rem) of z [B][G][L] <- W [n_rem][n_rem] . those rows, in place (glow.py:294).
+// wave != NULL (flow 0: ch_off == 0, n_rem == G): the rows are read un-squeezed from wave [B][L*G] instead (glow.py:284).
+int launch_flow_head_forward(const float* W, const float* wave, float* z, int batch, int G, int ch_off, int n_rem, int L,
+                             hipStream_t s);
+// part[b][i] = fp64 sum of squares of floats [i * FWD_SUMSQ_CHUNK, ...) of item b's n_item floats (nblk = ceil(n_item / chunk))
+int launch_sumsq_partials(const float* z, double* part, int batch, long long n_item, int nblk, hipStream_t s);
+// out[b * out_bstride + k] = sum of the n doubles at part + b * part_bstride + k * part_kstride, always in the same order
+int launch_sum_partials(const double* part, long long part_bstride, long long part_kstride, int n, double* out, int out_bstride,
+                        int nk, int batch, hipStream_t s);
 
 // WN start / end folds (fp32 WaveGlow): layer 0's in-layer weights on the FOLD_ROWS-row input [audio_0; 1; 0 ...] and the skip rows
 // seen through `end` (waveglow_kernels.hip).  Pack time: fp64 products rounded once to fp32.
@@ -33,7 +51,7 @@ int launch_wn_start_ones(const float* audio, float* a16, int batch, int G, int c
                          hipStream_t s);
 int launch_skip_end(const float* act, long long act_stride, int nl, const float* Wf, float* acc, bool first, bool tail,
                     const float* bf, const float* Winv, float* audio, float* wave, int batch, int C, int G, int ch_off,
-                    int n_half, int L, int ld, int pad, hipStream_t s);
+                    int n_half, int L, int ld, int pad, hipStream_t s, const CouplingForward* fwd = nullptr);
 
 // Winograd F(2,3) in-layer form (fp32 WaveGlow; the algebra is at the kernels in waveglow_kernels.hip).  Pack time: dense
 // [3][rows][C] = G2, G3, -W2 of in_w [rows][C][3].  Per layer: x and the flow's cond rows -> V1..V4 [4][B][C][ldp] and the copies

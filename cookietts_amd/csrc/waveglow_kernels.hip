@@ -328,15 +328,42 @@ __device__ __forceinline__ void coupling_tail(float4 (&e)[2 * H], const float* s
     }
 }
 
+// The forward direction of the same boundary (glow.py:305-307), for wave 0 of a tail workgroup - all 64 lanes, also those whose four
+// steps lie beyond L (they load and store nothing and add 0): a1 = exp(log_s) a1 + b in place (expf, one fma), log_s stored where
+// asked, and the workgroup's sum of log_s in fp64 - each lane its <= 4 H values in a fixed order, then the butterfly over the wave -
+// to its own slot of `part`.  No atomics: a second stage adds the slots in a fixed order.
+template <int H>
+__device__ __forceinline__ void coupling_forward(const float4 (&e)[2 * H], float* __restrict__ audio, const CouplingForward& f,
+                                                 int b, int G, int ch_off, int L, int n) {
+    double s = 0.0;
+    if (n < L) {
+        float* ab = audio + ((size_t)b * G + ch_off + H) * L + n;
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            float4 a = *reinterpret_cast<const float4*>(ab + (size_t)j * L);
+            const float4 ls = e[H + j];
+            a.x = fmaf(expf(ls.x), a.x, e[j].x); a.y = fmaf(expf(ls.y), a.y, e[j].y);
+            a.z = fmaf(expf(ls.z), a.z, e[j].z); a.w = fmaf(expf(ls.w), a.w, e[j].w);
+            *reinterpret_cast<float4*>(ab + (size_t)j * L) = a;
+            if (f.log_s) *reinterpret_cast<float4*>(f.log_s + (size_t)b * f.ls_bstride + (size_t)j * L + n) = ls;
+            s += ((double)ls.x + (double)ls.y) + ((double)ls.z + (double)ls.w);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if ((threadIdx.x & 63) == 0) f.part[(size_t)b * f.part_bstride + blockIdx.x] = s;
+}
+
 // e = Wend * out + bend; (b, log_s) = (e[:h], e[h:]); a1 = (a1 - b) / exp(log_s);
 // audio[ch_off : ch_off+2h] = Winv * [a0; a1]; optional un-squeeze to wave.
 // (glow.py:222, 337-340, 349).  Workgroup = 4 waves x 256 time steps; each wave reduces a
 // quarter of the C skip channels with 16-byte loads, partial sums meet in LDS.
-template <int H>
+// FWD: the same reduction, then coupling_forward instead (Winv, wave unused).
+template <int H, bool FWD>
 __global__ __launch_bounds__(256) void flow_tail_kernel(const float* __restrict__ out, float* __restrict__ audio,
                                                         float* __restrict__ wave, const float* __restrict__ Wend,
                                                         const float* __restrict__ bend, const float* __restrict__ Winv,
-                                                        int C, int G, int ch_off, int L, int ld, int pad) {
+                                                        int C, int G, int ch_off, int L, int ld, int pad, CouplingForward fw) {
     constexpr int E = 2 * H;
     __shared__ __attribute__((aligned(16))) float part[3][E][256];
     __shared__ float sWinv[E * E];
@@ -344,7 +371,7 @@ __global__ __launch_bounds__(256) void flow_tail_kernel(const float* __restrict_
     const int wv = threadIdx.x >> 6;
     const int b = blockIdx.y;
     const int n = blockIdx.x * 256 + lane * 4;
-    if (threadIdx.x < E * E) sWinv[threadIdx.x] = Winv[threadIdx.x];
+    if (!FWD && threadIdx.x < E * E) sWinv[threadIdx.x] = Winv[threadIdx.x];
     float4 e[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) e[j] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -366,7 +393,7 @@ __global__ __launch_bounds__(256) void flow_tail_kernel(const float* __restrict_
         for (int j = 0; j < E; ++j) *reinterpret_cast<float4*>(&part[wv - 1][j][lane * 4]) = e[j];
     }
     __syncthreads();
-    if (wv != 0 || n >= L) return;
+    if (wv != 0 || (!FWD && n >= L)) return;
 #pragma unroll
     for (int j = 0; j < E; ++j) {
         const float bj = bend[j];
@@ -377,7 +404,94 @@ __global__ __launch_bounds__(256) void flow_tail_kernel(const float* __restrict_
         }
         e[j].x += bj; e[j].y += bj; e[j].z += bj; e[j].w += bj;
     }
-    coupling_tail<H>(e, sWinv, audio, wave, b, G, ch_off, L, n);
+    if constexpr (FWD) coupling_forward<H>(e, audio, fw, b, G, ch_off, L, n);
+    else coupling_tail<H>(e, sWinv, audio, wave, b, G, ch_off, L, n);
+}
+
+// ------------------------------------------------------------ forward-direction head and sums ----
+// Head of a forward flow (glow.py:294; SQ: with the squeeze of glow.py:284 in front): one thread holds the E rows of four
+// consecutive columns, W [E][E] sits in LDS, rows [ch_off, ch_off + E) of z [B][G][L] <- W . rows, in place (a thread reads
+// all of its columns before it writes any).  SQ (flow 0, E == G, ch_off == 0): column l of row g is wave[b][G l + g] - the four
+// columns are 4 G consecutive floats, read as whole float4s (E % 4 == 0).
+template <int E, bool SQ>
+__global__ __launch_bounds__(256) void flow_head_forward_kernel(const float* __restrict__ W, const float* __restrict__ wave,
+                                                                float* __restrict__ z, int G, int ch_off, int L) {
+    __shared__ float sW[E * E];
+    for (int i = threadIdx.x; i < E * E; i += 256) sW[i] = W[i];
+    __syncthreads();
+    const int n = (blockIdx.x * 256 + threadIdx.x) * 4;
+    const int b = blockIdx.y;
+    if (n >= L) return;
+    float* zb = z + ((size_t)b * G + ch_off) * L + n;
+    float4 a[E];
+    if constexpr (SQ) {
+        const float* wb = wave + (size_t)b * G * L + (size_t)n * G;
+        float af[E * 4];                                       // af[4 i + s] = channel i, step n + s
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int i = 0; i < E; i += 4) {
+                const float4 v = *reinterpret_cast<const float4*>(wb + s * E + i);
+                af[(i + 0) * 4 + s] = v.x; af[(i + 1) * 4 + s] = v.y; af[(i + 2) * 4 + s] = v.z; af[(i + 3) * 4 + s] = v.w;
+            }
+#pragma unroll
+        for (int i = 0; i < E; ++i) a[i] = make_float4(af[4 * i], af[4 * i + 1], af[4 * i + 2], af[4 * i + 3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < E; ++j) a[j] = *reinterpret_cast<const float4*>(zb + (size_t)j * L);
+    }
+#pragma unroll
+    for (int i = 0; i < E; ++i) {
+        float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            const float w = sW[i * E + j];
+            m.x = fmaf(w, a[j].x, m.x); m.y = fmaf(w, a[j].y, m.y);
+            m.z = fmaf(w, a[j].z, m.z); m.w = fmaf(w, a[j].w, m.w);
+        }
+        *reinterpret_cast<float4*>(zb + (size_t)i * L) = m;
+    }
+}
+
+// fp64 sum over one workgroup: the butterfly over each wave, then the four waves in order (all 256 threads call it)
+__device__ __forceinline__ double block_sum_f64(double s, double* red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// part[b][blockIdx.x] = sum of v^2 in fp64 (every square exact) over floats [FWD_SUMSQ_CHUNK blockIdx.x, + FWD_SUMSQ_CHUNK) of item b
+__global__ __launch_bounds__(256) void sumsq_partials_kernel(const float* __restrict__ z, double* __restrict__ part,
+                                                             long long n_item, int nblk) {
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    const float* zb = z + (size_t)b * n_item;
+    double s = 0.0;
+#pragma unroll
+    for (int r = 0; r < FWD_SUMSQ_CHUNK / 1024; ++r) {
+        const long long i = (long long)blockIdx.x * FWD_SUMSQ_CHUNK + (r * 256 + threadIdx.x) * 4;
+        if (i < n_item) {                                      // n_item % 4 == 0: a float4 is all in or all out
+            const float4 v = *reinterpret_cast<const float4*>(zb + i);
+            s += ((double)v.x * (double)v.x + (double)v.y * (double)v.y) + ((double)v.z * (double)v.z + (double)v.w * (double)v.w);
+        }
+    }
+    s = block_sum_f64(s, red);
+    if (threadIdx.x == 0) part[(size_t)b * nblk + blockIdx.x] = s;
+}
+
+// Second stage of both sums: one wave per (k, b) adds its n slots, lane i the slots i, i + 64, ... in order, then the butterfly
+__global__ __launch_bounds__(64) void sum_partials_kernel(const double* __restrict__ part, long long part_bstride,
+                                                          long long part_kstride, int n, double* __restrict__ out,
+                                                          int out_bstride) {
+    const int k = blockIdx.x, b = blockIdx.y;
+    const double* p = part + (size_t)b * part_bstride + (size_t)k * part_kstride;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 64) s += p[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (threadIdx.x == 0) out[(size_t)b * out_bstride + k] = s;
 }
 
 
@@ -539,13 +653,15 @@ __global__ __launch_bounds__(256) void wn_start_ones_kernel(const float* __restr
 // of layer j, [C][E]), first group: acc = e; later groups: e += acc, and then either acc = e, or (TAIL, the last group) e += b'
 // and the flow tail of flow_tail_kernel.  Same reduction shape as flow_tail_kernel: 4 waves x 256 time steps, each wave a
 // quarter of the channels of every layer, NG 16-byte loads in flight per lane, partial sums meet in LDS.  Every workgroup
-// owns its columns: deterministic.
-template <int H, bool TAIL>
+// owns its columns: deterministic.  TAIL: SKEND_ACC (no tail), SKEND_TAIL, or SKEND_FWD - the forward direction's tail
+// (coupling_forward; Winv, wave unused).
+enum { SKEND_ACC = 0, SKEND_TAIL = 1, SKEND_FWD = 2 };
+template <int H, int TAIL>
 __global__ __launch_bounds__(256) void skip_end_kernel(const float* __restrict__ act, long long act_stride, int nl,
                                                        const float* __restrict__ Wf, float* __restrict__ acc, int first,
                                                        const float* __restrict__ bf, const float* __restrict__ Winv,
                                                        float* __restrict__ audio, float* __restrict__ wave,
-                                                       int C, int G, int ch_off, int L, int ld, int pad) {
+                                                       int C, int G, int ch_off, int L, int ld, int pad, CouplingForward fw) {
     constexpr int E = 2 * H;
     constexpr int NG = E <= 4 ? 8 : E <= 8 ? 4 : 2;            // 16-byte loads per lane in flight (E x NG weights in SGPRs)
     __shared__ __attribute__((aligned(16))) float part[3][E][256];
@@ -554,7 +670,7 @@ __global__ __launch_bounds__(256) void skip_end_kernel(const float* __restrict__
     const int wv = threadIdx.x >> 6;
     const int b = blockIdx.y;
     const int n = blockIdx.x * 256 + lane * 4;
-    if (TAIL && threadIdx.x < E * E) sWinv[threadIdx.x] = Winv[threadIdx.x];
+    if (TAIL == SKEND_TAIL && threadIdx.x < E * E) sWinv[threadIdx.x] = Winv[threadIdx.x];
     float4 e[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) e[j] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -583,7 +699,7 @@ __global__ __launch_bounds__(256) void skip_end_kernel(const float* __restrict__
         for (int j = 0; j < E; ++j) *reinterpret_cast<float4*>(&part[wv - 1][j][lane * 4]) = e[j];
     }
     __syncthreads();
-    if (wv != 0 || n >= L) return;
+    if (wv != 0 || (TAIL != SKEND_FWD && n >= L)) return;
     float* ab = acc + (size_t)b * E * ld + pad + n;
 #pragma unroll
     for (int j = 0; j < E; ++j) {
@@ -597,7 +713,7 @@ __global__ __launch_bounds__(256) void skip_end_kernel(const float* __restrict__
             e[j].x += pv.x; e[j].y += pv.y; e[j].z += pv.z; e[j].w += pv.w;
         }
     }
-    if constexpr (!TAIL) {
+    if constexpr (TAIL == SKEND_ACC) {
 #pragma unroll
         for (int j = 0; j < E; ++j) *reinterpret_cast<float4*>(ab + (size_t)j * ld) = e[j];
     } else {
@@ -606,7 +722,8 @@ __global__ __launch_bounds__(256) void skip_end_kernel(const float* __restrict__
             const float bj = bf[j];
             e[j].x += bj; e[j].y += bj; e[j].z += bj; e[j].w += bj;
         }
-        coupling_tail<H>(e, sWinv, audio, wave, b, G, ch_off, L, n);
+        if constexpr (TAIL == SKEND_FWD) coupling_forward<H>(e, audio, fw, b, G, ch_off, L, n);
+        else coupling_tail<H>(e, sWinv, audio, wave, b, G, ch_off, L, n);
     }
 }
 
@@ -709,15 +826,21 @@ int launch_wn_start(const float* audio, const float* Ws, const float* bs, float*
 
 int launch_flow_tail(const float* out, float* audio, float* wave, const float* Wend, const float* bend,
                      const float* Winv, int batch, int C, int G, int ch_off, int n_half, int L, int ld, int pad,
-                     hipStream_t s) {
+                     hipStream_t s, const CouplingForward* fwd) {
     CTTS_CHECK_ARG(L % 4 == 0 && C % 4 == 0, "flow_tail: L=%d C=%d", L, C);
+    CTTS_CHECK_ARG(fwd == nullptr || (fwd->part != nullptr && wave == nullptr), "flow_tail: forward direction needs the partial sums");
+    const CouplingForward fw = fwd ? *fwd : CouplingForward{};
     CTTS_CHECK_ARG(wave == nullptr || (ch_off == 0 && 2 * n_half == G && G % 4 == 0),
                    "flow_tail: un-squeeze needs the full group (ch_off=%d n_half=%d G=%d)", ch_off, n_half, G);
     dim3 grid((L + 255) / 256, batch);
 #define CTTS_TAIL_CASE(H)                                                                                       \
     case H:                                                                                                     \
-        hipLaunchKernelGGL(flow_tail_kernel<H>, grid, dim3(256), 0, s, out, audio, wave, Wend, bend, Winv, C, G, \
-                           ch_off, L, ld, pad);                                                                 \
+        if (fwd)                                                                                                \
+            hipLaunchKernelGGL((flow_tail_kernel<H, true>), grid, dim3(256), 0, s, out, audio, wave, Wend, bend, Winv, C, G, \
+                               ch_off, L, ld, pad, fw);                                                         \
+        else                                                                                                    \
+            hipLaunchKernelGGL((flow_tail_kernel<H, false>), grid, dim3(256), 0, s, out, audio, wave, Wend, bend, Winv, C, G, \
+                               ch_off, L, ld, pad, fw);                                                         \
         break;
     switch (n_half) {
         CTTS_TAIL_CASE(1) CTTS_TAIL_CASE(2) CTTS_TAIL_CASE(3) CTTS_TAIL_CASE(4)
@@ -806,7 +929,9 @@ int launch_wn_start_ones(const float* audio, float* a16, int batch, int G, int c
 
 int launch_skip_end(const float* act, long long act_stride, int nl, const float* Wf, float* acc, bool first, bool tail,
                     const float* bf, const float* Winv, float* audio, float* wave, int batch, int C, int G, int ch_off,
-                    int n_half, int L, int ld, int pad, hipStream_t s) {
+                    int n_half, int L, int ld, int pad, hipStream_t s, const CouplingForward* fwd) {
+    CTTS_CHECK_ARG(fwd == nullptr || (tail && fwd->part != nullptr && wave == nullptr), "skip_end: forward direction on the tail pass only");
+    const CouplingForward fw = fwd ? *fwd : CouplingForward{};
     CTTS_CHECK_ARG(L % 4 == 0 && C % 32 == 0 && ld % 4 == 0 && pad % 4 == 0 && nl >= 1, "skip_end: L=%d C=%d nl=%d", L, C, nl);
     CTTS_CHECK_ARG(acc != nullptr || (first && tail), "skip_end: a group after the first needs the accumulator");
     CTTS_CHECK_ARG(!tail || wave == nullptr || (ch_off == 0 && 2 * n_half == G && G % 4 == 0),
@@ -815,12 +940,15 @@ int launch_skip_end(const float* act, long long act_stride, int nl, const float*
     const int fi = first ? 1 : 0;
 #define CTTS_SKEND_CASE(H)                                                                                                \
     case H:                                                                                                               \
-        if (tail)                                                                                                         \
-            hipLaunchKernelGGL((skip_end_kernel<H, true>), grid, dim3(256), 0, s, act, act_stride, nl, Wf, acc, fi, bf, Winv, \
-                               audio, wave, C, G, ch_off, L, ld, pad);                                                    \
+        if (fwd)                                                                                                          \
+            hipLaunchKernelGGL((skip_end_kernel<H, SKEND_FWD>), grid, dim3(256), 0, s, act, act_stride, nl, Wf, acc, fi, bf, Winv, \
+                               audio, wave, C, G, ch_off, L, ld, pad, fw);                                                \
+        else if (tail)                                                                                                    \
+            hipLaunchKernelGGL((skip_end_kernel<H, SKEND_TAIL>), grid, dim3(256), 0, s, act, act_stride, nl, Wf, acc, fi, bf, Winv, \
+                               audio, wave, C, G, ch_off, L, ld, pad, fw);                                                \
         else                                                                                                              \
-            hipLaunchKernelGGL((skip_end_kernel<H, false>), grid, dim3(256), 0, s, act, act_stride, nl, Wf, acc, fi, bf, Winv, \
-                               audio, wave, C, G, ch_off, L, ld, pad);                                                    \
+            hipLaunchKernelGGL((skip_end_kernel<H, SKEND_ACC>), grid, dim3(256), 0, s, act, act_stride, nl, Wf, acc, fi, bf, Winv, \
+                               audio, wave, C, G, ch_off, L, ld, pad, fw);                                                \
         break;
     switch (n_half) {
         CTTS_SKEND_CASE(1) CTTS_SKEND_CASE(2) CTTS_SKEND_CASE(3) CTTS_SKEND_CASE(4)
@@ -831,6 +959,53 @@ int launch_skip_end(const float* act, long long act_stride, int nl, const float*
     }
 #undef CTTS_SKEND_CASE
     CTTS_CHECK_LAUNCH("skip_end");
+    return CTTS_OK;
+}
+
+int launch_flow_head_forward(const float* W, const float* wave, float* z, int batch, int G, int ch_off, int n_rem, int L,
+                             hipStream_t s) {
+    CTTS_CHECK_ARG(L % 4 == 0 && n_rem >= 2 && n_rem % 2 == 0 && ch_off >= 0 && ch_off + n_rem == G,
+                   "flow_head_forward: L=%d n_rem=%d ch_off=%d G=%d", L, n_rem, ch_off, G);
+    CTTS_CHECK_ARG(wave == nullptr || (ch_off == 0 && G % 4 == 0), "flow_head_forward: the squeeze needs the full group (ch_off=%d G=%d)",
+                   ch_off, G);
+    dim3 grid((L / 4 + 255) / 256, batch);
+#define CTTS_HEAD_LAUNCH(EE, SQ) \
+    hipLaunchKernelGGL((flow_head_forward_kernel<EE, SQ>), grid, dim3(256), 0, s, W, wave, z, G, ch_off, L)
+#define CTTS_HEAD_CASE(EE)             \
+    case EE:                           \
+        CTTS_HEAD_LAUNCH(EE, false);   \
+        break;
+#define CTTS_HEAD_CASE_SQ(EE)                                                       \
+    case EE:                                                                        \
+        if (wave) CTTS_HEAD_LAUNCH(EE, true); else CTTS_HEAD_LAUNCH(EE, false);     \
+        break;
+    switch (n_rem) {
+        CTTS_HEAD_CASE(2) CTTS_HEAD_CASE_SQ(4) CTTS_HEAD_CASE(6) CTTS_HEAD_CASE_SQ(8)
+        CTTS_HEAD_CASE(10) CTTS_HEAD_CASE_SQ(12) CTTS_HEAD_CASE(14) CTTS_HEAD_CASE_SQ(16)
+        default:
+            set_error("flow_head_forward: n_rem=%d unsupported (2..16, even)", n_rem);
+            return CTTS_E_ARG;
+    }
+#undef CTTS_HEAD_CASE_SQ
+#undef CTTS_HEAD_CASE
+#undef CTTS_HEAD_LAUNCH
+    CTTS_CHECK_LAUNCH("flow_head_forward");
+    return CTTS_OK;
+}
+
+int launch_sumsq_partials(const float* z, double* part, int batch, long long n_item, int nblk, hipStream_t s) {
+    CTTS_CHECK_ARG(n_item > 0 && n_item % 4 == 0 && (long long)nblk * FWD_SUMSQ_CHUNK >= n_item, "sumsq_partials: n=%lld nblk=%d",
+                   n_item, nblk);
+    hipLaunchKernelGGL(sumsq_partials_kernel, dim3(nblk, batch), dim3(256), 0, s, z, part, n_item, nblk);
+    CTTS_CHECK_LAUNCH("sumsq_partials");
+    return CTTS_OK;
+}
+
+int launch_sum_partials(const double* part, long long part_bstride, long long part_kstride, int n, double* out, int out_bstride,
+                        int nk, int batch, hipStream_t s) {
+    CTTS_CHECK_ARG(n >= 1 && nk >= 1, "sum_partials: n=%d nk=%d", n, nk);
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(nk, batch), dim3(64), 0, s, part, part_bstride, part_kstride, n, out, out_bstride);
+    CTTS_CHECK_LAUNCH("sum_partials");
     return CTTS_OK;
 }
 

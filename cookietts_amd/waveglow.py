@@ -5,7 +5,8 @@ Host-side mirror of the reference's ``WaveGlow`` ``nn.Module``
 kwargs, same ``state_dict`` keys (``upsample.*``, ``WN.{k}.{start,end,cond_layers.j,
 in_layers.i,res_skip_layers.i}.*`` with ``weight_g``/``weight_v``, ``convinv.{k}.conv.weight``),
 same ``infer(spect, speaker_id=None, sigma=1.0)`` contract, so reference checkpoints
-and callers drop in.  All arithmetic of ``infer`` runs in the C-ABI HIP library
+and callers drop in; ``forward(spect, audio, speaker_id=None)`` is the analysis pass (audio -> z, log_s, log det W;
+fp32 compute, no gradient) with ``nll`` and ``WaveGlowLoss`` on top.  All arithmetic of both runs in the C-ABI HIP library
 (``include/cookietts_hip.h``); PyTorch only owns device memory, the stream and the RNG
 draw.  There is no CPU fallback: without the library, or with CPU tensors, it raises.
 
@@ -28,7 +29,7 @@ import torch.nn as nn
 from . import _cache, _lib
 from ._wn import WNConv, folded_weight
 
-__all__ = ["WaveGlow", "Invertible1x1Conv", "WN"]
+__all__ = ["WaveGlow", "WaveGlowLoss", "Invertible1x1Conv", "WN"]
 
 
 class _Conv1dParams(nn.Module):
@@ -43,6 +44,23 @@ class _Conv1dParams(nn.Module):
             self.bias = nn.Parameter(torch.empty(out_ch).uniform_(-bound, bound))
         else:
             self.register_parameter("bias", None)
+
+
+class WaveGlowLoss(nn.Module):
+    """glow.py:44-62 on the tuple ``WaveGlow.forward`` returns: ``(sum z^2 / 2 sigma^2 - sum log_s - sum log det W) / z.numel()``."""
+
+    def __init__(self, sigma=1.0):
+        super().__init__()
+        self.sigma = sigma
+        self.sigma2 = sigma * sigma
+        self.sigma2_2 = 2 * sigma * sigma
+
+    def forward(self, model_output):
+        z, log_s_list, log_det_W_list = model_output
+        log_s_total = sum(torch.sum(log_s) for log_s in log_s_list)
+        log_det_W_total = sum(log_det_W_list)
+        loss = torch.sum(z * z) / self.sigma2_2 - log_s_total - log_det_W_total
+        return loss / (z.size(0) * z.size(1) * z.size(2))
 
 
 class Invertible1x1Conv(nn.Module):
@@ -171,6 +189,7 @@ class WaveGlow(_cache.PackedModule):
 
         self._compute_dtype = torch.float32
         self._f32_gemm_mode = None   # None: the library default; see set_f32_gemm_mode
+        self._fwd = None             # (the infer blob it belongs to, forward-mix blob, log det W_k [n_flows] fp32 on the host)
 
     # ------------------------------------------------------------------ plumbing ----
     def c_config(self):
@@ -194,6 +213,7 @@ class WaveGlow(_cache.PackedModule):
 
     def _invalidate(self):
         super()._invalidate()
+        self._fwd = None
         for m in self.convinv:
             if hasattr(m, 'W_inverse'):
                 del m.W_inverse
@@ -323,6 +343,21 @@ class WaveGlow(_cache.PackedModule):
     def steps_for(self, frames):
         return frames * self.hop_length // self.n_group
 
+    def _speaker_ids(self, speaker_id, device, B):
+        """-> int64 ids [B] on the device, or None for a single-speaker model."""
+        if not self.multispeaker:
+            return None
+        if speaker_id is None:      # the reference would feed cond_layers[0] too few channels and crash (glow.py:193-198)
+            raise RuntimeError("this WaveGlow is multispeaker (speaker_embed_dim > 0): pass speaker_id")
+        # range check like nn.Embedding's, where it costs no device sync (host ids); ids already on the device are
+        # checked by the kernel, which turns an out-of-range id into a NaN utterance instead of an out-of-bounds read
+        if not speaker_id.is_cuda and speaker_id.numel() and \
+                (int(speaker_id.min()) < 0 or int(speaker_id.max()) >= _lib.N_SPEAKERS):
+            raise IndexError("speaker id out of range of the embedding table")
+        ids = speaker_id.detach().to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+        assert ids.shape[0] == B, (tuple(ids.shape), B)
+        return ids
+
     # --------------------------------------------------------------------- the path ----
     def infer_from_noise(self, spect, z_scaled, speaker_id=None):
         """Deterministic entry: ``z_scaled`` [B, n_group, L] already multiplied by sigma.
@@ -343,17 +378,7 @@ class WaveGlow(_cache.PackedModule):
         assert tuple(z_scaled.shape) == (B, self.n_group, L), (tuple(z_scaled.shape), (B, self.n_group, L))
         mel = spect.detach().float().contiguous()
         z = z_scaled.detach().to(device=device, dtype=torch.float32).contiguous()
-        ids = None
-        if self.multispeaker:
-            if speaker_id is None:      # the reference would feed cond_layers[0] too few channels and crash (glow.py:193-198)
-                raise RuntimeError("this WaveGlow is multispeaker (speaker_embed_dim > 0): pass speaker_id")
-            # range check like nn.Embedding's, where it costs no device sync (host ids); ids already on the device are
-            # checked by the kernel, which turns an out-of-range id into a NaN utterance instead of an out-of-bounds read
-            if not speaker_id.is_cuda and speaker_id.numel() and \
-                    (int(speaker_id.min()) < 0 or int(speaker_id.max()) >= _lib.N_SPEAKERS):
-                raise IndexError("speaker id out of range of the embedding table")
-            ids = speaker_id.detach().to(device=device, dtype=torch.int64).reshape(-1).contiguous()
-            assert ids.shape[0] == B, (tuple(ids.shape), B)
+        ids = self._speaker_ids(speaker_id, device, B)
         mode = self._mode()
         _, _, ws_bytes, infer = _MODES[mode]
         cfg = self.c_config()
@@ -376,5 +401,102 @@ class WaveGlow(_cache.PackedModule):
         z = torch.randn(B, self.n_group, self.steps_for(F), device=spect.device, dtype=torch.float32)
         return self.infer_from_noise(spect, z * sigma, speaker_id=speaker_id)
 
+    # ------------------------------------------------------------- the analysis pass ----
+    def _ensure_forward_packed(self, device):
+        """-> (infer blob, forward-mix blob, log det W_k as fp32 on the host).  Packed on the first forward call and kept while the
+        infer blob it was packed beside is the live one (the PackedModule rules); ``infer`` alone never builds it."""
+        blob, _ = self._ensure_packed(device)
+        if self._fwd is None or self._fwd[0] is not blob:
+            lib = _lib.lib()
+            cfg = self.c_config()
+            nbytes = _lib.nbytes(lib.ctts_waveglow_forward_packed_bytes, C.byref(cfg), what="unsupported WaveGlow config")
+            with torch.cuda.device(device):
+                stream = _lib.stream(device)
+                fwd = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
+                keep, logdets = [], []
+                for k in range(self.n_flows):
+                    W = self.convinv[k].conv.weight.detach().squeeze(-1).float()
+                    logdets.append(torch.logdet(W.cpu()))                  # host fp32, as W_inverse is (glow.py:103-105)
+                    Wd = W.to(device).contiguous()
+                    keep.append(Wd)
+                    _lib.check(lib.ctts_waveglow_pack_forward_mix(C.byref(cfg), k, _lib.ptr(Wd), _lib.ptr(fwd), stream),
+                               f"ctts_waveglow_pack_forward_mix({k})")
+                torch.cuda.current_stream(device).synchronize()
+            self._fwd = (blob, fwd, torch.stack(logdets))
+        return self._fwd
+
+    def _forward_refusals(self, spect, audio):
+        """Everything ``forward`` / ``nll`` refuse, by name, before anything is packed or launched."""
+        if audio is None:
+            raise ValueError("WaveGlow.forward needs the audio [B, frames * hop_length] (glow.py:267); audio is None")
+        if self.spect_scaling:
+            raise NotImplementedError("spect_scaling=True is broken in the reference (glow.py:233-235)")
+        if self.training and torch.is_grad_enabled():
+            raise NotImplementedError("no backward pass: WaveGlow.forward on the HIP path is the analysis pass only - call "
+                                      "model.eval() or run it under torch.no_grad()")
+        mode = self._mode()
+        if mode != "f32":
+            raise NotImplementedError(f"WaveGlow.forward with compute mode {mode!r}: the 16-bit flow boundaries have no forward "
+                                      "form (fp32 compute only; set_f32_gemm_mode's bf16x3 / bf16x6 are fp32 tensors and do run)")
+        F = spect.shape[-1]
+        if audio.dim() != 2 or audio.shape[1] != F * self.hop_length:
+            raise ValueError(f"audio of shape {tuple(audio.shape)} for {F} frames: forward needs exactly frames * hop_length = "
+                             f"{F * self.hop_length} samples per item (a shorter audio moves the WN's zero padding, so its "
+                             "result is not a crop of the full-length one)")
+
+    def _forward_core(self, spect, audio, speaker_id, want_log_s):
+        """-> (z [B, G, L], log_s [B, S, L] or None, sums float64 [B, n_flows + 1], log det W_k fp32 on the host), fp32."""
+        if spect.dim() == 2:
+            spect = spect.unsqueeze(0)
+        self._forward_refusals(spect, audio)
+        device = spect.device
+        blob, fwd, logdets = self._ensure_forward_packed(device)
+        lib = _lib.lib()
+        B, M, F = spect.shape
+        assert M == self.n_mel_channels, (M, self.n_mel_channels)
+        assert audio.shape[0] == B, (tuple(audio.shape), B)
+        L = self.steps_for(F)
+        mel = spect.detach().float().contiguous()
+        wave = audio.detach().to(device=device, dtype=torch.float32).contiguous()
+        ids = self._speaker_ids(speaker_id, device, B)
+        cfg = self.c_config()
+        nbytes = _lib.nbytes(lib.ctts_waveglow_forward_workspace_bytes, C.byref(cfg), B, F, what="workspace query failed")
+        ws = self.workspace((device, B, F, "forward", nbytes), lambda: nbytes)
+        S = sum(c.conv.weight.shape[0] // 2 for c in self.convinv)      # rows of log_s: every flow's n_half
+        z = torch.empty(B, self.n_group, L, dtype=torch.float32, device=device)
+        log_s = torch.empty(B, S, L, dtype=torch.float32, device=device) if want_log_s else None
+        sums = torch.empty(B, self.n_flows + 1, dtype=torch.float64, device=device)
+        with torch.cuda.device(device):
+            _lib.check(lib.ctts_waveglow_forward_spk_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(fwd), _lib.ptr(mel), _lib.ptr(wave),
+                                                         _lib.ptr(ids), _lib.ptr(z), _lib.ptr(log_s), _lib.ptr(sums), B, F,
+                                                         _lib.ptr(ws), ws.numel() * 4, _lib.stream(device)),
+                       "ctts_waveglow_forward_spk_f32")
+        return z, log_s, sums, logdets
+
     def forward(self, spect, audio=None, speaker_id=None):
-        raise NotImplementedError("training direction (glow.py:267-312) is outside the inference hot path")
+        """``glow.WaveGlow.forward`` (glow.py:267-312) without a gradient: spect [B, n_mel, F], audio [B, F*hop] ->
+        ``(z, log_s_list, log_det_W_list)``.  ``z`` [B, n_group, L] has the early outputs first, in peel order - exactly the rows
+        ``infer_from_noise`` takes; ``log_s_list`` are views of one buffer; ``log_det_W_list[k] = B L logdet(W_k)``.  Tensors come
+        back detached, in spect's dtype.  fp32 compute only."""
+        z, log_s, _, logdets = self._forward_core(spect, audio, speaker_id, want_log_s=True)
+        dt = spect.dtype
+        log_s = log_s.to(dt)
+        out, off = [], 0
+        for c in self.convinv:
+            nh = c.conv.weight.shape[0] // 2
+            out.append(log_s[:, off:off + nh])
+            off += nh
+        B, _, L = z.shape
+        ld = (B * L * logdets).to(device=z.device, dtype=dt)
+        return z.to(dt), out, list(ld.unbind(0))
+
+    def nll(self, spect, audio, speaker_id=None, sigma=1.0):
+        """The negative log-likelihood ``WaveGlowLoss(sigma)`` gives ``forward``'s output, from the device's fp64 sums alone (log_s
+        is not materialised): ``{"loss": 0-dim tensor in spect's dtype, "per_item": [B] float64}``; item b's own
+        ``(sum z^2 / 2 sigma^2 - sum log_s - L sum_k logdet W_k) / (n_group L)``, whose mean is the loss."""
+        z, _, sums, logdets = self._forward_core(spect, audio, speaker_id, want_log_s=False)
+        L = z.shape[2]
+        logdet_total = float(logdets.double().sum())
+        per_item = (sums[:, self.n_flows] / (2.0 * sigma * sigma) - sums[:, :self.n_flows].sum(dim=1) - L * logdet_total) \
+            / (self.n_group * L)
+        return {"loss": per_item.mean().to(spect.dtype), "per_item": per_item}

@@ -244,6 +244,41 @@ int ctts_waveglow_flow_f32(const ctts_waveglow_config* cfg, const void* packed, 
                            const float* h_all, float* wave, int32_t batch, int32_t frames, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- the analysis pass: WaveGlow.forward (glow.py:267-312), fp32 entry only, no gradient -------------------------------
+ * audio -> z and log-likelihood terms: voice conversion (z under one speaker id, ctts_waveglow_infer_spk_f32 under another),
+ * scoring a checkpoint (WaveGlowLoss, glow.py:51-62) and the invertibility check infer(forward(x)) = x.  The WN stack is the
+ * infer path's own (same kernels, same form selection by the CTTS_F32_* knobs and the length, f32_gemm_mode honoured); new are
+ * the flow boundaries: a head kernel (forward 1x1 mix; flow 0 reads the waveform un-squeezed) and the forward direction of the
+ * tail kernels (a_1 = exp(log_s) a_1 + b with expf, log_s, fp64 partial sums).
+ * The forward mix matrices live in a blob of their own; the infer blob (`packed`) is read as it is. */
+size_t ctts_waveglow_forward_packed_bytes(const ctts_waveglow_config* cfg);
+/* w: [c][c] convinv.flow.conv.weight (c = the flow's remaining channels), fp32 on the device. */
+int ctts_waveglow_pack_forward_mix(const ctts_waveglow_config* cfg, int32_t flow, const float* w, void* packed_fwd,
+                                   void* stream);
+/* The infer workspace plus the fp64 slots of the sums; zero-filled once before its first use with this geometry.  0 with a
+ * message (ctts_last_error) for a config or geometry the plan refuses. */
+size_t ctts_waveglow_forward_workspace_bytes(const ctts_waveglow_config* cfg, int32_t batch, int32_t frames);
+/*   mel    [B][n_mel][F]     fp32 dense
+ *   audio  [B][F*hop]        fp32 dense (exactly F*hop samples: a shorter waveform moves the WN's zero padding)
+ *   speaker_ids              [B] int64 on the device; NULL is an error for a multispeaker config and ignored otherwise
+ *   z      [B][n_group][L]   out: early outputs first, in peel order - the row order ctts_waveglow_infer_spk_f32 takes as z_scaled
+ *   log_s  NULL, or [B][S][L], S = sum_k n_half_k: flow k's rows at offset sum_{j<k} n_half_j
+ *   sums   NULL, or double [B][n_flows + 1] on the device: sums[b][k] = sum of flow k's log_s over item b, sums[b][n_flows] =
+ *          sum of z^2 over item b.  Accumulated in fp64 from the stored fp32 values in two stages of fixed order (no atomics):
+ *          two calls give the same bits, and an item's sums do not depend on the batch it runs in. */
+int ctts_waveglow_forward_spk_f32(const ctts_waveglow_config* cfg, const void* packed, const void* packed_fwd, const float* mel,
+                                  const float* audio, const int64_t* speaker_ids, float* z, float* log_s, double* sums,
+                                  int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes, void* stream);
+/* One forward flow exactly as ctts_waveglow_forward_spk_f32 runs it (both share one helper), mirroring ctts_waveglow_flow_f32:
+ *   z      [B][n_group][L] dense: rows [ch_off, n_group) of flow `flow` are mixed and coupled in place, the rows above stay;
+ *   wave   NULL, or (flow 0 only) [B][L*n_group]: the rows are read from there un-squeezed instead of from z;
+ *   h_all  as ctts_wn_cond_f32 writes it;
+ *   log_s  NULL, or [B][n_half][L] dense: this flow's log_s;   sum_log_s  NULL, or double [B]: its sum per item.
+ * workspace: ctts_waveglow_forward_workspace_bytes(cfg, batch, frames) bytes. */
+int ctts_waveglow_flow_forward_f32(const ctts_waveglow_config* cfg, const void* packed, const void* packed_fwd, int32_t flow,
+                                   float* z, const float* wave, const float* h_all, float* log_s, double* sum_log_s,
+                                   int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- WaveFlow ("ax" core, waveflow=True): _4_mtw/waveglow/efficient_model_ax.py --------- */
 
 /* Constructor arguments that shape the path (efficient_model_ax.py:19-169, glow_ax.py:427-543).
