@@ -840,6 +840,8 @@ void load_tuning_locked() {
     g_tune.f32_winograd_plain = on("CTTS_F32_WINOGRAD_PLAIN");
     g_tune.f32_winograd_fused_min = num("CTTS_F32_WINOGRAD_FUSED_MIN", -1);
     g_tune.f32_winograd_no_fused = on("CTTS_F32_WINOGRAD_NO_FUSED");
+    g_tune.f32_winograd_f43_min = num("CTTS_F32_WINOGRAD_F43_MIN", -1);
+    g_tune.f32_winograd_no_f43 = on("CTTS_F32_WINOGRAD_NO_F43");
     g_tune_loaded = true;
 }
 }  // namespace

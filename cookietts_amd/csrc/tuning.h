@@ -33,6 +33,8 @@ struct Tuning {
     int f32_winograd_min;  // CTTS_F32_WINOGRAD_MIN: take the Winograd form for utterances of at least this many columns (steps per batch item); 0 = always (default in waveglow_api.hip)
     bool f32_winograd_plain;  // CTTS_F32_WINOGRAD_PLAIN: the Winograd form as five launches per layer (cond rows copied into pair order for every layer, T2 / T3 and even / odd as separate launches, d = 2 transform one column at a time): the A/B arm and the tests' reference of the merged form, bit-identical
     int f32_winograd_fused_min;  // CTTS_F32_WINOGRAD_FUSED_MIN: take the one-launch Winograd layer (wn_winograd_layer.hip) for utterances of at least this many columns; 0 = always (default in waveglow_api.hip).  Below it the Winograd form, where it engages, runs as the paired launches
+    int f32_winograd_f43_min;  // CTTS_F32_WINOGRAD_F43_MIN: take the F(4,3) form of the one-launch Winograd layer (quad columns, 1.5 C products per output and row) for utterances of at least this many columns; 0 = always (default in waveglow_api.hip).  Below it, and wherever the one-launch layer does not engage, the F(2,3) forms run
+    bool f32_winograd_no_f43;  // CTTS_F32_WINOGRAD_NO_F43: never the F(4,3) form: the one-launch F(2,3) layer at every size it engages at (the A/B arm, bit-equal to the library before the F(4,3) form)
     bool f32_winograd_no_fused;  // CTTS_F32_WINOGRAD_NO_FUSED: never the one-launch Winograd layer: T2 | T3 and even | odd as two launches of the conv-GEMM with the T planes in HBM (the A/B arm)
     bool wf_no_region_split; // CTTS_WF_NO_REGION_SPLIT: the fused WaveFlow layer as ONE launch per layer (no A | M | B regions on three streams)
     bool wf_no_row_queue;  // CTTS_WF_NO_ROW_QUEUE: never the one-launch-per-row work queue of the fused WaveFlow layers

@@ -53,6 +53,9 @@ struct Plan {
         // GATE packing (K = C + H; bias = in_b[i]); wg_dense = the dense [3][2C][C] G2, G3, -W2 of the layer being packed
         std::vector<size_t> wg_T2_A, wg_T3_A, wg_e_A, wg_o_A;
         size_t wg_dense;
+        // Winograd F(4,3) form of the one-launch layer (where wn_winograd_layer_f43_supported; empty otherwise): per layer U1..U4 in
+        // SPLIT packing (K = C), [U0 | C_i] and [U5 | C_i] in GATE packing (K = C + H); wg_dense then holds the dense [6][2C][C] U0..U5
+        std::vector<size_t> wq_U_A[4], wq_e_A, wq_o_A;
     };
     std::vector<Flow> fl;
     size_t total;
@@ -143,7 +146,13 @@ int make_plan(const ctts_waveglow_config* cfg, Plan& p) {
             f.wg_e_A.push_back(take((size_t)p.mb_in * (p.nch_rs + p.nch1h) * A_TILE));
             f.wg_o_A.push_back(take((size_t)p.mb_in * (p.nch_rs + p.nch1h) * A_TILE));
         }
-        f.wg_dense = take((size_t)3 * 2 * p.C * p.C);
+        const bool f43 = wn_winograd_layer_f43_supported(p.C, p.H);
+        for (int i = 0; f43 && i < c.n_layers; ++i) {
+            for (auto& u : f.wq_U_A) u.push_back(take((size_t)p.mb_in * p.nch_rs * A_TILE));
+            f.wq_e_A.push_back(take((size_t)p.mb_in * (p.nch_rs + p.nch1h) * A_TILE));
+            f.wq_o_A.push_back(take((size_t)p.mb_in * (p.nch_rs + p.nch1h) * A_TILE));
+        }
+        f.wg_dense = take((size_t)(f43 ? 6 : 3) * 2 * p.C * p.C);
     }
     p.total = o;
     return CTTS_OK;
@@ -175,6 +184,18 @@ int pair_ld(const Plan& p, const Geom& g) {
     for (int i = 0; i < p.c.n_layers; ++i) nt = std::max(nt, pair_geom(g, i).ntiles);
     return nt * GEMM_BN;
 }
+// Winograd F(4,3) form: quad-space geometry of layer i: Lq = ceil(L / 4d) d quad columns per batch item, in ntiles 64-column tiles
+// (the only width of that form); every layer uses the row stride ldq of the widest one
+PairGeom quad_geom(const Geom& g, int layer) {
+    const int d = 1 << layer;
+    const int Lq = (g.L + 4 * d - 1) / (4 * d) * d;
+    return {d, Lq, (Lq + 63) / 64};
+}
+int quad_ld(const Plan& p, const Geom& g) {
+    int nt = 0;
+    for (int i = 0; i < p.c.n_layers; ++i) nt = std::max(nt, quad_geom(g, i).ntiles);
+    return nt * 64;
+}
 // The form is taken only where the in-layer launch runs the fp32 MFMA loop, and for utterances of at least WINOGRAD_MIN_COLS columns
 // (steps per batch item).  The test is on the utterance, never on the batch: an utterance must come out bit for bit the same
 // whatever batch it runs in (tests/test_full_size.py), and both forms are bit-identical across the kernel shapes a batch size picks.
@@ -201,14 +222,28 @@ bool winograd_fused_engages(const Plan& p, const Geom& g) {
     return winograd_engages(p, g) && (long long)g.L >= min_cols;
 }
 
+// The F(4,3) form of the one-launch layer (wn_winograd_layer.h, WNWG_F43: 1.5 C products per output and row where F(2,3) spends 2 C)
+// where the one-launch layer engages, for utterances of at least WINOGRAD_F43_MIN_COLS columns - the length its A/B was run at (900
+// frames, profiles/r23_01_winograd_f43_gonogo.txt); the test is on the utterance alone.  CTTS_F32_WINOGRAD_F43_MIN: another
+// threshold (0 = always); CTTS_F32_WINOGRAD_NO_F43, and whatever switches the one-launch layer off: never.  Not bit-equal to F(2,3):
+// other products (float64 parity: tests/test_waveglow_winograd_f43_gpu.py).
+constexpr long long WINOGRAD_F43_MIN_COLS = 28800;
+bool winograd_f43_engages(const Plan& p, const Geom& g) {
+    const Tuning t = tuning();
+    if (t.f32_winograd_no_f43 || !wn_winograd_layer_f43_supported(p.C, p.H) || !gemm_f32_dma_staged(p.nch_rs + p.nch1h)) return false;
+    const long long min_cols = t.f32_winograd_f43_min >= 0 ? t.f32_winograd_f43_min : WINOGRAD_F43_MIN_COLS;
+    return winograd_fused_engages(p, g) && (long long)g.L >= min_cols;
+}
+
 struct Workspace {
     float *audio, *spect, *spk, *h_tmp, *h_all, *x, *act, *out;
     float* act_all;     // deferred-skip form: the gated activations of every layer of a flow ([n_layers] x act)
     float* a16;         // WN folds: layer 0's input [B][FOLD_ROWS][ld] = [audio_0; 1 on [0, L); 0]
     float* skend;       // WN folds: the skip/end accumulator [B][2 n_half][ld] between the groups of a flow
-    // Winograd in-layer form (NULL where it does not engage): V1..V4 [4][B][C][ldp], T2 / T3 [2][B][2C][ldp], h2e / h2o [2][B][H][ldp]
+    // Winograd in-layer form (NULL where it does not engage): V1..V4 [4][B][C][ldp], T2 / T3 [2][B][2C][ldp], h2e / h2o [2][B][H][ldp];
+    // the F(4,3) form keeps V0..V5 [6][B][C][ldq] and h(t_0)..h(t_3) [4][B][H][ldq] in the same two buffers (sized for the larger form)
     float *wgV, *wgT, *wgH;
-    int ldp;
+    int ldp, ldq;
     size_t total;  // floats
 };
 
@@ -229,12 +264,13 @@ void carve(const Plan& p, const Geom& g, int batch, float* base, Workspace& w) {
     w.a16 = take(B * FOLD_ROWS * g.ld);
     w.skend = take(B * p.c.n_group * g.ld);
     w.wgV = w.wgT = w.wgH = nullptr;
-    w.ldp = 0;
+    w.ldp = w.ldq = 0;
     if (winograd_engages(p, g)) {
         w.ldp = pair_ld(p, g);
-        w.wgV = take((size_t)4 * B * p.C * w.ldp);
+        w.ldq = winograd_f43_engages(p, g) ? quad_ld(p, g) : 0;
+        w.wgV = take(std::max((size_t)4 * w.ldp, (size_t)6 * w.ldq) * B * p.C);
         w.wgT = take((size_t)2 * B * 2 * p.C * w.ldp);
-        w.wgH = take((size_t)2 * B * p.H * w.ldp);
+        w.wgH = take(std::max((size_t)2 * w.ldp, (size_t)4 * w.ldq) * B * p.H);
     }
     w.total = o;
 }
@@ -333,7 +369,7 @@ int run_cond(const Plan& p, const Geom& g, const float* blob, const float* spect
 // 2 n_half-row image, and the last one of a flow is also the flow tail (coupling, inverse 1x1, un-squeeze into `wave`).
 struct WnFold { float* a16; float* skend; float* audio; float* wave; };
 // Winograd F(2,3) form of the in-layer GEMMs that read x (the whole-infer entry points, which own these buffers)
-struct WnWinograd { float* V; float* T; float* Hc; int ldp; };
+struct WnWinograd { float* V; float* T; float* Hc; int ldp; int ldq; };
 
 // One in-layer step in the Winograd form: transform, T2 = G2 V2, T3 = G3 V3, then the even and odd members of every pair
 //   act[t_e] = gate([W0 | C_i] [V1; h(t_e)] + b + T2 + T3),   act[t_o] = gate([-W2 | C_i] [V4; h(t_o)] + b + T2 - T3)
@@ -356,6 +392,28 @@ int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k
     const bool in_place = lean && pg.d % 4 == 0;
     const bool fused = lean && winograd_fused_engages(p, g);
     const float* h2 = h_all + (size_t)k * H * g.ld;
+    if (fused && wg.ldq > 0 && winograd_f43_engages(p, g)) {
+        // F(4,3): the quad transform (V0..V5, 1.5 C L floats), then ONE launch of the 64-column quad shape; no peel exists
+        const PairGeom qg = quad_geom(g, i);
+        const int ldq = wg.ldq;
+        int rc = launch_winograd_transform_quad(x, (long long)C * g.ld, h2, hstride, wg.V, wg.Hc, batch, C, H, qg.d, g.L, qg.Lp, g.ld, g.pad,
+                                                ldq, qg.ntiles * 64, !in_place, s);
+        if (rc) return rc;
+        WnWinogradLayerArgs w{};
+        w.form = WNWG_F43;
+        w.A_T2 = blob + f.wq_U_A[0][i]; w.A_T3 = blob + f.wq_U_A[1][i]; w.A_T4 = blob + f.wq_U_A[2][i]; w.A_T5 = blob + f.wq_U_A[3][i];
+        w.A_e = blob + f.wq_e_A[i]; w.A_o = blob + f.wq_o_A[i];
+        w.bias = blob + f.in_b[i];
+        w.V = wg.V; w.vplane = (long long)batch * C * ldq;
+        w.Hc = wg.Hc; w.hplane = (long long)batch * H * ldq;
+        w.h2 = h2; w.h_bstride = hstride;
+        w.act = act; w.act_bstride = (long long)C * g.ld;
+        w.C = C; w.H = H; w.batch = batch;
+        w.ldp = ldq; w.Lp = qg.Lp; w.ntiles = qg.ntiles;
+        w.d = qg.d; w.L = g.L; w.ld = g.ld; w.pad = g.pad;
+        w.in_place = in_place;
+        return launch_wn_winograd_layer(w, s);
+    }
     int rc = launch_winograd_transform(x, (long long)C * g.ld, h2, hstride, wg.V, wg.Hc, batch, C, H, pg.d, g.L, pg.Lp, g.ld, g.pad,
                                        ldp, pg.ntiles * GEMM_BN, !in_place, lean, s);
     if (rc) return rc;
@@ -549,7 +607,7 @@ int run_flow(const Plan& p, const Geom& g, const float* blob, int k, const Works
              float* wave, int batch, hipStream_t s, const CouplingForward* fwd = nullptr) {
     const Tuning t = tuning();
     const bool folded = !t.f32_no_wn_fold && !t.f32_no_defer_skip;
-    const WnWinograd wg{w.wgV, w.wgT, w.wgH, w.ldp};
+    const WnWinograd wg{w.wgV, w.wgT, w.wgH, w.ldp, w.ldq};
     const WnFold fw{w.a16, w.skend, audio, wave};
     int rc = run_wn_stack(p, g, blob, k, audio, h_all, w.x, w.act, w.out, batch, s, w.act_all, folded ? &fw : nullptr,
                           w.wgV ? &wg : nullptr, fwd);
@@ -1050,6 +1108,19 @@ int ctts_waveglow_pack_flow(const ctts_waveglow_config* cfg, int32_t k, const ct
             if ((rc = launch_pack_a(A, w->cond_w[2], GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, C, H, GEMM_EPI_GATE, C, 2 * C,
                                     (long long)2 * C * i, H, 1, s))) return rc;
     }
+    // Winograd F(4,3) form: U1..U4 (dense rows, SPLIT) and [U0 | C_i], [U5 | C_i] (pair rows, GATE) through the same dense scratch
+    for (int i = 0; i < (f.wq_e_A.empty() ? 0 : p.c.n_layers); ++i) {
+        float* dense = blob + f.wg_dense;
+        const size_t dn = (size_t)2 * C * C;
+        if ((rc = launch_winograd_g43(w->in_w[i], dense, 2 * C, C, s))) return rc;
+        for (int j = 0; j < 4; ++j)
+            if ((rc = launch_pack_a(blob + f.wq_U_A[j][i], dense + (1 + j) * dn, GEMM_BM, p.mb_in, p.nch_rs, 0, C, GEMM_EPI_SPLIT, C, 2 * C, 0, C, 1, s))) return rc;
+        if ((rc = launch_pack_a(blob + f.wq_e_A[i], dense, GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, 0, C, GEMM_EPI_GATE, C, 2 * C, 0, C, 1, s))) return rc;
+        if ((rc = launch_pack_a(blob + f.wq_o_A[i], dense + 5 * dn, GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, 0, C, GEMM_EPI_GATE, C, 2 * C, 0, C, 1, s))) return rc;
+        for (float* A : {blob + f.wq_e_A[i], blob + f.wq_o_A[i]})
+            if ((rc = launch_pack_a(A, w->cond_w[2], GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, C, H, GEMM_EPI_GATE, C, 2 * C,
+                                    (long long)2 * C * i, H, 1, s))) return rc;
+    }
     // WN start / end folds: layer 0 on [audio_0; 1] (K = [tap0, tap1, tap2] of one FOLD_ROWS chunk each, then the cond slice of
     // layer 0; bias in_b[0] as packed above) and the skip rows seen through `end`
     if ((rc = launch_fold_in0(w->in_w[0], w->start_w, w->start_b, blob + f.in0f_w, C, d.n_half, ks, s))) return rc;
@@ -1264,7 +1335,8 @@ int ctts_tuning_flags(void) {
            (t.bf16_ps ? (1 << 20) : 0) | (t.bf16_no_ps ? (1 << 21) : 0) | (t.taco_poll_delay_set ? (1 << 23) : 0) |
            (t.taco_valu ? (1 << 24) : 0) | (t.up_no_mfma ? (1 << 25) : 0) | (t.f32_no_wn_fold ? (1 << 26) : 0) |
            (t.taco_bg_no_pipe ? (1 << 27) : 0) | (t.f32_no_winograd ? (1 << 28) : 0) | (t.f32_winograd_min >= 0 ? (1 << 29) : 0) |
-           (t.f32_winograd_plain ? (1 << 30) : 0) | (t.f32_winograd_fused_min >= 0 ? 4 : 0) | (t.f32_winograd_no_fused ? 32 : 0);
+           (t.f32_winograd_plain ? (1 << 30) : 0) | (t.f32_winograd_fused_min >= 0 ? 4 : 0) | (t.f32_winograd_no_fused ? 32 : 0) |
+           (t.f32_winograd_f43_min >= 0 ? (1 << 6) : 0) | (t.f32_winograd_no_f43 ? (1 << 22) : 0);
 }
 
 int ctts_profile_create(void** handle) {

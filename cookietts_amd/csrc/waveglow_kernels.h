@@ -62,4 +62,12 @@ int launch_winograd_transform(const float* x, long long x_bstride, const float* 
                               int batch, int C, int H, int d, int L, int Lp, int ld, int pad, int ldp, int ncols, bool cond_rows,
                               bool vec_d2, hipStream_t s);
 
+// Winograd F(4,3) form of the same layers (points 0, +-1, +-2, inf; the algebra is at the kernels).  Pack time: dense [6][rows][C] =
+// U0..U5.  Per layer: V0..V5 [6][B][C][ldq] and, with cond_rows, the copies h(t_0)..h(t_3) [4][B][H][ldq] in quad order (Lq quad
+// columns, zeros up to ncols).
+int launch_winograd_g43(const float* in_w, float* dense, int rows, int C, hipStream_t s);
+int launch_winograd_transform_quad(const float* x, long long x_bstride, const float* h2, long long h_bstride, float* V, float* Hc,
+                                   int batch, int C, int H, int d, int L, int Lq, int ld, int pad, int ldq, int ncols, bool cond_rows,
+                                   hipStream_t s);
+
 }  // namespace ctts

@@ -630,6 +630,116 @@ __global__ __launch_bounds__(256) void winograd_transform_kernel(const float* __
     }
 }
 
+// --------------------------------------------------- Winograd F(4,3) in-layer form ----
+// The same conv on the output quad t_k = t_0 + k d, k = 0..3, from the six taps x_j = x[t_0 + (j - 1) d], j = 0..5, with the
+// interpolation points 0, +-1, +-2, inf:
+//   V0 = 4 x0 - 5 x2 + x4          V1 = -4 (x1 + x2) + (x3 + x4)     V2 = 4 (x1 - x2) - (x3 - x4)
+//   V3 = -2 (x1 - x3) - (x2 - x4)  V4 = 2 (x1 - x3) - (x2 - x4)      V5 = 4 x1 - 5 x3 + x5
+//   U0 = W0 / 4   U1 = -(W0 + W1 + W2) / 6   U2 = -(W0 - W1 + W2) / 6   U3 = W0 / 24 + W1 / 12 + W2 / 6
+//   U4 = W0 / 24 - W1 / 12 + W2 / 6   U5 = W2
+//   P_j = U_j V_j:  u[t_0] = P0 + (P1 + P2) + (P3 + P4)           u[t_1] = (P1 - P2) + 2 (P3 - P4)
+//                   u[t_2] = (P1 + P2) + 4 (P3 + P4)              u[t_3] = (P1 - P2) + 8 (P3 - P4) + P5
+// 1.5 C MACs per output and row.  Quad column q of a batch item stands for t_0 = (q / d) 4d + q % d; there are Lq = ceil(L / 4d) d.
+
+// dense[j] = U_j, j = 0..5, as [rows][C] (in_w: [rows][C][3]); fp64 sums rounded once
+__global__ __launch_bounds__(256) void winograd_g43_kernel(const float* __restrict__ in_w, float* __restrict__ dense, int n) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const double w0 = in_w[(size_t)idx * 3], w1 = in_w[(size_t)idx * 3 + 1], w2 = in_w[(size_t)idx * 3 + 2];
+    dense[idx] = (float)(w0 / 4.0);
+    dense[(size_t)n + idx] = (float)(-(w0 + w1 + w2) / 6.0);
+    dense[2 * (size_t)n + idx] = (float)(-(w0 - w1 + w2) / 6.0);
+    dense[3 * (size_t)n + idx] = (float)(w0 / 24.0 + w1 / 12.0 + w2 / 6.0);
+    dense[4 * (size_t)n + idx] = (float)(w0 / 24.0 - w1 / 12.0 + w2 / 6.0);
+    dense[5 * (size_t)n + idx] = in_w[(size_t)idx * 3 + 2];
+}
+
+// x [B][C][ld] and the flow's cond rows h2 [B][H][ld] -> V0..V5 [6][B][C][ldq] and the copies h(t_0)..h(t_3) [4][B][H][ldq] in
+// quad order (grid.y = C + H; grid.y = C: no cond rows - the layer kernel reads h2 in place).  Zero outside [0, L); columns
+// [Lq, ncols) are written as zeros.  One thread: four quad columns of one row.
+// MODE 1: d % 4 == 0 and L % 4 == 0 - four consecutive time steps per tap, 16-byte aligned, all inside or all outside
+// MODE 2: d == 2 and L % 4 == 0 - quad columns q4 .. q4 + 3 stand for t_0 = 4 q4 + {0, 1, 8, 9}: every tap lies in
+//         x[4 q4 - 4 .. 4 q4 + 20), six aligned 16-byte loads; Lq is even, so the columns q4 + 2, q4 + 3 can lie beyond it on their own
+// MODE 0: one column at a time
+template <int MODE>
+__global__ __launch_bounds__(256) void winograd_transform_quad_kernel(const float* __restrict__ x, long long x_bstride,
+                                                                      const float* __restrict__ h2, long long h_bstride,
+                                                                      float* __restrict__ V, float* __restrict__ Hc, int C, int H,
+                                                                      int d, int L, int Lq, int ld, int pad, int ldq, int ncols) {
+    const int q4 = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (q4 >= ncols) return;
+    const int row = blockIdx.y, b = blockIdx.z, B = gridDim.z;
+    const bool is_x = row < C;
+    const float* src = is_x ? x + (size_t)b * x_bstride + (size_t)row * ld + pad
+                            : h2 + (size_t)b * h_bstride + (size_t)(row - C) * ld + pad;
+    float tap[6][4];                                                  // tap[j][e] = x[t_0(q4 + e) + (j - 1) d]
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tap[j][e] = 0.f;
+    [[maybe_unused]] auto ld4 = [&](int t) { return (t >= 0 && t < L) ? *reinterpret_cast<const float4*>(src + t) : make_float4(0.f, 0.f, 0.f, 0.f); };
+    if constexpr (MODE == 1) {
+        if (q4 < Lq) {
+            const int t0 = (q4 / d) * 4 * d + q4 % d;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                if (!is_x && (j == 0 || j == 5)) continue;            // (cond rows: only the four members are copied)
+                const float4 v = ld4(t0 + (j - 1) * d);
+                tap[j][0] = v.x; tap[j][1] = v.y; tap[j][2] = v.z; tap[j][3] = v.w;
+            }
+        }
+    } else if constexpr (MODE == 2) {
+        if (q4 < Lq) {
+            float a[24];                                              // x[4 q4 - 4 + i]
+#pragma unroll
+            for (int u = 0; u < 6; ++u) {
+                const float4 v = ld4(4 * q4 - 4 + 4 * u);
+                a[4 * u] = v.x; a[4 * u + 1] = v.y; a[4 * u + 2] = v.z; a[4 * u + 3] = v.w;
+            }
+            const bool hi = q4 + 2 < Lq;                              // columns q4 + 2, q4 + 3 (Lq is even)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                tap[j][0] = a[4 + (j - 1) * 2]; tap[j][1] = a[5 + (j - 1) * 2];
+                tap[j][2] = hi ? a[12 + (j - 1) * 2] : 0.f; tap[j][3] = hi ? a[13 + (j - 1) * 2] : 0.f;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int q = q4 + e;
+            const int t0 = (q / d) * 4 * d + q % d;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                const int t = t0 + (j - 1) * d;
+                tap[j][e] = (q < Lq && t >= 0 && t < L && (is_x || (j >= 1 && j <= 4))) ? src[t] : 0.f;
+            }
+        }
+    }
+    if (is_x) {
+        const size_t plane = (size_t)B * C * ldq;
+        float* o = V + ((size_t)b * C + row) * ldq + q4;
+        float v[6][4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float x0 = tap[0][e], x1 = tap[1][e], x2 = tap[2][e], x3 = tap[3][e], x4 = tap[4][e], x5 = tap[5][e];
+            const float s12 = x1 + x2, d12 = x1 - x2, s34 = x3 + x4, d34 = x3 - x4, d13 = x1 - x3, d24 = x2 - x4;
+            v[0][e] = 4.f * x0 - 5.f * x2 + x4;
+            v[1][e] = s34 - 4.f * s12;
+            v[2][e] = 4.f * d12 - d34;
+            v[3][e] = -2.f * d13 - d24;
+            v[4][e] = 2.f * d13 - d24;
+            v[5][e] = 4.f * x1 - 5.f * x3 + x5;
+        }
+#pragma unroll
+        for (int j = 0; j < 6; ++j) *reinterpret_cast<float4*>(o + j * plane) = make_float4(v[j][0], v[j][1], v[j][2], v[j][3]);
+    } else {
+        const size_t plane = (size_t)B * H * ldq;
+        float* o = Hc + ((size_t)b * H + (row - C)) * ldq + q4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(o + k * plane) = make_float4(tap[k + 1][0], tap[k + 1][1], tap[k + 1][2], tap[k + 1][3]);
+    }
+}
+
 // a16[b][r][:] over the whole padded row: r < H: audio[b][ch_off + r][n], r == H: 1, other rows 0; 0 outside [pad, pad + L)
 template <int H>
 __global__ __launch_bounds__(256) void wn_start_ones_kernel(const float* __restrict__ audio, float* __restrict__ a16, int G,
@@ -904,6 +1014,33 @@ int launch_winograd_transform(const float* x, long long x_bstride, const float* 
         hipLaunchKernelGGL(winograd_transform_kernel<0>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lp,
                            ld, pad, ldp, ncols);
     CTTS_CHECK_LAUNCH("winograd_transform");
+    return CTTS_OK;
+}
+
+int launch_winograd_g43(const float* in_w, float* dense, int rows, int C, hipStream_t s) {
+    const int n = rows * C;
+    hipLaunchKernelGGL(winograd_g43_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in_w, dense, n);
+    CTTS_CHECK_LAUNCH("winograd_g43");
+    return CTTS_OK;
+}
+
+int launch_winograd_transform_quad(const float* x, long long x_bstride, const float* h2, long long h_bstride, float* V, float* Hc,
+                                   int batch, int C, int H, int d, int L, int Lq, int ld, int pad, int ldq, int ncols, bool cond_rows,
+                                   hipStream_t s) {
+    CTTS_CHECK_ARG(d >= 1 && Lq % d == 0 && (long long)Lq * 4 >= L && Lq <= ncols && ncols <= ldq && ncols % 4 == 0 && ldq % 4 == 0 &&
+                       ld % 4 == 0 && pad % 4 == 0 && pad + L <= ld && (!cond_rows || Hc != nullptr),
+                   "winograd_transform_quad: d=%d L=%d Lq=%d ncols=%d ldq=%d ld=%d pad=%d", d, L, Lq, ncols, ldq, ld, pad);
+    dim3 grid((ncols / 4 + 255) / 256, cond_rows ? C + H : C, batch);
+    if (d % 4 == 0 && L % 4 == 0)
+        hipLaunchKernelGGL(winograd_transform_quad_kernel<1>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lq,
+                           ld, pad, ldq, ncols);
+    else if (d == 2 && L % 4 == 0)
+        hipLaunchKernelGGL(winograd_transform_quad_kernel<2>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lq,
+                           ld, pad, ldq, ncols);
+    else
+        hipLaunchKernelGGL(winograd_transform_quad_kernel<0>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lq,
+                           ld, pad, ldq, ncols);
+    CTTS_CHECK_LAUNCH("winograd_transform_quad");
     return CTTS_OK;
 }
 

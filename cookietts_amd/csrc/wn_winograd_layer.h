@@ -5,6 +5,14 @@
 // run one after the other through ONE chunk stream of a workgroup that owns 128 packed rows (the tanh and the sigmoid rows of 64
 // channels) x 128 pair columns; T2 / T3 never leave the registers.  The operands are the panels and planes the lean form
 // (waveglow_api.hip, run_in_layer_winograd) already has.
+//
+// form = WNWG_F43 is the F(4,3) form of the same stream: a workgroup owns 128 packed rows x 64 QUAD columns (256 natural columns);
+// quad column q of a batch item stands for the natural columns t_k = (q / d) 4d + q % d + k d, k = 0..3, Lq = ceil(L / 4d) d.
+//   P_j = U_j V_j (j = 1..4),  a = P1 + P2, b = P1 - P2, c = P3 + P4, e = P3 - P4,
+//   act[t_0] = gate(a + c   + [U0 | C_i] [V0; h(t_0)] + b),   act[t_1] = gate(b + 2 e + C_i h(t_1) + b),
+//   act[t_2] = gate(a + 4 c + C_i h(t_2) + b),                act[t_3] = gate(b + 8 e + [U5 | C_i] [V5; h(t_3)] + b)
+// with U = G W, V = B^T x of the interpolation points 0, +-1, +-2, inf.  ldp / Lp / ntiles then describe the quad space, in tiles of
+// 64 columns; the only kernel width is 64, so no peel and no width-dependent choice exists.
 #pragma once
 
 #include "common.h"
@@ -12,26 +20,32 @@
 
 namespace ctts {
 
-constexpr int WNWG_MAX_CHUNKS = 320;      // chunk -> address table entries: 2 C / 16 + 2 (C + H) / 16 chunks (C = 512, H = 256: 160)
+constexpr int WNWG_MAX_CHUNKS = 320;      // chunk -> address table entries: 2 C / 16 + 2 (C + H) / 16 chunks (C = 512, H = 256: 160;
+                                          // F(4,3): 4 C / 16 + 2 (C + H) / 16 + 2 H / 16 = 256)
+constexpr int WNWG_F23 = 0, WNWG_F43 = 1;
 
 struct WnWinogradLayerArgs {
     // packed weights of the layer, as the lean form's launches take them: G2, G3 in SPLIT packing [2C / 256][C / 16][16][256],
     // [W0 | C_i], [-W2 | C_i] in GATE packing [2C / 256][(C + H) / 16][16][256]; bias in the GATE launch's block-local row order
+    // F(4,3): A_T2..A_T5 = U1..U4 (SPLIT), A_e = [U0 | C_i], A_o = [U5 | C_i] (GATE)
     const float *A_T2, *A_T3, *A_e, *A_o, *bias;
-    const float* V; long long vplane;         // V1..V4 [4][B][C][ldp]
-    const float* Hc; long long hplane;        // cond copies h2e, h2o [2][B][H][ldp] (in_place = 0)
+    const float *A_T4, *A_T5;
+    const float* V; long long vplane;         // V1..V4 [4][B][C][ldp]; F(4,3): V0..V5 [6][B][C][ldp]
+    const float* Hc; long long hplane;        // cond copies h2e, h2o [2][B][H][ldp] (in_place = 0); F(4,3): h(t_0)..h(t_3) [4][B][H][ldp]
     const float* h2; long long h_bstride;     // the flow's cond rows in the natural layout [B][H][ld] (in_place = 1: d % 4 == 0)
     float* act; long long act_bstride;        // [B][C][ld], natural columns
     int C, H, batch;
     int ldp, Lp, ntiles;                      // pair space: row stride, pair columns per batch item, 128-column tiles per batch item
     int d, L, ld, pad;                        // dilation; natural geometry
     int in_place;
+    int form;                                 // WNWG_F23 (0) or WNWG_F43
     // set by the launcher: column tiles (of the kernel's own width) per batch item and in the launch, first batch item, column origin
     int kt, kt_total, b0, col0;
 };
 
 // true when the kernel can run these channel counts (the caller selects the lean form otherwise)
 bool wn_winograd_layer_supported(int C, int H);
+bool wn_winograd_layer_f43_supported(int C, int H);
 int launch_wn_winograd_layer(const WnWinogradLayerArgs& a, hipStream_t stream);
 
 }  // namespace ctts

@@ -16,6 +16,16 @@
 // as two 64-row runs of two M-blocks - the lanes carry that, no second copy of the weights exists.
 // NT = 2 (128 columns) and NT = 1 (64 columns, for small grids and the tiles beyond the last whole round) sum every column's
 // products in the same order with the same instruction: bit-identical.
+//
+// F43 = 1 is the F(4,3) form on the same main-loop body (NT = 1 only): 64 QUAD columns = 256 natural columns, FOUR accumulator sets
+// (the 128 VGPRs S and D cost at NT = 2) and one stream of 4 n1 + 2 n2 + 2 nh chunks (nh = H / 16):
+//   [0, 4 n1)          X_j += U_(j+1) . V_(j+1), j = 0..3
+//                      then a = X0 + X1, b = X0 - X1, c = X2 + X3, e = X2 - X3, (X0..X3) <- (a + c, b + 2 e, a + 4 c, b + 8 e)
+//   [.., + n2)         X0 += [U0 | C_i] . [V0; h(t_0)]   then act[t_0] = gate(X0 + b)
+//   [.., + nh)         X1 += C_i . h(t_1)                then act[t_1]      (the cond chunks of the [U0 | C_i] panel: no third C_i)
+//   [.., + nh)         X2 += C_i . h(t_2)                then act[t_2]
+//   [.., + n2)         X3 += [U5 | C_i] . [V5; h(t_3)]   then act[t_3]
+// (interpolation points 0, +-1, +-2, inf: the output-side multipliers 1, 2, 4, 8 are exact scalings).
 #include "wn_winograd_layer.h"
 #include "tuning.h"
 
@@ -35,8 +45,10 @@ __device__ __forceinline__ float wg_tanh(float u) {
 
 }  // namespace
 
-template <int NT>
+template <int NT, int F43>
 __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnWinogradLayerArgs a) {
+    static_assert(!F43 || NT == 1, "the F(4,3) form runs on the 64-column shape");
+    constexpr int NI = F43 ? 4 : 2;                       // interior products = accumulator sets = natural columns per packed column
     constexpr int BN = 64 * NT;
     constexpr int A_ST = GEMM_KC * 128;                   // floats of a stage's A part
     constexpr int STG = A_ST + GEMM_KC * BN;              // floats per stage
@@ -62,8 +74,14 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
     const int b = a.b0 + gt / a.kt;
     const int n0 = a.col0 + (gt % a.kt) * BN;             // first pair column (of the batch item)
 
-    const int n1 = a.C / GEMM_KC, n2 = (a.C + a.H) / GEMM_KC;
-    const int c_e = 2 * n1, c_o = 2 * n1 + n2, nch = 2 * n1 + 2 * n2;
+    const int n1 = a.C / GEMM_KC, n2 = (a.C + a.H) / GEMM_KC, nh = a.H / GEMM_KC;
+    // the phases behind the interior products: the first and the last carry an end product (n2 chunks), the others cond rows alone
+    const int c_e = NI * n1;
+    int ps[NI + 1];
+    ps[0] = c_e;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) ps[k + 1] = ps[k] + (k == 0 || k == NI - 1 ? n2 : nh);
+    const int nch = ps[NI];
 
     // SPLIT-packed panels: this block's tanh rows are dense rows 64 cb .., its sigmoid rows dense rows C + 64 cb ..
     const int mb_t = (64 * cb) >> 8, loc_t = (64 * cb) & 255;
@@ -73,13 +91,17 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
         for (int c = t; c < nch; c += 256) {
             const float *ap, *bp;
             if (c < c_e) {
-                const int ph = c >= n1, loc = c - ph * n1;
-                ap = (ph ? a.A_T3 : a.A_T2) + ((size_t)mb_t * n1 + loc) * (GEMM_KC * 256) + loc_t;
+                const int ph = F43 ? c / n1 : (int)(c >= n1), loc = c - ph * n1;
+                ap = (ph == 0 ? a.A_T2 : ph == 1 ? a.A_T3 : ph == 2 ? a.A_T4 : a.A_T5) + ((size_t)mb_t * n1 + loc) * (GEMM_KC * 256) + loc_t;
                 bp = a.V + (1 + ph) * a.vplane + ((size_t)b * a.C + (size_t)loc * GEMM_KC) * a.ldp + n0;
             } else {
-                const int ph = c >= c_o, loc = c - c_e - ph * n2;
-                ap = (ph ? a.A_o : a.A_e) + ((size_t)(cb >> 1) * n2 + loc) * (GEMM_KC * 256) + (cb & 1) * 128;
-                if (loc < n1) bp = a.V + (ph ? 3 : 0) * a.vplane + ((size_t)b * a.C + (size_t)loc * GEMM_KC) * a.ldp + n0;
+                int ph = 0;
+#pragma unroll
+                for (int k = 1; k < NI; ++k) ph += c >= ps[k];
+                const bool last = ph == NI - 1;
+                const int loc = c - ps[ph] + (ph == 0 || last ? 0 : n1);      // k-chunk of the GATE panel (a middle phase: its cond chunks)
+                ap = (last ? a.A_o : a.A_e) + ((size_t)(cb >> 1) * n2 + loc) * (GEMM_KC * 256) + (cb & 1) * 128;
+                if (loc < n1) bp = a.V + (last ? NI + 1 : 0) * a.vplane + ((size_t)b * a.C + (size_t)loc * GEMM_KC) * a.ldp + n0;
                 else if (a.in_place) bp = a.h2 + (size_t)b * a.h_bstride + (size_t)(loc - n1) * GEMM_KC * a.ld;   // the lanes carry pad and column
                 else bp = a.Hc + ph * a.hplane + ((size_t)b * a.H + (size_t)(loc - n1) * GEMM_KC) * a.ldp + n0;
             }
@@ -90,7 +112,7 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
     }
 
     // 32-bit lane byte offsets of the DMA pieces.  A piece j of wave w = k-rows 2 (w + 4 j), + 1 of the stage (256 floats, lane order)
-    unsigned offa_g[2], offa_s[2], offb[NT], offb_e[NT], offb_o[NT];
+    unsigned offa_g[2], offa_s[2], offb[NT], offb_m[NI][NT];
     {
         const int col = (lane & 31) * 4;
         const long long delta = ((long long)(mb_s - mb_t) * n1) * (GEMM_KC * 256) + (loc_s - loc_t);
@@ -105,28 +127,32 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
         for (int j = 0; j < NT; ++j) {
             const int krow = (wave + 4 * j) * RPP + lane / UPR;
             offb[j] = (unsigned)(((size_t)krow * a.ldp + bcol) * 4);
-            offb_e[j] = offb_o[j] = 0;
+#pragma unroll
+            for (int k = 0; k < NI; ++k) offb_m[k][j] = 0;
             if (a.in_place) {
-                // the lane's unit starts at pair column q and is read at the natural column of q: four consecutive, 16-byte aligned
+                // the lane's unit starts at packed column q and is read at the natural column of q: four consecutive, 16-byte aligned
                 // columns (d % 4 == 0), clamped to the row's last aligned unit (those outputs are dropped by the L / Lp tests)
                 const int q = n0 + bcol;
-                const int te = (q / a.d) * (2 * a.d) + q % a.d;
+                const int te = (q / a.d) * (NI * a.d) + q % a.d;
                 const int lim = (a.ld - a.pad - 4) & ~3;
-                offb_e[j] = (unsigned)(((size_t)krow * a.ld + a.pad + min(te, lim)) * 4);
-                offb_o[j] = (unsigned)(((size_t)krow * a.ld + a.pad + min(te + a.d, lim)) * 4);
+#pragma unroll
+                for (int k = 0; k < NI; ++k) offb_m[k][j] = (unsigned)(((size_t)krow * a.ld + a.pad + min(te + k * a.d, lim)) * 4);
             }
         }
     }
-    const int m_e0 = a.in_place ? c_e + n1 : 0x7fffffff, m_e1 = c_o;      // mapped cond chunks of the even / odd phase
-    const int m_o0 = a.in_place ? c_o + n1 : 0x7fffffff;
+    int m_lo[NI];                                         // mapped cond chunks of phase k: [m_lo[k], ps[k + 1])
+#pragma unroll
+    for (int k = 0; k < NI; ++k) m_lo[k] = a.in_place ? ps[k] + (k == 0 || k == NI - 1 ? n1 : 0) : 0x7fffffff;
 
-    wg_f32x16 S[2][NT], D[2][NT];
+    wg_f32x16 X[NI][2][NT];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int k = 0; k < NI; ++k)
 #pragma unroll
-        for (int j = 0; j < NT; ++j)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { S[i][j][r] = 0.0f; D[i][j][r] = 0.0f; }
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) X[k][i][j][r] = 0.0f;
     __syncthreads();                                      // table and bias visible
 
     typedef __attribute__((address_space(3))) float* lds_fptr;
@@ -139,7 +165,8 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
     lds_fptr la_ = (lds_fptr)(lds + (buf) * STG + wave * 256);                                              \
     const uint4 e_ = ctab[c];                                                                               \
     const bool as_ = (c) < c_e;                                      /* wave-uniform: SPLIT-packed panel */ \
-    const bool me_ = (c) >= m_e0 && (c) < m_e1, mo_ = (c) >= m_o0;   /* wave-uniform: mapped cond chunk */
+    bool mk_[NI];                                                    /* wave-uniform: mapped cond chunk */ \
+    _Pragma("unroll") for (int k = 0; k < NI; ++k) mk_[k] = (c) >= m_lo[k] && (c) < ps[k + 1];
 #define WNWG_BASES()                                                                                        \
     const gbyte_ptr ac_ = reinterpret_cast<gbyte_ptr>(                                                      \
         ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)e_.y) << 32) |                   \
@@ -154,7 +181,8 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
             asm volatile("" : "+v"(o_));                                                                    \
             __builtin_amdgcn_global_load_lds((gfloat_ptr)(ac_ + o_), la_ + 1024 * (p), 16, 0, 0);           \
         } else if constexpr ((p) < 2 + NT) {                                                                \
-            unsigned o_ = me_ ? offb_e[(p) - 2] : mo_ ? offb_o[(p) - 2] : offb[(p) - 2];                     \
+            unsigned o_ = offb[(p) - 2];                                                                    \
+            _Pragma("unroll") for (int k = 0; k < NI; ++k) o_ = mk_[k] ? offb_m[k][(p) - 2] : o_;           \
             asm volatile("" : "+v"(o_));                                                                    \
             __builtin_amdgcn_global_load_lds((gfloat_ptr)(bp_ + o_), la_ + A_ST + 1024 * ((p) - 2), 16, 0, 0); \
         }                                                                                                   \
@@ -180,16 +208,16 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
 #define WNWG_READ_FRAGS(ks)                                                                                 \
     _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) av[ks][mt] = As[(2 * (ks) + lhi) * 128 + mt * 64];     \
     _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) bv[ks][nt] = Bs[(2 * (ks) + lhi) * BN + nt * 32];
-#define WNWG_MFMA(X, ks)                                                                                    \
+#define WNWG_MFMA(Y, ks)                                                                                    \
     _Pragma("unroll") for (int mt = 0; mt < 2; ++mt)                                                        \
         _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                                   \
-            X[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks][mt], bv[ks][nt], X[mt][nt], 0, 0, 0);
-#define WNWG_REGION(X, ks, p)                                                                               \
+            Y[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks][mt], bv[ks][nt], Y[mt][nt], 0, 0, 0);
+#define WNWG_REGION(Y, ks, p)                                                                               \
     __builtin_amdgcn_sched_barrier(0);                                                                      \
     if constexpr ((ks) + 1 < GEMM_KC / 2) { WNWG_READ_FRAGS((ks) + 1) }                                     \
-    WNWG_MFMA(X, ks)                                                                                        \
+    WNWG_MFMA(Y, ks)                                                                                        \
     WNWG_PIECE(p);
-#define WNWG_CHUNK(X)                                                                                       \
+#define WNWG_CHUNK(Y)                                                                                       \
     {                                                                                                       \
         const float* As = lds + cur * STG + wm * 32 + l31;                                                  \
         const float* Bs = lds + cur * STG + A_ST + wn * (32 * NT) + l31;                                    \
@@ -200,8 +228,8 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
         WNWG_READ_FRAGS(0)                                                                                  \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
         WNWG_BASES()                                                                                        \
-        WNWG_REGION(X, 0, 0) WNWG_REGION(X, 1, 1) WNWG_REGION(X, 2, 2) WNWG_REGION(X, 3, 3)                 \
-        WNWG_REGION(X, 4, 4) WNWG_REGION(X, 5, 4) WNWG_REGION(X, 6, 4) WNWG_REGION(X, 7, 4)                 \
+        WNWG_REGION(Y, 0, 0) WNWG_REGION(Y, 1, 1) WNWG_REGION(Y, 2, 2) WNWG_REGION(Y, 3, 3)                 \
+        WNWG_REGION(Y, 4, 4) WNWG_REGION(Y, 5, 4) WNWG_REGION(Y, 6, 4) WNWG_REGION(Y, 7, 4)                 \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
         WNWG_WAIT();                                        /* chunk ch + 1 landed, the newest in flight */ \
         __builtin_amdgcn_s_barrier();                                                                       \
@@ -209,42 +237,82 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
         cur = cur == 2 ? 0 : cur + 1;                                                                       \
     }
 
-    // gate and store one accumulator set: pair column n of the batch item -> natural column (n / d) 2d + n % d + par d
+    // gate and store one accumulator set: packed column n of the batch item -> natural column (n / d) NI d + n % d + par d
     float* dst = a.act + (size_t)b * a.act_bstride + (size_t)(cb * 64 + wm * 32) * a.ld + a.pad;
     const float* bias = lds + BIAS + wm * 32;
-#define WNWG_GATE(X, par)                                                                                   \
+#define WNWG_GATE(Y, par)                                                                                   \
     _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                                     \
         const int n = n0 + wn * (32 * NT) + nt * 32 + l31;                                                  \
-        const int ns = (n / a.d) * (2 * a.d) + n % a.d + (par) * a.d;                                       \
+        const int ns = (n / a.d) * (NI * a.d) + n % a.d + (par) * a.d;                                      \
         if (n < a.Lp && ns < a.L) {                                                                         \
             _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                \
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * lhi;                                           \
-                const float u0 = X[0][nt][r] + bias[row];                                                   \
-                const float u1 = X[1][nt][r] + bias[64 + row];                                              \
+                const float u0 = Y[0][nt][r] + bias[row];                                                   \
+                const float u1 = Y[1][nt][r] + bias[64 + row];                                              \
                 dst[(size_t)row * a.ld + ns] = wg_tanh(u0) * wg_sigmoid(u1);                                \
             }                                                                                               \
         }                                                                                                   \
     }
 
-    int ch = 0;
-    for (; ch < n1; ++ch) WNWG_CHUNK(S)
-    for (; ch < c_e; ++ch) WNWG_CHUNK(D)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float s = S[i][j][r], dd = D[i][j][r];
-                S[i][j][r] = s + dd;
-                D[i][j][r] = s - dd;
-            }
-    for (; ch < c_o; ++ch) WNWG_CHUNK(S)
-    WNWG_GATE(S, 0)
-    for (; ch < nch; ++ch) WNWG_CHUNK(D)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the re-issued tail DMAs still target LDS
+#define WNWG_RUN(k, end) for (; ch < (end); ++ch) WNWG_CHUNK(X[k])
+#define WNWG_DRAIN()                                                                                        \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      /* the re-issued tail DMAs still target LDS */    \
     __builtin_amdgcn_s_barrier();
-    WNWG_GATE(D, 1)
+    int ch = 0;
+    if constexpr (!F43) {
+        WNWG_RUN(0, n1)
+        WNWG_RUN(1, c_e)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float s = X[0][i][j][r], dd = X[1][i][j][r];
+                    X[0][i][j][r] = s + dd;
+                    X[1][i][j][r] = s - dd;
+                }
+        WNWG_RUN(0, ps[1])
+        WNWG_GATE(X[0], 0)
+        WNWG_RUN(1, nch)
+        WNWG_DRAIN()
+        WNWG_GATE(X[1], 1)
+    } else {
+        WNWG_RUN(0, n1)
+        WNWG_RUN(1, 2 * n1)
+        WNWG_RUN(2, 3 * n1)
+        WNWG_RUN(3, c_e)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float p1 = X[0][i][j][r], p2 = X[1][i][j][r], p3 = X[2][i][j][r], p4 = X[3][i][j][r];
+                    const float sa = p1 + p2, sb = p1 - p2, sc = p3 + p4, se = p3 - p4;
+                    X[0][i][j][r] = sa + sc;
+                    X[1][i][j][r] = sb + 2.0f * se;
+                    X[2][i][j][r] = sa + 4.0f * sc;
+                    X[3][i][j][r] = sb + 8.0f * se;
+                }
+        // the four sums exist HERE, in the accumulators' own registers: left to itself the compiler forms Y1..Y3 only in front of their
+        // phases and holds a, c and the four products until then (224 registers where 128 do)
+#pragma unroll
+        for (int k = 0; k < NI; ++k)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) asm volatile("" : "+v"(X[k][i][0]));
+        WNWG_RUN(0, ps[1])
+        WNWG_GATE(X[0], 0)
+        WNWG_RUN(1, ps[2])
+        WNWG_GATE(X[1], 1)
+        WNWG_RUN(2, ps[3])
+        WNWG_GATE(X[2], 2)
+        WNWG_RUN(3, nch)
+        WNWG_DRAIN()
+        WNWG_GATE(X[3], 3)
+    }
+#undef WNWG_DRAIN
+#undef WNWG_RUN
 #undef WNWG_GATE
 #undef WNWG_CHUNK
 #undef WNWG_REGION
@@ -260,14 +328,18 @@ bool wn_winograd_layer_supported(int C, int H) {
     return C >= 128 && C % 128 == 0 && H > 0 && H % GEMM_KC == 0 && 2 * (C / GEMM_KC) + 2 * ((C + H) / GEMM_KC) <= WNWG_MAX_CHUNKS;
 }
 
+bool wn_winograd_layer_f43_supported(int C, int H) {
+    return wn_winograd_layer_supported(C, H) && 4 * (C / GEMM_KC) + 2 * ((C + H) / GEMM_KC) + 2 * (H / GEMM_KC) <= WNWG_MAX_CHUNKS;
+}
+
 namespace {
-template <int NT>
+template <int NT, int F43 = 0>
 int launch_wnwg_shape(WnWinogradLayerArgs a, int kt, long long kt_total, hipStream_t stream) {
     a.kt = kt;
     a.kt_total = (int)kt_total;
     const long long blocks = 8ll * (a.C / 64) * ((kt_total + 7) / 8);
     CTTS_CHECK_ARG(blocks > 0 && blocks < (1ll << 31) && kt_total < (1ll << 31), "wn_winograd_layer: grid %lld", blocks);
-    hipLaunchKernelGGL((wn_winograd_layer_f32_kernel<NT>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((wn_winograd_layer_f32_kernel<NT, F43>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
     CTTS_CHECK_LAUNCH("wn_winograd_layer");
     return CTTS_OK;
 }
@@ -277,7 +349,10 @@ int launch_wn_winograd_layer(const WnWinogradLayerArgs& a_in, hipStream_t stream
     WnWinogradLayerArgs a = a_in;
     CTTS_CHECK_ARG(wn_winograd_layer_supported(a.C, a.H), "wn_winograd_layer: C=%d H=%d", a.C, a.H);
     CTTS_CHECK_ARG(a.A_T2 && a.A_T3 && a.A_e && a.A_o && a.bias && a.V && a.act && a.batch >= 1, "wn_winograd_layer: operand not set");
-    CTTS_CHECK_ARG(a.d >= 1 && a.L >= 1 && a.Lp >= 1 && a.ntiles >= 1 && a.Lp <= a.ntiles * 128 && a.ntiles * 128 <= a.ldp && a.ldp % 4 == 0 &&
+    const bool f43 = a.form == WNWG_F43;
+    const int tw = f43 ? 64 : 128;                        // columns of a tile that ntiles counts
+    CTTS_CHECK_ARG(a.form == WNWG_F23 || (f43 && wn_winograd_layer_f43_supported(a.C, a.H) && a.A_T4 && a.A_T5), "wn_winograd_layer: form %d", a.form);
+    CTTS_CHECK_ARG(a.d >= 1 && a.L >= 1 && a.Lp >= 1 && a.ntiles >= 1 && a.Lp <= a.ntiles * tw && a.ntiles * tw <= a.ldp && a.ldp % 4 == 0 &&
                        a.ld % 4 == 0 && a.pad >= 0 && a.pad % 4 == 0 && a.L + a.pad <= a.ld,
                    "wn_winograd_layer: geometry d=%d L=%d Lp=%d ntiles=%d ldp=%d ld=%d pad=%d", a.d, a.L, a.Lp, a.ntiles, a.ldp, a.ld, a.pad);
     // in place: a lane's four pair columns must be four consecutive, 16-byte aligned natural columns
@@ -286,6 +361,7 @@ int launch_wn_winograd_layer(const WnWinogradLayerArgs& a_in, hipStream_t stream
                    "wn_winograd_layer: cond rows (in_place=%d d=%d)", a.in_place, a.d);
     a.b0 = 0;
     a.col0 = 0;
+    if (f43) return launch_wnwg_shape<1, 1>(a, a.ntiles, (long long)a.ntiles * a.batch, stream);
     const Tuning tn = tuning();
     const int ncb = a.C / 64;
     const long long slots = 2ll * wf_row_cus();

@@ -1116,7 +1116,7 @@ int ctts_pcm16_concat(const void* audio, int32_t is_half, const int32_t* frames,
 int ctts_last_gemm_loop(void);
 
 /* Launch-shape overrides for A/B measurements (CTTS_F32_NO_GLDS, CTTS_F32_NO_SMALL, CTTS_F32_FORCE_SMALL, CTTS_GEMM_NO_XCD_PAIR, CTTS_BF16_NO_WIDE /
- * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD, CTTS_F32_NO_WINOGRAD, CTTS_F32_WINOGRAD_MIN, CTTS_F32_WINOGRAD_PLAIN, CTTS_F32_WINOGRAD_FUSED_MIN, CTTS_F32_WINOGRAD_NO_FUSED) never change results beyond the parity
+ * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD, CTTS_F32_NO_WINOGRAD, CTTS_F32_WINOGRAD_MIN, CTTS_F32_WINOGRAD_PLAIN, CTTS_F32_WINOGRAD_FUSED_MIN, CTTS_F32_WINOGRAD_NO_FUSED, CTTS_F32_WINOGRAD_F43_MIN, CTTS_F32_WINOGRAD_NO_F43) never change results beyond the parity
  * tolerance (CTTS_F32_NO_SPLITK changes the summation order of the fused WaveFlow layer at batch <= 2, see above; CTTS_F32_NO_WN_FOLD
  * brings back the fp32 WaveGlow WN stack without the start / end folds: WN layer 0 on the C-row x, the C-row deferred skip GEMM and the
  * C-row flow tail - the default folds W_in,0 . W_start into layer 0 and W_end . W_skip,i into a 2 n_half-row skip/end pass, which only
@@ -1131,11 +1131,17 @@ int ctts_last_gemm_loop(void);
  * form's own default threshold; 0 = always; again the utterance alone decides) a Winograd layer is ONE launch behind the transform
  * kernel: a workgroup runs the four products of a pair block through one chunk stream and T2 / T3 stay in registers -
  * ((S2 +- S3) + products) + b where the paired launches round ((products + b) + T2) +- T3, a re-ordered sum.
- * CTTS_F32_WINOGRAD_NO_FUSED keeps the paired launches at every size: the A/B arm).  The environment is read once,
+ * CTTS_F32_WINOGRAD_NO_FUSED keeps the paired launches at every size: the A/B arm.  Where the one-launch layer engages, utterances
+ * of at least CTTS_F32_WINOGRAD_F43_MIN columns (default 28 800; 0 = always; the utterance alone decides) run it as Winograd F(4,3)
+ * on output quads (t, t + d, t + 2d, t + 3d), interpolation points 0, +-1, +-2, inf: 1.5 C products per output and row where F(2,3)
+ * spends 2 C, four interior products combined in registers with the exact multipliers 1, 2, 4, 8, the transformed filters formed
+ * in fp64 and rounded once; the float64 parity of a flow stays inside the bound of the other forms.  CTTS_F32_WINOGRAD_NO_F43
+ * keeps the F(2,3) one-launch layer at every size: the A/B arm, bit-equal to the library before the F(4,3) form; whatever
+ * switches the one-launch layer off switches the F(4,3) form off with it).  The environment is read once,
  * at the first launch; this re-reads it (tests and profiling scripts that flip a knob in-process). */
 int ctts_tuning_reload(void);
 /* The knobs as the library currently sees them: bit 0 CTTS_F32_NO_GLDS, 1 CTTS_GEMM_NO_XCD_PAIR, 2 CTTS_F32_WINOGRAD_FUSED_MIN set,
- * 5 CTTS_F32_WINOGRAD_NO_FUSED,
+ * 5 CTTS_F32_WINOGRAD_NO_FUSED, 6 CTTS_F32_WINOGRAD_F43_MIN set, 22 CTTS_F32_WINOGRAD_NO_F43,
  * 3 CTTS_BF16_NO_WIDE, 4 CTTS_BF16_NO_PP, 7 CTTS_WF_NO_FUSE, 8 CTTS_TACO_NO_FUSE,
  * 9 CTTS_F32_NO_SMALL, 10 CTTS_F32_FORCE_SMALL, 11 CTTS_F32_NO_SPLITK, 12 CTTS_WF_NO_VEC_INTERP, 13 CTTS_F32_NO_DEFER_SKIP, 14 CTTS_WF_NO_REGION_SPLIT,
  * 15 CTTS_WF_NO_ROW_QUEUE, 16 CTTS_WF_ROW_QUEUE_MIN set, 17 CTTS_WF_INJECT_ABORT, 18 CTTS_WF_QUEUE_DEBUG != 0, 19 CTTS_F32_NO_ROUND_SPLIT,
@@ -1143,7 +1149,7 @@ int ctts_tuning_reload(void);
  * before the first poll of the persistent decoder's six vector exchanges; timing only), 24 CTTS_TACO_VALU
  * (ctts_taco_decoder_steps_f32 at batch <= 4 on the VALU kernels instead of the batched MFMA form), 25 CTTS_UP_NO_MFMA (the VALU upsampling kernel
  * also for the shape the MFMA one is built for: bit-identical), 26 CTTS_F32_NO_WN_FOLD, 27 CTTS_TACO_BG_NO_PIPE (the batched
- * decoder's plain schedule, the default above 64 rows, at every size), 28 CTTS_F32_NO_WINOGRAD, 29 CTTS_F32_WINOGRAD_MIN set, 30 CTTS_F32_WINOGRAD_PLAIN.  Bits 6 and 22 belonged to retired knobs and stay unused (2 and 5 did too, until the one-launch Winograd layer took them).
+ * decoder's plain schedule, the default above 64 rows, at every size), 28 CTTS_F32_NO_WINOGRAD, 29 CTTS_F32_WINOGRAD_MIN set, 30 CTTS_F32_WINOGRAD_PLAIN.  Bits 2, 5, 6 and 22 belonged to retired knobs until the one-launch Winograd layer (2, 5) and its F(4,3) form (6, 22) took them.
  * (Tests assert that a knob they set is the one in effect.) */
 int ctts_tuning_flags(void);
 

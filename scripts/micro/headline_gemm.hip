@@ -34,6 +34,56 @@ __global__ __launch_bounds__(256) void stream_3r5w_kernel(const float4* __restri
     dst[3 * n + i] = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
     dst[4 * n + i] = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w);
 }
+// stand-in for the traffic of the F(4,3) quad transform: six taps read, six V planes written per 16-byte unit
+__global__ __launch_bounds__(256) void stream_6r6w_kernel(const float4* __restrict__ src, float4* __restrict__ dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float4 v[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] = src[j * n + i];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const float4 p = v[j], q = v[(j + 1) % 6], r = v[(j + 2) % 6];
+        dst[j * n + i] = make_float4(p.x - q.x + r.x, p.y - q.y + r.y, p.z - q.z + r.z, p.w - q.w + r.w);
+    }
+}
+// The F(4,3) layer (wn_winograd_layer.h, form = WNWG_F43) straight from its packed operands, one thread per (quad column, channel,
+// batch item): what the one-launch kernel's chunk stream, half-panel addressing and quad map have to reproduce.
+__global__ __launch_bounds__(256) void f43_reference_kernel(const WnWinogradLayerArgs a, float* __restrict__ out) {
+    const int q = blockIdx.x * 256 + threadIdx.x, ch = blockIdx.y, b = blockIdx.z;
+    if (q >= a.Lp) return;
+    const int n1 = a.C / GEMM_KC, n2 = (a.C + a.H) / GEMM_KC, cb = ch >> 6, i = ch & 63;
+    auto split = [&](const float* P, int row, int kk) { return P[((size_t)(row >> 8) * n1 + kk / GEMM_KC) * (GEMM_KC * 256) + (kk % GEMM_KC) * 256 + (row & 255)]; };
+    auto gate = [&](const float* P, int r, int kk) { return P[((size_t)(cb >> 1) * n2 + kk / GEMM_KC) * (GEMM_KC * 256) + (kk % GEMM_KC) * 256 + (cb & 1) * 128 + r]; };
+    auto vq = [&](int j, int kk) { return a.V[j * a.vplane + ((size_t)b * a.C + kk) * a.ldp + q]; };
+    const float* U[4] = {a.A_T2, a.A_T3, a.A_T4, a.A_T5};
+    float pt[4], pg[4];
+    for (int j = 0; j < 4; ++j) {
+        float t = 0.f, g = 0.f;
+        for (int kk = 0; kk < a.C; ++kk) { const float v = vq(1 + j, kk); t = fmaf(split(U[j], ch, kk), v, t); g = fmaf(split(U[j], a.C + ch, kk), v, g); }
+        pt[j] = t; pg[j] = g;
+    }
+    float y[2][4];
+    for (int s = 0; s < 2; ++s) {
+        const float* p = s ? pg : pt;
+        const float sa = p[0] + p[1], sb = p[0] - p[1], sc = p[2] + p[3], se = p[2] - p[3];
+        y[s][0] = sa + sc; y[s][1] = sb + 2.f * se; y[s][2] = sa + 4.f * sc; y[s][3] = sb + 8.f * se;
+    }
+    for (int k = 0; k < 4; ++k) {
+        const int tk = (q / a.d) * (4 * a.d) + q % a.d + k * a.d;
+        if (tk >= a.L) continue;
+        const float* P = k == 3 ? a.A_o : a.A_e;
+        float t = 0.f, g = 0.f;
+        if (k == 0 || k == 3)
+            for (int kk = 0; kk < a.C; ++kk) { const float v = vq(k == 3 ? 5 : 0, kk); t = fmaf(gate(P, i, kk), v, t); g = fmaf(gate(P, 64 + i, kk), v, g); }
+        for (int kk = 0; kk < a.H; ++kk) {
+            const float v = a.h2[(size_t)b * a.h_bstride + (size_t)kk * a.ld + a.pad + tk];
+            t = fmaf(gate(P, i, a.C + kk), v, t); g = fmaf(gate(P, 64 + i, a.C + kk), v, g);
+        }
+        const float u0 = y[0][k] + t + a.bias[cb * 128 + i], u1 = y[1][k] + g + a.bias[cb * 128 + 64 + i];
+        out[(size_t)b * a.act_bstride + (size_t)ch * a.ld + a.pad + tk] = tanhf(u0) / (1.f + expf(-u1));
+    }
+}
 // out[0] = max |a - b|, out[1] = max |a| (as the bits of non-negative floats)
 __global__ __launch_bounds__(256) void max_diff_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n, unsigned* out) {
     float d = 0.f, m = 0.f;
@@ -111,6 +161,103 @@ int main(int argc, char** argv) {
             }
             return a;
         };
+        if (getenv("HG_F43")) {
+            // Go / no-go for the F(4,3) form of the one-launch layer: today's layer (the fused F(2,3) launch with its 64-column peel
+            // + the 3r5w transform stand-in) against the F(4,3) launch + a stand-in of its quad transform (6 planes of C x L / 4),
+            // same process, d = 128 and d = 8 alternating, rotating weights, arms alternated HG_ROUNDS times.  First the new
+            // kernel's output is compared with f43_reference_kernel on the same packed operands.
+            //   HG_WINOGRAD=1 HG_F43=1 [HG_ROUNDS=5]
+            const int slots = 4, n1 = C / GEMM_KC, n2 = (C + CC) / GEMM_KC;
+            const int Ln = L;
+            auto dil = [&](int i) { return (i & 1) ? 8 : 128; };
+            auto Lq_of = [&](int d) { return (Ln + 4 * d - 1) / (4 * d) * d; };
+            const int qt_max = (Lq_of(128) + 63) / 64, ldq = qt_max * 64;                // 114 tiles of 64 quad columns
+            const size_t vplane = (size_t)B * C * ldp, qplane = (size_t)B * C * ldq;
+            const size_t slot_f = (size_t)(16 * n1 + 8 * n2) * a_tile;                   // U1..U4 SPLIT, [U0 | C_i], [U5 | C_i] GATE
+            if ((size_t)slots * slot_f > (size_t)layers * 4 * nch * a_tile || 2 * Lp > Ln) return 1;
+            float *Vb, *Vq, *act2, *bias2;
+            unsigned* dmax;
+            CK(hipMalloc(&Vb, 4 * vplane * 4)); CK(hipMalloc(&Vq, 6 * qplane * 4)); CK(hipMalloc(&act2, (size_t)B * C * ld * 4));
+            CK(hipMalloc(&bias2, 1024 * 4)); CK(hipMalloc(&dmax, 8));
+            for (int p = 0; p < 4; ++p) CK(hipMemcpy(Vb + p * vplane, x + p * 1000, vplane * 4, hipMemcpyDeviceToDevice));
+            for (int p = 0; p < 6; ++p) CK(hipMemcpy(Vq + p * qplane, x + p * 1000, qplane * 4, hipMemcpyDeviceToDevice));
+            CK(hipMemcpy(bias2, x + 4096, 1024 * 4, hipMemcpyDeviceToDevice));
+            auto wslot = [&](int i) { return A + (size_t)(i % slots) * slot_f; };
+            auto f23_args = [&](int i) {
+                const float* w = wslot(i);
+                WnWinogradLayerArgs f{};
+                f.A_T2 = w; f.A_T3 = w + (size_t)4 * n1 * a_tile; f.A_e = w + (size_t)8 * n1 * a_tile; f.A_o = f.A_e + (size_t)4 * n2 * a_tile;
+                f.bias = bias2; f.V = Vb; f.vplane = (long long)vplane; f.h2 = h; f.h_bstride = (long long)CC * ld;
+                f.act = act; f.act_bstride = (long long)C * ld; f.C = C; f.H = CC; f.batch = B;
+                f.ldp = ldp; f.Lp = Lp; f.ntiles = wt; f.d = dil(i); f.L = 2 * Lp; f.ld = ld; f.pad = PADC; f.in_place = 1;
+                return f;
+            };
+            auto f43_args = [&](int i) {
+                const float* w = wslot(i);
+                WnWinogradLayerArgs f{};
+                f.form = WNWG_F43;
+                f.A_T2 = w; f.A_T3 = w + (size_t)4 * n1 * a_tile; f.A_T4 = w + (size_t)8 * n1 * a_tile; f.A_T5 = w + (size_t)12 * n1 * a_tile;
+                f.A_e = w + (size_t)16 * n1 * a_tile; f.A_o = f.A_e + (size_t)4 * n2 * a_tile;
+                f.bias = bias2; f.V = Vq; f.vplane = (long long)qplane; f.h2 = h; f.h_bstride = (long long)CC * ld;
+                f.act = act2; f.act_bstride = (long long)C * ld; f.C = C; f.H = CC; f.batch = B;
+                f.d = dil(i); f.L = Ln; f.ld = ld; f.pad = PADC; f.in_place = 1;
+                f.ldp = ldq; f.Lp = Lq_of(f.d); f.ntiles = (f.Lp + 63) / 64;
+                return f;
+            };
+            for (int i = 0; i < 2; ++i) {
+                WnWinogradLayerArgs f = f43_args(i);
+                CK(hipMemsetAsync(act, 0, (size_t)B * C * ld * 4, st)); CK(hipMemsetAsync(act2, 0, (size_t)B * C * ld * 4, st));
+                CK(hipMemsetAsync(dmax, 0, 8, st));
+                if (launch_wn_winograd_layer(f, st)) return 1;
+                hipLaunchKernelGGL(f43_reference_kernel, dim3((unsigned)((f.Lp + 255) / 256), C, B), dim3(256), 0, st, f, act);
+                const size_t n = (size_t)B * C * ld;
+                hipLaunchKernelGGL(max_diff_kernel, dim3(4096), dim3(256), 0, st, act, act2, n, dmax);
+                unsigned hd[2];
+                CK(hipMemcpyAsync(hd, dmax, 8, hipMemcpyDeviceToHost, st)); CK(hipStreamSynchronize(st));
+                float fd[2]; memcpy(fd, hd, 8);
+                printf("d = %3d, Lq = %d, %d tiles x %d: max |F(4,3) launch - reference| = %.3e, max |reference| = %.3e\n", f.d, f.Lp, f.ntiles, B, fd[0], fd[1]);
+                if (!(fd[0] <= 2e-5f) || !(fd[1] > 0.01f)) { printf("MISMATCH\n"); return 2; }
+            }
+            const size_t sn23 = vplane / 4, sn43 = qplane / 4;                 // 16-byte units of one V plane of either form
+            float4 *ssrc, *sdst;
+            const size_t sbytes = (5 * sn23 > 6 * sn43 ? 5 * sn23 : 6 * sn43) * 16;
+            CK(hipMalloc(&ssrc, sbytes)); CK(hipMalloc(&sdst, sbytes)); CK(hipMemset(ssrc, 0, sbytes));
+            unsetenv("CTTS_F32_NO_ROUND_SPLIT"); reload_tuning();              // today's arm with its peel, as the library runs it
+            auto layer = [&](int arm, int i, bool with_transform) {
+                if (with_transform) {
+                    if (arm) hipLaunchKernelGGL(stream_6r6w_kernel, dim3((unsigned)((sn43 + 255) / 256)), dim3(256), 0, st, ssrc, sdst, sn43);
+                    else hipLaunchKernelGGL(stream_3r5w_kernel, dim3((unsigned)((sn23 + 255) / 256)), dim3(256), 0, st, ssrc, sdst, sn23);
+                }
+                return launch_wn_winograd_layer(arm ? f43_args(i) : f23_args(i), st);
+            };
+            const int rounds = getenv("HG_ROUNDS") ? atoi(getenv("HG_ROUNDS")) : 5, reps = 12;
+            // [arm][0 = the layer launches alone, 1 = with the transform stand-in: what a layer costs]
+            float lo[2][2], hi[2][2], sum[2][2];
+            for (int arm = 0; arm < 2; ++arm) for (int w = 0; w < 2; ++w) { lo[arm][w] = 1e9f; hi[arm][w] = 0.f; sum[arm][w] = 0.f; }
+            static const char* names[2] = {"F(2,3) fused + peel", "F(4,3) one launch"};
+            for (int r = 0; r < rounds; ++r)
+                for (int arm = 0; arm < 2; ++arm)
+                    for (int w = 0; w < 2; ++w) {
+                        for (int i = 0; i < 4; ++i) if (layer(arm, i, w)) return 1;
+                        CK(hipStreamSynchronize(st));
+                        CK(hipEventRecord(e0, st));
+                        for (int i = 0; i < reps; ++i) if (layer(arm, i, w)) return 1;
+                        CK(hipEventRecord(e1, st));
+                        CK(hipStreamSynchronize(st));
+                        float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                        ms /= reps;
+                        printf("round %d  %-20s %-22s %.4f ms per layer\n", r, names[arm], w ? "+ transform stand-in" : "launches alone", ms);
+                        lo[arm][w] = ms < lo[arm][w] ? ms : lo[arm][w]; hi[arm][w] = ms > hi[arm][w] ? ms : hi[arm][w]; sum[arm][w] += ms;
+                    }
+            for (int w = 0; w < 2; ++w) {
+                const float s0 = hi[0][w] - lo[0][w], s1 = hi[1][w] - lo[1][w], spread = s0 > s1 ? s0 : s1;
+                const float gain = (sum[0][w] - sum[1][w]) / rounds;
+                printf("%s: F(2,3) %.4f ms (%.4f-%.4f), F(4,3) %.4f ms (%.4f-%.4f): gain %.4f ms = %.1f x the larger spread%s\n",
+                       w ? "per layer with the transform stand-in" : "layer launches alone", sum[0][w] / rounds, lo[0][w], hi[0][w], sum[1][w] / rounds,
+                       lo[1][w], hi[1][w], gain, gain / (spread > 0.f ? spread : 1e-9f), w ? (gain > 10.f * spread ? "  -> GO" : "  -> NO-GO") : "");
+            }
+            return 0;
+        }
         if (getenv("HG_FUSED")) {
             // The one-launch Winograd layer (wn_winograd_layer.hip) against the two launches it replaces - T2 | T3 and even | odd as
             // the lean form issues them (two parts each, T planes in HBM, second addend, mapped store, cond rows in place) - on the
