@@ -1,5 +1,5 @@
 // HiFi-GAN generator, split-bf16 products on fp32 tensors (ctts_hifigan_*_bf16x3 in include/cookietts_hip.h): the tensors,
-// the workspace, the epilogues and the launch sequence of hifigan.hip, with every product carried as hi + lo bf16 operands on
+// the workspace, the epilogue and the launch sequence of hifigan.hip, with every product carried as hi + lo bf16 operands on
 // v_mfma_f32_32x32x16_bf16 instead of v_mfma_f32_32x32x2_f32.  The plan is hifigan_plan.h's esz = 4 plan, unchanged.
 //
 // Arithmetic (bf16_rne = round to nearest even, one v_cvt_pk_bf16_f32):
@@ -11,7 +11,8 @@
 //                and channels >= Cin are exact zeros in both planes
 //   product      acc += w_hi * x_hi, then acc += w_lo * x_hi, then acc += w_hi * x_lo, fp32 accumulation, in that order for
 //                every K16 step; there is no lo * lo term
-//   epilogue     hg_conv_kernel's: bias, residual, the resblock running sum and 1 / n_k, tanh, interleaved phase store
+//   epilogue     hg_epilogue_f32, the one hg_conv_kernel calls: bias, residual, the resblock running sum and 1 / n_k, tanh,
+//                interleaved phase store
 // A non-finite activation gives NaN, not infinity: v - float(x_hi) is inf - inf in the lo plane.
 //
 // Layout.  A hi | lo pair is 4 bytes, so the LDS images and the packed blob have the fp32 path's sizes.  Both are K8-blocked
@@ -28,14 +29,13 @@
 // MFMA's own order inside a step: a function of the layer and its KC only, never of the block shape, tile count or batch, so an
 // item of a batch equals the same item run alone, bit for bit.
 //
-// Block shapes, the narrow-below-HG_NARROW_BELOW rule and the launch bound are hifigan.hip's.
+// Block shapes and the narrow-below-HG_NARROW_BELOW rule are hifigan_plan.h's (hg_launch); the launch bound is hifigan.hip's.
 #include "gemm_bf16.h"       // pack_bf16x2
 #include "hifigan_plan.h"
 
 namespace ctts {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -65,16 +65,8 @@ __global__ __launch_bounds__(256, 2) void hg_conv_bf16x3_kernel(const HgConvArgs
     extern __shared__ __attribute__((aligned(16))) u32x4 hg_lds_s[];
 
     const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = t >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int l31 = lane & 31, lhi = lane >> 5;
-
-    int id = blockIdx.x;
-    const int mb = id % a.MB;
-    id /= a.MB;
-    const int tile = id % a.ntiles;
-    const int b = id / a.ntiles;
+    const HgTile tc = hg_tile<WM>(a);
+    const auto& [mb, tile, b, wm, wn, l31, lhi] = tc;
     const int n0 = tile * BN;
 
     const int c0 = n0 - a.left;
@@ -88,12 +80,7 @@ __global__ __launch_bounds__(256, 2) void hg_conv_bf16x3_kernel(const HgConvArgs
     const float slope = a.slope;
 
     f32x16 acc[MT][2];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    hg_zero(acc);
 
     const int a_off = wm * (32 * MT) + l31;
     const int x_off = wn * 64 + l31;
@@ -167,61 +154,16 @@ __global__ __launch_bounds__(256, 2) void hg_conv_bf16x3_kernel(const HgConvArgs
         }
     }
 
-    // ---- epilogue: hg_conv_kernel's.  C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    const float* bias = a.bias + mb * BM;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int n = n0 + wn * 64 + nt * 32 + l31;
-            if (n >= a.L) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = wm * (32 * MT) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-                const int m = mb * BM + row;
-                if (m >= a.M) continue;
-                float v = acc[mt][nt][r] + bias[row];
-                if (a.epi == HG_EPI_STORE) {
-                    if (a.up > 1) {
-                        const int ph = m / a.cout, co = m - ph * a.cout;
-                        a.dst0[(size_t)b * a.dst0_bs + (size_t)co * a.dst0_ld + (size_t)n * a.up + ph] = v;
-                    } else {
-                        a.dst0[(size_t)b * a.dst0_bs + (size_t)m * a.dst0_ld + n] = v;
-                    }
-                } else if (a.epi == HG_EPI_RES) {
-                    v += a.res[(size_t)b * a.res_bs + (size_t)m * a.res_ld + n];
-                    if (a.dst0) a.dst0[(size_t)b * a.dst0_bs + (size_t)m * a.dst0_ld + n] = v;
-                    if (a.dst1) {
-                        float* d = a.dst1 + (size_t)b * a.dst1_bs + (size_t)m * a.dst1_ld + n;
-                        float s = (a.sum_flags & HG_SUM_FIRST) ? v : *d + v;
-                        if (a.sum_flags & HG_SUM_LAST) s = s / a.nk;
-                        *d = s;
-                    }
-                } else {
-                    a.dst0[(size_t)b * a.dst0_bs + (size_t)m * a.dst0_ld + n] = tanhf(v);
-                }
-            }
-        }
-    }
+    hg_epilogue_f32<MT, WM>(a, acc, tc, n0);
 }
 
 // A [MB][nch][ntap][KC / 8][hi, lo][BM][8] bf16: each folded fp32 weight split once, padding exact zeros in both planes; bias
 // stays fp32.  One thread per weight writes its hi and its lo.
 __global__ void hg_pack_bf16x3_kernel(const HgPackArgs p) {
-    const long long total = (long long)p.MB * p.nch * p.ntap * p.KC * p.BM;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (long long)p.MB * p.BM) {
-        const int m = (int)i;
-        p.bias[m] = m < p.M ? p.b[p.kind == HG_CONVT ? m % p.cout : m] : 0.0f;
-    }
-    if (i >= total) return;
-    long long q = i;
-    const int e = (int)(q & 7); q >>= 3;
-    const int r = (int)(q % p.BM); q /= p.BM;
-    const int kg = (int)(q % (p.KC / 8)); q /= (p.KC / 8);
-    const int j = (int)(q % p.ntap); q /= p.ntap;
-    const int ch = (int)(q % p.nch); q /= p.nch;
-    const int mb = (int)q;
+    hg_pack_bias(p, i);
+    if (i >= (long long)p.MB * p.nch * p.ntap * p.KC * p.BM) return;
+    const auto [e, r, kg, j, ch, mb] = hg_pack_k8(p, i);
     const float w = hg_weight_at(p, mb * p.BM + r, ch * p.KC + kg * 8 + e, j);
     const unsigned int hi = pack_bf16x2(w, 0.0f) & 0xffffu;
     const unsigned int lo = pack_bf16x2(w - __builtin_bit_cast(float, hi << 16), 0.0f) & 0xffffu;
@@ -232,40 +174,21 @@ __global__ void hg_pack_bf16x3_kernel(const HgPackArgs p) {
     A[at + plane] = (unsigned short)lo;
 }
 
-template <int MT, int WM, int KC>
-void hg_launch_shape_s(const HgConvArgs& a, int batch, int lds, hipStream_t s) {
-    hipLaunchKernelGGL((hg_conv_bf16x3_kernel<MT, WM, KC>), dim3((unsigned)((size_t)a.MB * a.ntiles * batch)), dim3(256), lds, s, a);
-}
-
-int hg_launch_s(const HgLayer& l, HgConvArgs a, const void* packed, int batch, hipStream_t s) {
-    a.A = reinterpret_cast<const float*>(static_cast<const char*>(packed) + l.A_off);
-    a.bias = reinterpret_cast<const float*>(static_cast<const char*>(packed) + l.bias_off);
-    a.Cin = l.Cin; a.ntap = l.ntap; a.dil = l.dil; a.left = l.left;
-    a.M = l.M; a.MB = l.MB; a.nch = l.nch;
-    // the half-width block of the same M-block height for launches too small to fill the chip (as the fp32 path does)
-    int WM = l.WM, MT = l.MT, BN = l.BN;
-    if (l.BM >= 64 && (long long)l.MB * ((a.L + BN - 1) / BN) * batch < HG_NARROW_BELOW) { WM *= 2; MT = 1; BN /= 2; }
-    a.ntiles = (a.L + BN - 1) / BN;
-    a.up = l.up; a.cout = l.cout;
-    // the fp32 plan's LDS figure covers this layout: the same weight bytes, and a tile that is no wider (no 16-byte row alignment)
-    const int lds = l.lds_bytes(BN);
-    const int key = MT * 100 + WM * 10 + (l.KC == 16);
-    switch (key) {
-        case 110: hg_launch_shape_s<1, 1, 8>(a, batch, lds, s); break;
-        case 111: hg_launch_shape_s<1, 1, 16>(a, batch, lds, s); break;
-        case 120: hg_launch_shape_s<1, 2, 8>(a, batch, lds, s); break;
-        case 121: hg_launch_shape_s<1, 2, 16>(a, batch, lds, s); break;
-        case 140: hg_launch_shape_s<1, 4, 8>(a, batch, lds, s); break;
-        case 141: hg_launch_shape_s<1, 4, 16>(a, batch, lds, s); break;
-        case 210: hg_launch_shape_s<2, 1, 8>(a, batch, lds, s); break;
-        case 211: hg_launch_shape_s<2, 1, 16>(a, batch, lds, s); break;
-        case 220: hg_launch_shape_s<2, 2, 8>(a, batch, lds, s); break;
-        case 221: hg_launch_shape_s<2, 2, 16>(a, batch, lds, s); break;
-        default: set_error("hifigan_bf16x3: no kernel shape %d", key); return CTTS_E_ARG;
+// the format as hg_launch and the entry bodies of hifigan_plan.h take it: the fp32 element and KC pair
+struct HgBf16x3 {
+    using T = float;
+    static constexpr int kc_lo = 8;
+    static constexpr const char* name = "hifigan_bf16x3";
+    static constexpr const char* kernel = "hg_conv_bf16x3_kernel";
+    static constexpr const char* pack_kernel = "hg_pack_bf16x3_kernel";
+    template <int MT, int WM, int KC>
+    static void launch(const HgConvArgs& a, unsigned blocks, int lds, hipStream_t s) {
+        hipLaunchKernelGGL((hg_conv_bf16x3_kernel<MT, WM, KC>), dim3(blocks), dim3(256), lds, s, a);
     }
-    CTTS_CHECK_LAUNCH("hg_conv_bf16x3_kernel");
-    return CTTS_OK;
-}
+    static void pack(const HgPackArgs& a, unsigned blocks, hipStream_t s) {
+        hipLaunchKernelGGL(hg_pack_bf16x3_kernel, dim3(blocks), dim3(256), 0, s, a);
+    }
+};
 
 }  // namespace
 }  // namespace ctts
@@ -274,54 +197,20 @@ using namespace ctts;
 
 extern "C" {
 
-size_t ctts_hifigan_packed_bf16x3_bytes(const ctts_hifigan_config* cfg) {
-    HgPlan p;
-    if (make_hg_plan(cfg, p, 4) != CTTS_OK) return 0;
-    return p.packed_bytes;
-}
+size_t ctts_hifigan_packed_bf16x3_bytes(const ctts_hifigan_config* cfg) { return hg_packed_bytes<HgBf16x3>(cfg); }
 
 int ctts_hifigan_pack_bf16x3(const ctts_hifigan_config* cfg, const float* weights, size_t weight_floats, void* packed, void* stream) {
-    HgPlan p;
-    int rc = make_hg_plan(cfg, p, 4);
-    if (rc) return rc;
-    CTTS_CHECK_ARG(weights != nullptr && packed != nullptr, "hifigan_pack_bf16x3: NULL pointer");
-    CTTS_CHECK_ARG(weight_floats == p.weight_floats, "hifigan_pack_bf16x3: %zu weight floats given, the config has %zu", weight_floats,
-                   p.weight_floats);
-    CTTS_CHECK_ARG((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "hifigan_pack_bf16x3: packed blob must be 16-byte aligned");
-    for (const HgLayer& l : p.layers) {
-        const HgPackArgs a = hg_pack_args<float>(l, weights, packed);
-        const long long total = (long long)l.packed_elems();     // >= MB * BM
-        hipLaunchKernelGGL(hg_pack_bf16x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), a);
-        CTTS_CHECK_LAUNCH("hg_pack_bf16x3_kernel");
-    }
-    return CTTS_OK;
+    return hg_pack<HgBf16x3>("hifigan_pack_bf16x3", true, cfg, weights, weight_floats, packed, stream);
 }
 
 size_t ctts_hifigan_workspace_bf16x3_bytes(const ctts_hifigan_config* cfg, int32_t batch, int32_t frames) {
-    HgPlan p;
-    HgGeom g;
-    if (make_hg_plan(cfg, p, 4) != CTTS_OK || hg_geometry(p, batch, frames, g) != CTTS_OK) return 0;
-    return g.total_elems * sizeof(float);
+    return hg_workspace_bytes<HgBf16x3>(cfg, batch, frames);
 }
 
 int ctts_hifigan_forward_bf16x3(const ctts_hifigan_config* cfg, const void* packed, const float* mel, int32_t mel_ld, float* audio,
                                 int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes, void* stream) {
-    HgPlan p;
-    HgGeom g;
-    int rc = make_hg_plan(cfg, p, 4);
-    if (rc) return rc;
-    if ((rc = hg_geometry(p, batch, frames, g))) return rc;
-    CTTS_CHECK_ARG(packed != nullptr && mel != nullptr && audio != nullptr && workspace != nullptr, "hifigan_forward_bf16x3: NULL pointer");
-    CTTS_CHECK_ARG(mel_ld >= frames, "hifigan_forward_bf16x3: mel_ld=%d < frames=%d", mel_ld, frames);
-    CTTS_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(packed) & 15) == 0,
-                   "hifigan_forward_bf16x3: packed blob and workspace must be 16-byte aligned");
-    if (workspace_bytes < g.total_elems * sizeof(float)) {
-        set_error("hifigan_forward_bf16x3: workspace %zu bytes < required %zu", workspace_bytes, g.total_elems * sizeof(float));
-        return CTTS_E_WORKSPACE;
-    }
-    hipStream_t s = as_stream(stream);
-    return hg_forward<float>(p, g, mel, mel_ld, audio, frames, static_cast<float*>(workspace),
-                             [&](const HgLayer& l, const HgConvArgs& a) { return hg_launch_s(l, a, packed, batch, s); });
+    return hg_forward_entry<HgBf16x3>("hifigan_forward_bf16x3", cfg, packed, mel, mel_ld, audio, batch, frames, workspace, workspace_bytes,
+                                      stream);
 }
 
 }  // extern "C"

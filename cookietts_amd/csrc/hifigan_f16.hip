@@ -1,8 +1,9 @@
 // HiFi-GAN generator, IEEE-half storage mode (ctts_hifigan_*_f16 in include/cookietts_hip.h): the arithmetic of
 // hifigan.hip with weights and every stored activation in IEEE half, products on v_mfma_f32_32x32x16_f16, accumulation,
 // bias, residual add, the resblock mean and tanh in fp32, and ONE rounding to half (round-to-nearest-even, IEEE overflow
-// to infinity, no clamping) per stored value.  The plan, the refusals and the sequence of launches are hifigan_plan.h's,
-// shared with the fp32 path; only the kernel, the pack kernel and the block-shape table live here.
+// to infinity, no clamping) per stored value.  The plan, the refusals, the sequence of launches, the launcher with its
+// block shapes and the bodies of the entries are hifigan_plan.h's, shared with the other two formats; only the kernel with its
+// half-unit epilogue and the pack kernel live here.
 //
 // Layout: activations are K8-blocked, [B][ceil(C / 8)][ld][8] halves with ld = L: the 8 channels 8g..8g+7 of one column
 // are one 16-byte unit, which is exactly what a lane of the f16 MFMA wants as its 8 consecutive K values.  A workgroup
@@ -21,7 +22,7 @@
 // HG_EPI_RES rounds v = acc + bias + float(res) once for dst0, and the stage's running sum as
 // half((float(sum) + v) [/ n_k]) from the unrounded v.  HG_EPI_TANH writes the fp32 waveform.
 //
-// Block shapes are the fp32 path's (256 threads = 4 waves, wave tile 32 MT x 64); KC = 32 where the two LDS images stay
+// Block shapes are hifigan_plan.h's (256 threads = 4 waves, wave tile 32 MT x 64); KC = 32 where the two LDS images stay
 // under HG_LDS_KC16 bytes, else 16.  A 128-column wave tile (blocks 32 x 512, 64 x 512, 128 x 256: a chunk's weights staged
 // once for twice the columns, 6 fragment reads for 8 MFMAs instead of 4 for 4) was measured SLOWER, 25.0 against 20.4 ms at
 // 16 x 900 frames: 176 VGPRs halve the workgroups per CU, and with no software pipeline in the main loop it is the other
@@ -34,7 +35,6 @@
 namespace ctts {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
@@ -55,16 +55,7 @@ __global__ __launch_bounds__(256, 2) void hg_conv_f16_kernel(const HgConvArgsH a
     extern __shared__ __attribute__((aligned(16))) f16x8 hg_lds_h[];
 
     const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = t >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int l31 = lane & 31, lhi = lane >> 5;
-
-    int id = blockIdx.x;
-    const int mb = id % a.MB;
-    id /= a.MB;
-    const int tile = id % a.ntiles;
-    const int b = id / a.ntiles;
+    const auto [mb, tile, b, wm, wn, l31, lhi] = hg_tile<WM>(a);
     const int n0 = tile * BN;
 
     const int c0 = n0 - a.left;
@@ -78,12 +69,7 @@ __global__ __launch_bounds__(256, 2) void hg_conv_f16_kernel(const HgConvArgsH a
     const int cin_groups = (a.Cin + 7) >> 3;
 
     f32x16 acc[MT][2];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    hg_zero(acc);
 
     const int a_off = wm * (32 * MT) + l31;
     const int x_off = wn * 64 + l31;
@@ -230,56 +216,28 @@ __global__ __launch_bounds__(256, 2) void hg_conv_f16_kernel(const HgConvArgsH a
 
 // A [MB][nch][ntap][KC / 8][BM][8]: each folded fp32 weight rounded once, padding exact zeros; bias stays fp32
 __global__ void hg_pack_f16_kernel(const HgPackArgsH p) {
-    const long long total = (long long)p.MB * p.nch * p.ntap * p.KC * p.BM;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (long long)p.MB * p.BM) {
-        const int m = (int)i;
-        p.bias[m] = m < p.M ? p.b[p.kind == HG_CONVT ? m % p.cout : m] : 0.0f;
-    }
-    if (i >= total) return;
-    long long q = i;
-    const int e = (int)(q & 7); q >>= 3;
-    const int r = (int)(q % p.BM); q /= p.BM;
-    const int kg = (int)(q % (p.KC / 8)); q /= (p.KC / 8);
-    const int j = (int)(q % p.ntap); q /= p.ntap;
-    const int ch = (int)(q % p.nch); q /= p.nch;
-    const int mb = (int)q;
+    hg_pack_bias(p, i);
+    if (i >= (long long)p.MB * p.nch * p.ntap * p.KC * p.BM) return;
+    const auto [e, r, kg, j, ch, mb] = hg_pack_k8(p, i);
     p.A[i] = (_Float16)hg_weight_at(p, mb * p.BM + r, ch * p.KC + kg * 8 + e, j);
 }
 
-template <int MT, int WM, int KC>
-void hg_launch_shape_h(const HgConvArgsH& a, int batch, int lds, hipStream_t s) {
-    hipLaunchKernelGGL((hg_conv_f16_kernel<MT, WM, KC>), dim3((unsigned)((size_t)a.MB * a.ntiles * batch)), dim3(256), lds, s, a);
-}
-
-int hg_launch_h(const HgLayer& l, HgConvArgsH a, const void* packed, int batch, hipStream_t s) {
-    a.A = reinterpret_cast<const _Float16*>(static_cast<const char*>(packed) + l.A_off);
-    a.bias = reinterpret_cast<const float*>(static_cast<const char*>(packed) + l.bias_off);
-    a.Cin = l.Cin; a.ntap = l.ntap; a.dil = l.dil; a.left = l.left;
-    a.M = l.M; a.MB = l.MB; a.nch = l.nch;
-    // the half-width block of the same M-block height for launches too small to fill the chip (as the fp32 path does)
-    int WM = l.WM, MT = l.MT, BN = l.BN;
-    if (l.BM >= 64 && (long long)l.MB * ((a.L + BN - 1) / BN) * batch < HG_NARROW_BELOW) { WM *= 2; MT = 1; BN /= 2; }
-    a.ntiles = (a.L + BN - 1) / BN;
-    a.up = l.up; a.cout = l.cout;
-    const int lds = l.lds_bytes(BN);
-    const int key = MT * 100 + WM * 10 + (l.KC == 32);
-    switch (key) {
-        case 110: hg_launch_shape_h<1, 1, 16>(a, batch, lds, s); break;
-        case 111: hg_launch_shape_h<1, 1, 32>(a, batch, lds, s); break;
-        case 120: hg_launch_shape_h<1, 2, 16>(a, batch, lds, s); break;
-        case 121: hg_launch_shape_h<1, 2, 32>(a, batch, lds, s); break;
-        case 140: hg_launch_shape_h<1, 4, 16>(a, batch, lds, s); break;
-        case 141: hg_launch_shape_h<1, 4, 32>(a, batch, lds, s); break;
-        case 210: hg_launch_shape_h<2, 1, 16>(a, batch, lds, s); break;
-        case 211: hg_launch_shape_h<2, 1, 32>(a, batch, lds, s); break;
-        case 220: hg_launch_shape_h<2, 2, 16>(a, batch, lds, s); break;
-        case 221: hg_launch_shape_h<2, 2, 32>(a, batch, lds, s); break;
-        default: set_error("hifigan_f16: no kernel shape %d", key); return CTTS_E_ARG;
+// the format as hg_launch and the entry bodies of hifigan_plan.h take it
+struct HgF16 {
+    using T = _Float16;
+    static constexpr int kc_lo = 16;
+    static constexpr const char* name = "hifigan_f16";
+    static constexpr const char* kernel = "hg_conv_f16_kernel";
+    static constexpr const char* pack_kernel = "hg_pack_f16_kernel";
+    template <int MT, int WM, int KC>
+    static void launch(const HgConvArgsH& a, unsigned blocks, int lds, hipStream_t s) {
+        hipLaunchKernelGGL((hg_conv_f16_kernel<MT, WM, KC>), dim3(blocks), dim3(256), lds, s, a);
     }
-    CTTS_CHECK_LAUNCH("hg_conv_f16_kernel");
-    return CTTS_OK;
-}
+    static void pack(const HgPackArgsH& a, unsigned blocks, hipStream_t s) {
+        hipLaunchKernelGGL(hg_pack_f16_kernel, dim3(blocks), dim3(256), 0, s, a);
+    }
+};
 
 }  // namespace
 }  // namespace ctts
@@ -288,54 +246,19 @@ using namespace ctts;
 
 extern "C" {
 
-size_t ctts_hifigan_packed_f16_bytes(const ctts_hifigan_config* cfg) {
-    HgPlan p;
-    if (make_hg_plan(cfg, p, 2) != CTTS_OK) return 0;
-    return p.packed_bytes;
-}
+size_t ctts_hifigan_packed_f16_bytes(const ctts_hifigan_config* cfg) { return hg_packed_bytes<HgF16>(cfg); }
 
 int ctts_hifigan_pack_f16(const ctts_hifigan_config* cfg, const float* weights, size_t weight_floats, void* packed, void* stream) {
-    HgPlan p;
-    int rc = make_hg_plan(cfg, p, 2);
-    if (rc) return rc;
-    CTTS_CHECK_ARG(weights != nullptr && packed != nullptr, "hifigan_pack_f16: NULL pointer");
-    CTTS_CHECK_ARG(weight_floats == p.weight_floats, "hifigan_pack_f16: %zu weight floats given, the config has %zu", weight_floats,
-                   p.weight_floats);
-    CTTS_CHECK_ARG((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "hifigan_pack_f16: packed blob must be 16-byte aligned");
-    for (const HgLayer& l : p.layers) {
-        const HgPackArgsH a = hg_pack_args<_Float16>(l, weights, packed);
-        const long long total = (long long)l.packed_elems();     // >= MB * BM
-        hipLaunchKernelGGL(hg_pack_f16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), a);
-        CTTS_CHECK_LAUNCH("hg_pack_f16_kernel");
-    }
-    return CTTS_OK;
+    return hg_pack<HgF16>("hifigan_pack_f16", true, cfg, weights, weight_floats, packed, stream);
 }
 
 size_t ctts_hifigan_workspace_f16_bytes(const ctts_hifigan_config* cfg, int32_t batch, int32_t frames) {
-    HgPlan p;
-    HgGeom g;
-    if (make_hg_plan(cfg, p, 2) != CTTS_OK || hg_geometry(p, batch, frames, g) != CTTS_OK) return 0;
-    return g.total_elems * sizeof(_Float16);
+    return hg_workspace_bytes<HgF16>(cfg, batch, frames);
 }
 
 int ctts_hifigan_forward_f16(const ctts_hifigan_config* cfg, const void* packed, const float* mel, int32_t mel_ld, float* audio,
                              int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes, void* stream) {
-    HgPlan p;
-    HgGeom g;
-    int rc = make_hg_plan(cfg, p, 2);
-    if (rc) return rc;
-    if ((rc = hg_geometry(p, batch, frames, g))) return rc;
-    CTTS_CHECK_ARG(packed != nullptr && mel != nullptr && audio != nullptr && workspace != nullptr, "hifigan_forward_f16: NULL pointer");
-    CTTS_CHECK_ARG(mel_ld >= frames, "hifigan_forward_f16: mel_ld=%d < frames=%d", mel_ld, frames);
-    CTTS_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(packed) & 15) == 0,
-                   "hifigan_forward_f16: packed blob and workspace must be 16-byte aligned");
-    if (workspace_bytes < g.total_elems * sizeof(_Float16)) {
-        set_error("hifigan_forward_f16: workspace %zu bytes < required %zu", workspace_bytes, g.total_elems * sizeof(_Float16));
-        return CTTS_E_WORKSPACE;
-    }
-    hipStream_t s = as_stream(stream);
-    return hg_forward<_Float16>(p, g, mel, mel_ld, audio, frames, static_cast<_Float16*>(workspace),
-                                [&](const HgLayer& l, const HgConvArgsH& a) { return hg_launch_h(l, a, packed, batch, s); });
+    return hg_forward_entry<HgF16>("hifigan_forward_f16", cfg, packed, mel, mel_ld, audio, batch, frames, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

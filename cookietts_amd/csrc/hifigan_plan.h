@@ -1,14 +1,31 @@
-// HiFi-GAN generator: what the fp32 path (hifigan.hip) and the IEEE-half path (hifigan_f16.hip) share - the layer list of a
-// config with its refusals, the workspace geometry, the launch arguments and the sequence of launches of one forward.
+// HiFi-GAN generator: what the fp32 path (hifigan.hip), the IEEE-half path (hifigan_f16.hip) and the split-bf16 path
+// (hifigan_bf16x3.hip) share - the layer list of a config with its refusals, the workspace geometry, the launch arguments and
+// the sequence of launches of one forward; the kernels' prologue, the fp32 epilogue and the pack helpers; the launcher with its
+// block-shape table; the bodies of the extern "C" entries.  A format's .hip file holds its conv kernel, its pack kernel, a
+// trait struct that names them (see hg_launch) and twelve one-line entries between the three of them.
 //
 // `esz` is the size of a stored activation / weight element: 4 = fp32 rows [C][ld], ld = roundup(L, 4); 2 = IEEE half in
 // the K8-blocked layout [ceil(C / 8)][ld][8], ld = L (a column of 8 channels is one 16-byte unit).
 //
-// A third format, split bf16 (hifigan_bf16x3.hip), keeps the fp32 tensors and carries each operand of a product as a hi | lo
-// pair of bf16 - 4 bytes, the fp32 element's.  It therefore IS the esz = 4 plan: the same layer list, KC (a K16 MFMA step is
-// 16 channels of one tap at KC = 16, 8 channels of two taps at KC = 8), lds_bytes(), packed_bytes, offsets, workspace geometry
-// and launch sequence; only the arrangement of a layer's packed weights ([MB][nch][ntap][KC / 8][hi, lo][BM][8] bf16) and of
-// the staged tile ([KC / 8][hi, lo][BN + (ntap - 1) * dil] units, never wider than the fp32 tile) differ.
+// Split bf16 keeps the fp32 tensors and carries each operand of a product as a hi | lo pair of bf16 - 4 bytes, the fp32
+// element's.  It therefore IS the esz = 4 plan: the same layer list, KC (a K16 MFMA step is 16 channels of one tap at KC = 16,
+// 8 channels of two taps at KC = 8), lds_bytes(), packed_bytes, offsets, workspace geometry and launch sequence; only the
+// arrangement of a layer's packed weights ([MB][nch][ntap][KC / 8][hi, lo][BM][8] bf16) and of the staged tile
+// ([KC / 8][hi, lo][BN + (ntap - 1) * dil] units, never wider than the fp32 tile) differ.
+//
+// Epilogues (no stand-alone elementwise launch anywhere in the model):
+//   HG_EPI_STORE  dst0 = v; with up > 1 the rows are (phase r, channel co) of a transposed conv and the store is
+//                 dst0[co][n * up + r]: the `up` stride-1 phase convolutions of ConvTranspose1d written interleaved
+//   HG_EPI_RES    v += res; dst0 = v (when given); dst1 = ((first ? 0 : dst1) + v) [/ nk when last]: the residual add, the sum
+//                 over the n_k resblocks of a stage and its 1 / n_k
+//   HG_EPI_TANH   dst0 = tanh(v) for rows < M (conv_post; its input slope is F.leaky_relu's default 0.01, models.py:134)
+// hg_epilogue_f32 is the two fp32-tensor formats'; the half format's (hifigan_f16.hip) does the same in half units.
+//
+// Block shapes (256 threads = 4 waves, wave tile 32 MT x 64): BM = 32 MT WM rows, BN = 64 (4 / WM) columns:
+//   M <= 32: 32 x 256    M <= 64: 64 x 256    else: 128 x 128 (M-blocks of 128 rows)
+// and, for launches too small to fill the chip with those (batch 1), 64 x 128 / 128 x 64 on the same packed weights.
+// The K chunk is the format's high KC (16 fp32 or split rows, 32 half rows) where the two LDS images stay under HG_LDS_KC16
+// bytes, else half of it.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -30,7 +47,7 @@ constexpr int HG_LDS_MAX = 64 * 1024;     // dynamic LDS a launch may ask for
 constexpr int HG_LDS_KC16 = 40 * 1024;    // the larger K chunk only while four workgroups still fit a CU's LDS
 constexpr int HG_NARROW_BELOW = 1024;     // workgroups (4 per CU) under which the half-width block shape is launched
 
-// T = float (hifigan.hip) or _Float16 (hifigan_f16.hip)
+// T = float (hifigan.hip, hifigan_bf16x3.hip) or _Float16 (hifigan_f16.hip)
 template <typename T>
 struct HgConvArgsT {
     const T* A;            // packed weights of the layer
@@ -38,7 +55,7 @@ struct HgConvArgsT {
     const T* x;            // input activations
     const float* xf;       // half path only: the fp32 mel [B][Cin][x_ld] of conv_pre (x is NULL then)
     long long x_bs;
-    int x_ld, x_vec;       // x_vec (fp32 path): rows are 16-byte aligned (float4 staging)
+    int x_ld, x_vec;       // x_vec (read by hg_conv_kernel only): rows are 16-byte aligned (float4 staging)
     int Cin, L;            // valid input channels; valid columns (input and output share the column domain)
     int ntap, dil, left;   // tap j reads column n + j * dil - left
     float slope;           // LeakyReLU slope applied to x while staging (1 = none)
@@ -291,6 +308,207 @@ __device__ __forceinline__ float hg_weight_at(const HgPackArgsT<T>& p, int m, in
     const int ph = m / p.cout, co = m - ph * p.cout;
     const int kk = p.up * (p.left - j) + ph + p.pad;
     return (kk >= 0 && kk < p.ku) ? p.w[((size_t)ci * p.cout + co) * p.ku + kk] : 0.0f;
+}
+
+// ---- pack kernels: the bias block (thread i < MB * BM writes bias[i]) and the K8 coordinates of element i of a layer's A ----
+template <typename T>
+__device__ __forceinline__ void hg_pack_bias(const HgPackArgsT<T>& p, long long i) {
+    if (i < (long long)p.MB * p.BM) {
+        const int m = (int)i;
+        p.bias[m] = m < p.M ? p.b[p.kind == HG_CONVT ? m % p.cout : m] : 0.0f;
+    }
+}
+
+struct HgK8 { int e, r, kg, j, ch, mb; };      // i = ((((mb * nch + ch) * ntap + j) * (KC / 8) + kg) * BM + r) * 8 + e
+
+template <typename T>
+__device__ __forceinline__ HgK8 hg_pack_k8(const HgPackArgsT<T>& p, long long q) {
+    HgK8 k;
+    k.e = (int)(q & 7); q >>= 3;
+    k.r = (int)(q % p.BM); q /= p.BM;
+    k.kg = (int)(q % (p.KC / 8)); q /= (p.KC / 8);
+    k.j = (int)(q % p.ntap); q /= p.ntap;
+    k.ch = (int)(q % p.nch); q /= p.nch;
+    k.mb = (int)q;
+    return k;
+}
+
+// ---- conv kernels: where a thread stands, the accumulators, the fp32 epilogue ----
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// M-block, column tile and batch item of the workgroup; the wave's place in the WM x (4 / WM) grid of waves; the lane's
+// column and half inside the 32x32 MFMA.  The tile's first column, n0 = tile * BN, is formed in the kernel itself: there the
+// compiler knows it for a multiple of BN from its first pass on, and folds the bounds tests of the float4 staging on that.
+struct HgTile { int mb, tile, b, wm, wn, l31, lhi; };
+
+template <int WM, typename Args>
+__device__ __forceinline__ HgTile hg_tile(const Args& a) {
+    constexpr int WN = 4 / WM;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    HgTile c;
+    c.wm = wave / WN; c.wn = wave % WN;
+    c.l31 = lane & 31; c.lhi = lane >> 5;
+    int id = blockIdx.x;
+    c.mb = id % a.MB;
+    id /= a.MB;
+    c.tile = id % a.ntiles;
+    c.b = id / a.ntiles;
+    return c;
+}
+
+template <int MT>
+__device__ __forceinline__ void hg_zero(f32x16 (&acc)[MT][2]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+}
+
+// fp32 tensors.  C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+template <int MT, int WM>
+__device__ __forceinline__ void hg_epilogue_f32(const HgConvArgsT<float>& a, const f32x16 (&acc)[MT][2], const HgTile c, const int n0) {
+    constexpr int BM = 32 * MT * WM;
+    const int mb = c.mb, b = c.b, wm = c.wm, wn = c.wn, l31 = c.l31, lhi = c.lhi;
+    const float* bias = a.bias + mb * BM;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const int n = n0 + wn * 64 + nt * 32 + l31;
+            if (n >= a.L) continue;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = wm * (32 * MT) + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                const int m = mb * BM + row;
+                if (m >= a.M) continue;
+                float v = acc[mt][nt][r] + bias[row];
+                if (a.epi == HG_EPI_STORE) {
+                    if (a.up > 1) {
+                        const int ph = m / a.cout, co = m - ph * a.cout;
+                        a.dst0[(size_t)b * a.dst0_bs + (size_t)co * a.dst0_ld + (size_t)n * a.up + ph] = v;
+                    } else {
+                        a.dst0[(size_t)b * a.dst0_bs + (size_t)m * a.dst0_ld + n] = v;
+                    }
+                } else if (a.epi == HG_EPI_RES) {
+                    v += a.res[(size_t)b * a.res_bs + (size_t)m * a.res_ld + n];
+                    if (a.dst0) a.dst0[(size_t)b * a.dst0_bs + (size_t)m * a.dst0_ld + n] = v;
+                    if (a.dst1) {
+                        float* d = a.dst1 + (size_t)b * a.dst1_bs + (size_t)m * a.dst1_ld + n;
+                        float s = (a.sum_flags & HG_SUM_FIRST) ? v : *d + v;
+                        if (a.sum_flags & HG_SUM_LAST) s = s / a.nk;
+                        *d = s;
+                    }
+                } else {
+                    a.dst0[(size_t)b * a.dst0_bs + (size_t)m * a.dst0_ld + n] = tanhf(v);
+                }
+            }
+        }
+    }
+}
+
+// ---- launcher.  Fmt is the trait struct beside a format's kernels:
+//   T                       float / _Float16: the element of HgConvArgsT / HgPackArgsT and of the workspace (esz = sizeof(T))
+//   kc_lo                   the low K chunk (8 / 16); the high one is twice that
+//   name, kernel            "hifigan..." for the no-kernel-shape message, the conv kernel's name for a launch error
+//   launch<MT, WM, KC>(args, blocks, lds, stream)     starts the conv kernel of that shape
+//   pack_kernel, pack(args, blocks, stream)           the pack kernel's name and its launch
+template <typename Fmt>
+int hg_launch(const HgLayer& l, HgConvArgsT<typename Fmt::T> a, const void* packed, int batch, hipStream_t s) {
+    using T = typename Fmt::T;
+    a.A = reinterpret_cast<const T*>(static_cast<const char*>(packed) + l.A_off);
+    a.bias = reinterpret_cast<const float*>(static_cast<const char*>(packed) + l.bias_off);
+    a.Cin = l.Cin; a.ntap = l.ntap; a.dil = l.dil; a.left = l.left;
+    a.M = l.M; a.MB = l.MB; a.nch = l.nch;
+    // a launch that would start fewer than HG_NARROW_BELOW workgroups takes the half-width block of the same M-block height
+    // (waves stacked along M): same packed weights, same K order, bit-identical results, twice the workgroups to spread
+    int WM = l.WM, MT = l.MT, BN = l.BN;
+    if (l.BM >= 64 && (long long)l.MB * ((a.L + BN - 1) / BN) * batch < HG_NARROW_BELOW) { WM *= 2; MT = 1; BN /= 2; }
+    a.ntiles = (a.L + BN - 1) / BN;
+    a.up = l.up; a.cout = l.cout;
+    if constexpr (std::is_same<T, float>::value)
+        a.x_vec = (a.x_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0 && a.x_bs % 4 == 0) ? 1 : 0;
+    // split bf16: the fp32 plan's LDS figure covers its layout - the same weight bytes, and a tile that is no wider (no
+    // 16-byte row alignment)
+    const int lds = l.lds_bytes(BN);
+    const unsigned blocks = (unsigned)((size_t)a.MB * a.ntiles * batch);
+    constexpr int K0 = Fmt::kc_lo, K1 = 2 * K0;
+    const int key = MT * 100 + WM * 10 + (l.KC == K1);
+    switch (key) {
+        case 110: Fmt::template launch<1, 1, K0>(a, blocks, lds, s); break;
+        case 111: Fmt::template launch<1, 1, K1>(a, blocks, lds, s); break;
+        case 120: Fmt::template launch<1, 2, K0>(a, blocks, lds, s); break;
+        case 121: Fmt::template launch<1, 2, K1>(a, blocks, lds, s); break;
+        case 140: Fmt::template launch<1, 4, K0>(a, blocks, lds, s); break;
+        case 141: Fmt::template launch<1, 4, K1>(a, blocks, lds, s); break;
+        case 210: Fmt::template launch<2, 1, K0>(a, blocks, lds, s); break;
+        case 211: Fmt::template launch<2, 1, K1>(a, blocks, lds, s); break;
+        case 220: Fmt::template launch<2, 2, K0>(a, blocks, lds, s); break;
+        case 221: Fmt::template launch<2, 2, K1>(a, blocks, lds, s); break;
+        default: set_error("%s: no kernel shape %d", Fmt::name, key); return CTTS_E_ARG;
+    }
+    CTTS_CHECK_LAUNCH(Fmt::kernel);
+    return CTTS_OK;
+}
+
+// ---- the bodies of the extern "C" entries; `entry` is the name the messages carry ("hifigan_pack_f16", ...) ----
+template <typename Fmt>
+size_t hg_packed_bytes(const ctts_hifigan_config* cfg) {
+    HgPlan p;
+    if (make_hg_plan(cfg, p, sizeof(typename Fmt::T)) != CTTS_OK) return 0;
+    return p.packed_bytes;
+}
+
+// one pack launch per layer; aligned16: the blob is refused unless 16-byte aligned
+template <typename Fmt>
+int hg_pack(const char* entry, bool aligned16, const ctts_hifigan_config* cfg, const float* weights, size_t weight_floats, void* packed,
+            void* stream) {
+    using T = typename Fmt::T;
+    HgPlan p;
+    int rc = make_hg_plan(cfg, p, sizeof(T));
+    if (rc) return rc;
+    CTTS_CHECK_ARG(weights != nullptr && packed != nullptr, "%s: NULL pointer", entry);
+    CTTS_CHECK_ARG(weight_floats == p.weight_floats, "%s: %zu weight floats given, the config has %zu", entry, weight_floats,
+                   p.weight_floats);
+    CTTS_CHECK_ARG(!aligned16 || (reinterpret_cast<uintptr_t>(packed) & 15) == 0, "%s: packed blob must be 16-byte aligned", entry);
+    for (const HgLayer& l : p.layers) {
+        const long long total = (long long)l.packed_elems();     // >= MB * BM
+        Fmt::pack(hg_pack_args<T>(l, weights, packed), (unsigned)((total + 255) / 256), as_stream(stream));
+        CTTS_CHECK_LAUNCH(Fmt::pack_kernel);
+    }
+    return CTTS_OK;
+}
+
+template <typename Fmt>
+size_t hg_workspace_bytes(const ctts_hifigan_config* cfg, int32_t batch, int32_t frames) {
+    HgPlan p;
+    HgGeom g;
+    if (make_hg_plan(cfg, p, sizeof(typename Fmt::T)) != CTTS_OK || hg_geometry(p, batch, frames, g) != CTTS_OK) return 0;
+    return g.total_elems * sizeof(typename Fmt::T);
+}
+
+template <typename Fmt>
+int hg_forward_entry(const char* entry, const ctts_hifigan_config* cfg, const void* packed, const float* mel, int32_t mel_ld, float* audio,
+                     int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes, void* stream) {
+    using T = typename Fmt::T;
+    HgPlan p;
+    HgGeom g;
+    int rc = make_hg_plan(cfg, p, sizeof(T));
+    if (rc) return rc;
+    if ((rc = hg_geometry(p, batch, frames, g))) return rc;
+    CTTS_CHECK_ARG(packed != nullptr && mel != nullptr && audio != nullptr && workspace != nullptr, "%s: NULL pointer", entry);
+    CTTS_CHECK_ARG(mel_ld >= frames, "%s: mel_ld=%d < frames=%d", entry, mel_ld, frames);
+    CTTS_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(packed) & 15) == 0,
+                   "%s: packed blob and workspace must be 16-byte aligned", entry);
+    if (workspace_bytes < g.total_elems * sizeof(T)) {
+        set_error("%s: workspace %zu bytes < required %zu", entry, workspace_bytes, g.total_elems * sizeof(T));
+        return CTTS_E_WORKSPACE;
+    }
+    hipStream_t s = as_stream(stream);
+    return hg_forward<T>(p, g, mel, mel_ld, audio, frames, static_cast<T*>(workspace),
+                         [&](const HgLayer& l, const HgConvArgsT<T>& a) { return hg_launch<Fmt>(l, a, packed, batch, s); });
 }
 
 }  // namespace

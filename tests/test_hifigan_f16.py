@@ -308,6 +308,25 @@ def test_hifigan_f16_batch_item_equals_single_call_bit_for_bit():
 
 
 @pytest.mark.gpu
+def test_hifigan_f16_wide_block_shapes_equal_the_narrow_ones_bit_for_bit():
+    """The wide shapes engage from HG_NARROW_BELOW = 1024 workgroups (hg_launch in hifigan_plan.h, one rule for the three
+    formats).  toy_rate4 at B=64 x 4096 frames: conv_pre (64 rows, 256-column tiles) starts 1 x 16 x 64 = 1024 workgroups ->
+    64 x 256; ups.0 (128 rows, 128-column tiles) 1 x 32 x 64 = 2048 -> 128 x 128.  A single item starts 16 / 32 and stays
+    narrow.  Same packed weights and same K order either way, so the items are equal bit for bit."""
+    cfg, sd, _ = _case("toy_rate4")
+    B, T = 64, 4096
+    assert (T + 255) // 256 * B >= 1024 and (T + 127) // 128 * B >= 1024 and (T + 127) // 128 < 1024
+    m = _model(cfg, sd).set_compute_dtype(torch.float16)
+    mel = torch.from_numpy(synthetic.synthetic_mel(B, T, cfg["num_mels"], seed=64)).to("cuda:0")
+    with torch.no_grad():
+        full = m(mel)
+        for i in (0, 63):
+            one = m(mel[i:i + 1])
+            assert torch.equal(full[i:i + 1], one), i
+    assert torch.isfinite(full).all()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("key,batch,frames", [("toy_rate4", 2, 3), ("toy_rb1", 3, 13), ("v3", 1, 67), ("toy_rb2", 2, 300)])
 def test_hifigan_f16_odd_lengths(key, batch, frames):
     """A 3-frame call, T % 8 != 0, a ragged last tile (T prod(u) not a multiple of the 128 / 256-column tiles): against the f16
