@@ -15,7 +15,8 @@ from .torchmoji import TorchMoji, torchmoji_feature_encoding  # noqa: F401
 from .vocoder import WaveGlowVocoder, load_waveglow  # noqa: F401
 from .waveglow import WaveGlow, WaveGlowLoss  # noqa: F401
 from .waveglow_ax import WaveGlow as WaveFlow  # noqa: F401  (efficient_model_ax.WaveGlow, waveflow=True)
+from .waveglow_ax import WaveFlowLoss  # noqa: F401  (efficient_loss.WaveGlowLoss on WaveFlow.forward's tuple)
 
-__all__ = ["set_f32_gemm_mode", "WaveGlow", "WaveGlowLoss", "WaveGlowVocoder", "load_waveglow", "WaveFlow", "HiFiGANGenerator", "load_hifigan", "Tacotron2", "load_model", "STFT", "TacotronSTFT", "Denoiser", "alignment_metric",
+__all__ = ["set_f32_gemm_mode", "WaveGlow", "WaveGlowLoss", "WaveGlowVocoder", "load_waveglow", "WaveFlow", "WaveFlowLoss", "HiFiGANGenerator", "load_hifigan", "Tacotron2", "load_model", "STFT", "TacotronSTFT", "Denoiser", "alignment_metric",
            "get_first_over_thresh", "BestOfN", "pcm16_concat", "synthetic", "TorchMoji",
            "torchmoji_feature_encoding"]

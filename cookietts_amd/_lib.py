@@ -277,6 +277,14 @@ SIGNATURES = {
                                              C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
     "ctts_waveflow_inverse_cond_f32": (C.c_int, [C.POINTER(WaveFlowConfig), _FP, _FP, _FP, C.c_int32, C.c_int32, _FP,
                                                  C.c_int32, C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
+    "ctts_waveflow_forward_packed_bytes": (C.c_size_t, [C.POINTER(WaveFlowConfig)]),
+    "ctts_waveflow_pack_forward_mix": (C.c_int, [C.POINTER(WaveFlowConfig), C.c_int32, _FP, _FP, _FP]),
+    "ctts_waveflow_forward_workspace_bytes": (C.c_size_t, [C.POINTER(WaveFlowConfig), C.c_int32, C.c_int32]),
+    "ctts_waveflow_forward_f32": (C.c_int, [C.POINTER(WaveFlowConfig), _FP, _FP, _FP, _FP, C.c_float, C.c_int32, _FP, _FP, _FP, _FP,
+                                            C.c_int32, C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
+    "ctts_waveflow_forward_cond_f32": (C.c_int, [C.POINTER(WaveFlowConfig), _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_float,
+                                                 C.c_int32, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP, C.c_size_t,
+                                                 _FP]),
     "ctts_waveflow_abort_status": (C.c_int, [C.POINTER(WaveFlowConfig), C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
     "ctts_wgax_packed_bytes": (C.c_size_t, [C.POINTER(WgaxConfig)]),
     "ctts_wgax_pack_flow": (C.c_int, [C.POINTER(WgaxConfig), C.c_int32, C.POINTER(WgaxFlowWeights), _FP, _FP]),
@@ -417,6 +425,9 @@ TUNING_BITS = {"CTTS_F32_NO_GLDS": 0, "CTTS_GEMM_NO_XCD_PAIR": 1, "CTTS_F32_WINO
                "CTTS_F32_WINOGRAD_NO_F43": 22,
                "CTTS_TACO_POLL_DELAY": 23, "CTTS_TACO_VALU": 24, "CTTS_UP_NO_MFMA": 25, "CTTS_F32_NO_WN_FOLD": 26, "CTTS_TACO_BG_NO_PIPE": 27,
                "CTTS_F32_NO_WINOGRAD": 28, "CTTS_F32_WINOGRAD_MIN": 29, "CTTS_F32_WINOGRAD_PLAIN": 30}
+# ctts_tuning_flags() is full below the sign bit: knobs added since then sit here (bit 31 = the int's sign bit) and are looked up by
+# tuning_active like the others
+TUNING_BITS_EXT = {"CTTS_WF_FWD_ROWWISE": 31}
 
 
 def tuning_reload():
@@ -426,7 +437,8 @@ def tuning_reload():
 
 def tuning_active(name):
     """True when the library currently runs with knob ``name`` set (``ctts_tuning_flags``)."""
-    return bool(lib().ctts_tuning_flags() >> TUNING_BITS[name] & 1)
+    bit = TUNING_BITS[name] if name in TUNING_BITS else TUNING_BITS_EXT[name]
+    return bool(lib().ctts_tuning_flags() >> bit & 1)
 
 
 PROF_WN_IN = 0

@@ -218,11 +218,17 @@ int launch_wf_row_persistent(const GemmArgs* layers_dev, const WfTailDesc* tails
                              int batch, int body, unsigned int* counter, unsigned int* flags, unsigned int* abort_word,
                              unsigned int epoch, hipStream_t stream);
 
+// WaveFlow analysis direction (gemm_f32_small.hip, wf_all_rows_layer_kernel): layer i of ALL `nrows` rows of a flow as one launch
+// over (row, batch item, 128-column tile); rows_dev = [nrows] GemmArgs of that layer in device memory (defaults applied, checked with
+// gemm_check_args and wf_row_persistent_supported by the caller; no segment marked fresh).  Same tile body and bits as the per-layer
+// 128 x 128 shape.  Source and destination rows must not alias: other rows' height taps read the same layer's input.
+int launch_wf_all_rows_layer(const GemmArgs* rows_dev, int nrows, int max_nseg, int L, int batch, hipStream_t stream);
+
 // Library DEFAULT of the main-loop selection (what CTTS_GEMM_DEFAULT resolves to), in the config structs' own encoding:
 // CTTS_GEMM_F32 (initially), CTTS_GEMM_BF16X3 (three bf16 MFMA products per fp32 operand pair, see
 // conv_gemm_f32_kernel<..., X3>) or CTTS_GEMM_BF16X6.  ctts_set_f32_gemm_mode (deprecated: prefer the per-model field).
 int get_gemm_f32_mode();
-// what the calling thread's most recent conv-GEMM launch ran (ctts_last_gemm_loop): bits 0-3 split level, 16 small shape, 32 split-K, 64 row queue, 128 its whole-flow form
+// what the calling thread's most recent conv-GEMM launch ran (ctts_last_gemm_loop): bits 0-3 split level, 16 small shape, 32 split-K, 64 row queue, 128 its whole-flow form, 256 the all-rows layer of the WaveFlow analysis pass
 void note_gemm_loop(int code);
 int last_gemm_loop();
 // true when a launch with this GemmArgs.gemm_mode / config f32_gemm_mode runs the split-bf16 main loop

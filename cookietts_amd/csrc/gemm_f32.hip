@@ -828,6 +828,7 @@ void load_tuning_locked() {
         g_tune.taco_poll_delay_set = e != nullptr;
     }
     g_tune.wf_no_vec_interp = on("CTTS_WF_NO_VEC_INTERP");
+    g_tune.wf_fwd_rowwise = on("CTTS_WF_FWD_ROWWISE");
     g_tune.wf_no_region_split = on("CTTS_WF_NO_REGION_SPLIT");
     g_tune.wf_no_row_queue = on("CTTS_WF_NO_ROW_QUEUE");
     g_tune.wf_row_queue_min = num("CTTS_WF_ROW_QUEUE_MIN", -1);

@@ -1783,6 +1783,19 @@ __global__ __launch_bounds__(256, 2) void wf_row_persistent_kernel(const WfRowAr
     }
 }
 
+// ---- WaveFlow analysis direction: one layer of EVERY row in one launch -----------------------------------------------------
+// Given the audio, every row's WN input is known: the fused layer i of all rows of a flow is one launch whose workgroups map
+// blockIdx -> (row, batch item, column tile) and read their row's GemmArgs from a device array - exactly what the per-layer launch
+// of that row would have been given, with X(layer, row) in full-height storage.  Same wait-free tile body (FRESH = false): nothing
+// here waits on another workgroup, no counters, no flags.
+template <int SEGS>
+__global__ __launch_bounds__(256, 2) void wf_all_rows_layer_kernel(const GemmArgs* __restrict__ rows, const int ntiles_s, const int per_row) {
+    typedef const __attribute__((address_space(4))) GemmArgs const_args;         // scalar loads of the descriptor
+    const int row = blockIdx.x / per_row, rem = blockIdx.x - row * per_row;
+    const_args& a = *((const_args*)rows + row);
+    gate_rs_small_tile<SEGS, false, const_args>(a, rem % ntiles_s, rem / ntiles_s);
+}
+
 template <int EPI, int XS>
 void launch_small_xs(dim3 grid, hipStream_t stream, const GemmArgs& a, int ntiles_s) {
     if constexpr (EPI == GEMM_EPI_GATE && XS == 0) {
@@ -1950,6 +1963,17 @@ int launch_wf_row_persistent(const GemmArgs* layers_dev, const WfTailDesc* tails
         note_gemm_loop(16 | 64 | (tails_dev ? 128 : 0));
     }
     CTTS_CHECK_LAUNCH("wf_row_persistent");
+    return CTTS_OK;
+}
+
+int launch_wf_all_rows_layer(const GemmArgs* rows_dev, int nrows, int max_nseg, int L, int batch, hipStream_t stream) {
+    const int nt = wf_row_tiles(L, 0);
+    const long long per_row = (long long)nt * batch, nblk = per_row * nrows;
+    CTTS_CHECK_ARG(rows_dev && nrows >= 1 && batch >= 1 && nt >= 1 && nblk < (1ll << 31), "waveflow all-rows layer: bad argument (grid %lld)", nblk);
+    if (max_nseg <= 4) hipLaunchKernelGGL((wf_all_rows_layer_kernel<4>), dim3((unsigned)nblk), dim3(256), 0, stream, rows_dev, nt, (int)per_row);
+    else hipLaunchKernelGGL((wf_all_rows_layer_kernel<GEMM_MAX_SEG>), dim3((unsigned)nblk), dim3(256), 0, stream, rows_dev, nt, (int)per_row);
+    note_gemm_loop(16 | 256);
+    CTTS_CHECK_LAUNCH("wf_all_rows_layer");
     return CTTS_OK;
 }
 

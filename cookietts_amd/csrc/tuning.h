@@ -41,6 +41,7 @@ struct Tuning {
     int wf_row_queue_min;  // CTTS_WF_ROW_QUEUE_MIN: take the row queue from this many 128-column items per layer on (A/B; default in waveflow_api.hip)
     int wf_queue_debug;    // CTTS_WF_QUEUE_DEBUG: 16 / 32 force the 128 x 128 / split-K body, 64 two workgroups per CU at every size, 128 one launch per ROW instead of one per flow
     int wf_inject_abort;   // CTTS_WF_INJECT_ABORT: (tests) start the call with the queue's abort word set
+    bool wf_fwd_rowwise;   // CTTS_WF_FWD_ROWWISE: the WaveFlow analysis pass (ctts_waveflow_forward_*) row by row through the inverse's per-layer launches also on models that have the all-rows form (A/B; same tile arithmetic)
     bool wf_no_vec_interp; // CTTS_WF_NO_VEC_INTERP: the scalar form of the WaveFlow conditioning interpolation (bit-identical)
 };
 

@@ -48,6 +48,8 @@ struct WfPlan {
     // one 128-row block holds every gate pair: the res/skip GEMM runs inside the in-layer kernel (GEMM_EPI_GATE_RS)
     bool fused() const { return C == 64 && c.gated_unit == 0; }
     // both 1x1 stages of a separable layer in one launch (waveflow_sep.hip): pointwise/gate + res/skip, C = 128
+    // the analysis direction's all-rows form (one launch per layer over every row): the fused dense layer on the fp32 MFMA tile
+    bool all_rows() const { return fused() && !sep && !gemm_mode_is_split(c.f32_gemm_mode); }
     bool sep_fused() const {
         return sep && precond && wf_sep_supported(C);
     }
@@ -160,9 +162,12 @@ struct WfQueueWs {
     WfTailDesc* tails;                               // [n_group]
     size_t control_bytes;                            // abort word .. end of the flags: zeroed at the start of every call
 };
-struct WfWs { float *rows, *mel_up, *cond_up, *dwout, *X, *act, *out; size_t total, xslot, cond_slot; WfQueueWs q; };
+// Analysis direction (ctts_waveflow_forward_*), behind the inverse's buffers: log_s of one flow, the fp64 partial sums, and - for
+// WfPlan::all_rows() models - full-height storage [n_group - 1][B][C][ld] of two layer inputs and the skip sum + the layer descriptors
+struct WfFwdWs { float *ls, *XA, *XB, *OUT; double* partials; GemmArgs* desc; int nblk; };
+struct WfWs { float *rows, *mel_up, *cond_up, *dwout, *X, *act, *out; size_t total, xslot, cond_slot; WfQueueWs q; WfFwdWs f; };
 
-void wf_carve(const WfPlan& p, const WfGeom& g, int batch, float* base, WfWs& w) {
+void wf_carve(const WfPlan& p, const WfGeom& g, int batch, float* base, WfWs& w, bool forward = false) {
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o = align_up(o + n); return base ? base + r : nullptr; };
     const size_t B = batch;
@@ -186,6 +191,18 @@ void wf_carve(const WfPlan& p, const WfGeom& g, int batch, float* base, WfWs& w)
         w.q.layers = reinterpret_cast<GemmArgs*>(take(((size_t)p.c.n_group * p.c.n_layers * sizeof(GemmArgs) + 3) / 4));
         w.q.tails = reinterpret_cast<WfTailDesc*>(take(((size_t)p.c.n_group * sizeof(WfTailDesc) + 3) / 4));
         w.q.status = reinterpret_cast<unsigned int*>(take(ALIGN_F));   // outside the per-call memset
+    }
+    w.f = WfFwdWs{};
+    if (forward) {
+        const size_t rows_h = p.c.n_group - 1;
+        w.f.nblk = (g.Lr + 255) / 256;
+        w.f.ls = take(B * p.c.n_group * g.Lr);
+        w.f.partials = reinterpret_cast<double*>(take(2 * (size_t)p.c.n_flows * B * w.f.nblk));
+        const bool ar = p.all_rows();
+        w.f.XA = take(ar ? rows_h * w.xslot : 0);
+        w.f.XB = take(ar && !p.c.merge_res_skip ? rows_h * w.xslot : 0);       // merge_res_skip reads X0 throughout
+        w.f.OUT = take(ar ? rows_h * w.xslot : 0);
+        w.f.desc = reinterpret_cast<GemmArgs*>(take(ar ? ((size_t)p.c.n_flows * p.c.n_layers * rows_h * sizeof(GemmArgs) + 3) / 4 : 0));
     }
     w.total = o;
 }
@@ -580,6 +597,149 @@ __global__ __launch_bounds__(256) void wf_mix_kernel(float* __restrict__ rows, c
     }
 }
 
+// ---- analysis direction (efficient_model_ax.py:184-277) ----------------------------------------------------------------------
+// rows[b][g][l] = y[b][G*l + g], y = PreEmphasis(audio) when p != 0 (efficient_loss.py:16-20: y[t] = x[t] - p x[t-1], reflected
+// at t = 0: y[0] = x[0] - p x[1])
+__global__ __launch_bounds__(256) void wf_fwd_squeeze_kernel(const float* __restrict__ audio, float* __restrict__ rows, int G,
+                                                             int L, int Lr, float p) {
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (l >= Lr) return;
+    const size_t T = (size_t)G * L;
+    const float* ab = audio + (size_t)b * T;
+    float* rb = rows + (size_t)b * G * Lr + l;
+    for (int g = 0; g < G; ++g) {
+        float v = 0.f;                                                          // row tail (l >= L) stays zero
+        if (l < L) {
+            const size_t t = (size_t)l * G + g;
+            v = ab[t];
+            if (p != 0.f) v = __builtin_fmaf(-p, t > 0 ? ab[t - 1] : ab[T > 1 ? 1 : 0], v);
+        }
+        rb[(size_t)g * Lr] = v;
+    }
+}
+
+// X0[r][b][c][pad + l] = ws[c] * rows[b][phys[r]][l] + bs[c] for every WN input row r = 0 .. nrows - 1 of a flow (wf_start_kernel
+// over all rows; blockIdx.z = r * batch + b)
+__global__ __launch_bounds__(256) void wf_fwd_start_rows_kernel(const float* __restrict__ rows, const float* __restrict__ ws,
+                                                                const float* __restrict__ bs, float* __restrict__ x, size_t xslot,
+                                                                RowMap map, int C, int G, int batch, int L, int Lr, int ld, int pad) {
+    const int n = (blockIdx.x * 256 + threadIdx.x) * 4;
+    const int r = blockIdx.z / batch, b = blockIdx.z - r * batch;
+    if (n >= L) return;
+    const float4 a = *reinterpret_cast<const float4*>(rows + ((size_t)b * G + map.phys[r]) * Lr + n);
+    const int c0 = blockIdx.y * 16;
+    float* xb = x + (size_t)r * xslot + (size_t)b * C * ld + pad + n;
+    const bool k1 = n + 1 < L, k2 = n + 2 < L, k3 = n + 3 < L;      // columns >= L are halo: keep them zero
+    for (int c = c0; c < c0 + 16 && c < C; ++c) {
+        const float w = ws[c], bias = bs[c];
+        float4 v;
+        v.x = wf_start_value(w, a.x, bias);
+        v.y = k1 ? wf_start_value(w, a.y, bias) : 0.f; v.z = k2 ? wf_start_value(w, a.z, bias) : 0.f; v.w = k3 ? wf_start_value(w, a.w, bias) : 0.f;
+        *reinterpret_cast<float4*>(xb + (size_t)c * ld) = v;
+    }
+}
+
+// e = Wend * out_r + bend; log_s = e[0], t = e[1]; rows[b][phys[r + 1]][l] = rows[..] * exp(log_s) + t; ls[b][r][l] = log_s
+// (efficient_modules.py:38) for WN rows r = r0 + blockIdx.z: one row per launch (row-wise form, out_rstride = 0) or all rows of a
+// flow (all-rows form).  The end conv sums as wf_tail_kernel does: four fma chains over C / 4 ascending channels, ((p0 + p1) + p2) + p3.
+__global__ __launch_bounds__(256) void wf_fwd_tail_kernel(const float* __restrict__ out, size_t out_rstride, float* __restrict__ rows,
+                                                          float* __restrict__ ls, const float* __restrict__ Wend,
+                                                          const float* __restrict__ bend, RowMap map, int r0, int C, int G, int L,
+                                                          int Lr, int ld, int pad) {
+    __shared__ __attribute__((aligned(16))) float part[3][2][256];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.y, r = r0 + blockIdx.z;
+    const int n = blockIdx.x * 256 + lane * 4;
+    float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = e0;
+    const int cq = C / 4;
+    const int cbeg = __builtin_amdgcn_readfirstlane(wv * cq);
+    const float* ob = out + (size_t)blockIdx.z * out_rstride + (size_t)b * C * ld + pad + n;
+    for (int c = cbeg; c < cbeg + cq; ++c) {
+        const float4 v = *reinterpret_cast<const float4*>(ob + (size_t)c * ld);
+        const float w0 = Wend[c], w1 = Wend[C + c];
+        e0.x = wf_end_fma(w0, v.x, e0.x); e0.y = wf_end_fma(w0, v.y, e0.y); e0.z = wf_end_fma(w0, v.z, e0.z); e0.w = wf_end_fma(w0, v.w, e0.w);
+        e1.x = wf_end_fma(w1, v.x, e1.x); e1.y = wf_end_fma(w1, v.y, e1.y); e1.z = wf_end_fma(w1, v.z, e1.z); e1.w = wf_end_fma(w1, v.w, e1.w);
+    }
+    if (wv > 0) {
+        *reinterpret_cast<float4*>(&part[wv - 1][0][lane * 4]) = e0;
+        *reinterpret_cast<float4*>(&part[wv - 1][1][lane * 4]) = e1;
+    }
+    __syncthreads();
+    if (wv != 0 || n >= L) return;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const float4 p0 = *reinterpret_cast<const float4*>(&part[q][0][lane * 4]);
+        const float4 p1 = *reinterpret_cast<const float4*>(&part[q][1][lane * 4]);
+        e0.x += p0.x; e0.y += p0.y; e0.z += p0.z; e0.w += p0.w;
+        e1.x += p1.x; e1.y += p1.y; e1.z += p1.z; e1.w += p1.w;
+    }
+    const float b0 = bend[0], b1 = bend[1];
+    float* rp = rows + ((size_t)b * G + map.phys[r + 1]) * Lr + n;
+    float4 a = *reinterpret_cast<const float4*>(rp);
+    const bool k1 = n + 1 < L, k2 = n + 2 < L, k3 = n + 3 < L;      // row tails stay zero
+    float4 s;
+    s.x = e0.x + b0; s.y = k1 ? e0.y + b0 : 0.f; s.z = k2 ? e0.z + b0 : 0.f; s.w = k3 ? e0.w + b0 : 0.f;
+    a.x = wf_row_forward(a.x, s.x, e1.x, b1);
+    a.y = k1 ? wf_row_forward(a.y, s.y, e1.y, b1) : 0.f;
+    a.z = k2 ? wf_row_forward(a.z, s.z, e1.z, b1) : 0.f;
+    a.w = k3 ? wf_row_forward(a.w, s.w, e1.w, b1) : 0.f;
+    *reinterpret_cast<float4*>(rp) = a;
+    *reinterpret_cast<float4*>(ls + ((size_t)b * G + r) * Lr + n) = s;
+}
+
+// Behind a flow's coupling, from its log_s rows ls[b][0 .. nrows)[l]: log_s_sum[b][l] (+)= their fp32 sum in row order
+// (ax:269-273), the optional copy into log_s[b][s_off + r][l], and stage one of the fp64 sum: a thread adds its column's rows in
+// row order, the block adds its 256 columns as a fixed tree -> partials[b][blockIdx.x].  No atomics: two calls give the same bits,
+// and an item's value does not depend on its batch.
+__global__ __launch_bounds__(256) void wf_fwd_reduce_kernel(const float* __restrict__ ls, int nrows, int G, int L, int Lr,
+                                                            float* __restrict__ log_s, int S, int s_off,
+                                                            float* __restrict__ log_s_sum, int first,
+                                                            double* __restrict__ partials, int nblk) {
+    __shared__ double red[256];
+    const int l = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    double s64 = 0.0;
+    if (l < L) {
+        float s32 = 0.f;
+        const float* lp = ls + (size_t)b * G * Lr + l;
+        for (int r = 0; r < nrows; ++r) {
+            const float v = lp[(size_t)r * Lr];
+            s32 += v;
+            s64 += (double)v;
+            if (log_s) log_s[((size_t)b * S + s_off + r) * L + l] = v;
+        }
+        float* o = log_s_sum + (size_t)b * L + l;
+        *o = first ? s32 : *o + s32;
+    }
+    red[threadIdx.x] = s64;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[(size_t)b * nblk + blockIdx.x] = red[0];
+}
+
+// stage two: sums[b][k] = the partials of flow k and item b, added in block order (one thread each)
+__global__ __launch_bounds__(64) void wf_fwd_sums_kernel(const double* __restrict__ partials, double* __restrict__ sums,
+                                                         int n_flows, int batch, int nblk) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_flows * batch) return;
+    const int k = i / batch, b = i - k * batch;
+    const double* p = partials + ((size_t)k * batch + b) * nblk;
+    double s = 0.0;
+    for (int j = 0; j < nblk; ++j) s += p[j];
+    sums[(size_t)b * n_flows + k] = s;
+}
+
+// offsets (floats) of the forward 1x1 matrices W_k in the forward blob; PermuteHeight needs none
+size_t wf_fwd_mix_offset(const WfPlan& p, int k) {
+    size_t o = 0;
+    if (p.c.mixing != CTTS_MIX_CONV1X1) return 0;
+    for (int j = 0; j < k; ++j) o = align_up(o + (size_t)p.n_rem[j] * p.n_rem[j]);
+    return o;
+}
+
 void wf_permutation(int k, int G, int* perm) {
     for (int g = 0; g < G; ++g) perm[g] = G - 1 - g;                       // reverse (k % 4 in {0,1})
     if (k % 4 == 2 || k % 4 == 3) {                                        // reverse each half separately
@@ -801,29 +961,44 @@ int wf_note_pending(const void* workspace, unsigned int* status, hipStream_t s) 
     return rc;
 }
 
+// The analysis direction of the same body (ctts_waveflow_forward_*): `z` is then the audio that goes IN, `audio` the latent that
+// comes OUT, and this says where the rest goes.  NULL = the inverse.
+struct WfForward {
+    const float* mix;            // forward blob: W_k of the 1x1-conv mixing (NULL with PermuteHeight)
+    float preemphasis;           // PreEmphasis coefficient applied to the audio first; 0 = none
+    int ignore_nan;              // NaN -> 0 behind every coupling (ax:253-254)
+    float* log_s;                // [B][S][L] or NULL
+    float* log_s_sum;            // [B][L]
+    double* sums;                // [B][n_flows]
+};
+
 int wf_inverse(const ctts_waveflow_config* cfg, const void* packed, const float* z, const float* cond, int cond_ld,
                int cond_pad, float* audio, int batch, int samples, int frames, void* workspace, size_t workspace_bytes,
-               void* stream) {
+               void* stream, const WfForward* fw = nullptr) {
     WfPlan p; WfGeom g; WfWs w;
     int rc = make_wf_plan(cfg, p); if (rc) return rc;
     rc = make_wf_geom(p, samples, g); if (rc) return rc;
-    CTTS_CHECK_ARG(packed && z && cond && audio && workspace && batch >= 1 && frames >= 1, "waveflow inverse: bad argument");
-    wf_carve(p, g, batch, static_cast<float*>(workspace), w);
+    const char* const what = fw ? "forward" : "inverse";
+    CTTS_CHECK_ARG(packed && z && cond && audio && workspace && batch >= 1 && frames >= 1, "waveflow %s: bad argument", what);
+    CTTS_CHECK_ARG(!fw || (fw->log_s_sum && fw->sums && (fw->mix || p.c.mixing != CTTS_MIX_CONV1X1) && batch <= 65535 / p.c.n_group),
+                   "waveflow forward: bad argument (log_s_sum, sums, the forward blob of a 1x1-conv model; batch * n_group <= 65535)");
+    wf_carve(p, g, batch, static_cast<float*>(workspace), w, fw != nullptr);
     if (w.total * sizeof(float) > workspace_bytes) {
-        set_error("waveflow inverse: workspace %zu bytes < required %zu", workspace_bytes, w.total * sizeof(float));
+        set_error("waveflow %s: workspace %zu bytes < required %zu", what, workspace_bytes, w.total * sizeof(float));
         return CTTS_E_WORKSPACE;
     }
     hipStream_t s = as_stream(stream);
     // the previous call of this thread on this workspace used the row queue: if it aborted, say so now instead of computing
     // on top of it (one stream synchronisation + 4 bytes; the caller sees CTTS_E_ABORT once, the call after that runs)
-    if ((rc = wf_check_pending(workspace, w.q.status, s))) return rc;
+    if (!fw && (rc = wf_check_pending(workspace, w.q.status, s))) return rc;
     const float* blob = static_cast<const float*>(packed);
     const int G = p.c.n_group, C = p.C, L = g.L, kh = p.c.kernel_size_h, kw = p.c.kernel_size_w;
     const int gkh = p.sep ? 1 : kh, gkw = p.sep ? 1 : kw;
     const long long cstride = (long long)C * g.ld;
     const dim3 lgrid((g.Lr + 255) / 256, batch);
 
-    hipLaunchKernelGGL(wf_squeeze_kernel, lgrid, dim3(256), 0, s, z, w.rows, G, L, g.Lr);
+    if (fw) hipLaunchKernelGGL(wf_fwd_squeeze_kernel, lgrid, dim3(256), 0, s, z, w.rows, G, L, g.Lr, fw->preemphasis);
+    else hipLaunchKernelGGL(wf_squeeze_kernel, lgrid, dim3(256), 0, s, z, w.rows, G, L, g.Lr);
     CTTS_CHECK_LAUNCH("wf_squeeze");
     if (!p.precond) {
         hipLaunchKernelGGL(wf_interp_kernel, dim3((L + 255) / 256, p.c.n_mel_channels, batch), dim3(256), 0, s, cond,
@@ -841,6 +1016,16 @@ int wf_inverse(const ctts_waveflow_config* cfg, const void* packed, const float*
     auto X = [&](int layer, int slot) { return w.X + ((size_t)layer * NS + slot) * w.xslot; };
     const bool no_fuse = tuning().wf_no_fuse;
     const bool fuse = p.fused() && !no_fuse;
+    // Analysis direction, all-rows form: every row's WN input is known, so layer i of ALL rows is one launch (gemm_f32_small.hip
+    // wf_all_rows_layer_kernel) on full-height storage - layer i reads XA / XB by parity and writes the other (never in place: other
+    // rows' height taps read the same input), the skip sum of row r is OUT[r].  The model selects it, CTTS_WF_FWD_ROWWISE (or a knob
+    // that takes the DMA-staged small tile away) falls back to the row-wise form.
+    const bool all_rows = fw && p.all_rows() && fuse && !tuning().wf_fwd_rowwise && !tuning().f32_no_glds && !tuning().f32_no_small;
+    // layer `layer`'s input of WN row `row`: the ring slot, or full-height storage
+    auto XR = [&](int layer, int row) {
+        return all_rows ? ((layer & 1) ? w.f.XB : w.f.XA) + (size_t)row * w.xslot : X(layer, row % NS);
+    };
+    auto OUT = [&](int row) { return all_rows ? w.f.OUT + (size_t)row * w.xslot : w.out; };
     // Region split of the fused layer (round 4): every layer launch used to wait for the slowest of the previous layer's 456
     // workgroups although tile t of layer i + 1 needs only tiles t - 1, t, t + 1 of layer i (dilation <= 128 < one 256-column
     // tile).  The columns are cut into three regions A | M (one tile) | B launched on three streams: A(i+1) and B(i+1) wait
@@ -862,7 +1047,7 @@ int wf_inverse(const ctts_waveflow_config* cfg, const void* packed, const float*
     // work per workgroup, and a layer's tail is small against it)
     // (the queue's tile bodies are the fp32-MFMA DMA-staged ones: under the split-bf16 modes, CTTS_F32_NO_GLDS or CTTS_F32_NO_SMALL
     // the layers are launched one by one as before)
-    bool queue_on = fuse && !p.sep && !tuning().wf_no_row_queue && q_items >= q_min &&
+    bool queue_on = !fw && fuse && !p.sep && !tuning().wf_no_row_queue && q_items >= q_min &&
                     (q_items < WF_ROW_QUEUE_MAX_ITEMS || tuning().wf_row_queue_min >= 0) &&
                     !gemm_mode_is_split(p.c.f32_gemm_mode) && !tuning().f32_no_glds && !tuning().f32_no_small;
     // Which tile body (measured, profiles/r4_12): below 400 items of 128 columns per layer the split-K body (items of 128 x 64, half
@@ -905,7 +1090,7 @@ int wf_inverse(const ctts_waveflow_config* cfg, const void* packed, const float*
     auto fused_args = [&](const WfPlan::Flow& f, int r, int i, int mark_fresh) {
         const int dw = p.c.dilation_w[i] > 0 ? p.c.dilation_w[i] : 1 << i;
         const bool merge = p.c.merge_res_skip != 0;
-        const int si = merge ? 0 : i, slot = r % NS;
+        const int si = merge ? 0 : i;
         const int dh = p.dh(i);
         const int a_min = std::max(0, kh - 1 - r / dh);
         GemmArgs a{};
@@ -924,7 +1109,7 @@ int wf_inverse(const ctts_waveflow_config* cfg, const void* packed, const float*
             // the current row's slot of layer i > 0 is what layer i - 1 of this very row wrote
             const int fresh = mark_fresh == 2 || (mark_fresh == 1 && src_row == r && si > 0) ? 1 : 0;
             for (int j = 0; j < gkw; ++j)
-                a.seg[ns++] = {X(si, src_row % NS), cstride, p.nch_c, (j - kw / 2) * dw, 0, fresh};
+                a.seg[ns++] = {XR(si, src_row), cstride, p.nch_c, (j - kw / 2) * dw, 0, fresh};
         }
         a.nch_total = (kh - a_min) * kw * p.nch_c;
         if (p.precond) {
@@ -938,9 +1123,9 @@ int wf_inverse(const ctts_waveflow_config* cfg, const void* packed, const float*
         const bool last = i == p.c.n_layers - 1 || merge;       // all rows of the res/skip GEMM are skip rows
         // x_{i+1}[row r] = x_i[row r] + res -> layer i+1's ring slot;  skip rows (+)= into w.out
         a.rs_wT = blob + f.rs_T[i]; a.rs_bias = blob + f.rs_Tb[i]; a.rs_rows = p.rs_rows(i);
-        a.dst0 = last ? w.out : X(i + 1, slot); a.dst0_bstride = cstride; a.acc0 = 1;
-        a.src0 = X(si, slot); a.src0_bstride = cstride;
-        a.dst1 = w.out; a.dst1_bstride = cstride; a.acc1 = i > 0 ? 1 : 0;
+        a.dst0 = last ? OUT(r) : XR(i + 1, r); a.dst0_bstride = cstride; a.acc0 = 1;
+        a.src0 = XR(si, r); a.src0_bstride = cstride;
+        a.dst1 = OUT(r); a.dst1_bstride = cstride; a.acc1 = i > 0 ? 1 : 0;
         a.split = last ? 0 : C;
         return a;
     };
@@ -1054,6 +1239,118 @@ int wf_inverse(const ctts_waveflow_config* cfg, const void* packed, const float*
         return CTTS_OK;
     };
 
+    // this flow's conditioning (cond_precomputed models), upsampled once for all rows and layers
+    auto flow_cond = [&](int k) -> int {
+        if (!p.precond) return CTTS_OK;
+        const float* fr = cond + (size_t)k * batch * 2 * C * p.c.n_layers * cond_ld;
+        if (g.pad % 4 == 0 && g.ld % 4 == 0 && w.cond_slot % 4 == 0 && !tuning().wf_no_vec_interp)
+            hipLaunchKernelGGL(wf_interp_cond_vec_kernel, dim3(((L + 3) / 4 + 255) / 256, 2 * C * p.c.n_layers, batch), dim3(256), 0, s,
+                               fr, w.cond_up, 2 * C, p.c.n_layers, frames, cond_ld, cond_pad, L, g.ld, g.pad, w.cond_slot);
+        else
+            hipLaunchKernelGGL(wf_interp_cond_kernel, dim3((L + 255) / 256, 2 * C * p.c.n_layers, batch), dim3(256), 0, s,
+                               fr, w.cond_up, 2 * C, p.c.n_layers, frames, cond_ld, cond_pad, L, g.ld, g.pad, w.cond_slot);
+        CTTS_CHECK_LAUNCH("wf_interp_cond");
+        return CTTS_OK;
+    };
+
+    if (fw) {
+        // ---- analysis direction (ax:234-277): flows in natural order; the mix is the same row-map composition (PermuteHeight is its
+        // own inverse) or the same pass over the rows with W_k; an early split peels the first n_early_size active rows off to the output
+        Ga = G;
+        for (int i = 0; i < G; ++i) phys[i] = i;
+        int outmap[64], nout = 0, s_off = 0, S = 0;
+        for (int k = 0; k < p.c.n_flows; ++k) S += p.n_rem[k] - 1;
+        auto mix = [&](int k) -> int {
+            if (p.c.mixing == CTTS_MIX_PERMUTE) return unmix(k);
+            RowMap m;
+            for (int i = 0; i < 64; ++i) m.phys[i] = i < Ga ? phys[i] : 0;
+            hipLaunchKernelGGL(wf_mix_kernel, lgrid, dim3(256), 0, s, w.rows, fw->mix + wf_fwd_mix_offset(p, k), m, Ga, G, g.Lr);
+            CTTS_CHECK_LAUNCH("wf_mix (forward)");
+            return CTTS_OK;
+        };
+        // all-rows form: the descriptors of the whole call - [flow][layer][row], independent of the row map - staged in the calling
+        // thread's pinned buffer and copied once
+        std::vector<size_t> d_off(p.c.n_flows + 1, 0);
+        int d_max_nseg = 0;
+        if (all_rows) {
+            for (int k = 0; k < p.c.n_flows; ++k) d_off[k + 1] = d_off[k] + (size_t)p.c.n_layers * (p.n_rem[k] - 1);
+            if ((rc = t_wf_desc.begin(d_off[p.c.n_flows] * sizeof(GemmArgs)))) return rc;
+            GemmArgs* host = reinterpret_cast<GemmArgs*>(t_wf_desc.host);
+            for (int k = 0; k < p.c.n_flows; ++k)
+                for (int i = 0; i < p.c.n_layers; ++i)
+                    for (int r = 0; r < p.n_rem[k] - 1; ++r) {
+                        GemmArgs& a = host[d_off[k] + (size_t)i * (p.n_rem[k] - 1) + r] = fused_args(p.fl[k], r, i, 0);
+                        gemm_apply_defaults(a);                     // (the tile body is launched without launch_gemm_f32:
+                        if ((rc = gemm_check_args(GEMM_EPI_GATE_RS, a))) return rc;   //  its defaults and checks are applied here)
+                        d_max_nseg = std::max(d_max_nseg, a.nseg);
+                        CTTS_CHECK_ARG(wf_row_persistent_supported(a), "waveflow forward: layer %d not supported by the tile body", i);
+                    }
+            CTTS_CHECK_HIP(hipMemcpyAsync(w.f.desc, host, d_off[p.c.n_flows] * sizeof(GemmArgs), hipMemcpyHostToDevice, s));
+            if ((rc = t_wf_desc.end(s))) return rc;
+        }
+        const dim3 sgrid(((L + 3) / 4 + 255) / 256, (C + 15) / 16, batch);
+        for (int k = 0; k < p.c.n_flows; ++k) {
+            const auto& f = p.fl[k];
+            if (p.n_rem[k] < Ga) {                                                 // ax:237-242: the early output leaves in front
+                const int es = Ga - p.n_rem[k];
+                for (int i = 0; i < es; ++i) outmap[nout++] = phys[i];
+                for (int i = es; i < Ga; ++i) phys[i - es] = phys[i];
+                Ga -= es;
+            }
+            if (p.c.mix_first && (rc = mix(k))) return rc;                         // ax:244-245
+            if ((rc = flow_cond(k))) return rc;
+            const int nr = Ga - 1;                                                 // WN rows 0 .. Ga - 2 (efficient_modules.py:30)
+            RowMap m;
+            for (int i = 0; i < 64; ++i) m.phys[i] = i < Ga ? phys[i] : 0;
+            if (all_rows) {
+                hipLaunchKernelGGL(wf_fwd_start_rows_kernel, dim3(sgrid.x, sgrid.y, (unsigned)(nr * batch)), dim3(256), 0, s, w.rows,
+                                   blob + f.start_w, blob + f.start_b, w.f.XA, w.xslot, m, C, G, batch, L, g.Lr, g.ld, g.pad);
+                CTTS_CHECK_LAUNCH("wf_fwd_start_rows");
+                for (int i = 0; i < p.c.n_layers; ++i)
+                    if ((rc = launch_wf_all_rows_layer(w.f.desc + d_off[k] + (size_t)i * nr, nr, d_max_nseg, L, batch, s))) return rc;
+                hipLaunchKernelGGL(wf_fwd_tail_kernel, dim3((g.Lr + 255) / 256, batch, nr), dim3(256), 0, s, w.f.OUT, w.xslot, w.rows,
+                                   w.f.ls, blob + f.end_w, blob + f.end_b, m, 0, C, G, L, g.Lr, g.ld, g.pad);
+                CTTS_CHECK_LAUNCH("wf_fwd_tail");
+            } else {
+                // row-wise form: the inverse's launches in natural row order on the ring; the row's input is the known audio row, so
+                // the next row's start conv runs BEFORE this row's tail overwrites it (its ring slot is free: this row's layers are queued)
+                hipLaunchKernelGGL(wf_start_kernel, sgrid, dim3(256), 0, s, w.rows, blob + f.start_w, blob + f.start_b, X(0, 0), C, G,
+                                   phys[0], L, g.Lr, g.ld, g.pad);
+                CTTS_CHECK_LAUNCH("wf_start");
+                for (int r = 0; r < nr; ++r) {
+                    if ((rc = per_layer_row(f, r, r % NS))) return rc;
+                    if (r + 1 < nr) {
+                        hipLaunchKernelGGL(wf_start_kernel, sgrid, dim3(256), 0, s, w.rows, blob + f.start_w, blob + f.start_b,
+                                           X(0, (r + 1) % NS), C, G, phys[r + 1], L, g.Lr, g.ld, g.pad);
+                        CTTS_CHECK_LAUNCH("wf_start");
+                    }
+                    hipLaunchKernelGGL(wf_fwd_tail_kernel, dim3((g.Lr + 255) / 256, batch, 1), dim3(256), 0, s, w.out, (size_t)0, w.rows,
+                                       w.f.ls, blob + f.end_w, blob + f.end_b, m, r, C, G, L, g.Lr, g.ld, g.pad);
+                    CTTS_CHECK_LAUNCH("wf_fwd_tail");
+                }
+            }
+            hipLaunchKernelGGL(wf_fwd_reduce_kernel, dim3(w.f.nblk, batch), dim3(256), 0, s, w.f.ls, nr, G, L, g.Lr, fw->log_s, S, s_off,
+                               fw->log_s_sum, k == 0 ? 1 : 0, w.f.partials + (size_t)k * batch * w.f.nblk, w.f.nblk);
+            CTTS_CHECK_LAUNCH("wf_fwd_reduce");
+            s_off += nr;
+            if (fw->ignore_nan) {
+                const size_t n4 = (size_t)batch * G * g.Lr / 4;
+                hipLaunchKernelGGL(wf_nan_to_zero_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, w.rows, n4);
+                CTTS_CHECK_LAUNCH("wf_nan_to_zero");
+            }
+            if (!p.c.mix_first && (rc = mix(k))) return rc;                        // ax:260-261
+        }
+        for (int i = 0; i < Ga; ++i) outmap[nout++] = phys[i];                     // ax:276-277
+        RowMap map;
+        for (int i = 0; i < 64; ++i) map.phys[i] = i < G ? outmap[i] : 0;
+        hipLaunchKernelGGL(wf_unsqueeze_kernel, dim3((L + 255) / 256, batch), dim3(256), 0, s, w.rows, audio, G, L, g.Lr, map);
+        CTTS_CHECK_LAUNCH("wf_unsqueeze");
+        hipLaunchKernelGGL(wf_fwd_sums_kernel, dim3((p.c.n_flows * batch + 63) / 64), dim3(64), 0, s, w.f.partials, fw->sums,
+                           p.c.n_flows, batch, w.f.nblk);
+        CTTS_CHECK_LAUNCH("wf_fwd_sums");
+        return CTTS_OK;
+    }
+
     for (int k = p.c.n_flows - 1; k >= 0; --k) {
         const auto& f = p.fl[k];
         if (!p.c.mix_first && (rc = unmix(k))) return rc;                      // ax:324-325
@@ -1086,16 +1383,7 @@ int wf_inverse(const ctts_waveflow_config* cfg, const void* packed, const float*
                 q_host_off += (size_t)(Ga - 1) * sizeof(WfTailDesc);
             }
         }
-        if (p.precond) {   // this flow's conditioning, upsampled once for all rows and layers
-            const float* fr = cond + (size_t)k * batch * 2 * C * p.c.n_layers * cond_ld;
-            if (g.pad % 4 == 0 && g.ld % 4 == 0 && w.cond_slot % 4 == 0 && !tuning().wf_no_vec_interp)
-                hipLaunchKernelGGL(wf_interp_cond_vec_kernel, dim3(((L + 3) / 4 + 255) / 256, 2 * C * p.c.n_layers, batch), dim3(256), 0, s,
-                                   fr, w.cond_up, 2 * C, p.c.n_layers, frames, cond_ld, cond_pad, L, g.ld, g.pad, w.cond_slot);
-            else
-                hipLaunchKernelGGL(wf_interp_cond_kernel, dim3((L + 255) / 256, 2 * C * p.c.n_layers, batch), dim3(256), 0, s,
-                                   fr, w.cond_up, 2 * C, p.c.n_layers, frames, cond_ld, cond_pad, L, g.ld, g.pad, w.cond_slot);
-            CTTS_CHECK_LAUNCH("wf_interp_cond");
-        }
+        if ((rc = flow_cond(k))) return rc;
         if (q_flow) {                                       // start of row 0, then every row and tail of the flow in one launch
             hipLaunchKernelGGL(wf_start_kernel, dim3(((L + 3) / 4 + 255) / 256, (C + 15) / 16, batch), dim3(256), 0, s,
                                w.rows, blob + f.start_w, blob + f.start_b, X(0, 0), C, G, phys[0], L, g.Lr, g.ld, g.pad);
@@ -1230,6 +1518,53 @@ int ctts_waveflow_inverse_f32(const ctts_waveflow_config* cfg, const void* packe
     CTTS_CHECK_ARG(cfg && !cfg->cond_precomputed, "waveflow inverse: this model takes per-flow conditioning "
                                                   "(ctts_waveflow_inverse_cond_f32)");
     return wf_inverse(cfg, packed, z, mel, 0, 0, audio, batch, samples, frames, workspace, workspace_bytes, stream);
+}
+
+size_t ctts_waveflow_forward_packed_bytes(const ctts_waveflow_config* cfg) {
+    WfPlan p;
+    if (make_wf_plan(cfg, p)) return 0;
+    return wf_fwd_mix_offset(p, p.c.n_flows) * sizeof(float);
+}
+
+int ctts_waveflow_pack_forward_mix(const ctts_waveflow_config* cfg, int32_t k, const float* W_k, void* fwd_blob, void* stream) {
+    WfPlan p;
+    int rc = make_wf_plan(cfg, p); if (rc) return rc;
+    CTTS_CHECK_ARG(k >= 0 && k < p.c.n_flows, "waveflow pack_forward_mix: flow %d", k);
+    if (p.c.mixing != CTTS_MIX_CONV1X1) return CTTS_OK;                        // PermuteHeight is its own inverse: nothing to hold
+    CTTS_CHECK_ARG(W_k && fwd_blob, "waveflow pack_forward_mix: NULL argument");
+    CTTS_CHECK_HIP(hipMemcpyAsync(static_cast<float*>(fwd_blob) + wf_fwd_mix_offset(p, k), W_k,
+                                  (size_t)p.n_rem[k] * p.n_rem[k] * sizeof(float), hipMemcpyDeviceToDevice, as_stream(stream)));
+    return CTTS_OK;
+}
+
+size_t ctts_waveflow_forward_workspace_bytes(const ctts_waveflow_config* cfg, int32_t batch, int32_t samples) {
+    WfPlan p; WfGeom g; WfWs w;
+    if (make_wf_plan(cfg, p) || make_wf_geom(p, samples, g) || batch < 1) return 0;
+    wf_carve(p, g, batch, nullptr, w, true);
+    return w.total * sizeof(float);
+}
+
+int ctts_waveflow_forward_f32(const ctts_waveflow_config* cfg, const void* packed, const void* fwd_blob, const float* audio,
+                              const float* mel, float preemphasis, int32_t ignore_nan, float* z, float* log_s, float* log_s_sum,
+                              double* sums, int32_t batch, int32_t samples, int32_t frames, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    CTTS_CHECK_ARG(cfg && !cfg->cond_precomputed, "waveflow forward: this model takes per-flow conditioning "
+                                                  "(ctts_waveflow_forward_cond_f32)");
+    const WfForward fw{static_cast<const float*>(fwd_blob), preemphasis, ignore_nan, log_s, log_s_sum, sums};
+    return wf_inverse(cfg, packed, audio, mel, 0, 0, z, batch, samples, frames, workspace, workspace_bytes, stream, &fw);
+}
+
+int ctts_waveflow_forward_cond_f32(const ctts_waveflow_config* cfg, const void* packed, const void* fwd_blob, const float* audio,
+                                   const float* cond, int32_t cond_ld, int32_t cond_pad, float preemphasis, int32_t ignore_nan,
+                                   float* z, float* log_s, float* log_s_sum, double* sums, int32_t batch, int32_t samples,
+                                   int32_t frames, void* workspace, size_t workspace_bytes, void* stream) {
+    CTTS_CHECK_ARG(cfg && cfg->cond_precomputed, "waveflow forward_cond: the model folds its cond layer "
+                                                 "(ctts_waveflow_forward_f32)");
+    CTTS_CHECK_ARG(cond_pad >= 0 && cond_ld >= cond_pad + frames, "waveflow forward_cond: cond_ld=%d pad=%d frames=%d",
+                   cond_ld, cond_pad, frames);
+    const WfForward fw{static_cast<const float*>(fwd_blob), preemphasis, ignore_nan, log_s, log_s_sum, sums};
+    return wf_inverse(cfg, packed, audio, cond, cond_ld, cond_pad, z, batch, samples, frames, workspace, workspace_bytes, stream,
+                      &fw);
 }
 
 int ctts_waveflow_abort_status(const ctts_waveflow_config* cfg, int32_t batch, int32_t samples, void* workspace,

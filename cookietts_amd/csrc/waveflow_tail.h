@@ -25,6 +25,8 @@ struct WfTailDesc {
 #if defined(__HIPCC__)
 __device__ __forceinline__ float wf_end_fma(float w, float v, float e) { return __builtin_fmaf(w, v, e); }
 __device__ __forceinline__ float wf_row_update(float a, float e0, float e1, float b0, float b1) { return (a - (e1 + b1)) / expf(e0 + b0); }
+// analysis direction (efficient_modules.py:38): out = a * exp(log_s) + t, with log_s = e0 + b0 already formed (it is stored too)
+__device__ __forceinline__ float wf_row_forward(float a, float log_s, float e1, float b1) { return __builtin_fmaf(a, expf(log_s), e1 + b1); }
 __device__ __forceinline__ float wf_start_value(float w, float a, float bias) { return __builtin_fmaf(w, a, bias); }
 #endif
 

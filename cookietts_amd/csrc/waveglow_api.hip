@@ -1336,7 +1336,8 @@ int ctts_tuning_flags(void) {
            (t.taco_valu ? (1 << 24) : 0) | (t.up_no_mfma ? (1 << 25) : 0) | (t.f32_no_wn_fold ? (1 << 26) : 0) |
            (t.taco_bg_no_pipe ? (1 << 27) : 0) | (t.f32_no_winograd ? (1 << 28) : 0) | (t.f32_winograd_min >= 0 ? (1 << 29) : 0) |
            (t.f32_winograd_plain ? (1 << 30) : 0) | (t.f32_winograd_fused_min >= 0 ? 4 : 0) | (t.f32_winograd_no_fused ? 32 : 0) |
-           (t.f32_winograd_f43_min >= 0 ? (1 << 6) : 0) | (t.f32_winograd_no_f43 ? (1 << 22) : 0);
+           (t.f32_winograd_f43_min >= 0 ? (1 << 6) : 0) | (t.f32_winograd_no_f43 ? (1 << 22) : 0) |
+           (t.wf_fwd_rowwise ? (int)(1u << 31) : 0);
 }
 
 int ctts_profile_create(void** handle) {

@@ -438,6 +438,7 @@ class WaveGlow(_cache.PackedModule):
         self._sep1d = (not waveflow) and isinstance(self.WN[0].WN.in_layers[0], nn.ModuleList)
         self._f32_gemm_mode = None
         self._compute_dtype = torch.float32
+        self._fwd = None             # (the inverse blob it belongs to, forward-mix blob or None, log|det W_k| per column, fp32 on the host)
 
     # ------------------------------------------------------------------ plumbing ----
     def c_config(self):
@@ -513,6 +514,7 @@ class WaveGlow(_cache.PackedModule):
 
     def _invalidate(self):
         super()._invalidate()
+        self._fwd = None
         for m in (self.convinv if isinstance(self.convinv, nn.ModuleList) else []):
             if hasattr(m, 'W_inverse'):
                 del m.W_inverse
@@ -830,7 +832,10 @@ class WaveGlow(_cache.PackedModule):
             return
         lib = _lib.lib()
         cfg = self.c_config()
-        for (device, B, T, _), ws in old.items():
+        for key, ws in old.items():
+            if len(key) != 4:              # a forward workspace: the analysis pass never runs the row queue
+                continue
+            device, B, T, _ = key
             with torch.cuda.device(device):
                 stream = _lib.stream(device)
                 _lib.check(lib.ctts_waveflow_abort_status(C.byref(cfg), B, T, _lib.ptr(ws), ws.numel() * 4, stream),
@@ -878,5 +883,153 @@ class WaveGlow(_cache.PackedModule):
             audio = audio[:, :-artifact_trimming * self.hop_length]
         return audio.to(input_dtype)
 
-    def forward(self, *a, **kw):
-        raise NotImplementedError("training direction is outside the inference hot path")
+    # ------------------------------------------------------------- the analysis pass ----
+    def _forward_refusals(self, audio):
+        """Everything ``forward`` / ``nll`` refuse, by name and in this order, before anything is packed or launched."""
+        if self.training and torch.is_grad_enabled():
+            raise NotImplementedError("training direction is outside the inference hot path: no backward pass - "
+                                      "WaveGlow.forward on the HIP path is the analysis pass only (call model.eval() or run "
+                                      "it under torch.no_grad())")
+        if not self.waveflow:
+            raise NotImplementedError("waveflow=False: the 1-D ax core has no forward form on the HIP path (the analysis pass is "
+                                      "built for waveflow=True)")
+        if audio is None:
+            raise ValueError("WaveGlow.forward needs the audio [B, T] or [B, 1, T] (efficient_model_ax.py:184); audio is None")
+        if audio.dim() not in (2, 3) or (audio.dim() == 3 and audio.shape[1] != 1) or audio.shape[-1] == 0 \
+                or audio.shape[-1] % self.n_group != 0:
+            raise ValueError(f"audio of shape {tuple(audio.shape)}: forward needs [B, T] or [B, 1, T] with T a multiple of "
+                             f"n_group = {self.n_group} (efficient_model_ax.py:225)")
+        if self.vol_scaling:
+            raise NotImplementedError("preceived_vol_scaling: the reference rewrites the caller's audio in place there "
+                                      "(efficient_model_ax.py:198-200); not built")
+
+    def _ensure_forward_packed(self, device):
+        """-> (inverse blob, forward-mix blob or None, log|det W_k| [n_flows] per column as fp32 on the host).  Packed on the
+        first forward call and kept while the inverse blob it was packed beside is the live one; ``infer`` alone never builds it."""
+        blob, ops = self._ensure_packed(device)
+        if self._fwd is None or self._fwd[0] is not blob:
+            lib = _lib.lib()
+            cfg = self.c_config()
+            fwd, unit = None, []
+            if self.channel_mixing == '1x1conv':
+                nbytes = _lib.nbytes(lib.ctts_waveflow_forward_packed_bytes, C.byref(cfg), what="unsupported WaveFlow config")
+                with torch.cuda.device(device):
+                    stream = _lib.stream(device)
+                    fwd = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
+                    keep = []
+                    for k in range(self.n_flows):
+                        W = self.convinv[k].weight.detach().squeeze(-1).float()
+                        unit.append(W.cpu().slogdet()[1])                       # efficient_modules.py:265: log|det|, host fp32
+                        Wd = W.to(device).contiguous()
+                        keep.append(Wd)
+                        _lib.check(lib.ctts_waveflow_pack_forward_mix(C.byref(cfg), k, _lib.ptr(Wd), _lib.ptr(fwd), stream),
+                                   f"ctts_waveflow_pack_forward_mix({k})")
+                    torch.cuda.current_stream(device).synchronize()
+                unit = torch.stack(unit)
+            else:
+                unit = None                                                    # PermuteHeight: L * const (efficient_modules.py:384, 397)
+            self._fwd = (blob, fwd, unit)
+        return self._fwd + (ops,)
+
+    def _log_det_W(self, unit, L):
+        """log_det_W_k of every flow as the reference takes it, fp32 on the host: ``L * slogdet(W_k)[1]`` (efficient_modules.py:265)
+        or PermuteHeight's ``L * const`` with sigma = 1 (:384, :397; ax:165)."""
+        if unit is not None:
+            return (L * unit).float()
+        const = -(0.5 * np.log(2 * np.pi) + np.log(1.0)) / self.n_flows
+        return torch.tensor([L * const] * self.n_flows, dtype=torch.float32)
+
+    def _forward_core(self, cond, audio, speaker_ids, want_log_s):
+        """-> (z [B, T], log_s [B, S, L] or None, log_s_sum [B, L], sums float64 [B, n_flows], log_det_W [n_flows] fp32 host)."""
+        self._forward_refusals(audio)
+        if cond.dim() == 2:
+            cond = cond[None, ...]
+        device = cond.device
+        blob, fwd, unit, ops = self._ensure_forward_packed(device)
+        lib = _lib.lib()
+        cfg = self.c_config()
+        mel = cond.detach().float().contiguous()
+        wave = audio.detach().to(device=device, dtype=torch.float32).reshape(audio.shape[0], -1).contiguous()
+        B, T = wave.shape
+        assert mel.shape[0] == B and mel.shape[1] == self.n_mel_channels * (2 if self.has_logvar_channels else 1)
+        L = T // self.n_group
+        nbytes = _lib.nbytes(lib.ctts_waveflow_forward_workspace_bytes, C.byref(cfg), B, T, what="WaveFlow forward workspace query failed")
+        ws = self.workspace((device, B, T, "forward", nbytes), lambda: nbytes)
+        n_rem, S = self.n_group, 0
+        self._log_s_rows = []
+        for k in range(self.n_flows):
+            if k % self.n_early_every == 0 and k > 0:
+                n_rem -= self.n_early_size
+            self._log_s_rows.append(n_rem - 1)
+            S += n_rem - 1
+        z = torch.empty(B, T, dtype=torch.float32, device=device)
+        log_s = torch.empty(B, S, L, dtype=torch.float32, device=device) if want_log_s else None
+        log_s_sum = torch.empty(B, L, dtype=torch.float32, device=device)
+        sums = torch.empty(B, self.n_flows, dtype=torch.float64, device=device)
+        pre = float(self.preempthasis) if self.preempthasis else 0.0
+        with torch.cuda.device(device):
+            stream = _lib.stream(device)
+            if self._folded:
+                _lib.check(lib.ctts_waveflow_forward_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(fwd), _lib.ptr(wave), _lib.ptr(mel),
+                                                        pre, 1 if self.ignore_nan else 0, _lib.ptr(z), _lib.ptr(log_s),
+                                                        _lib.ptr(log_s_sum), _lib.ptr(sums), B, T, mel.shape[2], _lib.ptr(ws),
+                                                        ws.numel() * 4, stream), "ctts_waveflow_forward_f32")
+            else:
+                frames, ld, n_cond = self._cond_frames(ops, mel, speaker_ids, stream, out_steps=L)
+                _lib.check(lib.ctts_waveflow_forward_cond_f32(C.byref(cfg), _lib.ptr(blob), _lib.ptr(fwd), _lib.ptr(wave),
+                                                             _lib.ptr(frames), ld, PAD, pre, 1 if self.ignore_nan else 0,
+                                                             _lib.ptr(z), _lib.ptr(log_s), _lib.ptr(log_s_sum), _lib.ptr(sums), B, T,
+                                                             n_cond, _lib.ptr(ws), ws.numel() * 4, stream),
+                           "ctts_waveflow_forward_cond_f32")
+        return z, log_s, log_s_sum, sums, self._log_det_W(unit, L)
+
+    def forward(self, cond, audio=None, speaker_ids=None, return_log_s=False):
+        """``efficient_model_ax.WaveGlow.forward`` (ax:184-277) of a ``waveflow=True`` model without a gradient: cond
+        [B, n_mel(*2), frames], audio [B, T] or [B, 1, T] (T a multiple of n_group) -> the reference's tuple ``(z [B, T],
+        logdet [B], logdet_w_sum [], log_s_sum [B, L])`` as fp32 device tensors; the stream is not synchronised.  ``z`` has the
+        early outputs first, in peel order: the latent ``inverse`` / ``infer_from_noise`` take.  ``log_det_W_k`` is taken on the
+        host in fp32 as the reference takes it; ``logdet = sum_k (log_det_W_k + sum log_s_k)`` from the device's fp64 sums, rounded
+        once.  ``return_log_s=True`` appends the per-flow ``log_s`` [B, n_rem_k - 1, L] as views of one buffer.
+
+        Models whose layers are the fused C = 64 GTU dense form (BASELINE config 4) run one launch per WN layer over all rows; every
+        other model - and a fused one under ``set_f32_gemm_mode("bf16x3" | "bf16x6")`` or ``CTTS_WF_FWD_ROWWISE=1`` - runs row by
+        row through the launches of ``inverse``."""
+        z, log_s, log_s_sum, sums, ldw = self._forward_core(cond, audio, speaker_ids, want_log_s=return_log_s)
+        ldw_dev = ldw.to(device=z.device, dtype=torch.float64)
+        logdet = (ldw_dev[None, :] + sums).sum(dim=1).float()
+        out = (z, logdet, ldw.sum().to(z.device), log_s_sum)
+        if return_log_s:
+            views, off = [], 0
+            for n in self._log_s_rows:
+                views.append(log_s[:, off:off + n])
+                off += n
+            out = out + (views,)
+        return out
+
+    def nll(self, cond, audio, speaker_ids=None, sigma=1.0):
+        """``efficient_loss.WaveGlowLoss(sigma)`` (:33-44) of ``forward``'s output from the fp64 sums (``log_s`` is not
+        materialised): ``{"loss": 0-dim fp32 tensor, "per_item": [B] float64}`` with item b's own
+        ``(sum z^2 / 2 sigma^2 - sum_k (log_det_W_k + sum log_s_k)) / T``, whose mean is the loss."""
+        z, _, _, sums, ldw = self._forward_core(cond, audio, speaker_ids, want_log_s=False)
+        z2 = z.double().pow(2).sum(dim=1)
+        logdet = (ldw.to(device=z.device, dtype=torch.float64)[None, :] + sums).sum(dim=1)
+        per_item = (z2 / (2.0 * sigma * sigma) - logdet) / z.shape[1]
+        return {"loss": per_item.mean().float(), "per_item": per_item}
+
+
+class WaveFlowLoss(nn.Module):
+    """``efficient_loss.WaveGlowLoss`` (:24-44) on ``WaveGlow.forward``'s tuple ``(z, logdet, logdet_w_sum, log_s_sum)``:
+    ``mean_b((sum z_b^2 / 2 sigma^2 - logdet_b) / T)``."""
+
+    def __init__(self, sigma=1., elementwise_mean=True):
+        super().__init__()
+        self.sigma2 = sigma ** 2
+        self.sigma2_2 = self.sigma2 * 2
+        self.mean = elementwise_mean
+
+    def forward(self, model_outputs):
+        z, logdet = model_outputs[0].float(), model_outputs[1].float()
+        loss = z.pow(2).sum(1) / self.sigma2_2
+        loss = loss - logdet
+        loss = loss / z.size(1)
+        return loss.mean()

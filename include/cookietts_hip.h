@@ -396,6 +396,49 @@ int ctts_waveflow_inverse_cond_f32(const ctts_waveflow_config* cfg, const void* 
                                    int32_t batch, int32_t samples, int32_t frames, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* ---- WaveFlow analysis pass: WaveGlow.forward(cond, audio) of the ax core (efficient_model_ax.py:184-277), waveflow=True ----
+ * audio [B][T] (T multiple of n_group) -> z [B][T] (the early outputs first, in peel order, then the rest, un-squeezed as ax:277:
+ * exactly the latent ctts_waveflow_inverse_* consumes), log_s [B][S][L] with S = sum_k (n_rem_k - 1) and L = T / n_group (flow k's
+ * rows at offset sum_{j<k} (n_rem_j - 1); NULL = not wanted), log_s_sum [B][L] fp32 (ax:269-273) and sums [B][n_flows] fp64
+ * (per item and flow, the sum of log_s over rows and columns).  No gradient: the analysis pass only.
+ * Per flow k: early split (k % n_early_every == 0, k > 0: the first n_early_size active rows leave to the output), the mix before
+ * (mix_first) or after the coupling - PermuteHeight composes into the row map (it is its own inverse, 0 bytes of forward blob),
+ * the 1x1 conv is one pass over the rows with W_k = convinv.k.weight from the forward blob - and the coupling
+ * (efficient_modules.py:28-40): row 0 passes, (log_s_r, t_r) = end(WN_2d(rows 0 .. Ga-2)), out[r+1] = fma(a[r+1], exp(log_s_r), t_r);
+ * then NaN -> 0 when `ignore_nan`.  `preemphasis` != 0 applies PreEmphasis (efficient_loss.py:16-20) to the audio first:
+ * y[0] = x[0] - p x[1] (the reference's reflection at t = 0, reproduced), y[t] = x[t] - p x[t-1].
+ * Summation order: the end conv of a column is four fma chains over C / 4 ascending channels added as ((p0 + p1) + p2) + p3 (as in
+ * the inverse); log_s_sum adds a flow's rows in row order and the flows in flow order, in fp32; the fp64 sums are two stages without
+ * atomics - a thread adds its column's rows in row order, a block its 256 columns as a fixed tree, one thread the blocks in order - so
+ * two calls give the same bits and an item's values do not depend on its batch.
+ * Two forms, selected by the model (never by the batch):
+ *   row-wise: rows 0 .. Ga-2 in natural order through the launches of the inverse's per-layer form (ring of history slots, every
+ *     config ctts_waveflow_inverse_* accepts, the bf16x3 / bf16x6 modes included); the row's input is the known audio row and the
+ *     tail multiplies and stores log_s.  The row queue is not used in this direction.
+ *   all-rows (C = 64, GTU, dense in-layers, fp32 MFMA mode: config 4): per flow one mix launch, one start launch over all rows, ONE
+ *     launch per WN layer over all (row, item, 128-column tile) blocks - each reads its row's descriptor from a device array, the
+ *     same segments and a_ch_off the per-layer launch of that row would get - and one tail launch over all rows: n_layers + 3
+ *     launches per flow where the row-wise form takes (Ga - 1) (n_layers + 2).  Nothing in it waits on another workgroup.
+ *     CTTS_WF_FWD_ROWWISE=1 forces the row-wise form (A/B arm; same tile arithmetic within one tile shape; the row-wise form
+ *     may pick the split-K shape at small sizes, which sums K in another order).  ctts_last_gemm_loop() bit 8 = all-rows layer.
+ * Workspace (ctts_waveflow_forward_workspace_bytes; zero-filled once before first use, one geometry per workspace): the inverse's
+ * buffers, then log_s of one flow [B][n_group][Lr], the fp64 partials, and for all-rows models three full-height tensors
+ * [n_group - 1][B][C][ld] (two layer inputs - one with merge_res_skip - and the skip sum; config 4 at B = 8 and 900 frames:
+ * 3 x 0.44 GB) + the descriptors, which reach it through the calling thread's pinned staging buffer with one copy per call
+ * (so, like the row queue, an all-rows call must not be recorded into a HIP graph). */
+size_t ctts_waveflow_forward_packed_bytes(const ctts_waveflow_config* cfg);   /* 0 with PermuteHeight mixing (and on a bad config) */
+int ctts_waveflow_pack_forward_mix(const ctts_waveflow_config* cfg, int32_t flow, const float* W_k, void* fwd_blob, void* stream);
+size_t ctts_waveflow_forward_workspace_bytes(const ctts_waveflow_config* cfg, int32_t batch, int32_t samples);
+int ctts_waveflow_forward_f32(const ctts_waveflow_config* cfg, const void* packed, const void* fwd_blob, const float* audio,
+                              const float* mel, float preemphasis, int32_t ignore_nan, float* z, float* log_s, float* log_s_sum,
+                              double* sums, int32_t batch, int32_t samples, int32_t frames, void* workspace,
+                              size_t workspace_bytes, void* stream);
+/* cond_precomputed models: cond as for ctts_waveflow_inverse_cond_f32 */
+int ctts_waveflow_forward_cond_f32(const ctts_waveflow_config* cfg, const void* packed, const void* fwd_blob, const float* audio,
+                                   const float* cond, int32_t cond_ld, int32_t cond_pad, float preemphasis, int32_t ignore_nan,
+                                   float* z, float* log_s, float* log_s_sum, double* sums, int32_t batch, int32_t samples,
+                                   int32_t frames, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Small operators the conditioning stacks and the output stage are composed from (padded row layout as for
  * ctts_conv1d_f32: x [B][C][ld], valid columns [pad, pad+T)):
  *   embed_rows:     x[b][row0 + e][pad .. pad+T) = table[ids[b]][e]          (speaker embedding concat, ax:286-291)
@@ -1107,7 +1150,8 @@ int ctts_pcm16_concat(const void* audio, int32_t is_half, const int32_t* frames,
  * the split-K shape sums in a different order than the other shapes, so the same utterance is bit-identical across
  * batch sizes only within one shape (CTTS_F32_NO_SPLITK: one K order at every size).  ctts_last_gemm_loop() reports what the most recent conv-GEMM launch of the calling
  * thread ran, so that a benchmark row can label itself: bits 0-3 = split level (0 fp32 MFMA, 3, 6), bit 4 = small shape,
- * bit 5 = split-K shape, bit 6 = the WaveFlow row queue, bit 7 = its whole-flow form (one launch per flow, see ctts_waveflow_inverse_f32).
+ * bit 5 = split-K shape, bit 6 = the WaveFlow row queue, bit 7 = its whole-flow form (one launch per flow, see ctts_waveflow_inverse_f32),
+ * bit 8 = the all-rows layer of the WaveFlow analysis pass (ctts_waveflow_forward_*).
  *
  * REMOVED: the process-wide default of ABI <= 5 (ctts_set_f32_gemm_mode / ctts_get_f32_gemm_mode; no-ops in ABI 6, gone in 7):
  * hidden state shared by every model and thread of a process.  CTTS_GEMM_DEFAULT (0) in a config struct always means fp32
@@ -1149,7 +1193,8 @@ int ctts_tuning_reload(void);
  * before the first poll of the persistent decoder's six vector exchanges; timing only), 24 CTTS_TACO_VALU
  * (ctts_taco_decoder_steps_f32 at batch <= 4 on the VALU kernels instead of the batched MFMA form), 25 CTTS_UP_NO_MFMA (the VALU upsampling kernel
  * also for the shape the MFMA one is built for: bit-identical), 26 CTTS_F32_NO_WN_FOLD, 27 CTTS_TACO_BG_NO_PIPE (the batched
- * decoder's plain schedule, the default above 64 rows, at every size), 28 CTTS_F32_NO_WINOGRAD, 29 CTTS_F32_WINOGRAD_MIN set, 30 CTTS_F32_WINOGRAD_PLAIN.  Bits 2, 5, 6 and 22 belonged to retired knobs until the one-launch Winograd layer (2, 5) and its F(4,3) form (6, 22) took them.
+ * decoder's plain schedule, the default above 64 rows, at every size), 28 CTTS_F32_NO_WINOGRAD, 29 CTTS_F32_WINOGRAD_MIN set, 30 CTTS_F32_WINOGRAD_PLAIN,
+ * 31 CTTS_WF_FWD_ROWWISE (the sign bit of the int: the WaveFlow analysis pass row by row, see ctts_waveflow_forward_f32).  Bits 2, 5, 6 and 22 belonged to retired knobs until the one-launch Winograd layer (2, 5) and its F(4,3) form (6, 22) took them.
  * (Tests assert that a knob they set is the one in effect.) */
 int ctts_tuning_flags(void);
 
