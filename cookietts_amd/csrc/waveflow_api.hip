@@ -42,17 +42,22 @@ struct WfPlan {
     size_t total;
     int ring;                        // ring slots per layer: (kh - 1) * max height dilation + 1 rows of history
     int dh(int i) const { return c.dilation_h_l[i] > 0 ? c.dilation_h_l[i] : c.dilation_h; }
+    int dw(int i) const { return c.dilation_w[i] > 0 ? c.dilation_w[i] : 1 << i; }
+    // merge_res_skip (glow_ax.py:612-626): no residual into `audio`, so every layer's queue holds the `start` outputs - layer i
+    // reads the ring of layer 0 (src), nothing is written to ring i + 1, and all rows of the res/skip GEMM are skip rows (last)
+    int src(int i) const { return c.merge_res_skip ? 0 : i; }
+    bool last(int i) const { return i == c.n_layers - 1 || c.merge_res_skip; }
+    // height tap ah of WN row r reads row r - (kh - 1 - ah) * dh: rows above the first do not exist, taps below a_min are skipped
+    int a_min(int r, int i) const { return std::max(0, c.kernel_size_h - 1 - r / dh(i)); }
     int rs_rows(int i) const { return (i < c.n_layers - 1 && !c.merge_res_skip) ? 2 * C : C; }
     int rs_mb(int i) const { return (rs_rows(i) + WF_BM - 1) / WF_BM; }
     int in_mb() const { return (C + 63) / 64; }
     // one 128-row block holds every gate pair: the res/skip GEMM runs inside the in-layer kernel (GEMM_EPI_GATE_RS)
     bool fused() const { return C == 64 && c.gated_unit == 0; }
-    // both 1x1 stages of a separable layer in one launch (waveflow_sep.hip): pointwise/gate + res/skip, C = 128
     // the analysis direction's all-rows form (one launch per layer over every row): the fused dense layer on the fp32 MFMA tile
     bool all_rows() const { return fused() && !sep && !gemm_mode_is_split(c.f32_gemm_mode); }
-    bool sep_fused() const {
-        return sep && precond && wf_sep_supported(C);
-    }
+    // both 1x1 stages of a separable layer in one launch (waveflow_sep.hip): pointwise/gate + res/skip, C = 128
+    bool sep_fused() const { return sep && precond && wf_sep_supported(C); }
 };
 
 int make_wf_plan(const ctts_waveflow_config* cfg, WfPlan& p) {
@@ -145,8 +150,7 @@ int make_wf_geom(const WfPlan& p, int samples, WfGeom& g) {
     g.L = samples / p.c.n_group;
     g.Lr = round_up(g.L, 4);
     int maxshift = 0;
-    for (int i = 0; i < p.c.n_layers; ++i)
-        maxshift = std::max(maxshift, (p.c.kernel_size_w / 2) * (p.c.dilation_w[i] > 0 ? p.c.dilation_w[i] : 1 << i));
+    for (int i = 0; i < p.c.n_layers; ++i) maxshift = std::max(maxshift, (p.c.kernel_size_w / 2) * p.dw(i));
     g.pad = round_up(maxshift > 128 ? maxshift : 128, 32);
     const int bn = gemm_bn(WF_BM);
     g.ntiles = (g.L + bn - 1) / bn;
@@ -756,30 +760,25 @@ using namespace ctts;
 
 namespace {
 
-// Shared body of the two entry points.  cond = mel [B][n_mel][frames] (dense) when the single linear cond layer is
-// folded into the GEMM, or the per-flow frame-rate conditioning [n_flows][B][2C*n_layers][cond_ld] (padded rows).
-// ---- region split of a fused-layer launch (see the runner) ----------------------------------------------------------
+// ---- region split of a fused-layer launch (WfRegionSplit, decided in WfCall::open) ------------------------------------------------
 constexpr int WF_TILE = 256;          // columns per region unit: every launch shape's tile width divides it
-#ifndef WF_SPLIT_MIN_BLOCKS
-#define WF_SPLIT_MIN_BLOCKS 256
-#endif
-#ifndef WF_NBIG
-#define WF_NBIG 2                     // big regions per layer (2: A | M | B on three streams)
-#endif
+// only where the launch is the 128 x 256 shape: below 256 blocks - batch <= 4 at 900 frames - a layer lasts ~35-100 us and three
+// launches + six event operations per layer make the call host-bound: measured 38.7 -> 78 ms at batch 1
+constexpr int WF_SPLIT_MIN_BLOCKS = 256;
+constexpr int WF_NBIG = 2;            // big regions per layer (2: A | M | B on three streams)
 constexpr int WF_NREG = 2 * WF_NBIG - 1;     // regions incl. the one-tile separators: big 0, sep 0, big 1, sep 1, ...
 // The row queue is taken from this many 128-column items per layer on: where the per-layer launches stop being the eight-wave
 // split-K tile (gemm_f32_small.hip gate_rs_splitk8_tile, up to GATE_RS_SPLITK_MAX_BLOCKS = 256 items).  Config 4, round 5: batch 1
 // (113 items) 30.9 ms per layer against 40.6 queued; batch 2 (226 items) 52.0 against 55.7 (until the eight-wave tile the queue was
 // 2 % ahead there: 56.9 against 58.3 ms, and the bound was 200); batch 3 (339 items) 74.4 queued against 92.9.
-#ifndef WF_ROW_QUEUE_MIN_ITEMS
-#define WF_ROW_QUEUE_MIN_ITEMS 257
-#endif
-#ifndef WF_ROW_QUEUE_MAX_ITEMS
-#define WF_ROW_QUEUE_MAX_ITEMS 1250
-#endif
-#ifndef WF_ROW_QUEUE_SPLITK_BELOW
-#define WF_ROW_QUEUE_SPLITK_BELOW 400
-#endif
+constexpr int WF_ROW_QUEUE_MIN_ITEMS = 257;
+// Upper bound: from ~1250 items per layer on - batch 10 at 900 frames: 204.0 ms queued against 207.6, batch 12: 245.1 against 243.4,
+// batch 16: 327 against 319 - the per-layer launches on the 128 x 256 shape with the region split are ahead again: more work per
+// workgroup, and a layer's tail is small against it
+constexpr int WF_ROW_QUEUE_MAX_ITEMS = 1250;
+// Which tile body (measured, profiles/r4_12): below 400 items of 128 columns per layer the split-K body (items of 128 x 64, half the
+// serial chain each: 97 -> 77 ms at batch 3 x 900 frames, 95 -> 66 at 8 x 300); the 128 x 128 body from there on
+constexpr int WF_ROW_QUEUE_SPLITK_BELOW = 400;
 // audio[b][:] = NaN when the row queue's abort word is set, and the workspace's sticky status word says so until a later
 // call reports it (CTTS_E_ABORT): the NaN is the in-stream marker, the status the one a caller can act on
 constexpr unsigned int WF_ABORT_MAGIC = 0xAB0F7001u;       // a value, not a flag: the workspace may start out as anything
@@ -837,6 +836,11 @@ struct WfRegionStreams {              // per host thread: one helper stream per 
 };
 thread_local WfRegionStreams t_wf_streams;
 
+// Region split of the fused layer (round 4): every layer launch used to wait for the slowest of the previous layer's 456
+// workgroups although tile t of layer i + 1 needs only tiles t - 1, t, t + 1 of layer i (dilation <= 128 < one 256-column
+// tile).  The columns are cut into three regions A | M (one tile) | B launched on three streams: A(i+1) and B(i+1) wait
+// for M(i) only, M(i+1) waits for A(i) and B(i), so the two halves drift by up to a layer and each half's tail overlaps
+// the other's next layer.  Same kernel, same tiles: bit-identical to the single launch (CTTS_WF_NO_REGION_SPLIT).
 struct WfRegionSplit {
     bool on = false;
     int ntiles = 0, L = 0;
@@ -961,8 +965,19 @@ int wf_note_pending(const void* workspace, unsigned int* status, hipStream_t s) 
     return rc;
 }
 
-// The analysis direction of the same body (ctts_waveflow_forward_*): `z` is then the audio that goes IN, `audio` the latent that
-// comes OUT, and this says where the rest goes.  NULL = the inverse.
+int wf_launched(const char* what) { CTTS_CHECK_LAUNCH(what); return CTTS_OK; }      // behind a kernel launch: its error, if any
+
+// What an entry point hands to a direction driver: `in` -> `out` is z -> audio (inverse) or audio -> z (analysis).  cond = mel
+// [B][n_mel][frames] (dense) when the single linear cond layer is folded into the GEMM, or the per-flow frame-rate conditioning
+// [n_flows][B][2C*n_layers][cond_ld] (padded rows).
+struct WfIo {
+    const ctts_waveflow_config* cfg; const void* packed;
+    const float *in, *cond; int cond_ld, cond_pad;
+    float* out; int batch, samples, frames;
+    void* workspace; size_t workspace_bytes; void* stream;
+};
+
+// The analysis direction (ctts_waveflow_forward_*): where everything but the latent goes.  WfCall::open(io, NULL) = the inverse.
 struct WfForward {
     const float* mix;            // forward blob: W_k of the 1x1-conv mixing (NULL with PermuteHeight)
     float preemphasis;           // PreEmphasis coefficient applied to the audio first; 0 = none
@@ -972,467 +987,454 @@ struct WfForward {
     double* sums;                // [B][n_flows]
 };
 
-int wf_inverse(const ctts_waveflow_config* cfg, const void* packed, const float* z, const float* cond, int cond_ld,
-               int cond_pad, float* audio, int batch, int samples, int frames, void* workspace, size_t workspace_bytes,
-               void* stream, const WfForward* fw = nullptr) {
-    WfPlan p; WfGeom g; WfWs w;
-    int rc = make_wf_plan(cfg, p); if (rc) return rc;
-    rc = make_wf_geom(p, samples, g); if (rc) return rc;
-    const char* const what = fw ? "forward" : "inverse";
-    CTTS_CHECK_ARG(packed && z && cond && audio && workspace && batch >= 1 && frames >= 1, "waveflow %s: bad argument", what);
-    CTTS_CHECK_ARG(!fw || (fw->log_s_sum && fw->sums && (fw->mix || p.c.mixing != CTTS_MIX_CONV1X1) && batch <= 65535 / p.c.n_group),
-                   "waveflow forward: bad argument (log_s_sum, sums, the forward blob of a 1x1-conv model; batch * n_group <= 65535)");
-    wf_carve(p, g, batch, static_cast<float*>(workspace), w, fw != nullptr);
-    if (w.total * sizeof(float) > workspace_bytes) {
-        set_error("waveflow %s: workspace %zu bytes < required %zu", what, workspace_bytes, w.total * sizeof(float));
-        return CTTS_E_WORKSPACE;
+// Logical row g of the current flow lives in physical row phys[g] of w.rows; n rows are active.  With early outputs only the LAST
+// n_rem rows of the squeezed latent are active in the last flows (the last split, ax:311-313).
+struct WfRowMap {
+    int phys[64], n = 0;
+    void reset(int G, int active) {                          // the last `active` of G rows, in place
+        n = active;
+        for (int i = 0; i < n; ++i) phys[i] = G - n + i;
     }
-    hipStream_t s = as_stream(stream);
-    // the previous call of this thread on this workspace used the row queue: if it aborted, say so now instead of computing
-    // on top of it (one stream synchronisation + 4 bytes; the caller sees CTTS_E_ABORT once, the call after that runs)
-    if (!fw && (rc = wf_check_pending(workspace, w.q.status, s))) return rc;
-    const float* blob = static_cast<const float*>(packed);
-    const int G = p.c.n_group, C = p.C, L = g.L, kh = p.c.kernel_size_h, kw = p.c.kernel_size_w;
-    const int gkh = p.sep ? 1 : kh, gkw = p.sep ? 1 : kw;
-    const long long cstride = (long long)C * g.ld;
-    const dim3 lgrid((g.Lr + 255) / 256, batch);
-
-    if (fw) hipLaunchKernelGGL(wf_fwd_squeeze_kernel, lgrid, dim3(256), 0, s, z, w.rows, G, L, g.Lr, fw->preemphasis);
-    else hipLaunchKernelGGL(wf_squeeze_kernel, lgrid, dim3(256), 0, s, z, w.rows, G, L, g.Lr);
-    CTTS_CHECK_LAUNCH("wf_squeeze");
-    if (!p.precond) {
-        hipLaunchKernelGGL(wf_interp_kernel, dim3((L + 255) / 256, p.c.n_mel_channels, batch), dim3(256), 0, s, cond,
-                           w.mel_up, p.c.n_mel_channels, p.kmel, frames, L, g.ld, g.pad);
-        CTTS_CHECK_LAUNCH("wf_interp");
+    void permute(int k) {                                    // PermuteHeight of flow k (its own inverse) composes into the map
+        int perm[64], tmp[64];
+        wf_permutation(k, n, perm);
+        for (int i = 0; i < n; ++i) tmp[i] = phys[perm[i]];
+        for (int i = 0; i < n; ++i) phys[i] = tmp[i];
     }
-
-    // Logical row g of the current flow lives in physical row phys[g] of w.rows.  With early outputs only the LAST
-    // n_rem rows of the squeezed latent are active at first (the last split, ax:311-313); the earlier chunks re-join in
-    // front, one per n_early_every flows (ax:340-341).
-    int phys[64], perm[64], tmp[64];
-    int Ga = p.n_rem[p.c.n_flows - 1];
-    for (int i = 0; i < Ga; ++i) phys[i] = G - Ga + i;
-    const int NS = p.ring;
-    auto X = [&](int layer, int slot) { return w.X + ((size_t)layer * NS + slot) * w.xslot; };
-    const bool no_fuse = tuning().wf_no_fuse;
-    const bool fuse = p.fused() && !no_fuse;
-    // Analysis direction, all-rows form: every row's WN input is known, so layer i of ALL rows is one launch (gemm_f32_small.hip
-    // wf_all_rows_layer_kernel) on full-height storage - layer i reads XA / XB by parity and writes the other (never in place: other
-    // rows' height taps read the same input), the skip sum of row r is OUT[r].  The model selects it, CTTS_WF_FWD_ROWWISE (or a knob
-    // that takes the DMA-staged small tile away) falls back to the row-wise form.
-    const bool all_rows = fw && p.all_rows() && fuse && !tuning().wf_fwd_rowwise && !tuning().f32_no_glds && !tuning().f32_no_small;
-    // layer `layer`'s input of WN row `row`: the ring slot, or full-height storage
-    auto XR = [&](int layer, int row) {
-        return all_rows ? ((layer & 1) ? w.f.XB : w.f.XA) + (size_t)row * w.xslot : X(layer, row % NS);
-    };
-    auto OUT = [&](int row) { return all_rows ? w.f.OUT + (size_t)row * w.xslot : w.out; };
-    // Region split of the fused layer (round 4): every layer launch used to wait for the slowest of the previous layer's 456
-    // workgroups although tile t of layer i + 1 needs only tiles t - 1, t, t + 1 of layer i (dilation <= 128 < one 256-column
-    // tile).  The columns are cut into three regions A | M (one tile) | B launched on three streams: A(i+1) and B(i+1) wait
-    // for M(i) only, M(i+1) waits for A(i) and B(i), so the two halves drift by up to a layer and each half's tail overlaps
-    // the other's next layer.  Same kernel, same tiles: bit-identical to the single launch (CTTS_WF_NO_REGION_SPLIT).
-    WfRegionSplit rsplit;
-    // (only where the launch is the 128 x 256 shape: below 256 blocks - batch <= 4 at 900 frames - a layer lasts ~35-100 us and
-    // three launches + six event operations per layer make the call host-bound: measured 38.7 -> 78 ms at batch 1)
-    rsplit.on = fuse && !tuning().wf_no_region_split && g.ntiles >= 8 && (long long)g.ntiles * batch >= WF_SPLIT_MIN_BLOCKS && !tuning().f32_force_small;
-    rsplit.ntiles = g.ntiles; rsplit.L = L;
-    // Row queue (round 4, gemm_f32_small.hip wf_row_persistent_kernel): the fused layers of a row as ONE launch whose workgroups take
-    // (layer, tile) items in order and wait for the three neighbouring tiles of the previous layer only.  Same tile body as the
-    // per-layer 128 x 128 shape: bit-identical to it (and to the 128 x 256 shape).  Descriptors: the GemmArgs of a whole flow are
-    // built on the host, copied once per flow, and a row's launch points at its slice.
-    const int q_items = wf_row_tiles(L, 0) * batch;
-    const int q_min = tuning().wf_row_queue_min >= 0 ? tuning().wf_row_queue_min : WF_ROW_QUEUE_MIN_ITEMS;
-    // (upper bound: from ~1250 items per layer on - batch 10 at 900 frames: 204.0 ms queued against 207.6, batch 12: 245.1 against
-    // 243.4, batch 16: 327 against 319 - the per-layer launches on the 128 x 256 shape with the region split are ahead again: more
-    // work per workgroup, and a layer's tail is small against it)
-    // (the queue's tile bodies are the fp32-MFMA DMA-staged ones: under the split-bf16 modes, CTTS_F32_NO_GLDS or CTTS_F32_NO_SMALL
-    // the layers are launched one by one as before)
-    bool queue_on = !fw && fuse && !p.sep && !tuning().wf_no_row_queue && q_items >= q_min &&
-                    (q_items < WF_ROW_QUEUE_MAX_ITEMS || tuning().wf_row_queue_min >= 0) &&
-                    !gemm_mode_is_split(p.c.f32_gemm_mode) && !tuning().f32_no_glds && !tuning().f32_no_small;
-    // Which tile body (measured, profiles/r4_12): below 400 items of 128 columns per layer the split-K body (items of 128 x 64, half
-    // the serial chain each: 97 -> 77 ms at batch 3 x 900 frames, 95 -> 66 at 8 x 300); the 128 x 128 body from there on
-    int q_body = 0;
-    if (!tuning().f32_no_splitk) q_body = q_items < WF_ROW_QUEUE_SPLITK_BELOW ? 1 : 0;
-    if (tuning().wf_queue_debug & 16) q_body = 0;
-    if (tuning().wf_queue_debug & 32) q_body = 1;
-    for (int i = 0; i < p.c.n_layers && queue_on; ++i)      // a fresh segment may reach one 128-column tile to either side
-        queue_on = (kw / 2) * (p.c.dilation_w[i] > 0 ? p.c.dilation_w[i] : 1 << i) <= 128;
-    size_t q_host_off = 0;                                 // bytes of the pinned host buffer the flows queued so far occupy
-    // whole-flow form: every row of a flow in ONE launch (tail stages between the rows); CTTS_WF_QUEUE_DEBUG=128: one launch per row
-    const bool q_flow = queue_on && !(tuning().wf_queue_debug & 128);
-    unsigned int q_launch = 0;
-    if (queue_on) {
-        if ((rc = t_wf_desc.begin((size_t)p.c.n_flows * G * (p.c.n_layers * sizeof(GemmArgs) + sizeof(WfTailDesc))))) return rc;
-        CTTS_CHECK_HIP(hipMemsetAsync(w.q.abort_word, 0, w.q.control_bytes, s));
-        if (tuning().wf_inject_abort) CTTS_CHECK_HIP(hipMemsetAsync(w.q.abort_word, 1, sizeof(unsigned int), s));   // (tests)
+    void peel_front(int count, WfRowMap& out) {              // analysis: the first `count` active rows leave, appended to `out`
+        for (int i = 0; i < count; ++i) out.phys[out.n++] = phys[i];
+        for (int i = count; i < n; ++i) phys[i - count] = phys[i];
+        n -= count;
     }
-    const bool sep_fuse = p.sep_fused() && !no_fuse;
-    // un-mix of flow k on the active rows: PermuteHeight composes into the map, the 1x1 conv is a pass over the rows
-    auto unmix = [&](int k) -> int {
-        if (p.c.mixing == CTTS_MIX_PERMUTE) {
-            wf_permutation(k, Ga, perm);
-            for (int i = 0; i < Ga; ++i) tmp[i] = phys[perm[i]];
-            for (int i = 0; i < Ga; ++i) phys[i] = tmp[i];
-            return CTTS_OK;
-        }
+    void rejoin_front(int count, int G) {                    // inverse: the `count` physical rows just before the active block re-join in front
+        for (int i = n - 1; i >= 0; --i) phys[i + count] = phys[i];
+        for (int i = 0; i < count; ++i) phys[i] = G - n - count + i;
+        n += count;
+    }
+    RowMap device() const {
         RowMap m;
-        for (int i = 0; i < 64; ++i) m.phys[i] = i < Ga ? phys[i] : 0;
-        hipLaunchKernelGGL(wf_mix_kernel, lgrid, dim3(256), 0, s, w.rows, blob + p.fl[k].winv, m, Ga, G, g.Lr);
-        CTTS_CHECK_LAUNCH("wf_mix");
-        return CTTS_OK;
-    };
+        for (int i = 0; i < 64; ++i) m.phys[i] = i < n ? phys[i] : 0;
+        return m;
+    }
+};
 
-    // the fused dense layer (no depthwise stage) of flow f, row r, layer i - the ONE place its launch arguments are made, for the
-    // per-layer launches, the region split and the row queue alike
-    // mark_fresh: 0 no marks (per-layer launches), 1 what the previous layer of the SAME row wrote (row queue, one launch per
-    // row), 2 every X segment (whole-flow queue: earlier rows were written inside the same launch too)
-    auto fused_args = [&](const WfPlan::Flow& f, int r, int i, int mark_fresh) {
-        const int dw = p.c.dilation_w[i] > 0 ? p.c.dilation_w[i] : 1 << i;
-        const bool merge = p.c.merge_res_skip != 0;
-        const int si = merge ? 0 : i;
-        const int dh = p.dh(i);
-        const int a_min = std::max(0, kh - 1 - r / dh);
+// One call of the runner, the shared body of the two directions: plan, geometry, carved workspace, the caller's tensors, the launch
+// forms decided once per call, the row map - and every descriptor and launch that both directions make.
+struct WfCall {
+    WfPlan p; WfGeom g; WfWs w;
+    const float *blob = nullptr, *cond = nullptr;
+    int cond_ld = 0, cond_pad = 0, batch = 0, frames = 0;
+    hipStream_t s = nullptr;
+    bool fuse = false, sep_fuse = false, all_rows = false;
+    WfRegionSplit rsplit;
+    WfRowMap rows;
+    long long cstride() const { return (long long)p.C * g.ld; }
+    dim3 lgrid() const { return dim3((g.Lr + 255) / 256, batch); }                  // a thread per column of w.rows
+    float* X(int layer, int slot) const { return w.X + ((size_t)layer * p.ring + slot) * w.xslot; }
+    // layer `layer`'s input of WN row `row`: the ring slot, or full-height storage
+    float* XR(int layer, int row) const {
+        return all_rows ? ((layer & 1) ? w.f.XB : w.f.XA) + (size_t)row * w.xslot : X(layer, row % p.ring);
+    }
+    float* OUT(int row) const { return all_rows ? w.f.OUT + (size_t)row * w.xslot : w.out; }      // the row's skip sum
+    // The prologue up to the first launch: plan, geometry, argument checks, carved workspace, launch forms.
+    int open(const WfIo& io, const WfForward* fw) {
+        int rc = make_wf_plan(io.cfg, p); if (rc) return rc;
+        rc = make_wf_geom(p, io.samples, g); if (rc) return rc;
+        const char* const what = fw ? "forward" : "inverse";
+        CTTS_CHECK_ARG(io.packed && io.in && io.cond && io.out && io.workspace && io.batch >= 1 && io.frames >= 1,
+                       "waveflow %s: bad argument", what);
+        CTTS_CHECK_ARG(!fw || (fw->log_s_sum && fw->sums && (fw->mix || p.c.mixing != CTTS_MIX_CONV1X1) && io.batch <= 65535 / p.c.n_group),
+                       "waveflow forward: bad argument (log_s_sum, sums, the forward blob of a 1x1-conv model; batch * n_group <= 65535)");
+        wf_carve(p, g, io.batch, static_cast<float*>(io.workspace), w, fw != nullptr);
+        if (w.total * sizeof(float) > io.workspace_bytes) {
+            set_error("waveflow %s: workspace %zu bytes < required %zu", what, io.workspace_bytes, w.total * sizeof(float));
+            return CTTS_E_WORKSPACE;
+        }
+        blob = static_cast<const float*>(io.packed); s = as_stream(io.stream);
+        cond = io.cond; cond_ld = io.cond_ld; cond_pad = io.cond_pad; batch = io.batch; frames = io.frames;
+        fuse = p.fused() && !tuning().wf_no_fuse;
+        sep_fuse = p.sep_fused() && !tuning().wf_no_fuse;
+        // Analysis direction, all-rows form: every row's WN input is known, so layer i of ALL rows is one launch (gemm_f32_small.hip
+        // wf_all_rows_layer_kernel) on full-height storage - layer i reads XA / XB by parity and writes the other (never in place: other
+        // rows' height taps read the same input), the skip sum of row r is OUT[r].  The model selects it, CTTS_WF_FWD_ROWWISE (or a knob
+        // that takes the DMA-staged small tile away) falls back to the row-wise form.
+        all_rows = fw && p.all_rows() && fuse && !tuning().wf_fwd_rowwise && !tuning().f32_no_glds && !tuning().f32_no_small;
+        rsplit.on = fuse && !tuning().wf_no_region_split && g.ntiles >= 8 && (long long)g.ntiles * batch >= WF_SPLIT_MIN_BLOCKS &&
+                    !tuning().f32_force_small;
+        rsplit.ntiles = g.ntiles; rsplit.L = g.L;
+        return CTTS_OK;
+    }
+    // The prologue's launches: w.rows <- the squeezed input (analysis: the pre-emphasised audio), and mel interpolated once to L steps
+    // (models whose cond layer is folded into the in-layer GEMM)
+    int squeeze(const float* in, const WfForward* fw) const {
+        if (fw) hipLaunchKernelGGL(wf_fwd_squeeze_kernel, lgrid(), dim3(256), 0, s, in, w.rows, p.c.n_group, g.L, g.Lr, fw->preemphasis);
+        else hipLaunchKernelGGL(wf_squeeze_kernel, lgrid(), dim3(256), 0, s, in, w.rows, p.c.n_group, g.L, g.Lr);
+        CTTS_CHECK_LAUNCH("wf_squeeze");
+        if (p.precond) return CTTS_OK;
+        hipLaunchKernelGGL(wf_interp_kernel, dim3((g.L + 255) / 256, p.c.n_mel_channels, batch), dim3(256), 0, s, cond, w.mel_up,
+                           p.c.n_mel_channels, p.kmel, frames, g.L, g.ld, g.pad);
+        return wf_launched("wf_interp");
+    }
+    // this flow's conditioning (cond_precomputed models), upsampled once for all rows and layers
+    int flow_cond(int k) const {
+        if (!p.precond) return CTTS_OK;
+        const int rows2c = 2 * p.C, nl = p.c.n_layers;
+        const bool vec = g.pad % 4 == 0 && g.ld % 4 == 0 && w.cond_slot % 4 == 0 && !tuning().wf_no_vec_interp;
+        const auto kernel = vec ? wf_interp_cond_vec_kernel : wf_interp_cond_kernel;                // a thread per 4 columns | per column
+        hipLaunchKernelGGL(kernel, dim3(((vec ? (g.L + 3) / 4 : g.L) + 255) / 256, rows2c * nl, batch), dim3(256), 0, s,
+                           cond + (size_t)k * batch * rows2c * nl * cond_ld, w.cond_up, rows2c, nl, frames, cond_ld, cond_pad, g.L, g.ld,
+                           g.pad, w.cond_slot);
+        return wf_launched("wf_interp_cond");
+    }
+    // mixing of flow k on the active rows, either direction: PermuteHeight composes into the map, the 1x1 conv is a pass over the
+    // rows with W (the inverse's packed W^-1, or W_k of the forward blob)
+    int mix(int k, const float* W) {
+        if (p.c.mixing == CTTS_MIX_PERMUTE) { rows.permute(k); return CTTS_OK; }
+        hipLaunchKernelGGL(wf_mix_kernel, lgrid(), dim3(256), 0, s, w.rows, W, rows.device(), rows.n, p.c.n_group, g.Lr);
+        return wf_launched("wf_mix");
+    }
+    // the start conv of physical row `row` into ring slot `slot` of layer 0
+    int start(const WfPlan::Flow& f, int row, int slot) const {
+        hipLaunchKernelGGL(wf_start_kernel, dim3(((g.L + 3) / 4 + 255) / 256, (p.C + 15) / 16, batch), dim3(256), 0, s, w.rows,
+                           blob + f.start_w, blob + f.start_b, X(0, slot), p.C, p.c.n_group, row, g.L, g.Lr, g.ld, g.pad);
+        return wf_launched("wf_start");
+    }
+    int nan_to_zero() const {
+        const size_t n4 = (size_t)batch * p.c.n_group * g.Lr / 4;
+        hipLaunchKernelGGL(wf_nan_to_zero_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, w.rows, n4);
+        return wf_launched("wf_nan_to_zero");
+    }
+    int unsqueeze(float* out, const WfRowMap& map) const {
+        hipLaunchKernelGGL(wf_unsqueeze_kernel, dim3((g.L + 255) / 256, batch), dim3(256), 0, s, w.rows, out, p.c.n_group, g.L, g.Lr,
+                           map.device());
+        return wf_launched("wf_unsqueeze");
+    }
+    // The in-layer GEMM of flow f, WN row r, layer i - the ONE place its descriptor is made, for every launch form: header, K
+    // segments (the dense height x width taps from a_min on, or the depthwise stage's output), conditioning (the upsampled addend, or
+    // the mel segment of the folded cond layer) and nseg.  The destinations are the caller's (res_skip, or the gated activations).
+    // mark_fresh: 0 no marks (per-layer launches, all-rows form), 1 what the previous layer of the SAME row wrote (row queue, one
+    // launch per row), 2 every X segment (whole-flow queue: earlier rows were written inside the same launch too)
+    GemmArgs in_gemm(const WfPlan::Flow& f, int r, int i, int mark_fresh) const {
+        const int kh = p.c.kernel_size_h, kw = p.c.kernel_size_w;
         GemmArgs a{};
         a.gate = p.c.gated_unit;
         a.gemm_mode = p.c.f32_gemm_mode;
         a.bm = WF_BM;
-        a.ld = g.ld; a.pad = g.pad; a.L = L; a.ntiles = g.ntiles; a.batch = batch;
+        a.ld = g.ld; a.pad = g.pad; a.L = g.L; a.ntiles = g.ntiles; a.batch = batch;
         a.dst_ld = g.ld; a.dst_pad = g.pad;
         a.A = blob + f.in_A[i]; a.bias = blob + f.in_b[i];
         a.a_nch_alloc = p.nch_in;
-        a.MB = p.in_mb(); a.M = 2 * C; a.pairC = C;
+        a.MB = p.in_mb(); a.M = 2 * p.C; a.pairC = p.C;
         int ns = 0;
-        a.a_ch_off = a_min * kw * p.nch_c;
-        for (int ah = a_min; ah < gkh; ++ah) {
-            const int src_row = r - (kh - 1 - ah) * dh;
-            // the current row's slot of layer i > 0 is what layer i - 1 of this very row wrote
-            const int fresh = mark_fresh == 2 || (mark_fresh == 1 && src_row == r && si > 0) ? 1 : 0;
-            for (int j = 0; j < gkw; ++j)
-                a.seg[ns++] = {XR(si, src_row), cstride, p.nch_c, (j - kw / 2) * dw, 0, fresh};
+        if (p.sep) {
+            a.seg[ns++] = {w.dwout, cstride(), p.nch_c, 0, 0, 0};
+            a.nch_total = p.nch_c;
+        } else {
+            const int si = p.src(i), dh = p.dh(i), dw = p.dw(i), a_min = p.a_min(r, i);
+            a.a_ch_off = a_min * kw * p.nch_c;
+            for (int ah = a_min; ah < kh; ++ah) {
+                const int src_row = r - (kh - 1 - ah) * dh;
+                // the current row's slot of layer i > 0 is what layer i - 1 of this very row wrote
+                const int fresh = mark_fresh == 2 || (mark_fresh == 1 && src_row == r && si > 0) ? 1 : 0;
+                for (int j = 0; j < kw; ++j) a.seg[ns++] = {XR(si, src_row), cstride(), p.nch_c, (j - kw / 2) * dw, 0, fresh};
+            }
+            a.nch_total = (kh - a_min) * kw * p.nch_c;
         }
-        a.nch_total = (kh - a_min) * kw * p.nch_c;
         if (p.precond) {
             a.addend = w.cond_up + (size_t)i * w.cond_slot;
-            a.addend_bstride = (long long)2 * C * g.ld;
+            a.addend_bstride = (long long)2 * p.C * g.ld;
         } else {
             a.seg[ns++] = {w.mel_up, (long long)p.kmel * g.ld, p.kmel / GEMM_KC, 0, 0, 0};
             a.nch_total += p.kmel / GEMM_KC;
         }
         a.nseg = ns;
-        const bool last = i == p.c.n_layers - 1 || merge;       // all rows of the res/skip GEMM are skip rows
-        // x_{i+1}[row r] = x_i[row r] + res -> layer i+1's ring slot;  skip rows (+)= into w.out
-        a.rs_wT = blob + f.rs_T[i]; a.rs_bias = blob + f.rs_Tb[i]; a.rs_rows = p.rs_rows(i);
-        a.dst0 = last ? OUT(r) : XR(i + 1, r); a.dst0_bstride = cstride; a.acc0 = 1;
-        a.src0 = XR(si, r); a.src0_bstride = cstride;
-        a.dst1 = OUT(r); a.dst1_bstride = cstride; a.acc1 = i > 0 ? 1 : 0;
-        a.split = last ? 0 : C;
         return a;
-    };
-
+    }
+    // Where the res/skip GEMM of row r, layer i goes: x_{i+1}[row r] = x_i[row r] + res -> layer i + 1's input of the row (its ring
+    // slot: its queue entry); skip rows (+)= into the row's skip sum.  fused: the GEMM is the in-layer launch's epilogue
+    // (GEMM_EPI_GATE_RS, transposed weights); else a launch of its own (GEMM_EPI_SPLIT).
+    void res_skip(GemmArgs& a, const WfPlan::Flow& f, int r, int i, bool fused) const {
+        if (fused) { a.rs_wT = blob + f.rs_T[i]; a.rs_bias = blob + f.rs_Tb[i]; a.rs_rows = p.rs_rows(i); }
+        a.dst0 = p.last(i) ? OUT(r) : XR(i + 1, r); a.dst0_bstride = cstride(); a.acc0 = 1;
+        a.src0 = XR(p.src(i), r); a.src0_bstride = cstride();
+        a.dst1 = OUT(r); a.dst1_bstride = cstride(); a.acc1 = i > 0 ? 1 : 0;
+        a.split = p.last(i) ? 0 : p.C;
+    }
+    // A fused layer whose tile body is launched without launch_gemm_f32 (row queue, all-rows form): built into the staging buffer,
+    // its defaults and checks applied here; max_nseg follows.
+    int stage(GemmArgs& a, const WfPlan::Flow& f, int r, int i, int mark_fresh, int& max_nseg, const char* form) const {
+        a = in_gemm(f, r, i, mark_fresh);
+        res_skip(a, f, r, i, true);
+        gemm_apply_defaults(a);
+        const int rc = gemm_check_args(GEMM_EPI_GATE_RS, a); if (rc) return rc;
+        max_nseg = std::max(max_nseg, a.nseg);
+        CTTS_CHECK_ARG(wf_row_persistent_supported(a), "waveflow %s: layer %d not supported by the tile body", form, i);
+        return CTTS_OK;
+    }
+    // depthwise stage of a separable in-layer: the height taps' ring slots -> w.dwout
+    int depthwise(const WfPlan::Flow& f, int r, int i) const {
+        const int C = p.C, L = g.L, kh = p.c.kernel_size_h, kw = p.c.kernel_size_w, dw = p.dw(i), a_min = p.a_min(r, i);
+        const float *wt = blob + f.dw_w[i], *bias = blob + f.dw_b[i];
+        WfSlots xs{};
+        for (int ah = a_min; ah < kh; ++ah) xs.p[ah] = XR(p.src(i), r - (kh - 1 - ah) * p.dh(i));
+        const dim3 vgrid(((L + 3) / 4 + 255) / 256, C, batch);
+        const bool vec = g.pad % 4 == 0 && g.ld % 4 == 0 && (dw <= 2 || dw % 4 == 0);
+        if (vec && kw == 7) launch_depthwise_vec<7>(vgrid, s, xs, wt, bias, w.dwout, C, kh, dw, a_min, L, g.ld, g.pad);
+        else if (vec && kw == 5) launch_depthwise_vec<5>(vgrid, s, xs, wt, bias, w.dwout, C, kh, dw, a_min, L, g.ld, g.pad);
+        else if (vec && kw == 3) launch_depthwise_vec<3>(vgrid, s, xs, wt, bias, w.dwout, C, kh, dw, a_min, L, g.ld, g.pad);
+        else
+            hipLaunchKernelGGL(wf_depthwise_kernel, dim3((L + 255) / 256, C, batch), dim3(256), 0, s, xs, wt, bias, w.dwout, C, kh, kw,
+                               dw, a_min, L, g.ld, g.pad);
+        return wf_launched("wf_depthwise");
+    }
+    // both 1x1 stages behind the depthwise stage in one launch (waveflow_sep.hip)
+    int sep_layer(const WfPlan::Flow& f, int r, int i) const {
+        WfSepArgs q{};
+        q.dwout = w.dwout;
+        q.A1 = blob + f.sA1[i]; q.b1 = blob + f.sb1[i]; q.A2 = blob + f.sA2[i]; q.b2 = blob + f.sb2[i];
+        q.cond = w.cond_up + (size_t)i * w.cond_slot;
+        q.xin = XR(p.src(i), r);
+        q.xout = p.last(i) ? nullptr : XR(i + 1, r);
+        q.gate = p.c.gated_unit;
+        q.split_bf16 = gemm_split_level(p.c.f32_gemm_mode) == 3 ? 1 : 0;   // (x6: the fused separable layer stays on fp32 MFMA)
+        q.out = w.out; q.acc_out = i > 0 ? 1 : 0; q.rs_rows = p.rs_rows(i);
+        q.L = g.L; q.ld = g.ld; q.pad = g.pad; q.ntiles = (g.L + 63) / 64;
+        const int rc = launch_wf_sep_layer(q, batch, s); if (rc) return rc;
+        note_gemm_loop(q.split_bf16 ? 3 : 0);
+        return CTTS_OK;
+    }
     // one row of the recurrence as one launch per layer (per-layer GEMM shapes, region split, separable / unfused forms)
-    auto per_layer_row = [&](const WfPlan::Flow& f, int r, int slot) -> int {
+    int per_layer_row(const WfPlan::Flow& f, int r) {
         int rc = CTTS_OK;
         if (rsplit.on && (rc = rsplit.begin_row(s))) return rc;
         for (int i = 0; i < p.c.n_layers; ++i) {
-            const int dw = p.c.dilation_w[i] > 0 ? p.c.dilation_w[i] : 1 << i;
-            // merge_res_skip (glow_ax.py:612-626): no residual into `audio`, so every layer's queue holds the
-            // `start` outputs - layer i reads the ring of layer 0 and nothing is written to ring i+1
-            const bool merge = p.c.merge_res_skip != 0;
-            const int si = merge ? 0 : i;
-            const int dh = p.dh(i);                                   // height tap ah reads row r - (kh-1-ah)*dh
-            const int a_min = std::max(0, kh - 1 - r / dh);           // earlier rows do not exist: skip those taps
-            GemmArgs a{};
-            a.gate = p.c.gated_unit;
-            a.gemm_mode = p.c.f32_gemm_mode;
-            a.bm = WF_BM;
-            a.ld = g.ld; a.pad = g.pad; a.L = L; a.ntiles = g.ntiles; a.batch = batch;
-            a.dst_ld = g.ld; a.dst_pad = g.pad;
-            a.A = blob + f.in_A[i]; a.bias = blob + f.in_b[i];
-            a.a_nch_alloc = p.nch_in;
-            a.MB = p.in_mb(); a.M = 2 * C; a.pairC = C;
-            int ns = 0;
-            if (p.sep) {
-                WfSlots xs{};
-                for (int ah = a_min; ah < kh; ++ah) xs.p[ah] = X(si, (r - (kh - 1 - ah) * dh) % NS);
-                const dim3 vgrid(((L + 3) / 4 + 255) / 256, C, batch);
-                const bool vec = g.pad % 4 == 0 && g.ld % 4 == 0 && (dw <= 2 || dw % 4 == 0);
-                if (vec && kw == 7) launch_depthwise_vec<7>(vgrid, s, xs, blob + f.dw_w[i], blob + f.dw_b[i], w.dwout, C, kh, dw, a_min, L, g.ld, g.pad);
-                else if (vec && kw == 5) launch_depthwise_vec<5>(vgrid, s, xs, blob + f.dw_w[i], blob + f.dw_b[i], w.dwout, C, kh, dw, a_min, L, g.ld, g.pad);
-                else if (vec && kw == 3) launch_depthwise_vec<3>(vgrid, s, xs, blob + f.dw_w[i], blob + f.dw_b[i], w.dwout, C, kh, dw, a_min, L, g.ld, g.pad);
-                else
-                    hipLaunchKernelGGL(wf_depthwise_kernel, dim3((L + 255) / 256, C, batch), dim3(256), 0, s, xs,
-                                       blob + f.dw_w[i], blob + f.dw_b[i], w.dwout, C, kh, kw, dw, a_min, L, g.ld, g.pad);
-                CTTS_CHECK_LAUNCH("wf_depthwise");
-                if (sep_fuse) {
-                    WfSepArgs q{};
-                    q.dwout = w.dwout;
-                    q.A1 = blob + f.sA1[i]; q.b1 = blob + f.sb1[i]; q.A2 = blob + f.sA2[i]; q.b2 = blob + f.sb2[i];
-                    q.cond = w.cond_up + (size_t)i * w.cond_slot;
-                    q.xin = X(si, slot);
-                    q.xout = (i == p.c.n_layers - 1 || merge) ? nullptr : X(i + 1, slot);
-                    q.gate = p.c.gated_unit;
-                    q.split_bf16 = gemm_split_level(p.c.f32_gemm_mode) == 3 ? 1 : 0;   // (x6: the fused separable layer stays on fp32 MFMA)
-                    q.out = w.out; q.acc_out = i > 0 ? 1 : 0; q.rs_rows = p.rs_rows(i);
-                    q.L = L; q.ld = g.ld; q.pad = g.pad; q.ntiles = (L + 63) / 64;
-                    if ((rc = launch_wf_sep_layer(q, batch, s))) return rc;
-                    note_gemm_loop(q.split_bf16 ? 3 : 0);
-                    continue;
-                }
-                a.a_ch_off = 0;
-                a.seg[ns++] = {w.dwout, cstride, p.nch_c, 0, 0, 0};
-                a.nch_total = p.nch_c;
-            } else {
-                a.a_ch_off = a_min * kw * p.nch_c;
-                for (int ah = a_min; ah < gkh; ++ah) {
-                    const int src_row = r - (kh - 1 - ah) * dh;
-                    for (int j = 0; j < gkw; ++j)
-                        a.seg[ns++] = {X(si, src_row % NS), cstride, p.nch_c, (j - kw / 2) * dw, 0, 0};
-                }
-                a.nch_total = (kh - a_min) * kw * p.nch_c;
+            if (p.sep && (rc = depthwise(f, r, i))) return rc;
+            if (sep_fuse) {
+                rc = sep_layer(f, r, i);
+            } else if (fuse) {
+                GemmArgs a = in_gemm(f, r, i, 0);
+                res_skip(a, f, r, i, true);
+                rc = rsplit.on ? rsplit.layer(a, i, s) : launch_gemm_f32(GEMM_EPI_GATE_RS, a, s);
+            } else {                                        // gated activations -> w.act, then the res/skip 1x1 over them
+                GemmArgs a = in_gemm(f, r, i, 0), q{};
+                a.dst0 = w.act; a.dst0_bstride = cstride();
+                if ((rc = launch_gemm_f32(GEMM_EPI_GATE, a, s))) return rc;
+                q.gemm_mode = p.c.f32_gemm_mode;
+                q.bm = WF_BM;
+                q.ld = g.ld; q.pad = g.pad; q.L = g.L; q.ntiles = g.ntiles; q.batch = batch;
+                q.dst_ld = g.ld; q.dst_pad = g.pad;
+                q.A = blob + f.rs_A[i]; q.bias = blob + f.rs_b[i];
+                q.nseg = 1; q.nch_total = p.nch_c; q.MB = p.rs_mb(i); q.M = p.rs_rows(i);
+                q.seg[0] = {w.act, cstride(), p.nch_c, 0, 0, 0};
+                res_skip(q, f, r, i, false);
+                rc = launch_gemm_f32(GEMM_EPI_SPLIT, q, s);
             }
-            if (p.precond) {
-                a.addend = w.cond_up + (size_t)i * w.cond_slot;
-                a.addend_bstride = (long long)2 * C * g.ld;
-            } else {
-                a.seg[ns++] = {w.mel_up, (long long)p.kmel * g.ld, p.kmel / GEMM_KC, 0, 0, 0};
-                a.nch_total += p.kmel / GEMM_KC;
-            }
-            a.nseg = ns;
-            const bool last = i == p.c.n_layers - 1 || merge;       // all rows of the res/skip GEMM are skip rows
-            if (fuse) {
-                if (!p.sep) a = fused_args(f, r, i, 0);
-                else {
-                    // x_{i+1}[row r] = x_i[row r] + res -> layer i+1's ring slot;  skip rows (+)= into w.out
-                    a.rs_wT = blob + f.rs_T[i]; a.rs_bias = blob + f.rs_Tb[i]; a.rs_rows = p.rs_rows(i);
-                    a.dst0 = last ? w.out : X(i + 1, slot); a.dst0_bstride = cstride; a.acc0 = 1;
-                    a.src0 = X(si, slot); a.src0_bstride = cstride;
-                    a.dst1 = w.out; a.dst1_bstride = cstride; a.acc1 = i > 0 ? 1 : 0;
-                    a.split = last ? 0 : C;
-                }
-                if (rsplit.on) {
-                    if ((rc = rsplit.layer(a, i, s))) return rc;
-                    continue;
-                }
-                if ((rc = launch_gemm_f32(GEMM_EPI_GATE_RS, a, s))) return rc;
-                continue;
-            }
-            a.dst0 = w.act; a.dst0_bstride = cstride;
-            if ((rc = launch_gemm_f32(GEMM_EPI_GATE, a, s))) return rc;
-
-            GemmArgs q{};
-            q.gemm_mode = p.c.f32_gemm_mode;
-            q.bm = WF_BM;
-            q.ld = g.ld; q.pad = g.pad; q.L = L; q.ntiles = g.ntiles; q.batch = batch;
-            q.dst_ld = g.ld; q.dst_pad = g.pad;
-            q.A = blob + f.rs_A[i]; q.bias = blob + f.rs_b[i];
-            q.nseg = 1; q.nch_total = p.nch_c; q.MB = p.rs_mb(i); q.M = p.rs_rows(i);
-            q.seg[0] = {w.act, cstride, p.nch_c, 0, 0, 0};
-            // x_{i+1}[row r] = x_i[row r] + res : written into layer i+1's ring slot (its queue entry)
-            q.dst0 = last ? w.out : X(i + 1, slot); q.dst0_bstride = cstride; q.acc0 = 1;
-            q.src0 = X(si, slot); q.src0_bstride = cstride;
-            q.dst1 = w.out; q.dst1_bstride = cstride; q.acc1 = i > 0 ? 1 : 0;
-            q.split = last ? 0 : C;
-            if ((rc = launch_gemm_f32(GEMM_EPI_SPLIT, q, s))) return rc;
+            if (rc) return rc;
         }
         if (rsplit.on && (rc = rsplit.end_row(s))) return rc;
         return CTTS_OK;
-    };
+    }
+};
 
-    // this flow's conditioning (cond_precomputed models), upsampled once for all rows and layers
-    auto flow_cond = [&](int k) -> int {
-        if (!p.precond) return CTTS_OK;
-        const float* fr = cond + (size_t)k * batch * 2 * C * p.c.n_layers * cond_ld;
-        if (g.pad % 4 == 0 && g.ld % 4 == 0 && w.cond_slot % 4 == 0 && !tuning().wf_no_vec_interp)
-            hipLaunchKernelGGL(wf_interp_cond_vec_kernel, dim3(((L + 3) / 4 + 255) / 256, 2 * C * p.c.n_layers, batch), dim3(256), 0, s,
-                               fr, w.cond_up, 2 * C, p.c.n_layers, frames, cond_ld, cond_pad, L, g.ld, g.pad, w.cond_slot);
-        else
-            hipLaunchKernelGGL(wf_interp_cond_kernel, dim3((L + 255) / 256, 2 * C * p.c.n_layers, batch), dim3(256), 0, s,
-                               fr, w.cond_up, 2 * C, p.c.n_layers, frames, cond_ld, cond_pad, L, g.ld, g.pad, w.cond_slot);
-        CTTS_CHECK_LAUNCH("wf_interp_cond");
-        return CTTS_OK;
-    };
-
-    if (fw) {
-        // ---- analysis direction (ax:234-277): flows in natural order; the mix is the same row-map composition (PermuteHeight is its
-        // own inverse) or the same pass over the rows with W_k; an early split peels the first n_early_size active rows off to the output
-        Ga = G;
-        for (int i = 0; i < G; ++i) phys[i] = i;
-        int outmap[64], nout = 0, s_off = 0, S = 0;
-        for (int k = 0; k < p.c.n_flows; ++k) S += p.n_rem[k] - 1;
-        auto mix = [&](int k) -> int {
-            if (p.c.mixing == CTTS_MIX_PERMUTE) return unmix(k);
-            RowMap m;
-            for (int i = 0; i < 64; ++i) m.phys[i] = i < Ga ? phys[i] : 0;
-            hipLaunchKernelGGL(wf_mix_kernel, lgrid, dim3(256), 0, s, w.rows, fw->mix + wf_fwd_mix_offset(p, k), m, Ga, G, g.Lr);
-            CTTS_CHECK_LAUNCH("wf_mix (forward)");
-            return CTTS_OK;
-        };
-        // all-rows form: the descriptors of the whole call - [flow][layer][row], independent of the row map - staged in the calling
-        // thread's pinned buffer and copied once
-        std::vector<size_t> d_off(p.c.n_flows + 1, 0);
-        int d_max_nseg = 0;
-        if (all_rows) {
-            for (int k = 0; k < p.c.n_flows; ++k) d_off[k + 1] = d_off[k] + (size_t)p.c.n_layers * (p.n_rem[k] - 1);
-            if ((rc = t_wf_desc.begin(d_off[p.c.n_flows] * sizeof(GemmArgs)))) return rc;
-            GemmArgs* host = reinterpret_cast<GemmArgs*>(t_wf_desc.host);
-            for (int k = 0; k < p.c.n_flows; ++k)
-                for (int i = 0; i < p.c.n_layers; ++i)
-                    for (int r = 0; r < p.n_rem[k] - 1; ++r) {
-                        GemmArgs& a = host[d_off[k] + (size_t)i * (p.n_rem[k] - 1) + r] = fused_args(p.fl[k], r, i, 0);
-                        gemm_apply_defaults(a);                     // (the tile body is launched without launch_gemm_f32:
-                        if ((rc = gemm_check_args(GEMM_EPI_GATE_RS, a))) return rc;   //  its defaults and checks are applied here)
-                        d_max_nseg = std::max(d_max_nseg, a.nseg);
-                        CTTS_CHECK_ARG(wf_row_persistent_supported(a), "waveflow forward: layer %d not supported by the tile body", i);
-                    }
-            CTTS_CHECK_HIP(hipMemcpyAsync(w.f.desc, host, d_off[p.c.n_flows] * sizeof(GemmArgs), hipMemcpyHostToDevice, s));
-            if ((rc = t_wf_desc.end(s))) return rc;
-        }
-        const dim3 sgrid(((L + 3) / 4 + 255) / 256, (C + 15) / 16, batch);
-        for (int k = 0; k < p.c.n_flows; ++k) {
-            const auto& f = p.fl[k];
-            if (p.n_rem[k] < Ga) {                                                 // ax:237-242: the early output leaves in front
-                const int es = Ga - p.n_rem[k];
-                for (int i = 0; i < es; ++i) outmap[nout++] = phys[i];
-                for (int i = es; i < Ga; ++i) phys[i - es] = phys[i];
-                Ga -= es;
-            }
-            if (p.c.mix_first && (rc = mix(k))) return rc;                         // ax:244-245
-            if ((rc = flow_cond(k))) return rc;
-            const int nr = Ga - 1;                                                 // WN rows 0 .. Ga - 2 (efficient_modules.py:30)
-            RowMap m;
-            for (int i = 0; i < 64; ++i) m.phys[i] = i < Ga ? phys[i] : 0;
-            if (all_rows) {
-                hipLaunchKernelGGL(wf_fwd_start_rows_kernel, dim3(sgrid.x, sgrid.y, (unsigned)(nr * batch)), dim3(256), 0, s, w.rows,
-                                   blob + f.start_w, blob + f.start_b, w.f.XA, w.xslot, m, C, G, batch, L, g.Lr, g.ld, g.pad);
-                CTTS_CHECK_LAUNCH("wf_fwd_start_rows");
-                for (int i = 0; i < p.c.n_layers; ++i)
-                    if ((rc = launch_wf_all_rows_layer(w.f.desc + d_off[k] + (size_t)i * nr, nr, d_max_nseg, L, batch, s))) return rc;
-                hipLaunchKernelGGL(wf_fwd_tail_kernel, dim3((g.Lr + 255) / 256, batch, nr), dim3(256), 0, s, w.f.OUT, w.xslot, w.rows,
-                                   w.f.ls, blob + f.end_w, blob + f.end_b, m, 0, C, G, L, g.Lr, g.ld, g.pad);
-                CTTS_CHECK_LAUNCH("wf_fwd_tail");
-            } else {
-                // row-wise form: the inverse's launches in natural row order on the ring; the row's input is the known audio row, so
-                // the next row's start conv runs BEFORE this row's tail overwrites it (its ring slot is free: this row's layers are queued)
-                hipLaunchKernelGGL(wf_start_kernel, sgrid, dim3(256), 0, s, w.rows, blob + f.start_w, blob + f.start_b, X(0, 0), C, G,
-                                   phys[0], L, g.Lr, g.ld, g.pad);
-                CTTS_CHECK_LAUNCH("wf_start");
-                for (int r = 0; r < nr; ++r) {
-                    if ((rc = per_layer_row(f, r, r % NS))) return rc;
-                    if (r + 1 < nr) {
-                        hipLaunchKernelGGL(wf_start_kernel, sgrid, dim3(256), 0, s, w.rows, blob + f.start_w, blob + f.start_b,
-                                           X(0, (r + 1) % NS), C, G, phys[r + 1], L, g.Lr, g.ld, g.pad);
-                        CTTS_CHECK_LAUNCH("wf_start");
-                    }
-                    hipLaunchKernelGGL(wf_fwd_tail_kernel, dim3((g.Lr + 255) / 256, batch, 1), dim3(256), 0, s, w.out, (size_t)0, w.rows,
-                                       w.f.ls, blob + f.end_w, blob + f.end_b, m, r, C, G, L, g.Lr, g.ld, g.pad);
-                    CTTS_CHECK_LAUNCH("wf_fwd_tail");
-                }
-            }
-            hipLaunchKernelGGL(wf_fwd_reduce_kernel, dim3(w.f.nblk, batch), dim3(256), 0, s, w.f.ls, nr, G, L, g.Lr, fw->log_s, S, s_off,
-                               fw->log_s_sum, k == 0 ? 1 : 0, w.f.partials + (size_t)k * batch * w.f.nblk, w.f.nblk);
-            CTTS_CHECK_LAUNCH("wf_fwd_reduce");
-            s_off += nr;
-            if (fw->ignore_nan) {
-                const size_t n4 = (size_t)batch * G * g.Lr / 4;
-                hipLaunchKernelGGL(wf_nan_to_zero_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, w.rows, n4);
-                CTTS_CHECK_LAUNCH("wf_nan_to_zero");
-            }
-            if (!p.c.mix_first && (rc = mix(k))) return rc;                        // ax:260-261
-        }
-        for (int i = 0; i < Ga; ++i) outmap[nout++] = phys[i];                     // ax:276-277
-        RowMap map;
-        for (int i = 0; i < 64; ++i) map.phys[i] = i < G ? outmap[i] : 0;
-        hipLaunchKernelGGL(wf_unsqueeze_kernel, dim3((L + 255) / 256, batch), dim3(256), 0, s, w.rows, audio, G, L, g.Lr, map);
-        CTTS_CHECK_LAUNCH("wf_unsqueeze");
-        hipLaunchKernelGGL(wf_fwd_sums_kernel, dim3((p.c.n_flows * batch + 63) / 64), dim3(64), 0, s, w.f.partials, fw->sums,
-                           p.c.n_flows, batch, w.f.nblk);
-        CTTS_CHECK_LAUNCH("wf_fwd_sums");
+// Row queue (round 4, gemm_f32_small.hip wf_row_persistent_kernel), inverse only: the fused layers of a row as ONE launch whose
+// workgroups take (layer, tile) items in order and wait for the three neighbouring tiles of the previous layer only.  Same tile body
+// as the per-layer 128 x 128 shape: bit-identical to it (and to the 128 x 256 shape).  Descriptors: the GemmArgs of a whole flow are
+// built on the host, copied once per flow, and a row's launch points at its slice.
+struct WfRowQueue {
+    bool on = false, flow = false; // flow: the whole-flow form - every row of a flow in ONE launch (tail stages between the rows)
+    int body = 0, max_nseg = 0;    // tile body; widest descriptor of the flow staged last
+    unsigned int n_launch = 0;
+    size_t host_off = 0;           // bytes of the pinned host buffer the flows queued so far occupy
+    // the call's decisions; when on, the pinned buffer is taken and the control words are zeroed
+    int begin(const WfCall& c) {
+        const WfPlan& p = c.p;
+        const auto& t = tuning();
+        const int items = wf_row_tiles(c.g.L, 0) * c.batch;
+        const int min_items = t.wf_row_queue_min >= 0 ? t.wf_row_queue_min : WF_ROW_QUEUE_MIN_ITEMS;
+        // (the queue's tile bodies are the fp32-MFMA DMA-staged ones: under the split-bf16 modes, CTTS_F32_NO_GLDS or CTTS_F32_NO_SMALL
+        // the layers are launched one by one as before)
+        on = c.fuse && !p.sep && !t.wf_no_row_queue && items >= min_items && (items < WF_ROW_QUEUE_MAX_ITEMS || t.wf_row_queue_min >= 0) &&
+             !gemm_mode_is_split(p.c.f32_gemm_mode) && !t.f32_no_glds && !t.f32_no_small;
+        if (!t.f32_no_splitk) body = items < WF_ROW_QUEUE_SPLITK_BELOW ? 1 : 0;
+        if (t.wf_queue_debug & 16) body = 0;
+        if (t.wf_queue_debug & 32) body = 1;
+        for (int i = 0; i < p.c.n_layers && on; ++i)        // a fresh segment may reach one 128-column tile to either side
+            on = (p.c.kernel_size_w / 2) * p.dw(i) <= 128;
+        flow = on && !(t.wf_queue_debug & 128);              // CTTS_WF_QUEUE_DEBUG=128: one launch per row
+        if (!on) return CTTS_OK;
+        const int rc = t_wf_desc.begin((size_t)p.c.n_flows * p.c.n_group * (p.c.n_layers * sizeof(GemmArgs) + sizeof(WfTailDesc)));
+        if (rc) return rc;
+        CTTS_CHECK_HIP(hipMemsetAsync(c.w.q.abort_word, 0, c.w.q.control_bytes, c.s));
+        if (t.wf_inject_abort) CTTS_CHECK_HIP(hipMemsetAsync(c.w.q.abort_word, 1, sizeof(unsigned int), c.s));   // (tests)
         return CTTS_OK;
     }
+    // this flow's descriptors - and, in the whole-flow form, the tail stage behind every row - one copy each
+    int stage_flow(const WfCall& c, const WfPlan::Flow& f) {
+        const WfPlan& p = c.p;
+        const int nr = c.rows.n - 1;
+        GemmArgs* host = reinterpret_cast<GemmArgs*>(t_wf_desc.host + host_off);
+        size_t n = 0;
+        max_nseg = 0;
+        for (int r = 0; r < nr; ++r)
+            for (int i = 0; i < p.c.n_layers; ++i)
+                if (const int rc = c.stage(host[n++], f, r, i, flow ? 2 : 1, max_nseg, "row queue")) return rc;
+        CTTS_CHECK_HIP(hipMemcpyAsync(c.w.q.layers, host, n * sizeof(GemmArgs), hipMemcpyHostToDevice, c.s));
+        host_off += n * sizeof(GemmArgs);
+        if (!flow) return CTTS_OK;
+        WfTailDesc* th = reinterpret_cast<WfTailDesc*>(t_wf_desc.host + host_off);
+        for (int r = 0; r < nr; ++r) {
+            WfTailDesc d{};
+            d.out = c.w.out; d.out_bstride = c.cstride();
+            d.rows = c.w.rows; d.Wend = c.blob + f.end_w; d.bend = c.blob + f.end_b;
+            d.ws = c.blob + f.start_w; d.bs = c.blob + f.start_b;
+            d.x0 = r + 1 < nr ? c.X(0, (r + 1) % p.ring) : nullptr; d.x0_bstride = c.cstride();
+            d.C = p.C; d.G = p.c.n_group; d.row = c.rows.phys[r + 1]; d.L = c.g.L; d.Lr = c.g.Lr; d.ld = c.g.ld; d.pad = c.g.pad;
+            th[r] = d;
+        }
+        CTTS_CHECK_HIP(hipMemcpyAsync(c.w.q.tails, th, (size_t)nr * sizeof(WfTailDesc), hipMemcpyHostToDevice, c.s));
+        host_off += (size_t)nr * sizeof(WfTailDesc);
+        return CTTS_OK;
+    }
+    // rows r0 .. r0 + nrows - 1 of the staged flow as one launch (whole-flow form: all of them, with the tail stages)
+    int launch(const WfCall& c, int r0, int nrows) {
+        const unsigned int li = n_launch++;
+        const WfQueueWs& q = c.w.q;
+        return launch_wf_row_persistent(q.layers + (size_t)r0 * c.p.c.n_layers, flow ? q.tails : nullptr, nrows, c.p.c.n_layers, max_nseg,
+                                        c.g.L, c.batch, body, q.counters + li, q.flags, q.abort_word, li + 1, c.s);
+    }
+    // behind the call's last kernel: release the pinned buffer; a bounded wait of the row queue expired (never, by construction):
+    // the audio is NaN, not plausible noise, and this thread's next call on this workspace looks at the status first
+    int end(const WfCall& c, float* audio, const void* workspace) {
+        int rc = t_wf_desc.end(c.s); if (rc) return rc;
+        hipLaunchKernelGGL(wf_abort_poison_kernel, dim3(c.batch), dim3(256), 0, c.s, c.w.q.abort_word, audio,
+                           (long long)c.p.c.n_group * c.g.L, c.w.q.status);
+        CTTS_CHECK_LAUNCH("wf_abort_poison");
+        return wf_note_pending(workspace, c.w.q.status, c.s);
+    }
+};
 
+// z -> audio (ctts_waveflow_inverse_*, ax:309-346): flows in reverse order, each the row recurrence in the row queue or as per-layer
+// launches; the earlier chunks of an early-output model re-join in front, one per n_early_every flows (ax:340-341)
+int wf_synthesize(const WfIo& io) {
+    WfCall c;
+    int rc = c.open(io, nullptr); if (rc) return rc;
+    // the previous call of this thread on this workspace used the row queue: if it aborted, say so now instead of computing
+    // on top of it (one stream synchronisation + 4 bytes; the caller sees CTTS_E_ABORT once, the call after that runs)
+    if ((rc = wf_check_pending(io.workspace, c.w.q.status, c.s))) return rc;
+    const WfPlan& p = c.p;
+    const int G = p.c.n_group;
+    if ((rc = c.squeeze(io.in, nullptr))) return rc;
+    c.rows.reset(G, p.n_rem[p.c.n_flows - 1]);
+    WfRowQueue q;
+    if ((rc = q.begin(c))) return rc;
     for (int k = p.c.n_flows - 1; k >= 0; --k) {
         const auto& f = p.fl[k];
-        if (!p.c.mix_first && (rc = unmix(k))) return rc;                      // ax:324-325
-        int q_max_nseg = 0;
-        if (queue_on) {                                                        // this flow's descriptors, one copy
-            GemmArgs* host = reinterpret_cast<GemmArgs*>(t_wf_desc.host + q_host_off);
-            size_t n = 0;
-            for (int r = 0; r < Ga - 1; ++r)
-                for (int i = 0; i < p.c.n_layers; ++i) {
-                    GemmArgs& a = host[n++] = fused_args(f, r, i, q_flow ? 2 : 1);
-                    gemm_apply_defaults(a);                     // (the tile body is launched without launch_gemm_f32:
-                    if ((rc = gemm_check_args(GEMM_EPI_GATE_RS, a))) return rc;   //  its defaults and checks are applied here)
-                    q_max_nseg = std::max(q_max_nseg, a.nseg);
-                    CTTS_CHECK_ARG(wf_row_persistent_supported(a), "waveflow row queue: layer %d not supported by the tile body", i);
-                }
-            CTTS_CHECK_HIP(hipMemcpyAsync(w.q.layers, host, n * sizeof(GemmArgs), hipMemcpyHostToDevice, s));
-            q_host_off += n * sizeof(GemmArgs);
-            if (q_flow) {                                                      // the tail stage behind every row
-                WfTailDesc* th = reinterpret_cast<WfTailDesc*>(t_wf_desc.host + q_host_off);
-                for (int r = 0; r < Ga - 1; ++r) {
-                    WfTailDesc d{};
-                    d.out = w.out; d.out_bstride = cstride;
-                    d.rows = w.rows; d.Wend = blob + f.end_w; d.bend = blob + f.end_b;
-                    d.ws = blob + f.start_w; d.bs = blob + f.start_b;
-                    d.x0 = r + 1 < Ga - 1 ? X(0, (r + 1) % NS) : nullptr; d.x0_bstride = cstride;
-                    d.C = C; d.G = G; d.row = phys[r + 1]; d.L = L; d.Lr = g.Lr; d.ld = g.ld; d.pad = g.pad;
-                    th[r] = d;
-                }
-                CTTS_CHECK_HIP(hipMemcpyAsync(w.q.tails, th, (size_t)(Ga - 1) * sizeof(WfTailDesc), hipMemcpyHostToDevice, s));
-                q_host_off += (size_t)(Ga - 1) * sizeof(WfTailDesc);
-            }
+        if (!p.c.mix_first && (rc = c.mix(k, c.blob + f.winv))) return rc;     // ax:324-325
+        const int nr = c.rows.n - 1;                                           // WN rows 0 .. n - 2 (efficient_modules.py:42-65)
+        if (q.on && (rc = q.stage_flow(c, f))) return rc;
+        if ((rc = c.flow_cond(k))) return rc;
+        if (q.flow) {                                       // start of row 0, then every row and tail of the flow in one launch
+            if ((rc = c.start(f, c.rows.phys[0], 0))) return rc;
+            if ((rc = q.launch(c, 0, nr))) return rc;
         }
-        if ((rc = flow_cond(k))) return rc;
-        if (q_flow) {                                       // start of row 0, then every row and tail of the flow in one launch
-            hipLaunchKernelGGL(wf_start_kernel, dim3(((L + 3) / 4 + 255) / 256, (C + 15) / 16, batch), dim3(256), 0, s,
-                               w.rows, blob + f.start_w, blob + f.start_b, X(0, 0), C, G, phys[0], L, g.Lr, g.ld, g.pad);
-            CTTS_CHECK_LAUNCH("wf_start");
-            const unsigned int li = q_launch++;
-            if ((rc = launch_wf_row_persistent(w.q.layers, w.q.tails, Ga - 1, p.c.n_layers, q_max_nseg, L, batch, q_body,
-                                               w.q.counters + li, w.q.flags, w.q.abort_word, li + 1, s)))
-                return rc;
-        }
-        for (int r = 0; r < Ga - 1 && !q_flow; ++r) {
-            const int slot = r % NS;
-            hipLaunchKernelGGL(wf_start_kernel, dim3(((L + 3) / 4 + 255) / 256, (C + 15) / 16, batch), dim3(256), 0, s,
-                               w.rows, blob + f.start_w, blob + f.start_b, X(0, slot), C, G, phys[r], L, g.Lr, g.ld, g.pad);
-            CTTS_CHECK_LAUNCH("wf_start");
-            if (queue_on) {
-                const unsigned int li = q_launch++;
-                if ((rc = launch_wf_row_persistent(w.q.layers + (size_t)r * p.c.n_layers, nullptr, 1, p.c.n_layers, q_max_nseg, L, batch, q_body,
-                                                   w.q.counters + li, w.q.flags, w.q.abort_word, li + 1, s)))
-                    return rc;
-            } else if ((rc = per_layer_row(f, r, slot))) {
-                return rc;
-            }
-            hipLaunchKernelGGL(wf_tail_kernel, dim3((g.Lr + 255) / 256, batch), dim3(256), 0, s, w.out, w.rows,
-                               blob + f.end_w, blob + f.end_b, C, G, phys[r + 1], L, g.Lr, g.ld, g.pad);
+        for (int r = 0; r < nr && !q.flow; ++r) {
+            if ((rc = c.start(f, c.rows.phys[r], r % p.ring))) return rc;
+            if ((rc = q.on ? q.launch(c, r, 1) : c.per_layer_row(f, r))) return rc;
+            hipLaunchKernelGGL(wf_tail_kernel, c.lgrid(), dim3(256), 0, c.s, c.w.out, c.w.rows, c.blob + f.end_w, c.blob + f.end_b, p.C, G,
+                               c.rows.phys[r + 1], c.g.L, c.g.Lr, c.g.ld, c.g.pad);
             CTTS_CHECK_LAUNCH("wf_tail");
         }
-        const size_t n4 = (size_t)batch * G * g.Lr / 4;
-        hipLaunchKernelGGL(wf_nan_to_zero_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, w.rows, n4);
-        CTTS_CHECK_LAUNCH("wf_nan_to_zero");
-        if (p.c.mix_first && (rc = unmix(k))) return rc;                       // ax:337-338
-        if (k > 0 && p.n_rem[k - 1] > Ga) {                                    // ax:340-341: the early chunk re-joins in front
-            const int grow = p.n_rem[k - 1] - Ga;
-            for (int i = Ga - 1; i >= 0; --i) phys[i + grow] = phys[i];
-            for (int i = 0; i < grow; ++i) phys[i] = G - Ga - grow + i;
-            Ga += grow;
-        }
+        if ((rc = c.nan_to_zero())) return rc;
+        if (p.c.mix_first && (rc = c.mix(k, c.blob + f.winv))) return rc;      // ax:337-338
+        if (k > 0 && p.n_rem[k - 1] > c.rows.n) c.rows.rejoin_front(p.n_rem[k - 1] - c.rows.n, G);
     }
-    RowMap map;
-    for (int i = 0; i < 64; ++i) map.phys[i] = i < G ? phys[i] : 0;
-    hipLaunchKernelGGL(wf_unsqueeze_kernel, dim3((L + 255) / 256, batch), dim3(256), 0, s, w.rows, audio, G, L, g.Lr, map);
-    CTTS_CHECK_LAUNCH("wf_unsqueeze");
-    if (queue_on && (rc = t_wf_desc.end(s))) return rc;
-    if (queue_on) {      // a bounded wait of the row queue expired (never, by construction): the audio is NaN, not plausible noise
-        hipLaunchKernelGGL(wf_abort_poison_kernel, dim3(batch), dim3(256), 0, s, w.q.abort_word, audio, (long long)G * L,
-                           w.q.status);
-        CTTS_CHECK_LAUNCH("wf_abort_poison");
-        if ((rc = wf_note_pending(workspace, w.q.status, s))) return rc;   // this thread's next call on this workspace looks at the status first
+    if ((rc = c.unsqueeze(io.out, c.rows))) return rc;
+    return q.on ? q.end(c, io.out, io.workspace) : CTTS_OK;
+}
+
+// ---- analysis direction (ax:234-277) -------------------------------------------------------------------------------------------
+// end conv + affine update + log_s of WN rows r0 .. r0 + nrows - 1 from the skip sums at `out` (rstride apart)
+int wf_fwd_tail(const WfCall& c, const WfPlan::Flow& f, const RowMap& m, const float* out, size_t rstride, int r0, int nrows) {
+    hipLaunchKernelGGL(wf_fwd_tail_kernel, dim3((c.g.Lr + 255) / 256, c.batch, nrows), dim3(256), 0, c.s, out, rstride, c.w.rows, c.w.f.ls,
+                       c.blob + f.end_w, c.blob + f.end_b, m, r0, c.p.C, c.p.c.n_group, c.g.L, c.g.Lr, c.g.ld, c.g.pad);
+    return wf_launched("wf_fwd_tail");
+}
+
+// All-rows form: the descriptors of the whole call - [flow][layer][row], independent of the row map - staged in the calling thread's
+// pinned buffer and copied once.  off[k]: first descriptor of flow k.
+int wf_stage_all_rows(const WfCall& c, std::vector<size_t>& off, int& max_nseg) {
+    const WfPlan& p = c.p;
+    for (int k = 0; k < p.c.n_flows; ++k) off[k + 1] = off[k] + (size_t)p.c.n_layers * (p.n_rem[k] - 1);
+    if (const int rc = t_wf_desc.begin(off[p.c.n_flows] * sizeof(GemmArgs))) return rc;
+    GemmArgs* host = reinterpret_cast<GemmArgs*>(t_wf_desc.host);
+    for (int k = 0; k < p.c.n_flows; ++k)
+        for (int i = 0; i < p.c.n_layers; ++i)
+            for (int r = 0; r < p.n_rem[k] - 1; ++r)
+                if (const int rc = c.stage(host[off[k] + (size_t)i * (p.n_rem[k] - 1) + r], p.fl[k], r, i, 0, max_nseg, "forward")) return rc;
+    CTTS_CHECK_HIP(hipMemcpyAsync(c.w.f.desc, host, off[p.c.n_flows] * sizeof(GemmArgs), hipMemcpyHostToDevice, c.s));
+    return t_wf_desc.end(c.s);
+}
+
+// the coupling of one flow, all-rows form: the start conv of every row, one launch per layer, the tail over all rows
+int wf_all_rows_flow(const WfCall& c, const WfPlan::Flow& f, const RowMap& m, int nr, const GemmArgs* desc, int max_nseg) {
+    const WfGeom& g = c.g;
+    hipLaunchKernelGGL(wf_fwd_start_rows_kernel, dim3(((g.L + 3) / 4 + 255) / 256, (c.p.C + 15) / 16, (unsigned)(nr * c.batch)), dim3(256),
+                       0, c.s, c.w.rows, c.blob + f.start_w, c.blob + f.start_b, c.w.f.XA, c.w.xslot, m, c.p.C, c.p.c.n_group, c.batch, g.L,
+                       g.Lr, g.ld, g.pad);
+    CTTS_CHECK_LAUNCH("wf_fwd_start_rows");
+    for (int i = 0; i < c.p.c.n_layers; ++i)
+        if (const int rc = launch_wf_all_rows_layer(desc + (size_t)i * nr, nr, max_nseg, g.L, c.batch, c.s)) return rc;
+    return wf_fwd_tail(c, f, m, c.w.f.OUT, c.w.xslot, 0, nr);
+}
+
+// Row-wise form: the inverse's launches in natural row order on the ring; the row's input is the known audio row, so the next row's
+// start conv runs BEFORE this row's tail overwrites it (its ring slot is free: this row's layers are queued)
+int wf_row_wise_flow(WfCall& c, const WfPlan::Flow& f, const RowMap& m, int nr) {
+    int rc = c.start(f, c.rows.phys[0], 0); if (rc) return rc;
+    for (int r = 0; r < nr; ++r) {
+        if ((rc = c.per_layer_row(f, r))) return rc;
+        if (r + 1 < nr && (rc = c.start(f, c.rows.phys[r + 1], (r + 1) % c.p.ring))) return rc;
+        if ((rc = wf_fwd_tail(c, f, m, c.w.out, 0, r, 1))) return rc;
     }
     return CTTS_OK;
+}
+
+// audio -> z, log_s, log-likelihood sums (ctts_waveflow_forward_*): flows in natural order; the mix is the same row-map composition
+// or the same pass over the rows with W_k; an early split peels the first n_early_size active rows off to the output (ax:237-242)
+int wf_analyze(const WfIo& io, const WfForward& fw) {
+    WfCall c;
+    int rc = c.open(io, &fw); if (rc) return rc;
+    const WfPlan& p = c.p;
+    const WfWs& w = c.w;
+    const int G = p.c.n_group, L = c.g.L, batch = c.batch;
+    if ((rc = c.squeeze(io.in, &fw))) return rc;
+    c.rows.reset(G, G);
+    WfRowMap out;                                            // the latent's rows in output order: early outputs first
+    int s_off = 0, S = 0, d_max_nseg = 0;
+    for (int k = 0; k < p.c.n_flows; ++k) S += p.n_rem[k] - 1;
+    std::vector<size_t> d_off(p.c.n_flows + 1, 0);
+    if (c.all_rows && (rc = wf_stage_all_rows(c, d_off, d_max_nseg))) return rc;
+    for (int k = 0; k < p.c.n_flows; ++k) {
+        const auto& f = p.fl[k];
+        const float* W = fw.mix + wf_fwd_mix_offset(p, k);
+        if (p.n_rem[k] < c.rows.n) c.rows.peel_front(c.rows.n - p.n_rem[k], out);
+        if (p.c.mix_first && (rc = c.mix(k, W))) return rc;                    // ax:244-245
+        if ((rc = c.flow_cond(k))) return rc;
+        const int nr = c.rows.n - 1;                                           // WN rows 0 .. n - 2 (efficient_modules.py:30)
+        const RowMap m = c.rows.device();
+        if ((rc = c.all_rows ? wf_all_rows_flow(c, f, m, nr, w.f.desc + d_off[k], d_max_nseg) : wf_row_wise_flow(c, f, m, nr))) return rc;
+        hipLaunchKernelGGL(wf_fwd_reduce_kernel, dim3(w.f.nblk, batch), dim3(256), 0, c.s, w.f.ls, nr, G, L, c.g.Lr, fw.log_s, S, s_off,
+                           fw.log_s_sum, k == 0 ? 1 : 0, w.f.partials + (size_t)k * batch * w.f.nblk, w.f.nblk);
+        CTTS_CHECK_LAUNCH("wf_fwd_reduce");
+        s_off += nr;
+        if (fw.ignore_nan && (rc = c.nan_to_zero())) return rc;
+        if (!p.c.mix_first && (rc = c.mix(k, W))) return rc;                   // ax:260-261
+    }
+    c.rows.peel_front(c.rows.n, out);                                          // ax:276-277
+    if ((rc = c.unsqueeze(io.out, out))) return rc;
+    hipLaunchKernelGGL(wf_fwd_sums_kernel, dim3((p.c.n_flows * batch + 63) / 64), dim3(64), 0, c.s, w.f.partials, fw.sums, p.c.n_flows,
+                       batch, w.f.nblk);
+    return wf_launched("wf_fwd_sums");
 }
 
 }  // namespace
@@ -1517,7 +1519,7 @@ int ctts_waveflow_inverse_f32(const ctts_waveflow_config* cfg, const void* packe
                               size_t workspace_bytes, void* stream) {
     CTTS_CHECK_ARG(cfg && !cfg->cond_precomputed, "waveflow inverse: this model takes per-flow conditioning "
                                                   "(ctts_waveflow_inverse_cond_f32)");
-    return wf_inverse(cfg, packed, z, mel, 0, 0, audio, batch, samples, frames, workspace, workspace_bytes, stream);
+    return wf_synthesize({cfg, packed, z, mel, 0, 0, audio, batch, samples, frames, workspace, workspace_bytes, stream});
 }
 
 size_t ctts_waveflow_forward_packed_bytes(const ctts_waveflow_config* cfg) {
@@ -1551,7 +1553,7 @@ int ctts_waveflow_forward_f32(const ctts_waveflow_config* cfg, const void* packe
     CTTS_CHECK_ARG(cfg && !cfg->cond_precomputed, "waveflow forward: this model takes per-flow conditioning "
                                                   "(ctts_waveflow_forward_cond_f32)");
     const WfForward fw{static_cast<const float*>(fwd_blob), preemphasis, ignore_nan, log_s, log_s_sum, sums};
-    return wf_inverse(cfg, packed, audio, mel, 0, 0, z, batch, samples, frames, workspace, workspace_bytes, stream, &fw);
+    return wf_analyze({cfg, packed, audio, mel, 0, 0, z, batch, samples, frames, workspace, workspace_bytes, stream}, fw);
 }
 
 int ctts_waveflow_forward_cond_f32(const ctts_waveflow_config* cfg, const void* packed, const void* fwd_blob, const float* audio,
@@ -1563,8 +1565,7 @@ int ctts_waveflow_forward_cond_f32(const ctts_waveflow_config* cfg, const void* 
     CTTS_CHECK_ARG(cond_pad >= 0 && cond_ld >= cond_pad + frames, "waveflow forward_cond: cond_ld=%d pad=%d frames=%d",
                    cond_ld, cond_pad, frames);
     const WfForward fw{static_cast<const float*>(fwd_blob), preemphasis, ignore_nan, log_s, log_s_sum, sums};
-    return wf_inverse(cfg, packed, audio, cond, cond_ld, cond_pad, z, batch, samples, frames, workspace, workspace_bytes, stream,
-                      &fw);
+    return wf_analyze({cfg, packed, audio, cond, cond_ld, cond_pad, z, batch, samples, frames, workspace, workspace_bytes, stream}, fw);
 }
 
 int ctts_waveflow_abort_status(const ctts_waveflow_config* cfg, int32_t batch, int32_t samples, void* workspace,
@@ -1596,8 +1597,7 @@ int ctts_waveflow_inverse_cond_f32(const ctts_waveflow_config* cfg, const void* 
                                                  "(ctts_waveflow_inverse_f32)");
     CTTS_CHECK_ARG(cond_pad >= 0 && cond_ld >= cond_pad + frames, "waveflow inverse_cond: cond_ld=%d pad=%d frames=%d",
                    cond_ld, cond_pad, frames);
-    return wf_inverse(cfg, packed, z, cond, cond_ld, cond_pad, audio, batch, samples, frames, workspace,
-                      workspace_bytes, stream);
+    return wf_synthesize({cfg, packed, z, cond, cond_ld, cond_pad, audio, batch, samples, frames, workspace, workspace_bytes, stream});
 }
 
 int ctts_embed_rows_f32(const float* table, const int64_t* ids, float* x, int32_t row0, int32_t embed_dim,
