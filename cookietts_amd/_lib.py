@@ -346,6 +346,7 @@ SIGNATURES = {
     "ctts_resample_rows_f32": (C.c_int, [_FP, _FP] + [C.c_int32] * 9 + [C.c_float, _FP]),
     "ctts_interleave_phases_f32": (C.c_int, [_FP, _FP] + [C.c_int32] * 10 + [_FP]),
     "ctts_last_gemm_loop": (C.c_int, []),
+    "ctts_last_winograd_f43_width": (C.c_int, []),
     "ctts_tuning_reload": (C.c_int, []),
     "ctts_tuning_flags": (C.c_int, []),
     "ctts_profile_create": (C.c_int, [C.POINTER(C.c_void_p)]),

@@ -184,8 +184,8 @@ int pair_ld(const Plan& p, const Geom& g) {
     for (int i = 0; i < p.c.n_layers; ++i) nt = std::max(nt, pair_geom(g, i).ntiles);
     return nt * GEMM_BN;
 }
-// Winograd F(4,3) form: quad-space geometry of layer i: Lq = ceil(L / 4d) d quad columns per batch item, in ntiles 64-column tiles
-// (the only width of that form); every layer uses the row stride ldq of the widest one
+// Winograd F(4,3) form: quad-space geometry of layer i: Lq = ceil(L / 4d) d quad columns per batch item, in ntiles 64-column tiles;
+// every layer uses the row stride ldq of the widest one, in whole 128-column tiles (the CTTS_F32_NO_SMALL shape of the layer)
 PairGeom quad_geom(const Geom& g, int layer) {
     const int d = 1 << layer;
     const int Lq = (g.L + 4 * d - 1) / (4 * d) * d;
@@ -194,7 +194,7 @@ PairGeom quad_geom(const Geom& g, int layer) {
 int quad_ld(const Plan& p, const Geom& g) {
     int nt = 0;
     for (int i = 0; i < p.c.n_layers; ++i) nt = std::max(nt, quad_geom(g, i).ntiles);
-    return nt * 64;
+    return round_up(nt * 64, 128);
 }
 // The form is taken only where the in-layer launch runs the fp32 MFMA loop, and for utterances of at least WINOGRAD_MIN_COLS columns
 // (steps per batch item).  The test is on the utterance, never on the batch: an utterance must come out bit for bit the same
@@ -393,11 +393,13 @@ int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k
     const bool fused = lean && winograd_fused_engages(p, g);
     const float* h2 = h_all + (size_t)k * H * g.ld;
     if (fused && wg.ldq > 0 && winograd_f43_engages(p, g)) {
-        // F(4,3): the quad transform (V0..V5, 1.5 C L floats), then ONE launch of the 64-column quad shape; no peel exists
+        // F(4,3): the quad transform (V0..V5, 1.5 C L floats), then ONE launch of the quad shape (the same shape at every grid size: no
+        // peel); the 128-column arm reads whole 128-column tiles, so the transform fills them
         const PairGeom qg = quad_geom(g, i);
         const int ldq = wg.ldq;
+        const int ncols = tuning().f32_no_small ? round_up(qg.ntiles * 64, 128) : qg.ntiles * 64;
         int rc = launch_winograd_transform_quad(x, (long long)C * g.ld, h2, hstride, wg.V, wg.Hc, batch, C, H, qg.d, g.L, qg.Lp, g.ld, g.pad,
-                                                ldq, qg.ntiles * 64, !in_place, s);
+                                                ldq, ncols, !in_place, s);
         if (rc) return rc;
         WnWinogradLayerArgs w{};
         w.form = WNWG_F43;
@@ -1324,6 +1326,7 @@ int ctts_waveglow_infer_spk_f32(const ctts_waveglow_config* cfg, const void* pac
 }
 
 int ctts_last_gemm_loop(void) { return last_gemm_loop(); }
+int ctts_last_winograd_f43_width(void) { return last_wn_winograd_f43_width(); }
 int ctts_tuning_reload(void) { reload_tuning(); return CTTS_OK; }
 int ctts_tuning_flags(void) {
     const Tuning t = tuning();

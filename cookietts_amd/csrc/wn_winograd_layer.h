@@ -12,7 +12,13 @@
 //   act[t_0] = gate(a + c   + [U0 | C_i] [V0; h(t_0)] + b),   act[t_1] = gate(b + 2 e + C_i h(t_1) + b),
 //   act[t_2] = gate(a + 4 c + C_i h(t_2) + b),                act[t_3] = gate(b + 8 e + [U5 | C_i] [V5; h(t_3)] + b)
 // with U = G W, V = B^T x of the interpolation points 0, +-1, +-2, inf.  ldp / Lp / ntiles then describe the quad space, in tiles of
-// 64 columns; the only kernel width is 64, so no peel and no width-dependent choice exists.
+// 64 columns.  Three kernels run it, bit-identical like NT = 1 / 2 of the F(2,3) form (every column's products are summed in the same
+// order): 64 quad columns with TWO consecutive chunks per stage (32 k-deep stages, half the barriers, the chunk table fetched one
+// stage ahead) - what the launcher takes at every size; the same shape with one chunk per stage (CTTS_F32_FORCE_SMALL, the kernel of
+// the rounds before); and 128 quad columns = 512 natural columns, whose four accumulator sets are 256 registers: ONE workgroup per CU,
+// one wave per SIMD with the whole 512-register file (CTTS_F32_NO_SMALL; slower, profiles/r26_01_f43_wide_gonogo.txt; it needs
+// ldp >= 128 ceil(ntiles / 2)).  Two chunks per stage need H % 32 == 0 (C % 128 == 0 holds), so that every phase is whole stages;
+// other H keep one chunk per stage.
 #pragma once
 
 #include "common.h"
@@ -47,5 +53,7 @@ struct WnWinogradLayerArgs {
 bool wn_winograd_layer_supported(int C, int H);
 bool wn_winograd_layer_f43_supported(int C, int H);
 int launch_wn_winograd_layer(const WnWinogradLayerArgs& a, hipStream_t stream);
+// quad columns (64 or 128) of the calling thread's most recent F(4,3) layer launch; 0 before the first
+int last_wn_winograd_f43_width();
 
 }  // namespace ctts

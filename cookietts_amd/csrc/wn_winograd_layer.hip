@@ -26,12 +26,16 @@
 //   [.., + nh)         X2 += C_i . h(t_2)                then act[t_2]
 //   [.., + n2)         X3 += [U5 | C_i] . [V5; h(t_3)]   then act[t_3]
 // (interpolation points 0, +-1, +-2, inf: the output-side multipliers 1, 2, 4, 8 are exact scalings).
+// The F(4,3) form also runs with KD = 2: a stage holds two consecutive chunks (every phase is an even number of chunks), 16 k-step
+// regions and 32 NT MFMAs per wave between two barriers, and with NT = 2 (128 quad columns, 256 accumulator registers pinned to the
+// accumulator half of the file, one workgroup per CU).  Same products in the same order per accumulator element: bit-identical.
 #include "wn_winograd_layer.h"
 #include "tuning.h"
 
 namespace ctts {
 
 typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned wg_u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -45,13 +49,15 @@ __device__ __forceinline__ float wg_tanh(float u) {
 
 }  // namespace
 
-template <int NT, int F43>
-__global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnWinogradLayerArgs a) {
-    static_assert(!F43 || NT == 1, "the F(4,3) form runs on the 64-column shape");
+template <int NT, int F43, int KD, int TP>
+__global__ __launch_bounds__(256, (F43 && NT == 2) ? 1 : 2) void wn_winograd_layer_f32_kernel(const WnWinogradLayerArgs a) {
+    static_assert(KD == 1 || (KD == 2 && F43 && TP), "two chunks per stage: the F(4,3) form (its phases are whole stages, see the launcher)");
     constexpr int NI = F43 ? 4 : 2;                       // interior products = accumulator sets = natural columns per packed column
     constexpr int BN = 64 * NT;
-    constexpr int A_ST = GEMM_KC * 128;                   // floats of a stage's A part
-    constexpr int STG = A_ST + GEMM_KC * BN;              // floats per stage
+    constexpr int A_ST = GEMM_KC * 128;                   // floats of a chunk's A part
+    constexpr int CST = A_ST + GEMM_KC * BN;              // floats per chunk
+    constexpr int STG = KD * CST;                         // floats per stage: KD consecutive chunks of the stream
+    constexpr int NP = 2 + NT;                            // DMA pieces per wave and chunk
     constexpr int TAB = 3 * STG;                          // chunk table: {A address, B address} = 4 dwords per chunk
     constexpr int BIAS = TAB + 4 * WNWG_MAX_CHUNKS;
     constexpr int UPR = BN / 4;                           // 16-byte units per k-row of the B stage
@@ -158,46 +164,76 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
     typedef __attribute__((address_space(3))) float* lds_fptr;
     typedef const __attribute__((address_space(1))) float* gfloat_ptr;
     typedef const __attribute__((address_space(1))) char* gbyte_ptr;
-    const uint4* ctab = reinterpret_cast<const uint4*>(lds + TAB);
+    const wg_u32x4* ctab = reinterpret_cast<const wg_u32x4*>(lds + TAB);
     // Every DMA address is a wave-uniform 64-bit base (SGPR pair) + a 32-bit lane offset laundered through an empty asm, so that
     // the compiler keeps the global_load_lds_dwordx4 v, s[a:b] form (gemm_f32.hip, CTTS_GLDS_PIECE)
+    // TP = 1: the table entries of a stage are fetched one iteration AHEAD by an asm read the compiler does not see, and waited for
+    // in front of the barrier.  Read as a plain load (TP = 0), the table makes the compiler drain EVERY DMA in flight first - it
+    // cannot tell the table from the stages the DMA writes - i.e. an s_waitcnt vmcnt(0) at the head of every chunk, which gives the
+    // two-chunks-ahead staging away.  (LDS returns in order, so an uncounted read only makes the compiler's own counted waits
+    // conservative; nothing touches tn_ between its read and its wait.)
+    wg_u32x4 tn_[KD];
+    const unsigned tab_lds = (unsigned)reinterpret_cast<uintptr_t>((lds_fptr)(lds + TAB));
+#define WNWG_TAB_ISSUE(c)                                                                                   \
+    _Pragma("unroll") for (int j = 0; j < KD; ++j) asm volatile("ds_read_b128 %0, %1" : "=v"(tn_[j]) : "v"(tab_lds + 16u * (unsigned)((c) + j)));
+#define WNWG_TAB_WAIT()                                                                                     \
+    do {                                                                                                    \
+        if constexpr (KD == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tn_[0]), "+v"(tn_[KD - 1]) : : "memory"); \
+        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tn_[0]) : : "memory");                              \
+    } while (0)
 #define WNWG_ADDR(buf, c)                                                                                   \
     lds_fptr la_ = (lds_fptr)(lds + (buf) * STG + wave * 256);                                              \
-    const uint4 e_ = ctab[c];                                                                               \
+    wg_u32x4 e_[KD];                                                                                        \
+    _Pragma("unroll") for (int j = 0; j < KD; ++j) {                                                        \
+        if constexpr (TP) e_[j] = tn_[j];                                                                   \
+        else e_[j] = ctab[(c) + j];                                                                         \
+    }                                                                                                       \
     const bool as_ = (c) < c_e;                                      /* wave-uniform: SPLIT-packed panel */ \
     bool mk_[NI];                                                    /* wave-uniform: mapped cond chunk */ \
     _Pragma("unroll") for (int k = 0; k < NI; ++k) mk_[k] = (c) >= m_lo[k] && (c) < ps[k + 1];
 #define WNWG_BASES()                                                                                        \
-    const gbyte_ptr ac_ = reinterpret_cast<gbyte_ptr>(                                                      \
-        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)e_.y) << 32) |                   \
-        (unsigned)__builtin_amdgcn_readfirstlane((int)e_.x));                                               \
-    const gbyte_ptr bp_ = reinterpret_cast<gbyte_ptr>(                                                      \
-        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)e_.w) << 32) |                   \
-        (unsigned)__builtin_amdgcn_readfirstlane((int)e_.z));
+    gbyte_ptr ac_[KD], bp_[KD];                                                                             \
+    _Pragma("unroll") for (int j = 0; j < KD; ++j) {                                                        \
+        ac_[j] = reinterpret_cast<gbyte_ptr>(                                                               \
+            ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)e_[j].y) << 32) |            \
+            (unsigned)__builtin_amdgcn_readfirstlane((int)e_[j].x));                                        \
+        bp_[j] = reinterpret_cast<gbyte_ptr>(                                                               \
+            ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)e_[j].w) << 32) |            \
+            (unsigned)__builtin_amdgcn_readfirstlane((int)e_[j].z));                                        \
+    }
+    // piece p of a stage: piece p % NP of its chunk p / NP
 #define WNWG_PIECE(p)                                                                                       \
     do {                                                                                                    \
-        if constexpr ((p) < 2) {                                                                            \
-            unsigned o_ = as_ ? offa_s[(p)] : offa_g[(p)];                                                  \
-            asm volatile("" : "+v"(o_));                                                                    \
-            __builtin_amdgcn_global_load_lds((gfloat_ptr)(ac_ + o_), la_ + 1024 * (p), 16, 0, 0);           \
-        } else if constexpr ((p) < 2 + NT) {                                                                \
-            unsigned o_ = offb[(p) - 2];                                                                    \
-            _Pragma("unroll") for (int k = 0; k < NI; ++k) o_ = mk_[k] ? offb_m[k][(p) - 2] : o_;           \
-            asm volatile("" : "+v"(o_));                                                                    \
-            __builtin_amdgcn_global_load_lds((gfloat_ptr)(bp_ + o_), la_ + A_ST + 1024 * ((p) - 2), 16, 0, 0); \
+        if constexpr ((p) < KD * NP) {                                                                      \
+            constexpr int sj_ = (p) / NP, q_ = (p) % NP;                                                    \
+            if constexpr (q_ < 2) {                                                                         \
+                unsigned o_ = as_ ? offa_s[q_] : offa_g[q_];                                                \
+                asm volatile("" : "+v"(o_));                                                                \
+                __builtin_amdgcn_global_load_lds((gfloat_ptr)(ac_[sj_] + o_), la_ + sj_ * CST + 1024 * q_, 16, 0, 0); \
+            } else {                                                                                        \
+                unsigned o_ = offb[q_ - 2];                                                                 \
+                _Pragma("unroll") for (int k = 0; k < NI; ++k) o_ = mk_[k] ? offb_m[k][q_ - 2] : o_;        \
+                asm volatile("" : "+v"(o_));                                                                \
+                __builtin_amdgcn_global_load_lds((gfloat_ptr)(bp_[sj_] + o_), la_ + sj_ * CST + A_ST + 1024 * (q_ - 2), 16, 0, 0); \
+            }                                                                                               \
         }                                                                                                   \
     } while (0)
 #define WNWG_WAIT()                                                                                         \
     do {                                                                                                    \
-        if constexpr (NT == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                             \
+        if constexpr (KD * NP == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                        \
+        else if constexpr (KD * NP == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                   \
+        else if constexpr (KD * NP == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                   \
         else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");                                               \
     } while (0)
 
-    // 2 + NT DMAs per thread per chunk, in order: vmcnt(2 + NT) = "everything but the newest chunk has landed" (the last two
-    // iterations re-issue the final chunk into a stage nobody reads any more: the DMA count per iteration stays constant)
+    // KD (2 + NT) DMAs per thread per stage, in order: vmcnt(that) = "everything but the newest stage has landed" (the last two
+    // iterations re-issue the final stage into a stage nobody reads any more: the DMA count per iteration stays constant)
     {
-        { WNWG_ADDR(0, 0) WNWG_BASES() WNWG_PIECE(0); WNWG_PIECE(1); WNWG_PIECE(2); WNWG_PIECE(3); }
-        { WNWG_ADDR(1, 1) WNWG_BASES() WNWG_PIECE(0); WNWG_PIECE(1); WNWG_PIECE(2); WNWG_PIECE(3); }
+        if constexpr (TP) { WNWG_TAB_ISSUE(0) WNWG_TAB_WAIT(); }
+        { WNWG_ADDR(0, 0) WNWG_BASES() WNWG_PIECE(0); WNWG_PIECE(1); WNWG_PIECE(2); WNWG_PIECE(3); WNWG_PIECE(4); WNWG_PIECE(5); WNWG_PIECE(6); WNWG_PIECE(7); }
+        if constexpr (TP) { WNWG_TAB_ISSUE(KD) WNWG_TAB_WAIT(); }
+        { WNWG_ADDR(1, KD) WNWG_BASES() WNWG_PIECE(0); WNWG_PIECE(1); WNWG_PIECE(2); WNWG_PIECE(3); WNWG_PIECE(4); WNWG_PIECE(5); WNWG_PIECE(6); WNWG_PIECE(7); }
+        if constexpr (TP) { WNWG_TAB_ISSUE(2 * KD < nch ? 2 * KD : nch - KD) WNWG_TAB_WAIT(); }
         WNWG_WAIT();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -217,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
     if constexpr ((ks) + 1 < GEMM_KC / 2) { WNWG_READ_FRAGS((ks) + 1) }                                     \
     WNWG_MFMA(Y, ks)                                                                                        \
     WNWG_PIECE(p);
-#define WNWG_CHUNK(Y)                                                                                       \
+#define WNWG_CHUNK1(Y)                                                                                      \
     {                                                                                                       \
         const float* As = lds + cur * STG + wm * 32 + l31;                                                  \
         const float* Bs = lds + cur * STG + A_ST + wn * (32 * NT) + l31;                                    \
@@ -229,12 +265,67 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
         __builtin_amdgcn_sched_barrier(0);                                                                  \
         WNWG_BASES()                                                                                        \
         WNWG_REGION(Y, 0, 0) WNWG_REGION(Y, 1, 1) WNWG_REGION(Y, 2, 2) WNWG_REGION(Y, 3, 3)                 \
-        WNWG_REGION(Y, 4, 4) WNWG_REGION(Y, 5, 4) WNWG_REGION(Y, 6, 4) WNWG_REGION(Y, 7, 4)                 \
+        WNWG_REGION(Y, 4, 4)                                                                                \
+        if constexpr (TP) { WNWG_TAB_ISSUE(ch + 3 < nch ? ch + 3 : nch - 1) }                               \
+        WNWG_REGION(Y, 5, 4) WNWG_REGION(Y, 6, 4) WNWG_REGION(Y, 7, 4)                                      \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
+        if constexpr (TP) WNWG_TAB_WAIT();                                                                  \
         WNWG_WAIT();                                        /* chunk ch + 1 landed, the newest in flight */ \
         __builtin_amdgcn_s_barrier();                                                                       \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
         cur = cur == 2 ? 0 : cur + 1;                                                                       \
+    }
+    // KD = 2: a stage is two chunks = 16 k-step regions between two barriers.  The fragments run one region ahead ACROSS the chunk
+    // and the stage boundary: the wait for the next stage's landing and the barrier stand in front of the LAST region (technique of
+    // the hand-written small loop, gemm_f32_small.hip), which reads the next stage's first fragments under its own MFMAs.  Every
+    // fragment read of this stage has returned before the barrier (lgkmcnt(0): issued a whole region earlier), so the DMA that
+    // the next iteration aims at this stage's successor-but-one - the stage two barriers back - never meets a pending read.
+    // Same products, same order per accumulator element as KD = 1: bit-identical.
+    float fa[8 * KD][2], fb[8 * KD][NT];
+#define WNWG_RD(r, Ap, Bp)                                                                                  \
+    _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) fa[r][mt] = (Ap)[((r) >> 3) * CST + (2 * ((r) & 7) + lhi) * 128 + mt * 64]; \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) fb[r][nt] = (Bp)[((r) >> 3) * CST + (2 * ((r) & 7) + lhi) * BN + nt * 32];
+#define WNWG_MM(Y, r)                                                                                       \
+    _Pragma("unroll") for (int mt = 0; mt < 2; ++mt)                                                        \
+        _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                                   \
+            Y[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[r][mt], fb[r][nt], Y[mt][nt], 0, 0, 0);
+#define WNWG_R2(Y, r)                                                                                       \
+    __builtin_amdgcn_sched_barrier(0);                                                                      \
+    WNWG_RD((r) + 1, As, Bs)                                                                                \
+    WNWG_MM(Y, r)                                                                                           \
+    WNWG_PIECE(r);
+#define WNWG_CHUNK2(Y)                                                                                      \
+    {                                                                                                       \
+        const float* As = lds + cur * STG + wm * 32 + l31;                                                  \
+        const float* Bs = lds + cur * STG + A_ST + wn * (32 * NT) + l31;                                    \
+        const int nx = cur == 2 ? 0 : cur + 1;                                                              \
+        const float* An = lds + nx * STG + wm * 32 + l31;                                                   \
+        const float* Bn = lds + nx * STG + A_ST + wn * (32 * NT) + l31;                                     \
+        const int nb = cur >= 1 ? cur - 1 : 2;              /* the stage of chunks ch - 2, ch - 1 */        \
+        const int cn = ch + 2 * KD < nch ? ch + 2 * KD : nch - KD;                                          \
+        WNWG_ADDR(nb, cn)                                                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        WNWG_BASES()                                                                                        \
+        WNWG_R2(Y, 0) WNWG_R2(Y, 1) WNWG_R2(Y, 2) WNWG_R2(Y, 3) WNWG_R2(Y, 4) WNWG_R2(Y, 5) WNWG_R2(Y, 6) WNWG_R2(Y, 7)   \
+        WNWG_R2(Y, 8) WNWG_R2(Y, 9)                                                                         \
+        WNWG_TAB_ISSUE(ch + 3 * KD < nch ? ch + 3 * KD : nch - KD)                                          \
+        WNWG_R2(Y, 10) WNWG_R2(Y, 11) WNWG_R2(Y, 12) WNWG_R2(Y, 13) WNWG_R2(Y, 14)                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        WNWG_TAB_WAIT();                                    /* ... and this stage is read out */            \
+        WNWG_WAIT();                                        /* the next stage landed, the newest in flight */ \
+        __builtin_amdgcn_s_barrier();                                                                       \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        WNWG_RD(0, An, Bn)                                                                                  \
+        WNWG_MM(Y, 15)                                                                                      \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        cur = nx;                                                                                           \
+    }
+#define WNWG_CHUNK(Y)                                                                                       \
+    if constexpr (KD == 1) WNWG_CHUNK1(Y) else WNWG_CHUNK2(Y)
+    if constexpr (KD == 2) {
+        const float* As = lds + wm * 32 + l31;
+        const float* Bs = lds + A_ST + wn * (32 * NT) + l31;
+        WNWG_RD(0, As, Bs)
     }
 
     // gate and store one accumulator set: packed column n of the batch item -> natural column (n / d) NI d + n % d + par d
@@ -254,7 +345,7 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
         }                                                                                                   \
     }
 
-#define WNWG_RUN(k, end) for (; ch < (end); ++ch) WNWG_CHUNK(X[k])
+#define WNWG_RUN(k, end) for (; ch < (end); ch += KD) WNWG_CHUNK(X[k])
 #define WNWG_DRAIN()                                                                                        \
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      /* the re-issued tail DMAs still target LDS */    \
     __builtin_amdgcn_s_barrier();
@@ -288,19 +379,28 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
             for (int j = 0; j < NT; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
+                    if constexpr (NT == 2)
+                        if (r == 0) asm volatile("" : "+a"(X[0][i][j]), "+a"(X[1][i][j]), "+a"(X[2][i][j]), "+a"(X[3][i][j]));
                     const float p1 = X[0][i][j][r], p2 = X[1][i][j][r], p3 = X[2][i][j][r], p4 = X[3][i][j][r];
                     const float sa = p1 + p2, sb = p1 - p2, sc = p3 + p4, se = p3 - p4;
                     X[0][i][j][r] = sa + sc;
                     X[1][i][j][r] = sb + 2.0f * se;
                     X[2][i][j][r] = sa + 4.0f * sc;
                     X[3][i][j][r] = sb + 8.0f * se;
+                    // (128 quad columns: one 16-register block of the four sets at a time, so that the butterfly never holds more)
+                    if constexpr (NT == 2)
+                        if (r == 15) asm volatile("" : "+a"(X[0][i][j]), "+a"(X[1][i][j]), "+a"(X[2][i][j]), "+a"(X[3][i][j]));
                 }
         // the four sums exist HERE, in the accumulators' own registers: left to itself the compiler forms Y1..Y3 only in front of their
         // phases and holds a, c and the four products until then (224 registers where 128 do)
 #pragma unroll
         for (int k = 0; k < NI; ++k)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) asm volatile("" : "+v"(X[k][i][0]));
+            for (int i = 0; i < 2; ++i) {
+                // (128 quad columns: 256 accumulator registers - the accumulator half of the one-wave-per-SIMD register file)
+                if constexpr (NT == 2) { asm volatile("" : "+a"(X[k][i][0])); asm volatile("" : "+a"(X[k][i][1])); }
+                else asm volatile("" : "+v"(X[k][i][0]));
+            }
         WNWG_RUN(0, ps[1])
         WNWG_GATE(X[0], 0)
         WNWG_RUN(1, ps[2])
@@ -315,12 +415,19 @@ __global__ __launch_bounds__(256, 2) void wn_winograd_layer_f32_kernel(const WnW
 #undef WNWG_RUN
 #undef WNWG_GATE
 #undef WNWG_CHUNK
+#undef WNWG_CHUNK2
+#undef WNWG_R2
+#undef WNWG_MM
+#undef WNWG_RD
+#undef WNWG_CHUNK1
 #undef WNWG_REGION
 #undef WNWG_MFMA
 #undef WNWG_READ_FRAGS
 #undef WNWG_WAIT
 #undef WNWG_PIECE
 #undef WNWG_BASES
+#undef WNWG_TAB_WAIT
+#undef WNWG_TAB_ISSUE
 #undef WNWG_ADDR
 }
 
@@ -333,17 +440,22 @@ bool wn_winograd_layer_f43_supported(int C, int H) {
 }
 
 namespace {
-template <int NT, int F43 = 0>
+thread_local int t_last_f43_width = 0;
+
+template <int NT, int F43, int KD, int TP>
 int launch_wnwg_shape(WnWinogradLayerArgs a, int kt, long long kt_total, hipStream_t stream) {
     a.kt = kt;
     a.kt_total = (int)kt_total;
     const long long blocks = 8ll * (a.C / 64) * ((kt_total + 7) / 8);
     CTTS_CHECK_ARG(blocks > 0 && blocks < (1ll << 31) && kt_total < (1ll << 31), "wn_winograd_layer: grid %lld", blocks);
-    hipLaunchKernelGGL((wn_winograd_layer_f32_kernel<NT, F43>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((wn_winograd_layer_f32_kernel<NT, F43, KD, TP>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
     CTTS_CHECK_LAUNCH("wn_winograd_layer");
     return CTTS_OK;
 }
+
 }  // namespace
+
+int last_wn_winograd_f43_width() { return t_last_f43_width; }
 
 int launch_wn_winograd_layer(const WnWinogradLayerArgs& a_in, hipStream_t stream) {
     WnWinogradLayerArgs a = a_in;
@@ -361,8 +473,24 @@ int launch_wn_winograd_layer(const WnWinogradLayerArgs& a_in, hipStream_t stream
                    "wn_winograd_layer: cond rows (in_place=%d d=%d)", a.in_place, a.d);
     a.b0 = 0;
     a.col0 = 0;
-    if (f43) return launch_wnwg_shape<1, 1>(a, a.ntiles, (long long)a.ntiles * a.batch, stream);
     const Tuning tn = tuning();
+    if (f43) {
+        // 64 quad columns with two chunks per stage at every grid size: 3.786 ms per config-2 layer where the parent's kernel (one chunk
+        // per stage, table read by a plain load: kept as the CTTS_F32_FORCE_SMALL arm) takes 4.002 and the 128-column shape 4.233
+        // (profiles/r26_01_f43_wide_gonogo.txt).  The 128-column shape stays reachable as the CTTS_F32_NO_SMALL arm; all three sum
+        // every column's products in the same order: bit-identical.
+        // (two chunks per stage: every phase - n1, n2 or nh chunks - must be a whole number of stages; C % 128 == 0 already holds)
+        const bool kd2 = a.H % (2 * GEMM_KC) == 0;
+        if (tn.f32_no_small && kd2) {
+            const int wt = (a.ntiles + 1) / 2;            // 128-column tiles per batch item
+            CTTS_CHECK_ARG((long long)wt * 128 <= a.ldp, "wn_winograd_layer: %d tiles of 128 quad columns beyond ldp=%d", wt, a.ldp);
+            t_last_f43_width = 128;
+            return launch_wnwg_shape<2, 1, 2, 1>(a, wt, (long long)wt * a.batch, stream);
+        }
+        t_last_f43_width = 64;
+        if (tn.f32_force_small || !kd2) return launch_wnwg_shape<1, 1, 1, 0>(a, a.ntiles, (long long)a.ntiles * a.batch, stream);
+        return launch_wnwg_shape<1, 1, 2, 1>(a, a.ntiles, (long long)a.ntiles * a.batch, stream);
+    }
     const int ncb = a.C / 64;
     const long long slots = 2ll * wf_row_cus();
     const int kt_narrow = (a.Lp + 63) / 64;
@@ -370,7 +498,7 @@ int launch_wn_winograd_layer(const WnWinogradLayerArgs& a_in, hipStream_t stream
     // the narrow shape where the wide one would run fewer than two whole rounds (the role of gemm_f32_small_applies): no peel exists
     // there, and three narrow workgroups fit a CU.  Measured at one 900-frame utterance (904 wide workgroups): 72.2 against 73.2 ms
     // per step (profiles/r17_01_winograd_fused_ab.txt); from four utterances on the wide shape with its peel is level or ahead
-    if (!tn.f32_no_small && (tn.f32_force_small || ncb * tiles < 2 * slots)) return launch_wnwg_shape<1>(a, kt_narrow, (long long)kt_narrow * a.batch, stream);
+    if (!tn.f32_no_small && (tn.f32_force_small || ncb * tiles < 2 * slots)) return launch_wnwg_shape<1, 0, 1, 0>(a, kt_narrow, (long long)kt_narrow * a.batch, stream);
     // Round-aligned launch (gemm_f32.hip, launch_gemm_f32): the tiles beyond the last whole round of 2 x CUs workgroups - they lie at
     // the end of the last batch item - go to a launch of the narrow shape FIRST, and the wide launch covers the rest
     if (!tn.f32_no_round_split && !tn.f32_no_small) {
@@ -382,11 +510,11 @@ int launch_wn_winograd_layer(const WnWinogradLayerArgs& a_in, hipStream_t stream
             r.b0 = a.batch - 1;
             r.col0 = (int)(a.ntiles - rem_tiles) * 128;
             const int kt = (a.Lp - r.col0 + 63) / 64;
-            if (int rc = launch_wnwg_shape<1>(r, kt, kt, stream)) return rc;
+            if (int rc = launch_wnwg_shape<1, 0, 1, 0>(r, kt, kt, stream)) return rc;
             tiles -= rem_tiles;
         }
     }
-    return launch_wnwg_shape<2>(a, a.ntiles, tiles, stream);
+    return launch_wnwg_shape<2, 0, 1, 0>(a, a.ntiles, tiles, stream);
 }
 
 }  // namespace ctts

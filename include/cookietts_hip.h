@@ -1158,6 +1158,9 @@ int ctts_pcm16_concat(const void* audio, int32_t is_half, const int32_t* frames,
  * MFMA, and so do the two entry points without a config struct (ctts_lstm_seq_f32's input projection,
  * ctts_taco_decoder_init_f32's processed memory). */
 int ctts_last_gemm_loop(void);
+/* Quad columns per workgroup (64 or 128) of the calling thread's most recent Winograd F(4,3) in-layer launch of the fp32 WaveGlow; 0
+ * before the first.  64 always, unless CTTS_F32_NO_SMALL selects the 128-column one-workgroup-per-CU shape (an A/B arm; same bits). */
+int ctts_last_winograd_f43_width(void);
 
 /* Launch-shape overrides for A/B measurements (CTTS_F32_NO_GLDS, CTTS_F32_NO_SMALL, CTTS_F32_FORCE_SMALL, CTTS_GEMM_NO_XCD_PAIR, CTTS_BF16_NO_WIDE /
  * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD, CTTS_F32_NO_WINOGRAD, CTTS_F32_WINOGRAD_MIN, CTTS_F32_WINOGRAD_PLAIN, CTTS_F32_WINOGRAD_FUSED_MIN, CTTS_F32_WINOGRAD_NO_FUSED, CTTS_F32_WINOGRAD_F43_MIN, CTTS_F32_WINOGRAD_NO_F43) never change results beyond the parity

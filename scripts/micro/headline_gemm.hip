@@ -23,6 +23,36 @@ void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(s
 bool gemm_f32_small_applies(int, const GemmArgs&) { return false; }
 int launch_gemm_f32_small(int, const GemmArgs&, hipStream_t) { return CTTS_E_ARG; }
 int wf_row_cus() { return 256; }
+// Whole wide rounds below which the F(4,3) layer stays on the 64-column shape (a wide round = one workgroup per CU)
+constexpr int WNWG_F43_WIDE_MIN_ROUNDS = 2;
+
+// The F(4,3) launch as the go / no-go of the 128-column shape ran it (HG_F43_WIDE; the library keeps the 64-column shape at every
+// size, wn_winograd_layer.hip): a.ntiles counts 64-column tiles, KDN / KDW = chunks per stage of the 64- and of the 128-column
+// shape.  narrow / wide: that shape everywhere; neither: by grid size, with the round-aligned peel of the F(2,3) branch.
+template <int KDN, int KDW>
+int launch_wnwg_f43(const WnWinogradLayerArgs& a, bool narrow, bool wide, bool no_round_split, hipStream_t stream) {
+    const int ncb = a.C / 64;
+    const long long slots = wf_row_cus();                 // 512 registers per lane: one workgroup per CU
+    const int wt = (a.ntiles + 1) / 2;                    // 128-column tiles per batch item
+    long long tiles = (long long)wt * a.batch;
+    if (!wide && (narrow || ncb * tiles < WNWG_F43_WIDE_MIN_ROUNDS * slots || (long long)wt * 128 > a.ldp)) {
+        return launch_wnwg_shape<1, 1, KDN, 1>(a, a.ntiles, (long long)a.ntiles * a.batch, stream);
+    }
+    CTTS_CHECK_ARG((long long)wt * 128 <= a.ldp, "wn_winograd_layer: %d tiles of 128 quad columns beyond ldp=%d", wt, a.ldp);
+    if (!wide && !no_round_split) {
+        const long long rounds = ncb * tiles / slots;
+        const long long rem_tiles = (ncb * tiles - rounds * slots + ncb - 1) / ncb;
+        if (rounds >= 2 && rem_tiles > 0 && rem_tiles * ncb <= slots * 3 / 10 && rem_tiles < wt && (long long)(wt - rem_tiles) * 128 < a.Lp) {
+            WnWinogradLayerArgs r = a;
+            r.b0 = a.batch - 1;
+            r.col0 = (int)(wt - rem_tiles) * 128;
+            const int kt = (a.Lp - r.col0 + 63) / 64;
+            if (int rc = launch_wnwg_shape<1, 1, KDN, 1>(r, kt, kt, stream)) return rc;
+            tiles -= rem_tiles;
+        }
+    }
+    return launch_wnwg_shape<2, 1, KDW, 1>(a, wt, tiles, stream);
+}
 }  // namespace ctts
 using namespace ctts;
 // stand-in for the traffic of a Winograd F(2,3) input transform: every thread reads 3 and writes 5 16-byte units
@@ -204,6 +234,74 @@ int main(int argc, char** argv) {
                 f.ldp = ldq; f.Lp = Lq_of(f.d); f.ntiles = (f.Lp + 63) / 64;
                 return f;
             };
+            if (getenv("HG_F43_WIDE")) {
+                // Go / no-go for the shapes of the F(4,3) layer (profiles/r26_01_f43_wide_gonogo.txt): the parent's kernel (64 quad columns,
+                // one chunk per stage, chunk table read by a plain load) against the same shape with the table fetched ahead, with
+                // two chunks per stage, and the 128-quad-column one-workgroup-per-CU shape with one and with two chunks per stage (with
+                // their round-aligned peel).  Every arm is first compared with f43_reference_kernel and bit for bit with the parent's.
+                //   HG_WINOGRAD=1 HG_F43=1 HG_F43_WIDE=1 [HG_ROUNDS=5]
+                constexpr int NA = 5;
+                static const char* an[NA] = {"64 col, KD 1, plain table (parent)", "64 col, KD 1, table ahead", "64 col, KD 2", "128 col, KD 1 + peel", "128 col, KD 2 + peel"};
+                unsetenv("CTTS_F32_NO_ROUND_SPLIT"); reload_tuning();
+                auto run_arm = [&](int arm, WnWinogradLayerArgs f) {
+                    f.b0 = 0; f.col0 = 0;
+                    switch (arm) {
+                        case 0: return launch_wnwg_shape<1, 1, 1, 0>(f, f.ntiles, (long long)f.ntiles * f.batch, st);
+                        case 1: return launch_wnwg_f43<1, 1>(f, true, false, false, st);
+                        case 2: return launch_wnwg_f43<2, 1>(f, true, false, false, st);
+                        case 3: return launch_wnwg_f43<1, 1>(f, false, false, false, st);
+                        default: return launch_wnwg_f43<1, 2>(f, false, false, false, st);
+                    }
+                };
+                float* act3;
+                CK(hipMalloc(&act3, (size_t)B * C * ld * 4));
+                const size_t n = (size_t)B * C * ld;
+                for (int i = 0; i < 2; ++i) {
+                    WnWinogradLayerArgs f = f43_args(i);
+                    CK(hipMemsetAsync(act, 0, n * 4, st));
+                    f.act = act3; CK(hipMemsetAsync(act3, 0, n * 4, st));
+                    if (run_arm(0, f)) return 1;
+                    hipLaunchKernelGGL(f43_reference_kernel, dim3((unsigned)((f.Lp + 255) / 256), C, B), dim3(256), 0, st, f43_args(i), act);
+                    for (int arm = 0; arm < NA; ++arm) {
+                        f.act = act2; CK(hipMemsetAsync(act2, 0, n * 4, st)); CK(hipMemsetAsync(dmax, 0, 8, st));
+                        if (run_arm(arm, f)) return 1;
+                        unsigned hd[2], hb[2];
+                        hipLaunchKernelGGL(max_diff_kernel, dim3(4096), dim3(256), 0, st, act, act2, n, dmax);
+                        CK(hipMemcpyAsync(hd, dmax, 8, hipMemcpyDeviceToHost, st)); CK(hipStreamSynchronize(st));
+                        CK(hipMemsetAsync(dmax, 0, 8, st));
+                        hipLaunchKernelGGL(max_diff_kernel, dim3(4096), dim3(256), 0, st, act3, act2, n, dmax);
+                        CK(hipMemcpyAsync(hb, dmax, 8, hipMemcpyDeviceToHost, st)); CK(hipStreamSynchronize(st));
+                        float fd[2], fb[2]; memcpy(fd, hd, 8); memcpy(fb, hb, 8);
+                        printf("d = %3d  %-36s max |arm - reference| = %.3e (max |reference| %.3e), max |arm - parent's| = %.1e, width %d\n", f.d, an[arm], fd[0],
+                               fd[1], fb[0], arm >= 3 ? 128 : 64);
+                        if (!(fd[0] <= 2e-5f) || !(fd[1] > 0.01f) || fb[0] != 0.f) { printf("MISMATCH\n"); return 2; }
+                    }
+                }
+                const int rounds = getenv("HG_ROUNDS") ? atoi(getenv("HG_ROUNDS")) : 5, reps = 12;
+                float lo[NA], hi[NA], sum[NA];
+                for (int arm = 0; arm < NA; ++arm) { lo[arm] = 1e9f; hi[arm] = 0.f; sum[arm] = 0.f; }
+                for (int r = 0; r < rounds; ++r)
+                    for (int arm = 0; arm < NA; ++arm) {
+                        for (int i = 0; i < 4; ++i) if (run_arm(arm, f43_args(i))) return 1;
+                        CK(hipStreamSynchronize(st));
+                        CK(hipEventRecord(e0, st));
+                        for (int i = 0; i < reps; ++i) if (run_arm(arm, f43_args(i))) return 1;
+                        CK(hipEventRecord(e1, st));
+                        CK(hipStreamSynchronize(st));
+                        float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                        ms /= reps;
+                        printf("round %d  %-36s %.4f ms per layer\n", r, an[arm], ms);
+                        lo[arm] = ms < lo[arm] ? ms : lo[arm]; hi[arm] = ms > hi[arm] ? ms : hi[arm]; sum[arm] += ms;
+                    }
+                for (int arm = 1; arm < NA; ++arm) {
+                    const float s0 = hi[0] - lo[0], s1 = hi[arm] - lo[arm], spread = s0 > s1 ? s0 : s1;
+                    const float gain = (sum[0] - sum[arm]) / rounds;
+                    printf("%-36s %.4f ms (%.4f-%.4f) against the parent's %.4f ms (%.4f-%.4f): gain %.4f ms = %.1f x the larger spread%s\n", an[arm],
+                           sum[arm] / rounds, lo[arm], hi[arm], sum[0] / rounds, lo[0], hi[0], gain, gain / (spread > 0.f ? spread : 1e-9f),
+                           gain > 10.f * spread && gain >= 0.18f ? "  -> GO" : "  -> NO-GO");
+                }
+                return 0;
+            }
             for (int i = 0; i < 2; ++i) {
                 WnWinogradLayerArgs f = f43_args(i);
                 CK(hipMemsetAsync(act, 0, (size_t)B * C * ld * 4, st)); CK(hipMemsetAsync(act2, 0, (size_t)B * C * ld * 4, st));
