@@ -158,6 +158,11 @@ class RetryStatus(C.Structure):
                 ("n_without_winner", C.c_int32), ("max_best_length", C.c_int32), ("max_best_T", C.c_int32)]
 
 
+class TacoLossParams(C.Structure):
+    """``ctts_taco_loss_params``."""
+    _fields_ = [("gate_positive_weight", C.c_double), ("sigma", C.c_double), ("weights", C.c_double * 9)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check every symbol the
 # header declares is exported.
 _CFG = C.POINTER(WaveGlowConfig)
@@ -328,7 +333,14 @@ SIGNATURES = {
     "ctts_alignment_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "ctts_alignment_metric_f32": (C.c_int, [_FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_float, _FP, _FP,
                                             C.c_size_t, _FP]),
+    "ctts_alignment_metric_masked_f32": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_float, _FP, _FP,
+                                                   C.c_size_t, _FP]),
     "ctts_first_over_thresh_f32": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_float, _FP, _FP]),
+    "ctts_taco_loss_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "ctts_taco_loss_f32": (C.c_int, [C.POINTER(TacoLossParams)] + [_FP] * 13 + [C.c_int32] * 4 + [_FP, _FP, _FP, C.c_size_t,
+                                                                                                  _FP]),
+    "ctts_taco_loss_finalize_f32": (C.c_int, [C.POINTER(TacoLossParams)] + [_FP] * 9 + [C.c_int32] * 4 + [_FP, _FP, _FP,
+                                                                                                          C.c_size_t, _FP]),
     "ctts_taco_stop_state_bytes": (C.c_size_t, [C.c_int32]),
     "ctts_taco_stop_reset": (C.c_int, [_FP, C.c_int32, C.c_int32, _FP]),
     "ctts_taco_stop_rule_f32": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _FP, _FP]),

@@ -4,6 +4,7 @@
 //
 //   stage 1  align_rows_kernel    grid (dec tiles, B): per decoder step the max / first arg-max over encoder
 //                                 tokens (one wave per row) and, per tile, the column sums over the valid steps
+//                                 (<true>: steps past a second per-item length read as zero, for Tacotron2Loss)
 //   stage 2  align_finish_kernel  grid (B): fixed-order reduction of the tile sums and the six scores
 //   first_over_thresh_kernel      grid (B): first step whose gate reaches the threshold (else T-1)
 // All reductions have a fixed order: results are run-to-run identical.
@@ -20,12 +21,17 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// MASKED: decoder steps at or past valid_len[b] read as zero (the state the reference's first alignment_metric call leaves
+// its argument in, utils.py:81, when a second call scores the same tensor against other lengths: loss_function.py:251, :270)
+template <bool MASKED>
 __global__ __launch_bounds__(256) void align_rows_kernel(const float* __restrict__ al, const float* __restrict__ out_len,
+                                                         const float* __restrict__ valid_len,
                                                          float* __restrict__ values, float* __restrict__ idx,
                                                          float* __restrict__ partial, int dec, int enc, int tiles) {
     const int b = blockIdx.y, tile = blockIdx.x;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const float olen = out_len ? out_len[b] : (float)(dec - 1);
+    const float vlen = MASKED ? valid_len[b] : 0.f;
     const float* A = al + (size_t)b * dec * enc;
     const int d0 = tile * AL_ROWS;
     // max / first arg-max over the encoder axis (torch.max(dim): first maximal index)
@@ -36,7 +42,7 @@ __global__ __launch_bounds__(256) void align_rows_kernel(const float* __restrict
         float best = -INFINITY;
         int bi = 0x7fffffff;
         for (int e = lane; e < enc; e += 64) {
-            const float v = row[e];
+            const float v = (MASKED && !((float)d < vlen)) ? 0.f : row[e];
             if (v > best) { best = v; bi = e; }             // ascending e per lane: first occurrence kept
         }
 #pragma unroll
@@ -55,7 +61,7 @@ __global__ __launch_bounds__(256) void align_rows_kernel(const float* __restrict
         float s = 0.f;
         for (int r = 0; r < AL_ROWS; ++r) {
             const int d = d0 + r;
-            if (d < dec && (float)d < olen) s += A[(size_t)d * enc + e];
+            if (d < dec && (float)d < olen && (!MASKED || (float)d < vlen)) s += A[(size_t)d * enc + e];
         }
         partial[((size_t)b * tiles + tile) * enc + e] = s;
     }
@@ -204,6 +210,14 @@ size_t ctts_alignment_workspace_bytes(int32_t batch, int32_t dec, int32_t enc) {
 int ctts_alignment_metric_f32(const float* alignments, const float* input_lengths, const float* output_lengths,
                               int32_t batch, int32_t dec, int32_t enc, float enc_min_thresh, double* out,
                               void* workspace, size_t workspace_bytes, void* stream) {
+    return ctts_alignment_metric_masked_f32(alignments, input_lengths, output_lengths, nullptr, batch, dec, enc, enc_min_thresh,
+                                            out, workspace, workspace_bytes, stream);
+}
+
+int ctts_alignment_metric_masked_f32(const float* alignments, const float* input_lengths, const float* output_lengths,
+                                     const float* valid_lengths, int32_t batch, int32_t dec, int32_t enc,
+                                     float enc_min_thresh, double* out, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
     CTTS_CHECK_ARG(alignments && out && workspace && batch >= 1 && dec >= 1 && enc >= 1, "alignment_metric: bad argument");
     const size_t need = ctts_alignment_workspace_bytes(batch, dec, enc);
     if (workspace_bytes < need) {
@@ -215,8 +229,12 @@ int ctts_alignment_metric_f32(const float* alignments, const float* input_length
     float* values = static_cast<float*>(workspace);
     float* idx = values + (size_t)batch * dec;
     float* partial = idx + (size_t)batch * dec;
-    hipLaunchKernelGGL(align_rows_kernel, dim3(tiles, batch), dim3(256), 0, s, alignments, output_lengths, values, idx,
-                       partial, dec, enc, tiles);
+    if (valid_lengths)
+        hipLaunchKernelGGL(align_rows_kernel<true>, dim3(tiles, batch), dim3(256), 0, s, alignments, output_lengths,
+                           valid_lengths, values, idx, partial, dec, enc, tiles);
+    else
+        hipLaunchKernelGGL(align_rows_kernel<false>, dim3(tiles, batch), dim3(256), 0, s, alignments, output_lengths,
+                           valid_lengths, values, idx, partial, dec, enc, tiles);
     CTTS_CHECK_LAUNCH("align_rows");
     hipLaunchKernelGGL(align_finish_kernel, dim3(batch), dim3(256), 0, s, values, idx, partial, input_lengths,
                        output_lengths, out, dec, enc, tiles, enc_min_thresh);

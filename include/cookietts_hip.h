@@ -1032,6 +1032,14 @@ size_t ctts_alignment_workspace_bytes(int32_t batch, int32_t dec, int32_t enc);
 int ctts_alignment_metric_f32(const float* alignments, const float* input_lengths, const float* output_lengths,
                               int32_t batch, int32_t dec, int32_t enc, float enc_min_thresh, double* out,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* The same metric with a validity cut: valid_lengths device fp32 [batch] or NULL; decoder steps d >= valid_lengths[b] read as
+ * zero (row max 0 at arg-max 0, nothing added to the encoder totals).  This is what the reference's SECOND alignment_metric call
+ * of Tacotron2Loss (loss_function.py:270) sees: the first call (:251) zeroed its argument past the ground-truth length in place
+ * (utils.py:81).  NULL: ctts_alignment_metric_f32 itself, bit for bit.  Same workspace. */
+int ctts_alignment_metric_masked_f32(const float* alignments, const float* input_lengths, const float* output_lengths,
+                                     const float* valid_lengths, int32_t batch, int32_t dec, int32_t enc,
+                                     float enc_min_thresh, double* out, void* workspace, size_t workspace_bytes,
+                                     void* stream);
 /* utils/model/utils.py:47-56 (= text2speech.py:152-161) `get_first_over_thresh(x, threshold)`:
  * x [batch][T] fp32 -> out int32 [batch], first step with x >= threshold, else T-1. */
 int ctts_first_over_thresh_f32(const float* x, int32_t batch, int32_t T, float threshold, int32_t* out, void* stream);
@@ -1128,6 +1136,58 @@ int ctts_retry_vocoder_batch_f32(const ctts_retry_config* cfg, const void* state
  * capacity and offsets[batch] is minus the total; batch * (ld + silence_samples) always suffices. */
 int ctts_pcm16_concat(const void* audio, int32_t is_half, const int32_t* frames, int32_t batch, int64_t ld, int32_t hop,
                       int32_t silence_samples, int16_t* pcm, int64_t pcm_capacity, int64_t* offsets, void* stream);
+
+/* ---- Tacotron2Loss on the outputs of the teacher-forced pass (_2_ttm/tacotron2_tm/loss_function.py:96-290) --------
+ * No gradient: the validation loss, the per-file score table and the inference-style attention score.  Every per-item number is
+ * summed on the device into one fp64 table [batch][CTTS_TACO_LOSS_COLUMNS]; the batch terms [CTTS_TACO_LOSS_TERMS] are sums over
+ * that table in item order.  No float atomics: results repeat bit for bit, and an item's row does not depend on its neighbours
+ * except in the two columns marked (batch).  No input is written (the reference overwrites pred_mel_postnet, :200, and the
+ * alignments, utils.py:81).
+ *
+ * table columns:  0 mel_length   1 spec_SE   2 postnet_SE        sum over t < mel_length, m of (pred - gt)^2        (:189-202)
+ *                 3 spec_MFSE    4 postnet_MFSE                  sum over t < mel_length of A_t * (A_t / n_mel), A_t = sum_m |d| (:205-213)
+ *                 5 gate_BCE     sum over ALL t < T of BCEWithLogits(pos_weight)                                  (:216-218)
+ *                 6 diag_att     7 diag_frames                   guided-attention numerator and mel_length; both 0 where
+ *                                                                pres_prev_state != 0                              (:234-241)
+ *                 8 sylps_kld    1 + logvar - exp(logvar) - mu^2     9 sylps_AE     10 sylps_SE                     (:221-232)
+ *                 11-16          alignment_metric against mel_lengths: diagonality, avg_prob, max / min / avg focus, p_missing_enc (:251)
+ *                 17 pred_mel_length   first frame >= 5 whose gate sigmoid reaches 0.7, else T - 1                  (:266-269)
+ *                 18-23          alignment_metric against pred_mel_length on the alignments cut at mel_length       (:270)
+ *                 24 att_score   :276-283 in IEEE double, Python's operation order and max(); may be NaN
+ *                 25 att_score_filled  column 24 with NaN replaced by the mean of the others, as float32 (:286-287)  (batch)
+ *                 26 spec_MSE    column 1 / (mel_length * n_mel), the file_losses entry (:197)
+ *                 the mis_dur punishment of column 24 reads max(mel_lengths)                                          (batch)
+ * terms:          0 spec_MSE  1 postnet_MSE  2 spec_MFSE  3 postnet_MFSE  4 gate_loss  5 sylps_kld  6 sylps_MAE  7 sylps_MSE
+ *                 8 diag_att  9 loss = sum of terms 0-8 times weights[0-8], in that order (:152-161)
+ *                 10 diagonality  11 avg_max_attention  12 weighted_score */
+#define CTTS_TACO_LOSS_COLUMNS 27
+#define CTTS_TACO_LOSS_TERMS 13
+typedef struct {
+    double gate_positive_weight;   /* hparams.gate_positive_weight */
+    double sigma;                  /* hparams.DiagonalGuidedAttention_sigma */
+    double weights[9];             /* the <term>_weight of terms 0-8 after loss_scalars */
+} ctts_taco_loss_params;
+/* 0 with a ctts_last_error message for a size below 1. */
+size_t ctts_taco_loss_workspace_bytes(int32_t batch, int32_t n_mel, int32_t T, int32_t enc);
+/* pred_mel, pred_mel_postnet, gt_mel [batch][n_mel][T]; gate_logits, gate_target [batch][T]; alignments [batch][T][enc];
+ * sylps_mu, sylps_logvar, pred_sylps, gt_sylps, pres_prev_state fp32 [batch]; mel_lengths, text_lengths int32 [batch]; all on
+ * the device, fp32 tensors contiguous.  Lengths must be at least 1; a length beyond T / enc is read as T / enc everywhere (sums,
+ * counts, metrics and the score alike).
+ * Eight launches: lengths (sigmoid, first five frames zeroed, first over 0.7), mel + gate pass over (64-frame tile, item), guided
+ * attention over (32-frame block, item), the two metrics (two launches each), finalize (one workgroup).  A small workspace: CTTS_E_WORKSPACE. */
+int ctts_taco_loss_f32(const ctts_taco_loss_params* params, const float* pred_mel, const float* pred_mel_postnet,
+                       const float* gt_mel, const float* gate_logits, const float* gate_target, const float* alignments,
+                       const float* sylps_mu, const float* sylps_logvar, const float* pred_sylps, const float* gt_sylps,
+                       const int32_t* mel_lengths, const int32_t* text_lengths, const float* pres_prev_state, int32_t batch,
+                       int32_t n_mel, int32_t T, int32_t enc, double* table, double* terms, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* The finalize launch alone, on a workspace a ctts_taco_loss_f32 call of the same geometry has filled (tile partials, predicted
+ * lengths).  metric_gt / metric_pred [batch][6]: the two metric tables to score, or NULL for the ones in the workspace. */
+int ctts_taco_loss_finalize_f32(const ctts_taco_loss_params* params, const double* metric_gt, const double* metric_pred,
+                                const float* sylps_mu, const float* sylps_logvar, const float* pred_sylps,
+                                const float* gt_sylps, const int32_t* mel_lengths, const int32_t* text_lengths,
+                                const float* pres_prev_state, int32_t batch, int32_t n_mel, int32_t T, int32_t enc,
+                                double* table, double* terms, const void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- main loop of the fp32 conv-GEMM ------------------------------------------------------------------------
  * Every fp32 path of the library (WaveGlow fp32, WaveFlow, the ax WaveGlow, conv1d / LSTM input projections, STFT)
