@@ -158,6 +158,12 @@ class RetryStatus(C.Structure):
                 ("n_without_winner", C.c_int32), ("max_best_length", C.c_int32), ("max_best_T", C.c_int32)]
 
 
+class MelErrorConfig(C.Structure):
+    """``ctts_mel_error_config``."""
+    _fields_ = [("n_windows", C.c_int32), ("filter_lengths", C.c_int32 * 8), ("hop_length", C.c_int32),
+                ("n_mel_channels", C.c_int32), ("framing", C.c_int32), ("clamp_val", C.c_float), ("mag_eps", C.c_float)]
+
+
 class TacoLossParams(C.Structure):
     """``ctts_taco_loss_params``."""
     _fields_ = [("gate_positive_weight", C.c_double), ("sigma", C.c_double), ("weights", C.c_double * 9)]
@@ -341,6 +347,11 @@ SIGNATURES = {
                                                                                                   _FP]),
     "ctts_taco_loss_finalize_f32": (C.c_int, [C.POINTER(TacoLossParams)] + [_FP] * 9 + [C.c_int32] * 4 + [_FP, _FP, _FP,
                                                                                                           C.c_size_t, _FP]),
+    "ctts_mel_error_packed_bytes": (C.c_size_t, [C.POINTER(MelErrorConfig)]),
+    "ctts_mel_error_pack": (C.c_int, [C.POINTER(MelErrorConfig), C.c_int32, _FP, _FP, _FP, _FP]),
+    "ctts_mel_error_workspace_bytes": (C.c_size_t, [C.POINTER(MelErrorConfig)] + [C.c_int32] * 3),
+    "ctts_mel_error_f32": (C.c_int, [C.POINTER(MelErrorConfig)] + [_FP] * 6 + [C.c_int32] * 5 + [_FP] * 4 + [C.c_int32, _FP,
+                                                                                                     C.c_size_t, _FP]),
     "ctts_taco_stop_state_bytes": (C.c_size_t, [C.c_int32]),
     "ctts_taco_stop_reset": (C.c_int, [_FP, C.c_int32, C.c_int32, _FP]),
     "ctts_taco_stop_rule_f32": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _FP, _FP]),

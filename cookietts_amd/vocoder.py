@@ -25,7 +25,7 @@ import torch
 from .waveglow import WaveGlow
 from .waveglow_ax import WaveGlow as WaveGlowAx
 
-__all__ = ["WaveGlowVocoder", "load_waveglow", "waveglow_from_checkpoint", "is_ax_config"]
+__all__ = ["WaveGlowVocoder", "load_waveglow", "waveglow_from_checkpoint", "is_ax_config", "validate"]
 
 # keyword arguments only efficient_model_ax.WaveGlow.__init__ has (efficient_model_ax.py:18-19): the first five are
 # REQUIRED there, so every config written for the ax core names them; the rest are its optional extras
@@ -176,3 +176,24 @@ def load_waveglow(vocoder_path, device='cuda', sigma=0.8, trust_checkpoint=False
     model = waveglow_from_checkpoint(checkpoint).to(device).eval()
     vocoder = WaveGlowVocoder(model, sigma=sigma, speaker_lookup=checkpoint.get('speaker_lookup'))
     return vocoder, checkpoint['waveglow_config']
+
+
+def validate(model, mels, gt_audio, gt_lengths, metric, sigma, speaker_ids=None):
+    """What ``_4_mtw/waveglow/train.py:188-193, 256-291`` does around the metric, for a whole batch: ``model.infer(mels, speaker_ids,
+    sigma=sigma)`` in eval mode under ``torch.random.fork_rng`` with ``manual_seed(0)`` (the same z at every validation), then
+    ``metric.forward`` (a :class:`~cookietts_amd.mel_error.MelSpectrogramError`) of the generated audio against ``gt_audio`` with
+    ``gt_lengths``.  -> ``(average_MSE, average_MAE, result_dict)``.  The model's train / eval mode is left as it was found and the
+    global RNG state is not advanced; no file is read and nothing is plotted."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            devices = [mels.device.index if mels.device.index is not None else torch.cuda.current_device()] if mels.is_cuda else []
+            with torch.random.fork_rng(devices=devices):
+                torch.random.manual_seed(0)
+                audio = model.infer(mels, speaker_ids, sigma=sigma)
+            audio = audio.to(device=gt_audio.device, dtype=torch.float32)
+            result = metric(audio.reshape(audio.shape[0], -1), gt_audio, gt_lengths=gt_lengths)
+    finally:
+        model.train(was_training)
+    return result["average_MSE"], result["average_MAE"], result

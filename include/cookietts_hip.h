@@ -1189,6 +1189,51 @@ int ctts_taco_loss_finalize_f32(const ctts_taco_loss_params* params, const doubl
                                 const float* pres_prev_state, int32_t batch, int32_t n_mel, int32_t T, int32_t enc,
                                 double* table, double* terms, const void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Vocoder validation score: paired multi-window log-mel MSE / MAE (_4_mtw/waveglow/train.py:258-278, --------
+ * _4_mtw/hifigan/train.py:205-223) ------------------------------------------------------------------------------------
+ * For every item b of a batch and every STFT window w, the log-mel of the generated audio is compared with the log-mel of the
+ * ground truth (or with an already-computed ground-truth log-mel), over the ground truth's frames.  Both signals are ragged: each
+ * item has its own length and is reflect-padded at its own end.  All sums are fp64 in a fixed order, without atomics: results
+ * repeat bit for bit and an item's row does not depend on its neighbours.  No input is written.
+ *
+ * table: double [batch][n_windows][CTTS_MEL_ERROR_COLUMNS] followed by CTTS_MEL_ERROR_TERMS batch terms.
+ *   columns:  0 n_frames   1 SAE = sum |d|   2 SSE = sum d^2   3 MAE = SAE / (n_mel * n_frames)   4 MSE = SSE / (n_mel * n_frames)
+ *   terms:    0 average_MSE  1 average_MAE: the mean over (item, window) pairs of the pair means, summed item-major and
+ *             window-minor (train.py:271-278, 294-295)   2 + w: l1[w] = sum_b SAE / sum_b (n_mel * n_frames)  (hifigan/train.py:208-210)
+ * n_frames(b) = min(ground-truth frames, generated frames): callers that validate lengths make that the ground truth's count. */
+#define CTTS_MEL_ERROR_MAX_WINDOWS 8
+#define CTTS_MEL_ERROR_COLUMNS 5
+#define CTTS_MEL_ERROR_TERMS (2 + CTTS_MEL_ERROR_MAX_WINDOWS)
+#define CTTS_MEL_ERROR_TACOTRON 0 /* utils/audio/stft.py:79-111: reflect-pad N/2, frames = T / hop + 1 */
+#define CTTS_MEL_ERROR_NV 1       /* hifigan/nvSTFT.py:92-101: reflect-pad (N - hop) / 2, no centring, frames = (T + 2 pad - N) / hop + 1 */
+#define CTTS_MEL_ERROR_SANITIZE 1 /* flags: the generated audio is read as nan_to_zero(clamp(x, -0.999, 0.999)) (train.py:259-260) */
+typedef struct ctts_mel_error_config {
+    int32_t n_windows;                                    /* 1 to 8 */
+    int32_t filter_lengths[CTTS_MEL_ERROR_MAX_WINDOWS];   /* each a multiple of 16 in [32, 4096] */
+    int32_t hop_length;
+    int32_t n_mel_channels;                               /* 1 to 256 */
+    int32_t framing;                                      /* CTTS_MEL_ERROR_TACOTRON | CTTS_MEL_ERROR_NV */
+    float clamp_val;                                      /* log(max(., clamp_val)) */
+    float mag_eps;                                        /* 0, or nvSTFT's 1e-9: the magnitude is sqrt(re^2 + im^2 + mag_eps) */
+} ctts_mel_error_config;
+/* 0 with a ctts_last_error message for a refused config. */
+size_t ctts_mel_error_packed_bytes(const ctts_mel_error_config* cfg);
+/* One call per window: forward_basis [2*(N/2+1)][N] (window folded in, as ctts_stft_pack takes it), mel_basis [n_mel][N/2+1]. */
+int ctts_mel_error_pack(const ctts_mel_error_config* cfg, int32_t window, const float* forward_basis, const float* mel_basis,
+                        void* packed, void* stream);
+/* T_pred_max / T_gt_max: widths of the two audio tensors; T_gt_max = 0 for the gt_mel form.  0 for a refused config or size. */
+size_t ctts_mel_error_workspace_bytes(const ctts_mel_error_config* cfg, int32_t batch, int32_t T_pred_max, int32_t T_gt_max);
+/* pred [batch][T_pred], gt [batch][T_gt] fp32; pred_lengths, gt_lengths int32 [batch]; all on the device.  Exactly one of gt and
+ * gt_mel ([batch][n_mel][mel_frames], n_windows == 1) is given; with gt_mel, gt_lengths counts FRAMES of gt_mel.  Lengths are
+ * read as they are, clamped to the tensor widths; reflect indices are folded into [0, length), so no read leaves an item's row.
+ * mae_map, pred_map, gt_map: all three or none; [batch][n_windows][n_mel][map_frames], written only below each item's n_frames
+ * (the caller zero-fills).  Per window: framing (one launch, both signals), magnitude GEMM, fused mel-projection + error tiles;
+ * then one finalize workgroup.  A small workspace: CTTS_E_WORKSPACE. */
+int ctts_mel_error_f32(const ctts_mel_error_config* cfg, const void* packed, const float* pred, const int32_t* pred_lengths,
+                       const float* gt, const int32_t* gt_lengths, const float* gt_mel, int32_t flags, int32_t batch,
+                       int32_t T_pred, int32_t T_gt, int32_t mel_frames, double* table, float* mae_map, float* pred_map,
+                       float* gt_map, int32_t map_frames, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- main loop of the fp32 conv-GEMM ------------------------------------------------------------------------
  * Every fp32 path of the library (WaveGlow fp32, WaveFlow, the ax WaveGlow, conv1d / LSTM input projections, STFT)
  * goes through one conv-GEMM.  mode 0 (default): v_mfma_f32_32x32x2_f32, exact fp32 products.  mode 1 ("split bf16"):
