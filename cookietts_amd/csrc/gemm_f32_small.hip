@@ -18,7 +18,6 @@
 //     stages, two chunks ahead, three DMA pieces per chunk per wave, counted vmcnt + s_barrier.
 #include <algorithm>
 #include <atomic>
-#include <mutex>
 
 #include <type_traits>
 
@@ -1852,19 +1851,11 @@ int launch_gemm_f32_small(int epi, const GemmArgs& a, hipStream_t stream) {
         const int nt = (a.L + K_BN - 1) / K_BN;
         const long long nblk = (long long)nt * a.batch;
         CTTS_CHECK_ARG(nblk > 0 && nblk < (1ll << 31), "gemm (split-K fused shape): grid %lld", nblk);
-        constexpr size_t LDS = K_LDS_FLOATS * sizeof(float);         // above the 64 KiB default: opt in once per kernel
+        constexpr size_t LDS = K_LDS_FLOATS * sizeof(float);         // above the 64 KiB default: opt in (allow_dynamic_lds)
         const int vi = a.nseg <= 4 ? 0 : 1;
-        const void* fns[2] = {reinterpret_cast<const void*>(conv_gemm_f32_gate_rs_splitk8_kernel<4>),
-                              reinterpret_cast<const void*>(conv_gemm_f32_gate_rs_splitk8_kernel<GEMM_MAX_SEG>)};
-        {   // once per process and kernel (one process per GPU); a failure is reported by every call that meets it
-            static std::mutex mu;
-            static bool attr_set[2] = {false, false};
-            std::lock_guard<std::mutex> lk(mu);
-            if (!attr_set[vi]) {
-                CTTS_CHECK_HIP(hipFuncSetAttribute(fns[vi], hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-                attr_set[vi] = true;
-            }
-        }
+        int rc = vi == 0 ? CTTS_ALLOW_LDS(conv_gemm_f32_gate_rs_splitk8_kernel<4>, (int)LDS)
+                         : CTTS_ALLOW_LDS(conv_gemm_f32_gate_rs_splitk8_kernel<GEMM_MAX_SEG>, (int)LDS);
+        if (rc) return rc;
         if (vi == 0) hipLaunchKernelGGL((conv_gemm_f32_gate_rs_splitk8_kernel<4>), dim3((unsigned)nblk), dim3(512), LDS, stream, a, nt);
         else hipLaunchKernelGGL((conv_gemm_f32_gate_rs_splitk8_kernel<GEMM_MAX_SEG>), dim3((unsigned)nblk), dim3(512), LDS, stream, a, nt);
         note_gemm_loop(16 | 32);                                     // fp32 MFMA whatever the mode (see cookietts_hip.h)
@@ -1942,18 +1933,10 @@ int launch_wf_row_persistent(const GemmArgs* layers_dev, const WfTailDesc* tails
     const dim3 grid((unsigned)std::max<long long>(want, 1));
     const int vi = max_nseg <= 4 ? 0 : 1;
     if (body == 1) {
-        constexpr size_t LDS = K_LDS_FLOATS * sizeof(float);            // above the 64 KiB default: opt in once per kernel
-        {
-            static std::mutex mu;
-            static bool attr_set[2] = {false, false};
-            std::lock_guard<std::mutex> lk(mu);
-            if (!attr_set[vi]) {
-                const void* fn = vi == 0 ? reinterpret_cast<const void*>(wf_row_persistent_kernel<4, 1>)
-                                         : reinterpret_cast<const void*>(wf_row_persistent_kernel<GEMM_MAX_SEG, 1>);
-                CTTS_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-                attr_set[vi] = true;
-            }
-        }
+        constexpr size_t LDS = K_LDS_FLOATS * sizeof(float);            // above the 64 KiB default: opt in (allow_dynamic_lds)
+        int rc = vi == 0 ? CTTS_ALLOW_LDS((wf_row_persistent_kernel<4, 1>), (int)LDS)
+                         : CTTS_ALLOW_LDS((wf_row_persistent_kernel<GEMM_MAX_SEG, 1>), (int)LDS);
+        if (rc) return rc;
         if (vi == 0) hipLaunchKernelGGL((wf_row_persistent_kernel<4, 1>), grid, dim3(256), LDS, stream, w);
         else hipLaunchKernelGGL((wf_row_persistent_kernel<GEMM_MAX_SEG, 1>), grid, dim3(256), LDS, stream, w);
         note_gemm_loop(16 | 32 | 64 | (tails_dev ? 128 : 0));

@@ -46,7 +46,7 @@ struct BgArgs {
     BgPiece x[4];
     int cend[4];                // chunk index at which piece i ends (cend[3] = nchunks)
     int rows, batch;            // valid rows (the last tile may be padded), real items (columns beyond are padding)
-    // A GEMM may be spread over several LAUNCHES (pipelined step, batched_steps): this role covers chunks [c_begin, c_end) of K;
+    // A GEMM may be spread over several LAUNCHES (pipelined step, BgStep::run_pipelined): this role covers chunks [c_begin, c_end) of K;
     // pmode 1 (EARLY): its sums go to slot `pslot` of `part` and nothing else happens; pmode 2 (FINAL): the sums of slots
     // [0, npart) are added (slot order, then its own) before the epilogue.  pmode 0, c_end = 0: the whole K in one launch.
     // part: [slot][m-tile][item tile][lane][4].
@@ -552,7 +552,6 @@ __global__ __launch_bounds__(WAVES * 64) void bg_cell_attn_kernel(const BgArgs a
     else if (blockIdx.y == 0) attn_pre_body(at, apre, astart, *reinterpret_cast<BgAttnLds*>(bg_lds), blockIdx.x - nblk);
 }
 
-// more than 64 KiB of dynamic LDS has to be allowed per kernel, once (per instantiation: the flag is a template static)
 // both directions of a bidirectional layer advance in ONE launch per time step (blockIdx.z = direction)
 template <int MTW, int NT, int S>
 __global__ __launch_bounds__(256) void bg_seq2_kernel(const BgArgs a0, const BgArgs a1) {
@@ -560,16 +559,6 @@ __global__ __launch_bounds__(256) void bg_seq2_kernel(const BgArgs a0, const BgA
     if (blockIdx.z == 0) bg_body<MTW, NT, S, 4, BG_EPI_SEQ>(a0, bg_lds, blockIdx.x, blockIdx.y);
     else bg_body<MTW, NT, S, 4, BG_EPI_SEQ>(a1, bg_lds, blockIdx.x, blockIdx.y);
 }
-
-template <class K, K kernel>
-int bg_allow_lds(int bytes) {
-    static bool done = false;
-    if (!done && bytes > 64 * 1024)
-        CTTS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    done = true;
-    return CTTS_OK;
-}
-#define BG_ALLOW_LDS(kernel, bytes) bg_allow_lds<decltype(&kernel), &kernel>(bytes)
 
 // Cells.  Shapes (measured, profiles/r6_03 ... r6_07).  DMA traffic of a cell GEMM = W x (B / 16) x (1 / NT + 1 / MTW): every
 // workgroup re-reads the X columns of its items, so more m-tiles per workgroup cut it - but a CU sustains only ~45 GB/s with
@@ -598,10 +587,10 @@ inline int bg_launch_cell(const BgArgs& a, int nb_pad, const AttnArgs* attn, flo
         static_assert(LDS <= 160 * 1024, "LDS of a CU");                                                                          \
         const int nblk = (a.tiles + M - 1) / M;                                                                                   \
         if (attn) {                                                                                                               \
-            if ((rc = BG_ALLOW_LDS((bg_cell_attn_kernel<M, N, SS, WV>), LDS))) return rc;                                         \
+            if ((rc = CTTS_ALLOW_LDS((bg_cell_attn_kernel<M, N, SS, WV>), LDS))) return rc;                                       \
             hipLaunchKernelGGL((bg_cell_attn_kernel<M, N, SS, WV>), dim3(nblk + batch, ny), dim3(64 * WV), LDS, s, a, nblk, *attn, apre, astart);                        \
         } else {                                                                                                                  \
-            if ((rc = BG_ALLOW_LDS((bg_kernel<M, N, SS, WV, BG_EPI_CELL>), LDS))) return rc;                                      \
+            if ((rc = CTTS_ALLOW_LDS((bg_kernel<M, N, SS, WV, BG_EPI_CELL>), LDS))) return rc;                                    \
             hipLaunchKernelGGL((bg_kernel<M, N, SS, WV, BG_EPI_CELL>), dim3(nblk, ny), dim3(64 * WV), LDS, s, a);                 \
         }                                                                                                                         \
     }
@@ -675,7 +664,7 @@ inline int bg_launch_multi8(BgRoles& m, int nb_pad, hipStream_t s) {
 #define BG_M8(MM, N, SS)                                                                                          \
     {                                                                                                             \
         constexpr int LDS = bg_lds_bytes<MM, N, SS, 8>() > bg_lds_bytes<1, 1, 8, 8>() ? bg_lds_bytes<MM, N, SS, 8>() : bg_lds_bytes<1, 1, 8, 8>(); \
-        if ((rc = BG_ALLOW_LDS((bg_multi8_kernel<MM, N, SS>), LDS))) return rc;                                   \
+        if ((rc = CTTS_ALLOW_LDS((bg_multi8_kernel<MM, N, SS>), LDS))) return rc;                                 \
         hipLaunchKernelGGL((bg_multi8_kernel<MM, N, SS>), dim3(blocks), dim3(512), LDS, s, m.small, m.n_small, m.small_epi, m.cell[0], \
                            m.n_cell[0], m.nblk_cell[0], m.cell[1], m.n_cell[1], m.nblk_cell[1], m.pre ? *m.pre : none, m.apre, m.astart); \
     }
@@ -694,7 +683,7 @@ inline int bg_launch_post_multi4(const AttnArgs& at, const float* qbuf, const fl
     {                                                                                                             \
         constexpr int LDS = bg_lds_bytes<MM, N, SS, 4>() > BGA_POST_LDS_BYTES ? bg_lds_bytes<MM, N, SS, 4>() : BGA_POST_LDS_BYTES; \
         const int nb0 = (c0.tiles + MM - 1) / MM, nb1 = (c1.tiles + MM - 1) / MM;                                 \
-        if ((rc = BG_ALLOW_LDS((bg_post_multi4_kernel<MM, N, SS>), LDS))) return rc;                              \
+        if ((rc = CTTS_ALLOW_LDS((bg_post_multi4_kernel<MM, N, SS>), LDS))) return rc;                            \
         hipLaunchKernelGGL((bg_post_multi4_kernel<MM, N, SS>), dim3(batch + (nb0 + nb1) * ny), dim3(256), LDS, s, at, qbuf, apre, astart, \
                            batch, c0, nb0 * ny, nb0, c1, nb1 * ny, nb1);                                          \
     }
@@ -712,7 +701,7 @@ inline int bg_launch_seq(const BgArgs& a0, const BgArgs& a1, int ndir, int nb_pa
 #define BG_SEQ(M, N, SS)                                                                                              \
     {                                                                                                                 \
         constexpr int LDS = bg_lds_bytes<M, N, SS, 4>();                                                              \
-        if ((rc = BG_ALLOW_LDS((bg_seq2_kernel<M, N, SS>), LDS))) return rc;                                          \
+        if ((rc = CTTS_ALLOW_LDS((bg_seq2_kernel<M, N, SS>), LDS))) return rc;                                        \
         hipLaunchKernelGGL((bg_seq2_kernel<M, N, SS>), dim3((a0.tiles + M - 1) / M, nb_pad <= 32 ? 1 : nb_pad / 64, ndir), \
                            dim3(256), LDS, s, a0, a1);                                                                \
     }
@@ -731,7 +720,7 @@ template <int EPI>
 int bg_launch_small(const BgArgs& a, int nb_pad, hipStream_t s) {
     constexpr int LDS = bg_lds_bytes<1, 1, 8, 8>();
     int rc;
-    if ((rc = BG_ALLOW_LDS((bg_kernel<1, 1, 8, 8, EPI>), LDS))) return rc;
+    if ((rc = CTTS_ALLOW_LDS((bg_kernel<1, 1, 8, 8, EPI>), LDS))) return rc;
     hipLaunchKernelGGL((bg_kernel<1, 1, 8, 8, EPI>), dim3(a.tiles, (nb_pad + 15) / 16), dim3(512), LDS, s, a);
     CTTS_CHECK_LAUNCH("bg_small");
     return CTTS_OK;

@@ -259,7 +259,7 @@ int bgx_launch_shape2(const BgArgs& a0, const BgArgs& a1, int nb_pad, hipStream_
                    "bf16x3 cell pair: %d rows are not whole item groups of %d", nb_pad, 16 * NT);
     const int nblk0 = (a0.tiles + MTW - 1) / MTW, nblk1 = (a1.tiles + MTW - 1) / MTW, ny = nb_pad / (16 * NT);
     int rc;
-    if ((rc = BG_ALLOW_LDS((bgx_cell2_kernel<MTW, NT, S, WAVES>), LDS))) return rc;
+    if ((rc = CTTS_ALLOW_LDS((bgx_cell2_kernel<MTW, NT, S, WAVES>), LDS))) return rc;
     hipLaunchKernelGGL((bgx_cell2_kernel<MTW, NT, S, WAVES>), dim3(nblk0 + nblk1, ny), dim3(64 * WAVES), LDS, s, a0, nblk0, a1);
     CTTS_CHECK_LAUNCH("bgx_cell2");
     return CTTS_OK;
@@ -274,10 +274,10 @@ int bgx_launch_shape(const BgArgs& a, int nb_pad, const AttnArgs* attn, float* a
     const int nblk = (a.tiles + MTW - 1) / MTW, ny = nb_pad / (16 * NT);
     int rc;
     if (attn) {
-        if ((rc = BG_ALLOW_LDS((bgx_cell_attn_kernel<MTW, NT, S, WAVES>), LDS))) return rc;
+        if ((rc = CTTS_ALLOW_LDS((bgx_cell_attn_kernel<MTW, NT, S, WAVES>), LDS))) return rc;
         hipLaunchKernelGGL((bgx_cell_attn_kernel<MTW, NT, S, WAVES>), dim3(nblk + batch, ny), dim3(64 * WAVES), LDS, s, a, nblk, *attn, apre, astart);
     } else {
-        if ((rc = BG_ALLOW_LDS((bgx_cell_kernel<MTW, NT, S, WAVES>), LDS))) return rc;
+        if ((rc = CTTS_ALLOW_LDS((bgx_cell_kernel<MTW, NT, S, WAVES>), LDS))) return rc;
         hipLaunchKernelGGL((bgx_cell_kernel<MTW, NT, S, WAVES>), dim3(nblk, ny), dim3(64 * WAVES), LDS, s, a);
     }
     CTTS_CHECK_LAUNCH("bgx_cell");

@@ -801,95 +801,75 @@ __global__ __launch_bounds__(256) void hidden_state_kernel(const float* __restri
 #include "tacotron_batched.h"
 #include "tacotron_batched_bf16x3.h"
 
-// the split-bf16 cell launch of the plain schedule: one shape for every batch above 64 rows (NT and the K split fix an item's bits).
-// Four m-tiles x 32 items per workgroup, 3-deep ring (144 KiB), four waves: of the shapes that fit the LDS and the vmcnt budget it
-// is the fastest on all three cells at 128 and 256 rows - attention RNN at 256 rows 59.4 us against 79.3 as <2, 4, 3, 4> (the fp32
-// launch's tile), 89.9 as <4, 4, 4, 2>, and 94.8 for the fp32 launch (scripts/micro/taco_cell_bf16x3.hip,
-// profiles/r18_00_taco_cell_bf16x3_ab.txt)
-inline int bgx_launch_cell(const BgArgs& a, const float* planes, int nb_pad, const AttnArgs* attn, float* apre, int* astart, int batch,
-                           hipStream_t s) {
-    return bgx_launch_shape<4, 2, 3, 4>(bgx_args(a, planes), nb_pad, attn, apre, astart, batch, s);
-}
-// two independent cells as the two roles of one launch of that shape; a0's workgroups are the first of every grid row
-inline int bgx_launch_cell2(const BgArgs& a0, const float* planes0, const BgArgs& a1, const float* planes1, int nb_pad, hipStream_t s) {
-    return bgx_launch_shape2<4, 2, 3, 4>(bgx_args(a0, planes0), bgx_args(a1, planes1), nb_pad, s);
-}
-
 // One decoder step of the batched form (4 < batch <= MAX_BATCH, and batch <= 4 where the persistent kernel is not used): seven
-// dependent launches.  Plain schedule (more than 64 items, or CTTS_TACO_BG_NO_PIPE):
-//   attention RNN (bg CELL) + the attention's part 1 as extra workgroups -> query rows (bg LINEAR) -> attention part 2 (one
-//   workgroup per item) -> decoder RNN -> second decoder RNN -> projection row set [mel | gate | first prenet layer] (bg PROJ)
-//   -> second prenet layer (bg PRENET2)
-// Pipelined schedule (<= 64 items): the same seven launches, but the K columns of a cell whose inputs exist EARLY are summed in
-// the launches of the latency-bound stages (independent roles of one launch, tacotron_batched.h "heterogeneous launches"), and the
-// cell's own launch only adds the columns that arrive last:
-//   1  attention RNN FINAL: prenet columns + [ctx | dec_h] and [att_h] sums of the previous step's launches 6 / 7; attention part 1
-//   2  query rows                 + decoder RNN EARLY on att_h(step)
-//   3  attention part 2           + decoder RNN EARLY on dec_h(step - 1) + second decoder RNN EARLY on d2_h(step - 1)
-//   4  decoder RNN FINAL: context columns + both sums          5  second decoder RNN FINAL: dec_h(step) columns + its sum
-//   6  projection row set         + next step's attention RNN EARLY on [ctx(step) | dec_h(step)]
-//   7  second prenet layer        + next step's attention RNN EARLY on att_h(step)
-// Teacher-forced loop (prenet_all != NULL; Decoder.forward, model.py:829-844 with p_teacher_forcing = 1): the prenet of every step
-// was computed before the loop (prenet_all [max_steps][NB][P], ctts_taco_prenet_frames_f32) and the projection runs once after it
-// over the recorded hidden_out (ctts_taco_project_frames_f32), so launches 6 and 7 are gone: five launches per step.  Launch 1
-// carries the attention's part 1 in both schedules; launches 3 and 5 also record [dec_h + d2_h | ctx] into hidden_out.  In the
-// pipelined schedule the EARLY sums that launches 6 / 7 hosted move: the attention RNN's [ctx | dec_h] columns are summed by its
-// own launch (FINAL over [prenet | ctx | dec_h]), its att_h columns ride in launch 2 of the step before (slot 0).  Above 16 rows
-// the next step's attention RNN is a role of launch 5 and its attention part 1 rides in launch 4: four launches per step (`merge`).
-// Split-bf16 cells (bf16x3, more than 64 rows): the plain schedule of either loop with its cell launches on the split planes
-// (bgx_launch_cell; the teacher-forced loop's two-role launch 5 is bgx_launch_cell2); every other launch is the fp32 one.
-int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uint8_t* keep_masks, float* mel_out, float* gate_out,
-                  float* align_out, float* hidden_out, int batch, int text_len, int step0, int n_steps, int max_steps, hipStream_t s,
-                  const float* prenet_all = nullptr, bool bf16x3 = false) {
-    const auto& c = p.c;
-    const int NB = ws_rows(p, batch);
-    const bool forced = prenet_all != nullptr;
+// dependent launches, in one of two schedules (run_plain, run_pipelined below).  BgStep is what a call decides once - which loop,
+// which schedule, which cell format - with the one builder of every launch's arguments and the cell launchers, the only place
+// that knows fp32 tiles from split planes.
+struct BgStep {
+    enum Cell { ATT, DEC, D2 };
+    // what the entry point hands over (aggregate initialisation, in this order) ...
+    const DecPlan& p; const DecWs& w; const float* blob;
+    const uint8_t* keep_masks; float *mel_out, *gate_out, *align_out, *hidden_out;
+    const float* prenet_all;                 // teacher-forced loop: the prenet of every step [max_steps][NB][P]; NULL: free-running
     // split-bf16 cells: the plain schedule's three cell launches (more than 64 rows), both loops; `blob` then ends in the planes
-    const bool x3 = bf16x3 && NB > 64;
+    const bool x3;
+    const int batch, text_len, max_steps;
+    hipStream_t s;
+    // ... and what follows from it
+    const int NB = ws_rows(p, batch), nyb = NB / 16;
+    const bool forced = prenet_all != nullptr;
     // above 16 rows the second decoder RNN of step t and the attention RNN of step t + 1 - independent of each other - are two roles of
     // ONE launch (four launches per step): 53.5 against 58.4, 69.9 / 84.5, 130.9 / 134.0, 206.8 / 213.3 us per step at 32 / 64 / 128 / 256
     // rows; at 16 rows, where the role has the attention RNN's narrower launch shape, 50.4 against 50.2 (profiles/r16_02)
     const bool merge = forced && NB > 16;
-    const int Pn = c.prenet_dim, Ra = c.attention_rnn_dim, Rd = c.decoder_rnn_dim, Rd2 = c.second_decoder_rnn_dim, Dm = c.memory_dim;
     const bool pipe = NB <= 64 && !tuning().taco_bg_no_pipe;
-    const int nyb = NB / 16;
-    int rc;
-    // the three cells' GEMMs for a given step parity (cur = step & 1): X pieces and state, K range / partial mode set by the caller
-    auto att_args = [&](int step) {
-        const int cur = step & 1;
+    const int Pn = p.c.prenet_dim, Ra = p.c.attention_rnn_dim, Rd = p.c.decoder_rnn_dim, Rd2 = p.c.second_decoder_rnn_dim, Dm = p.c.memory_dim;
+    // K chunk boundaries of the pieces (bg_set_x order): att [prenet | ctx | dec_h | att_h], dec [att_h | ctx | dec_h], d2 [dec_h | d2_h]
+    const int aP = Pn / BG_KC, aD = (Pn + Dm + Rd) / BG_KC, aK = p.bg_att.nchunks;
+    const int dA = Ra / BG_KC, dC = (Ra + Dm) / BG_KC, dK = p.bg_dec.nchunks;
+    const int sD = Rd / BG_KC, sK = p.bg_d2.nchunks;
+
+    // ---- argument builders ----
+    // a GEMM over the packed matrix m, its X the pieces p0 .. p3 side by side (bg_set_x)
+    BgArgs gemm(const BgMat& m, const float* p0, int n0, const float* p1 = nullptr, int n1 = 0, const float* p2 = nullptr, int n2 = 0,
+                const float* p3 = nullptr, int n3 = 0) const {
         BgArgs a{};
-        a.W = blob + p.bg_att.off; a.rows = p.bg_att.rows; a.batch = batch;
-        bg_set_x(a, p.bg_att, forced ? prenet_all + (size_t)step * NB * Pn : w.prenet, Pn, w.ctx, Dm, w.dec_h[cur], Rd, w.att_h[cur], Ra);
+        a.W = blob + m.off; a.rows = m.rows; a.batch = batch;
+        bg_set_x(a, m, p0, n0, p1, n1, p2, n2, p3, n3);
+        return a;
+    }
+    // the three cells' GEMMs of a step (state by the step's parity): X pieces and state; K range / partial mode by early / final_
+    BgArgs att(int step) const {
+        const int cur = step & 1;
+        BgArgs a = gemm(p.bg_att, forced ? prenet_all + (size_t)step * NB * Pn : w.prenet, Pn, w.ctx, Dm, w.dec_h[cur], Rd, w.att_h[cur], Ra);
         a.bih = blob + p.att[2]; a.bhh = blob + p.att[3]; a.c = w.att_c; a.h_new = w.att_h[cur ^ 1]; a.H = Ra;
         a.part = w.part_att; a.nt_total = nyb;
         return a;
-    };
-    auto dec_args = [&](int cur) {
-        BgArgs a{};
-        a.W = blob + p.bg_dec.off; a.rows = p.bg_dec.rows; a.batch = batch;
-        bg_set_x(a, p.bg_dec, w.att_h[cur ^ 1], Ra, w.ctx, Dm, w.dec_h[cur], Rd, nullptr, 0);
+    }
+    BgArgs dec(int step) const {
+        const int cur = step & 1;
+        BgArgs a = gemm(p.bg_dec, w.att_h[cur ^ 1], Ra, w.ctx, Dm, w.dec_h[cur], Rd);
         a.bih = blob + p.dec[2]; a.bhh = blob + p.dec[3]; a.c = w.dec_c; a.h_new = w.dec_h[cur ^ 1]; a.H = Rd;
         a.part = w.part_dec; a.nt_total = nyb;
         return a;
-    };
-    auto d2_args = [&](int step) {
+    }
+    BgArgs d2(int step) const {
         const int cur = step & 1;
-        BgArgs a{};
-        a.W = blob + p.bg_d2.off; a.rows = p.bg_d2.rows; a.batch = batch;
-        bg_set_x(a, p.bg_d2, w.dec_h[cur ^ 1], Rd, w.d2_h[cur], Rd2, nullptr, 0, nullptr, 0);
+        BgArgs a = gemm(p.bg_d2, w.dec_h[cur ^ 1], Rd, w.d2_h[cur], Rd2);
         a.bih = blob + p.d2[2]; a.bhh = blob + p.d2[3]; a.c = w.d2_c; a.h_new = w.d2_h[cur ^ 1]; a.H = Rd2;
         a.hsum = w.hsum; a.hres = w.dec_h[cur ^ 1];
         if (forced) { a.hid = hidden_out; a.hid_D = Rd2 + Dm; a.step = step; a.max_steps = max_steps; }
         a.part = w.part_d2; a.nt_total = nyb;
         return a;
-    };
-    auto early = [](BgArgs a, int c0, int c1, int slot) { a.c_begin = c0; a.c_end = c1; a.pmode = 1; a.pslot = slot; return a; };
-    auto final_ = [](BgArgs a, int c0, int c1, int nslots) { a.c_begin = c0; a.c_end = c1; a.pmode = 2; a.npart = nslots; return a; };
-    // K chunk boundaries of the pieces (bg_set_x order): att [prenet | ctx | dec_h | att_h], dec [att_h | ctx | dec_h], d2 [dec_h | d2_h]
-    const int aP = Pn / BG_KC, aD = (Pn + Dm + Rd) / BG_KC, aK = p.bg_att.nchunks;
-    const int dA = Ra / BG_KC, dC = (Ra + Dm) / BG_KC, dK = p.bg_dec.nchunks;
-    const int sD = Rd / BG_KC, sK = p.bg_d2.nchunks;
-    auto attn_args = [&](int step) {
+    }
+    // a cell's columns [c0, c1) as an EARLY sum into partial slot `slot` / as its FINAL launch, which adds `nslots` slots
+    static BgArgs early(BgArgs a, int c0, int c1, int slot) { a.c_begin = c0; a.c_end = c1; a.pmode = 1; a.pslot = slot; return a; }
+    static BgArgs final_(BgArgs a, int c0, int c1, int nslots) { a.c_begin = c0; a.c_end = c1; a.pmode = 2; a.npart = nslots; return a; }
+    // the attention RNN's FINAL launch of the pipelined schedule: free-running the prenet columns + the two sums of the launches
+    // before it, teacher-forced [prenet | ctx | dec_h] + the att_h sum
+    BgArgs att_final(int step) const { return final_(att(step), 0, forced ? aD : aP, forced ? 1 : 2); }
+    AttnArgs attn(int step) const {
+        const auto& c = p.c;
         AttnArgs at{};
         at.Wq = blob + p.query_w; at.v = blob + p.v_w; at.Wloc = blob + p.loc_conv_w; at.Wd = blob + p.loc_dense_w;
         at.G = blob + p.loc_fold;
@@ -901,98 +881,253 @@ int batched_steps(const DecPlan& p, const DecWs& w, const float* blob, const uin
         at.step = step; at.max_steps = max_steps;
         if (forced) { at.hid = hidden_out; at.hid_D = Rd2 + Dm; at.hid_off = Rd2; }
         return at;
-    };
-    if (pipe && forced && n_steps > 0) {      // the att_h sum of step0's attention RNN, as launch 2 of the step before would leave it
+    }
+    BgArgs query(int step) const {       // query rows (model.py:126)
+        BgArgs q = gemm(p.bg_q, w.att_h[(step & 1) ^ 1], Ra);
+        q.y = w.qbuf; q.ldy = p.c.attention_dim;
+        return q;
+    }
+    // the next step's dropout masks; NULL after the last step, which has no prenet to run
+    const unsigned char* keep(int step) const { return step + 1 < max_steps ? keep_masks + (size_t)(step + 1) * 2 * batch * Pn : nullptr; }
+    // projection row set on [dec_h + d2_h | ctx] (model.py:755-765) + first prenet layer of the next step (:187-190)
+    BgArgs proj(int step) const {
+        BgArgs pr = gemm(p.bg_proj, w.hsum, Rd2, w.ctx, Dm);
+        pr.bias = blob + p.pd_proj_b; pr.keep = keep(step); pr.mel_out = mel_out; pr.gate_out = gate_out; pr.act_out = w.h1;
+        pr.n_mel = p.c.n_mel_channels; pr.P = Pn; pr.step = step; pr.max_steps = max_steps;
+        return pr;
+    }
+    BgArgs prenet2(int step) const {     // second prenet layer
+        BgArgs w2 = gemm(p.bg_w2, w.h1, Pn);
+        w2.keep = keep(step); w2.act_out = w.prenet; w2.P = Pn;
+        return w2;
+    }
+    // roles of a heterogeneous launch (BgRoles)
+    void small_role(BgRoles& m, const BgArgs& a, const BgMat& mat, int epi) const { m.small = a; m.n_small = mat.tiles * nyb; m.small_epi = epi; }
+    static void cell_role(BgRoles& m, int i, const BgArgs& a) { m.cell[i] = a; m.n_cell[i] = 1; }
+    void pre_role(BgRoles& m, const AttnArgs& at) const { m.pre = &at; m.apre = w.apre; m.astart = w.astart; m.n_pre = batch; }
+
+    // ---- launchers ----
+    // one cell, on fp32 tiles or split planes; ride != NULL: that attention part 1 as extra workgroups.  fp32: the launch shape is the
+    // cell's own but for the attention RNN with a rider, which takes its narrower one (bg_cell_shape).  Split planes: one shape for
+    // every batch above 64 rows (NT and the K split fix an item's bits) - four m-tiles x 32 items per workgroup, 3-deep ring (144 KiB),
+    // four waves: of the shapes that fit the LDS and the vmcnt budget it is the fastest on all three cells at 128 and 256 rows -
+    // attention RNN at 256 rows 59.4 us against 79.3 as <2, 4, 3, 4> (the fp32 launch's tile), 89.9 as <4, 4, 4, 2>, and 94.8 for the
+    // fp32 launch (scripts/micro/taco_cell_bf16x3.hip, profiles/r18_00_taco_cell_bf16x3_ab.txt)
+    int cell(Cell which, const BgArgs& a, const AttnArgs* ride) const {
+        const size_t planes[3] = {p.x3_att, p.x3_dec, p.x3_d2};
+        if (x3) return bgx_launch_shape<4, 2, 3, 4>(bgx_args(a, blob + planes[which]), NB, ride, w.apre, w.astart, batch, s);
+        return bg_launch_cell(a, NB, ride, w.apre, w.astart, batch, s, which == ATT && ride);
+    }
+    // the second decoder RNN of a step and the attention RNN of the next as two roles of one launch (d2's workgroups first): on fp32
+    // tiles the attention part 2's launch with no attention workgroup (`at` is only carried), on split planes the cells' shape
+    int d2_and_next_att(const AttnArgs& at, const BgArgs& d2_a, const BgArgs& att_a) const {
+        if (x3) return bgx_launch_shape2<4, 2, 3, 4>(bgx_args(d2_a, blob + p.x3_d2), bgx_args(att_a, blob + p.x3_att), NB, s);
+        return bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, 0, d2_a, att_a, NB, s);
+    }
+    int record_hidden(int step) const {        // free-running loop with hidden_out: [dec_h + d2_h | ctx] of this step
+        const int nxt = (step & 1) ^ 1;
+        hipLaunchKernelGGL(hidden_state_kernel, dim3(batch), dim3(256), 0, s, w.dec_h[nxt], w.d2_h[nxt], w.ctx, hidden_out, Rd, Dm, step, max_steps);
+        CTTS_CHECK_LAUNCH("hidden_state");
+        return CTTS_OK;
+    }
+
+    int run_plain(int step0, int n_steps) const;
+    int run_pipelined(int step0, int n_steps) const;
+    int run(int step0, int n_steps) const { return pipe ? run_pipelined(step0, n_steps) : run_plain(step0, n_steps); }
+};
+
+// Plain schedule (more than 64 items, or CTTS_TACO_BG_NO_PIPE), free-running loop:
+//   1  attention RNN (bg CELL) + the attention's part 1 as extra workgroups     2  query rows (bg LINEAR)
+//   3  attention part 2 (one workgroup per item)     4  decoder RNN     5  second decoder RNN
+//   6  projection row set [mel | gate | first prenet layer] (bg PROJ)           7  second prenet layer (bg PRENET2)
+// Teacher-forced loop (prenet_all != NULL; Decoder.forward, model.py:829-844 with p_teacher_forcing = 1): the prenet of every step
+// was computed before the loop (prenet_all [max_steps][NB][P], ctts_taco_prenet_frames_f32) and the projection runs once after it
+// over the recorded hidden_out (ctts_taco_project_frames_f32), so launches 6 and 7 are gone: five launches per step; launches 3
+// and 5 also record [dec_h + d2_h | ctx] into hidden_out.  Above 16 rows the next step's attention RNN is a role of launch 5 and
+// its attention part 1 rides in launch 4: four launches per step (`merge`), and only a call's first step has a launch 1.
+// Split-bf16 cells (bf16x3, more than 64 rows): either loop with its cell launches 1, 4, 5 on the split planes (BgStep::cell,
+// d2_and_next_att); every other launch is the fp32 one.
+int BgStep::run_plain(int step0, int n_steps) const {
+    int rc;
+    bool att_done = false;       // this step's attention RNN ran as a role of the step before
+    for (int step = step0; step < step0 + n_steps; ++step) {
+        const bool more = step + 1 < step0 + n_steps;          // the next step belongs to this call
+        const AttnArgs at = attn(step), at_next = attn(step + 1);
+        const AttnArgs* ride = merge && more ? &at_next : nullptr;
+        // 1: attention RNN on [prenet | context | decoder hidden], recurrent on its own hidden state (model.py:707-717)
+        if (!att_done && (rc = cell(ATT, att(step), &at))) return rc;
+        if ((rc = bg_launch_small<BG_EPI_LINEAR>(query(step), NB, s))) return rc;                          // 2
+        if ((rc = CTTS_ALLOW_LDS(attn_post_kernel, BGA_POST_LDS_BYTES))) return rc;                         // 3
+        hipLaunchKernelGGL(attn_post_kernel, dim3(batch), dim3(256), BGA_POST_LDS_BYTES, s, at, w.qbuf, w.apre, w.astart);
+        CTTS_CHECK_LAUNCH("attn_post");
+        // 4, 5: decoder RNN on [attention hidden | context] (model.py:741-747), second decoder RNN on its output (:749-755).
+        // Teacher-forced, as two roles of one launch with the next attention RNN: on split planes 89.7 against 101.9 us per step as
+        // two launches at 128 rows, 151.6 / 153.4 at 256; with the attention RNN's workgroups first 90.3 and 156.6 (profiles/r19_00)
+        if ((rc = cell(DEC, dec(step), ride))) return rc;
+        if ((rc = ride ? d2_and_next_att(at, d2(step), att(step + 1)) : cell(D2, d2(step), nullptr))) return rc;
+        att_done = ride != nullptr;
+        if (forced) continue;                              // no projection, no prenet
+        if ((rc = bg_launch_small<BG_EPI_PROJ>(proj(step), NB, s))) return rc;                             // 6
+        if (keep(step) && (rc = bg_launch_small<BG_EPI_PRENET2>(prenet2(step), NB, s))) return rc;         // 7
+        if (hidden_out && (rc = record_hidden(step))) return rc;
+    }
+    return CTTS_OK;
+}
+
+// Pipelined schedule (<= 64 items): the same seven launches, but the K columns of a cell whose inputs exist EARLY are summed in
+// the launches of the latency-bound stages (independent roles of one launch, tacotron_batched.h "heterogeneous launches"), and the
+// cell's own launch only adds the columns that arrive last:
+//   0  (before a call's first step) what the previous call's last step did not leave: the EARLY sums of step0's attention RNN and
+//      its attention part 1
+//   1  attention RNN FINAL: prenet columns + [ctx | dec_h] and [att_h] sums of the previous step's launches 6 / 7
+//   2  query rows                 + decoder RNN EARLY on att_h(step)
+//   3  attention part 2           + decoder RNN EARLY on dec_h(step - 1) + second decoder RNN EARLY on d2_h(step - 1)
+//   4  decoder RNN FINAL: context columns + both sums          5  second decoder RNN FINAL: dec_h(step) columns + its sum
+//   6  projection row set         + next step's attention RNN EARLY on [ctx(step) | dec_h(step)]
+//   7  second prenet layer        + next step's attention RNN EARLY on att_h(step) + its attention part 1
+// Teacher-forced loop (see run_plain: no launches 6 and 7): the EARLY sums they hosted move - the attention RNN's [ctx | dec_h]
+// columns are summed by its own launch (FINAL over [prenet | ctx | dec_h], with the attention's part 1 riding), its att_h columns
+// ride in launch 2 of the step before (slot 0; launch 0 for step0).  `merge` as in the plain schedule.
+int BgStep::run_pipelined(int step0, int n_steps) const {
+    int rc;
+    if (n_steps > 0) {                                          // 0
+        const AttnArgs at0 = attn(step0);
         BgRoles m{};
-        m.cell[0] = early(att_args(step0), aD, aK, 0); m.n_cell[0] = 1;
-        if ((rc = bg_launch_multi8(m, NB, s))) return rc;
-    } else if (pipe && n_steps > 0) {      // what the previous call's last step did not leave: the EARLY sums of step0's attention RNN and
-        const AttnArgs at0 = attn_args(step0);                  // its attention part 1
-        BgRoles m{};
-        m.cell[0] = early(att_args(step0), aP, aD, 0); m.n_cell[0] = 1;
-        m.cell[1] = early(att_args(step0), aD, aK, 1); m.n_cell[1] = 1;
-        m.pre = &at0; m.apre = w.apre; m.astart = w.astart; m.n_pre = batch;
+        cell_role(m, 0, forced ? early(att(step0), aD, aK, 0) : early(att(step0), aP, aD, 0));
+        if (!forced) { cell_role(m, 1, early(att(step0), aD, aK, 1)); pre_role(m, at0); }
         if ((rc = bg_launch_multi8(m, NB, s))) return rc;
     }
+    bool att_done = false;       // this step's attention RNN ran as a role of the step before
     for (int step = step0; step < step0 + n_steps; ++step) {
-        const int cur = step & 1, nxt = cur ^ 1;
         const bool more = step + 1 < step0 + n_steps;          // the next step belongs to this call: leave its EARLY sums
-        const AttnArgs at = attn_args(step), at_next = attn_args(step + 1);
-        // 1: attention RNN on [prenet | context | decoder hidden], recurrent on its own hidden state (model.py:707-717); in the plain
-        // schedule the attention's part 1 rides along, in the pipelined one it ran in the previous step's launch 7
-        // (teacher-forced loop: only a call's first step launches it - see launch 5)
-        auto att_launch = [&](int st) { return pipe ? final_(att_args(st), 0, forced ? aD : aP, forced ? 1 : 2) : att_args(st); };
-        if (x3) {
-            if (!(merge && step > step0) && (rc = bgx_launch_cell(att_args(step), blob + p.x3_att, NB, &at, w.apre, w.astart, batch, s))) return rc;
-        } else if (!(merge && step > step0) &&
-                   (rc = bg_launch_cell(att_launch(step), NB, pipe && !forced ? nullptr : &at, w.apre, w.astart, batch, s))) return rc;
-        // teacher-forced loop: the NEXT step's attention part 1 rides in launch 4, its attention RNN is a role of launch 5
+        const AttnArgs at = attn(step), at_next = attn(step + 1);
         const AttnArgs* ride = merge && more ? &at_next : nullptr;
-        BgArgs q{};     // 2: query rows (model.py:126)
-        q.W = blob + p.bg_q.off; q.rows = p.bg_q.rows; q.batch = batch;
-        bg_set_x(q, p.bg_q, w.att_h[nxt], Ra, nullptr, 0, nullptr, 0, nullptr, 0);
-        q.y = w.qbuf; q.ldy = c.attention_dim;
-        if (pipe) {
-            BgRoles m{};
-            m.small = q; m.n_small = p.bg_q.tiles * nyb; m.small_epi = BG_EPI_LINEAR;
-            m.cell[0] = early(dec_args(cur), 0, dA, 0); m.n_cell[0] = 1;
-            if (forced && more) { m.cell[1] = early(att_args(step + 1), aD, aK, 0); m.n_cell[1] = 1; }
-            if ((rc = bg_launch_multi8(m, NB, s))) return rc;
-            // 3: attention part 2 + the EARLY sums on last step's dec_h / d2_h
-            if ((rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, batch, early(dec_args(cur), dC, dK, 1),
-                                            early(d2_args(step), sD, sK, 0), NB, s))) return rc;
-            // 4, 5: decoder RNN on [attention hidden | context] (model.py:741-747), second decoder RNN on its output (:749-755)
-            if ((rc = bg_launch_cell(final_(dec_args(cur), dA, dC, 2), NB, ride, w.apre, w.astart, batch, s, 0))) return rc;
-            if (ride) rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, 0, final_(d2_args(step), 0, sD, 1), att_launch(step + 1), NB, s);
-            else rc = bg_launch_cell(final_(d2_args(step), 0, sD, 1), NB, nullptr, nullptr, nullptr, batch, s);
-            if (rc) return rc;
-        } else {
-            if ((rc = bg_launch_small<BG_EPI_LINEAR>(q, NB, s))) return rc;
-            if ((rc = BG_ALLOW_LDS(attn_post_kernel, BGA_POST_LDS_BYTES))) return rc;
-            hipLaunchKernelGGL(attn_post_kernel, dim3(batch), dim3(256), BGA_POST_LDS_BYTES, s, at, w.qbuf, w.apre, w.astart);
-            CTTS_CHECK_LAUNCH("attn_post");
-            if (x3) {      // (`ride` is NULL in the free-running loop: the three cells as three launches)
-                if ((rc = bgx_launch_cell(dec_args(cur), blob + p.x3_dec, NB, ride, w.apre, w.astart, batch, s))) return rc;
-                // teacher-forced loop: the second decoder RNN and the next step's attention RNN as two roles of one launch - 89.7 against
-                // 101.9 us per step as two launches at 128 rows, 151.6 / 153.4 at 256; with the attention RNN's workgroups first
-                // 90.3 and 156.6 (profiles/r19_00)
-                if (ride) rc = bgx_launch_cell2(d2_args(step), blob + p.x3_d2, att_args(step + 1), blob + p.x3_att, NB, s);
-                else rc = bgx_launch_cell(d2_args(step), blob + p.x3_d2, NB, nullptr, nullptr, nullptr, batch, s);
-            } else if ((rc = bg_launch_cell(dec_args(cur), NB, ride, w.apre, w.astart, batch, s, 0))) return rc;
-            else if (ride) rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, 0, d2_args(step), att_launch(step + 1), NB, s);
-            else rc = bg_launch_cell(d2_args(step), NB, nullptr, nullptr, nullptr, batch, s);
-            if (rc) return rc;
+        if (!att_done && (rc = cell(ATT, att_final(step), forced ? &at : nullptr))) return rc;             // 1
+        BgRoles m2{};                                                                                       // 2
+        small_role(m2, query(step), p.bg_q, BG_EPI_LINEAR);
+        cell_role(m2, 0, early(dec(step), 0, dA, 0));
+        if (forced && more) cell_role(m2, 1, early(att(step + 1), aD, aK, 0));
+        if ((rc = bg_launch_multi8(m2, NB, s))) return rc;
+        if ((rc = bg_launch_post_multi4(at, w.qbuf, w.apre, w.astart, batch, early(dec(step), dC, dK, 1), early(d2(step), sD, sK, 0),
+                                        NB, s))) return rc;                                                 // 3
+        if ((rc = cell(DEC, final_(dec(step), dA, dC, 2), ride))) return rc;                                // 4
+        const BgArgs d2_final = final_(d2(step), 0, sD, 1);                                                 // 5
+        if ((rc = ride ? d2_and_next_att(at, d2_final, att_final(step + 1)) : cell(D2, d2_final, nullptr))) return rc;
+        att_done = ride != nullptr;
+        if (forced) continue;                              // no projection, no prenet
+        BgRoles m6{}, m7{};
+        small_role(m6, proj(step), p.bg_proj, BG_EPI_PROJ);                                                 // 6
+        if (more) cell_role(m6, 0, early(att(step + 1), aP, aD, 0));
+        if ((rc = bg_launch_multi8(m6, NB, s))) return rc;
+        if (keep(step)) small_role(m7, prenet2(step), p.bg_w2, BG_EPI_PRENET2);                            // 7
+        if (more) {
+            cell_role(m7, 0, early(att(step + 1), aD, aK, 1));
+            pre_role(m7, at_next);                         // (reads what launch 3 left: weights, position)
         }
-        if (forced) continue;                              // no projection, no prenet: five launches
-        const unsigned char* keep = step + 1 < max_steps ? keep_masks + (size_t)(step + 1) * 2 * batch * Pn : nullptr;
-        BgArgs pr{}, w2{};
-        // 6: projection row set on [dec_h + d2_h | ctx] (model.py:755-765) + first prenet layer of the next step (:187-190)
-        pr.W = blob + p.bg_proj.off; pr.rows = p.bg_proj.rows; pr.batch = batch;
-        bg_set_x(pr, p.bg_proj, w.hsum, Rd2, w.ctx, Dm, nullptr, 0, nullptr, 0);
-        pr.bias = blob + p.pd_proj_b; pr.keep = keep; pr.mel_out = mel_out; pr.gate_out = gate_out; pr.act_out = w.h1;
-        pr.n_mel = c.n_mel_channels; pr.P = Pn; pr.step = step; pr.max_steps = max_steps;
-        // 7: second prenet layer
-        w2.W = blob + p.bg_w2.off; w2.rows = p.bg_w2.rows; w2.batch = batch;
-        bg_set_x(w2, p.bg_w2, w.h1, Pn, nullptr, 0, nullptr, 0, nullptr, 0);
-        w2.keep = keep; w2.act_out = w.prenet; w2.P = Pn;
-        if (pipe) {
-            BgRoles m{};
-            m.small = pr; m.n_small = p.bg_proj.tiles * nyb; m.small_epi = BG_EPI_PROJ;
-            if (more) { m.cell[0] = early(att_args(step + 1), aP, aD, 0); m.n_cell[0] = 1; }
-            if ((rc = bg_launch_multi8(m, NB, s))) return rc;
-            BgRoles m2{};
-            if (keep) { m2.small = w2; m2.n_small = p.bg_w2.tiles * nyb; m2.small_epi = BG_EPI_PRENET2; }
-            if (more) {
-                m2.cell[0] = early(att_args(step + 1), aD, aK, 1); m2.n_cell[0] = 1;
-                m2.pre = &at_next; m2.apre = w.apre; m2.astart = w.astart; m2.n_pre = batch;     // (reads what launch 3 left: weights, position)
+        if ((rc = bg_launch_multi8(m7, NB, s))) return rc;
+        if (hidden_out && (rc = record_hidden(step))) return rc;
+    }
+    return CTTS_OK;
+}
+
+// The VALU per-launch form of the free-running loop (batch <= MAX_NB): the form for shapes the batched one does not take and,
+// through CTTS_TACO_VALU, an independent cross-check of both other forms
+int valu_steps(const DecPlan& p, const DecWs& w, const float* blob, const uint8_t* keep_masks, float* mel_out, float* gate_out,
+               float* align_out, float* hidden_out, int batch, int text_len, int step0, int n_steps, int max_steps, hipStream_t s) {
+    int rc;
+    const auto& c = p.c;
+    const int NB = pad_batch(batch);
+    // Early partial sums (see LstmPart and the heterogeneous kernels above).  Column windows of the three cells:
+    //   attention RNN  input [prenet | ctx | dec_h]: fresh = prenet, early = ctx, dec_h and W_hh.att_h  (behind project/prenet)
+    //   decoder RNN    input [att_h | ctx]:          fresh = ctx,    early = att_h and W_hh.dec_h       (behind the attention)
+    //   2nd decoder    input [dec_h]:                fresh = dec_h,  early = W_hh.d2_h                  (behind the attention)
+    const int Pn = c.prenet_dim, Ra = c.attention_rnn_dim, Rd = c.decoder_rnn_dim, Rd2 = c.second_decoder_rnn_dim;
+    const bool fast = c.window_range <= 16 && c.memory_dim <= ADM && c.attention_dim <= AAD && c.attention_dim % 4 == 0 &&
+                      c.location_n_filters <= AF && c.location_kernel_size <= AK && c.attention_rnn_dim <= 1536;
+    constexpr int R_DEC = 6, R_D2 = 8, R_ATT = 8;     // units per partial workgroup: 4 + 128 + 96 <= 256 CUs at config 5
+    const bool fuse = fast && n_steps > 0 && Rd % R_DEC == 0 && Rd2 % R_D2 == 0 && Ra % R_ATT == 0 &&
+                      NB * (p.I_dec + Rd) + 4 * R_DEC * NB <= ATTN_SMEM_FLOATS &&
+                      NB * (p.I_d2 + Rd2) + 4 * R_D2 * NB <= ATTN_SMEM_FLOATS &&
+                      NB * (p.I_att + Ra) + 4 * R_ATT * NB <= PROJ_FUSED_SMEM_FLOATS && !tuning().taco_no_fuse;
+    const LstmPart att_early{nullptr, w.gp_att, Pn, p.I_att, 1}, att_fresh{w.gp_att, nullptr, 0, Pn, 0};
+    const LstmPart dec_early{nullptr, w.gp_dec, 0, Ra, 1}, dec_fresh{w.gp_dec, nullptr, Ra, p.I_dec, 0};
+    const LstmPart d2_early{nullptr, w.gp_d2, 0, 0, 1}, d2_fresh{w.gp_d2, nullptr, 0, p.I_d2, 0};
+    if (fuse) {   // the first step of this call has nothing to hide behind: its early part runs in line
+        const int cur = step0 & 1;
+        rc = launch_lstm_nb(NB, blob, p.att, w.prenet, Pn, w.ctx, c.memory_dim, w.dec_h[cur], Rd, w.att_h[cur], nullptr,
+                            nullptr, p.I_att, Ra, s, &att_early);
+        if (rc) return rc;
+    }
+    for (int step = step0; step < step0 + n_steps; ++step) {
+        const int cur = step & 1, nxt = cur ^ 1;    // h ping-pong: read [cur], write [nxt]
+        // attention RNN on [prenet | context | decoder hidden]   (model.py:707-717)
+        rc = launch_lstm_nb(NB, blob, p.att, w.prenet, Pn, w.ctx, c.memory_dim, w.dec_h[cur], Rd,
+                            w.att_h[cur], w.att_h[nxt], w.att_c, p.I_att, Ra, s, fuse ? &att_fresh : nullptr);
+        if (rc) return rc;
+        AttnArgs a{};
+        a.Wq = blob + p.query_w; a.v = blob + p.v_w; a.Wloc = blob + p.loc_conv_w; a.Wd = blob + p.loc_dense_w;
+        a.scalars = blob + p.scalars;
+        a.att_h = w.att_h[nxt]; a.memory = w.memory; a.pm = w.pm;
+        a.w = w.w; a.cum = w.cum; a.ctx = w.ctx; a.pos = w.pos; a.align_out = align_out; a.lengths = w.lengths;
+        a.T = text_len; a.A = c.attention_dim; a.Ra = c.attention_rnn_dim; a.Dm = c.memory_dim;
+        a.F = c.location_n_filters; a.K = c.location_kernel_size; a.R = c.window_range;
+        a.step = step; a.max_steps = max_steps;
+        if (fast) {
+            const int gblocks = (c.attention_dim + 7) / 8;
+            if (NB == 1) hipLaunchKernelGGL(gemv_rows_kernel<1>, dim3(gblocks), dim3(256), 0, s, a.Wq, a.att_h, w.qbuf, c.attention_dim, c.attention_rnn_dim);
+            else if (NB == 2) hipLaunchKernelGGL(gemv_rows_kernel<2>, dim3(gblocks), dim3(256), 0, s, a.Wq, a.att_h, w.qbuf, c.attention_dim, c.attention_rnn_dim);
+            else hipLaunchKernelGGL(gemv_rows_kernel<4>, dim3(gblocks), dim3(256), 0, s, a.Wq, a.att_h, w.qbuf, c.attention_dim, c.attention_rnn_dim);
+            CTTS_CHECK_LAUNCH("gemv_rows");
+            if (fuse) {
+                const LstmCall e1 = make_call(blob, p.dec, w.att_h[nxt], Ra, w.ctx, c.memory_dim, nullptr, 0, w.dec_h[cur],
+                                              p.I_dec, Rd, NB, dec_early);
+                const LstmCall e2 = make_call(blob, p.d2, w.dec_h[nxt], Rd, nullptr, 0, nullptr, 0, w.d2_h[cur], p.I_d2, Rd2,
+                                              NB, d2_early);
+                const int n1 = Rd / R_DEC, n2 = Rd2 / R_D2;
+                const dim3 grid(batch + n1 + n2);
+                if (NB == 1) hipLaunchKernelGGL((attention_partials_kernel<1, R_DEC, R_D2>), grid, dim3(256), 0, s, a, w.qbuf, batch, e1, n1, e2);
+                else if (NB == 2) hipLaunchKernelGGL((attention_partials_kernel<2, R_DEC, R_D2>), grid, dim3(256), 0, s, a, w.qbuf, batch, e1, n1, e2);
+                else hipLaunchKernelGGL((attention_partials_kernel<4, R_DEC, R_D2>), grid, dim3(256), 0, s, a, w.qbuf, batch, e1, n1, e2);
+            } else {
+                hipLaunchKernelGGL(attention_window_kernel, dim3(batch), dim3(256), 0, s, a, w.qbuf);
             }
-            if ((rc = bg_launch_multi8(m2, NB, s))) return rc;
+        } else if (c.location_n_filters <= 32) {
+            hipLaunchKernelGGL(attention_step_kernel<32>, dim3(batch), dim3(256), 0, s, a);
         } else {
-            if ((rc = bg_launch_small<BG_EPI_PROJ>(pr, NB, s))) return rc;
-            if (keep && (rc = bg_launch_small<BG_EPI_PRENET2>(w2, NB, s))) return rc;
+            hipLaunchKernelGGL(attention_step_kernel<64>, dim3(batch), dim3(256), 0, s, a);
         }
+        CTTS_CHECK_LAUNCH("attention_step");
+        // decoder RNN on [attention hidden | context], second decoder RNN on the first's output
+        rc = launch_lstm_nb(NB, blob, p.dec, w.att_h[nxt], c.attention_rnn_dim, w.ctx, c.memory_dim, nullptr, 0,
+                            w.dec_h[cur], w.dec_h[nxt], w.dec_c, p.I_dec, c.decoder_rnn_dim, s, fuse ? &dec_fresh : nullptr);
+        if (rc) return rc;
+        rc = launch_lstm_nb(NB, blob, p.d2, w.dec_h[nxt], c.decoder_rnn_dim, nullptr, 0, nullptr, 0, w.d2_h[cur],
+                            w.d2_h[nxt], w.d2_c, p.I_d2, c.second_decoder_rnn_dim, s, fuse ? &d2_fresh : nullptr);
+        if (rc) return rc;
+        ProjArgs q{};
+        q.Wp = blob + p.proj_w; q.bp = blob + p.proj_b; q.W1T = blob + p.prenet_w1; q.W2T = blob + p.prenet_w2;
+        q.dec_h = w.dec_h[nxt]; q.d2_h = w.d2_h[nxt]; q.ctx = w.ctx;
+        q.keep = step + 1 < max_steps ? keep_masks + (size_t)(step + 1) * 2 * batch * c.prenet_dim : nullptr;
+        q.mel_out = mel_out; q.gate_out = gate_out; q.prenet_out = w.prenet;
+        q.n_mel = c.n_mel_channels; q.Rd = c.second_decoder_rnn_dim; q.Dm = c.memory_dim; q.P = c.prenet_dim;
+        q.B = batch; q.step = step; q.max_steps = max_steps;
+        // (splitting this stage into three multi-workgroup GEMV launches was measured: 12.8 + 5.2 + 5.2 us vs 22 us
+        // here - every dependent launch costs ~5 us before its first useful byte, so fewer launches win)
+        if (fuse && step + 1 < step0 + n_steps) {
+            // ... and behind it, the early part of the NEXT step's attention RNN
+            const LstmCall e = make_call(blob, p.att, w.prenet, Pn, w.ctx, c.memory_dim, w.dec_h[nxt], Rd, w.att_h[nxt],
+                                         p.I_att, Ra, NB, att_early);
+            const dim3 grid(batch + Ra / R_ATT);
+            if (NB == 1) hipLaunchKernelGGL((project_partial_kernel<1, R_ATT>), grid, dim3(256), 0, s, q, batch, e);
+            else if (NB == 2) hipLaunchKernelGGL((project_partial_kernel<2, R_ATT>), grid, dim3(256), 0, s, q, batch, e);
+            else hipLaunchKernelGGL((project_partial_kernel<4, R_ATT>), grid, dim3(256), 0, s, q, batch, e);
+        } else {
+            hipLaunchKernelGGL(project_prenet_kernel, dim3(batch), dim3(256), 0, s, q);
+        }
+        CTTS_CHECK_LAUNCH("project_prenet");
         if (hidden_out) {
-            hipLaunchKernelGGL(hidden_state_kernel, dim3(batch), dim3(256), 0, s, w.dec_h[nxt], w.d2_h[nxt], w.ctx, hidden_out, Rd, Dm, step, max_steps);
+            hipLaunchKernelGGL(hidden_state_kernel, dim3(batch), dim3(256), 0, s, w.dec_h[nxt], w.d2_h[nxt], w.ctx, hidden_out, Rd2,
+                               c.memory_dim, step, max_steps);
             CTTS_CHECK_LAUNCH("hidden_state");
         }
     }
@@ -1161,6 +1296,66 @@ int bg_pack(float* dst, const BgMat& m, const BgSeg* segs, int nseg, int interle
 static_assert(AW == 33 && ADM == 512 && AAD == 256 && AF == 32 && AK == 31, "make_dec_plan's bg_ok restates these limits");
 bool bg_supported(const DecPlan& p) { return p.bg_ok; }
 
+// the shapes the split-bf16 (bf16x3) mode is not built for, before any launch
+int x3_refuse(const DecPlan& p, const char* what) {
+    CTTS_CHECK_ARG(p.x3_bad == nullptr, "%s: %s is not a multiple of 32 (the split planes' K chunk)", what, p.x3_bad);
+    CTTS_CHECK_ARG(bg_supported(p), "%s: this decoder shape has no batched form (ctts_taco_decoder_max_batch is %d, bf16x3 needs %d)", what,
+                   MAX_NB, MAX_BATCH);
+    return CTTS_OK;
+}
+
+// ---- the step entry points' common opening ------------------------------------------------------------------------------------
+// what: the entry point's name in its messages; x3_what: its name in x3_refuse's (NULL: an fp32 entry point); fp32: the entry
+// point a bf16x3 one turns into at 64 rows or fewer, where the step is bound by the weight stream and keeps its fp32 schedules,
+// bit for bit
+struct StepsEntry { const char *what, *x3_what; const StepsEntry* fp32; bool forced; };
+const StepsEntry STEPS_FREE{"decoder steps", nullptr, nullptr, false};
+const StepsEntry STEPS_FREE_X3{"decoder bf16x3 steps", "decoder bf16x3 steps", &STEPS_FREE, false};
+const StepsEntry STEPS_FORCED{"forced decoder steps", nullptr, nullptr, true};
+const StepsEntry STEPS_FORCED_X3{"forced decoder steps", "forced decoder bf16x3 steps", &STEPS_FORCED, true};
+
+// plan, refusals in the entry points' order, workspace carved; x3: run the cells on the split planes.  (The free-running entry
+// points have no workspace_bytes and no text_len check.)
+int open_steps(const StepsEntry* e, const ctts_taco_decoder_config* cfg, bool pointers, int batch, int text_len, int step0, int n_steps,
+               int max_steps, void* workspace, size_t workspace_bytes, DecPlan& p, DecWs& w, bool& x3) {
+    int rc = make_dec_plan(cfg, p); if (rc) return rc;
+    if (e->x3_what) {
+        if ((rc = x3_refuse(p, e->x3_what))) return rc;
+        if (batch <= 64) e = e->fp32;
+    }
+    x3 = e->x3_what != nullptr;
+    CTTS_CHECK_ARG(pointers, "%s: NULL pointer", e->what);
+    if (e->forced)
+        CTTS_CHECK_ARG(bg_supported(p), "%s: this decoder shape has no batched form (ctts_taco_decoder_max_batch is %d)", e->what, MAX_NB);
+    const int max_batch = bg_supported(p) ? MAX_BATCH : MAX_NB;
+    CTTS_CHECK_ARG(batch >= 1 && batch <= max_batch && step0 >= 0 && n_steps >= 0 && step0 + n_steps <= max_steps,
+                   "%s: batch=%d (1..%d) step0=%d n_steps=%d max_steps=%d", e->what, batch, max_batch, step0, n_steps, max_steps);
+    if (e->forced) CTTS_CHECK_ARG(text_len >= 1, "%s: text_len=%d", e->what, text_len);
+    dec_carve(p, batch, text_len, static_cast<float*>(workspace), w);
+    if (e->forced)
+        CTTS_CHECK_ARG(w.total * sizeof(float) <= workspace_bytes, "%s: workspace %zu bytes < required %zu", e->what, workspace_bytes,
+                       w.total * sizeof(float));
+    return CTTS_OK;
+}
+
+// a step entry point: open, choose the form, run (free-running loop: prenet_all is NULL; teacher-forced: keep_masks, mel_out, gate_out)
+int run_steps(const StepsEntry& e, const ctts_taco_decoder_config* cfg, const void* packed, const uint8_t* keep_masks, const float* prenet_all,
+              float* mel_out, float* gate_out, float* align_out, float* hidden_out, int batch, int text_len, int step0, int n_steps,
+              int max_steps, void* workspace, size_t workspace_bytes, void* stream) {
+    DecPlan p; DecWs w; bool x3;
+    const bool pointers = packed && align_out && workspace && (e.forced ? prenet_all && hidden_out : keep_masks && mel_out && gate_out);
+    const int rc = open_steps(&e, cfg, pointers, batch, text_len, step0, n_steps, max_steps, workspace, workspace_bytes, p, w, x3);
+    if (rc) return rc;
+    const float* blob = static_cast<const float*>(packed);
+    // the batched MFMA form serves every batch it is built for: at batch <= 4 it is also ahead of the VALU kernels (default
+    // widths 64 against 88 us/step, the non-default golden shape 43 against 63: profiles/r6_05)
+    if (e.forced || batch > MAX_NB || (bg_supported(p) && !tuning().taco_valu))
+        return BgStep{p, w, blob, keep_masks, mel_out, gate_out, align_out, hidden_out, prenet_all, x3, batch, text_len, max_steps,
+                      as_stream(stream)}.run(step0, n_steps);
+    return valu_steps(p, w, blob, keep_masks, mel_out, gate_out, align_out, hidden_out, batch, text_len, step0, n_steps, max_steps,
+                      as_stream(stream));
+}
+
 }  // namespace
 }  // namespace ctts
 
@@ -1297,137 +1492,20 @@ int ctts_taco_decoder_init_f32(const ctts_taco_decoder_config* cfg, const void* 
 int ctts_taco_decoder_steps_f32(const ctts_taco_decoder_config* cfg, const void* packed, const uint8_t* keep_masks,
                                 float* mel_out, float* gate_out, float* align_out, int32_t batch, int32_t text_len,
                                 int32_t step0, int32_t n_steps, int32_t max_steps, void* workspace, void* stream) {
-    return ctts_taco_decoder_steps_hidden_f32(cfg, packed, keep_masks, mel_out, gate_out, align_out, nullptr, batch, text_len, step0,
-                                              n_steps, max_steps, workspace, stream);
+    return run_steps(STEPS_FREE, cfg, packed, keep_masks, nullptr, mel_out, gate_out, align_out, nullptr, batch, text_len, step0, n_steps,
+                     max_steps, workspace, 0, stream);
 }
 
 int ctts_taco_decoder_steps_hidden_f32(const ctts_taco_decoder_config* cfg, const void* packed, const uint8_t* keep_masks,
                                        float* mel_out, float* gate_out, float* align_out, float* hidden_out, int32_t batch,
                                        int32_t text_len, int32_t step0, int32_t n_steps, int32_t max_steps, void* workspace,
                                        void* stream) {
-    DecPlan p; DecWs w;
-    int rc = make_dec_plan(cfg, p); if (rc) return rc;
-    CTTS_CHECK_ARG(packed && keep_masks && mel_out && gate_out && align_out && workspace, "decoder steps: NULL pointer");
-    const int max_batch = bg_supported(p) ? MAX_BATCH : MAX_NB;
-    CTTS_CHECK_ARG(batch >= 1 && batch <= max_batch && step0 >= 0 && n_steps >= 0 && step0 + n_steps <= max_steps,
-                   "decoder steps: batch=%d (1..%d) step0=%d n_steps=%d max_steps=%d", batch, max_batch, step0, n_steps, max_steps);
-    dec_carve(p, batch, text_len, static_cast<float*>(workspace), w);
-    // the batched MFMA form serves every batch it is built for: at batch <= 4 it is also ahead of the VALU kernels below (default
-    // widths 64 against 88 us/step, the non-default golden shape 43 against 63: profiles/r6_05), which stay as the form for shapes
-    // it does not take and, through CTTS_TACO_VALU, as an independent cross-check of both other forms
-    if (batch > MAX_NB || (bg_supported(p) && !tuning().taco_valu))
-        return batched_steps(p, w, static_cast<const float*>(packed), keep_masks, mel_out, gate_out, align_out, hidden_out, batch,
-                             text_len, step0, n_steps, max_steps, as_stream(stream));
-    const auto& c = p.c;
-    const int NB = pad_batch(batch);
-    hipStream_t s = as_stream(stream);
-    const float* blob = static_cast<const float*>(packed);
-    // Early partial sums (see LstmPart and the heterogeneous kernels above).  Column windows of the three cells:
-    //   attention RNN  input [prenet | ctx | dec_h]: fresh = prenet, early = ctx, dec_h and W_hh.att_h  (behind project/prenet)
-    //   decoder RNN    input [att_h | ctx]:          fresh = ctx,    early = att_h and W_hh.dec_h       (behind the attention)
-    //   2nd decoder    input [dec_h]:                fresh = dec_h,  early = W_hh.d2_h                  (behind the attention)
-    const int Pn = c.prenet_dim, Ra = c.attention_rnn_dim, Rd = c.decoder_rnn_dim, Rd2 = c.second_decoder_rnn_dim;
-    const bool fast = c.window_range <= 16 && c.memory_dim <= ADM && c.attention_dim <= AAD && c.attention_dim % 4 == 0 &&
-                      c.location_n_filters <= AF && c.location_kernel_size <= AK && c.attention_rnn_dim <= 1536;
-    constexpr int R_DEC = 6, R_D2 = 8, R_ATT = 8;     // units per partial workgroup: 4 + 128 + 96 <= 256 CUs at config 5
-    const bool fuse = fast && n_steps > 0 && Rd % R_DEC == 0 && Rd2 % R_D2 == 0 && Ra % R_ATT == 0 &&
-                      NB * (p.I_dec + Rd) + 4 * R_DEC * NB <= ATTN_SMEM_FLOATS &&
-                      NB * (p.I_d2 + Rd2) + 4 * R_D2 * NB <= ATTN_SMEM_FLOATS &&
-                      NB * (p.I_att + Ra) + 4 * R_ATT * NB <= PROJ_FUSED_SMEM_FLOATS && !tuning().taco_no_fuse;
-    const LstmPart att_early{nullptr, w.gp_att, Pn, p.I_att, 1}, att_fresh{w.gp_att, nullptr, 0, Pn, 0};
-    const LstmPart dec_early{nullptr, w.gp_dec, 0, Ra, 1}, dec_fresh{w.gp_dec, nullptr, Ra, p.I_dec, 0};
-    const LstmPart d2_early{nullptr, w.gp_d2, 0, 0, 1}, d2_fresh{w.gp_d2, nullptr, 0, p.I_d2, 0};
-    if (fuse) {   // the first step of this call has nothing to hide behind: its early part runs in line
-        const int cur = step0 & 1;
-        rc = launch_lstm_nb(NB, blob, p.att, w.prenet, Pn, w.ctx, c.memory_dim, w.dec_h[cur], Rd, w.att_h[cur], nullptr,
-                            nullptr, p.I_att, Ra, s, &att_early);
-        if (rc) return rc;
-    }
-    for (int step = step0; step < step0 + n_steps; ++step) {
-        const int cur = step & 1, nxt = cur ^ 1;    // h ping-pong: read [cur], write [nxt]
-        // attention RNN on [prenet | context | decoder hidden]   (model.py:707-717)
-        rc = launch_lstm_nb(NB, blob, p.att, w.prenet, Pn, w.ctx, c.memory_dim, w.dec_h[cur], Rd,
-                            w.att_h[cur], w.att_h[nxt], w.att_c, p.I_att, Ra, s, fuse ? &att_fresh : nullptr);
-        if (rc) return rc;
-        AttnArgs a{};
-        a.Wq = blob + p.query_w; a.v = blob + p.v_w; a.Wloc = blob + p.loc_conv_w; a.Wd = blob + p.loc_dense_w;
-        a.scalars = blob + p.scalars;
-        a.att_h = w.att_h[nxt]; a.memory = w.memory; a.pm = w.pm;
-        a.w = w.w; a.cum = w.cum; a.ctx = w.ctx; a.pos = w.pos; a.align_out = align_out; a.lengths = w.lengths;
-        a.T = text_len; a.A = c.attention_dim; a.Ra = c.attention_rnn_dim; a.Dm = c.memory_dim;
-        a.F = c.location_n_filters; a.K = c.location_kernel_size; a.R = c.window_range;
-        a.step = step; a.max_steps = max_steps;
-        if (fast) {
-            const int gblocks = (c.attention_dim + 7) / 8;
-            if (NB == 1) hipLaunchKernelGGL(gemv_rows_kernel<1>, dim3(gblocks), dim3(256), 0, s, a.Wq, a.att_h, w.qbuf, c.attention_dim, c.attention_rnn_dim);
-            else if (NB == 2) hipLaunchKernelGGL(gemv_rows_kernel<2>, dim3(gblocks), dim3(256), 0, s, a.Wq, a.att_h, w.qbuf, c.attention_dim, c.attention_rnn_dim);
-            else hipLaunchKernelGGL(gemv_rows_kernel<4>, dim3(gblocks), dim3(256), 0, s, a.Wq, a.att_h, w.qbuf, c.attention_dim, c.attention_rnn_dim);
-            CTTS_CHECK_LAUNCH("gemv_rows");
-            if (fuse) {
-                const LstmCall e1 = make_call(blob, p.dec, w.att_h[nxt], Ra, w.ctx, c.memory_dim, nullptr, 0, w.dec_h[cur],
-                                              p.I_dec, Rd, NB, dec_early);
-                const LstmCall e2 = make_call(blob, p.d2, w.dec_h[nxt], Rd, nullptr, 0, nullptr, 0, w.d2_h[cur], p.I_d2, Rd2,
-                                              NB, d2_early);
-                const int n1 = Rd / R_DEC, n2 = Rd2 / R_D2;
-                const dim3 grid(batch + n1 + n2);
-                if (NB == 1) hipLaunchKernelGGL((attention_partials_kernel<1, R_DEC, R_D2>), grid, dim3(256), 0, s, a, w.qbuf, batch, e1, n1, e2);
-                else if (NB == 2) hipLaunchKernelGGL((attention_partials_kernel<2, R_DEC, R_D2>), grid, dim3(256), 0, s, a, w.qbuf, batch, e1, n1, e2);
-                else hipLaunchKernelGGL((attention_partials_kernel<4, R_DEC, R_D2>), grid, dim3(256), 0, s, a, w.qbuf, batch, e1, n1, e2);
-            } else {
-                hipLaunchKernelGGL(attention_window_kernel, dim3(batch), dim3(256), 0, s, a, w.qbuf);
-            }
-        } else if (c.location_n_filters <= 32) {
-            hipLaunchKernelGGL(attention_step_kernel<32>, dim3(batch), dim3(256), 0, s, a);
-        } else {
-            hipLaunchKernelGGL(attention_step_kernel<64>, dim3(batch), dim3(256), 0, s, a);
-        }
-        CTTS_CHECK_LAUNCH("attention_step");
-        // decoder RNN on [attention hidden | context], second decoder RNN on the first's output
-        rc = launch_lstm_nb(NB, blob, p.dec, w.att_h[nxt], c.attention_rnn_dim, w.ctx, c.memory_dim, nullptr, 0,
-                            w.dec_h[cur], w.dec_h[nxt], w.dec_c, p.I_dec, c.decoder_rnn_dim, s, fuse ? &dec_fresh : nullptr);
-        if (rc) return rc;
-        rc = launch_lstm_nb(NB, blob, p.d2, w.dec_h[nxt], c.decoder_rnn_dim, nullptr, 0, nullptr, 0, w.d2_h[cur],
-                            w.d2_h[nxt], w.d2_c, p.I_d2, c.second_decoder_rnn_dim, s, fuse ? &d2_fresh : nullptr);
-        if (rc) return rc;
-        ProjArgs q{};
-        q.Wp = blob + p.proj_w; q.bp = blob + p.proj_b; q.W1T = blob + p.prenet_w1; q.W2T = blob + p.prenet_w2;
-        q.dec_h = w.dec_h[nxt]; q.d2_h = w.d2_h[nxt]; q.ctx = w.ctx;
-        q.keep = step + 1 < max_steps ? keep_masks + (size_t)(step + 1) * 2 * batch * c.prenet_dim : nullptr;
-        q.mel_out = mel_out; q.gate_out = gate_out; q.prenet_out = w.prenet;
-        q.n_mel = c.n_mel_channels; q.Rd = c.second_decoder_rnn_dim; q.Dm = c.memory_dim; q.P = c.prenet_dim;
-        q.B = batch; q.step = step; q.max_steps = max_steps;
-        // (splitting this stage into three multi-workgroup GEMV launches was measured: 12.8 + 5.2 + 5.2 us vs 22 us
-        // here - every dependent launch costs ~5 us before its first useful byte, so fewer launches win)
-        if (fuse && step + 1 < step0 + n_steps) {
-            // ... and behind it, the early part of the NEXT step's attention RNN
-            const LstmCall e = make_call(blob, p.att, w.prenet, Pn, w.ctx, c.memory_dim, w.dec_h[nxt], Rd, w.att_h[nxt],
-                                         p.I_att, Ra, NB, att_early);
-            const dim3 grid(batch + Ra / R_ATT);
-            if (NB == 1) hipLaunchKernelGGL((project_partial_kernel<1, R_ATT>), grid, dim3(256), 0, s, q, batch, e);
-            else if (NB == 2) hipLaunchKernelGGL((project_partial_kernel<2, R_ATT>), grid, dim3(256), 0, s, q, batch, e);
-            else hipLaunchKernelGGL((project_partial_kernel<4, R_ATT>), grid, dim3(256), 0, s, q, batch, e);
-        } else {
-            hipLaunchKernelGGL(project_prenet_kernel, dim3(batch), dim3(256), 0, s, q);
-        }
-        CTTS_CHECK_LAUNCH("project_prenet");
-        if (hidden_out) {
-            hipLaunchKernelGGL(hidden_state_kernel, dim3(batch), dim3(256), 0, s, w.dec_h[nxt], w.d2_h[nxt], w.ctx, hidden_out, Rd2,
-                               c.memory_dim, step, max_steps);
-            CTTS_CHECK_LAUNCH("hidden_state");
-        }
-    }
-    return CTTS_OK;
+    return run_steps(STEPS_FREE, cfg, packed, keep_masks, nullptr, mel_out, gate_out, align_out, hidden_out, batch, text_len, step0,
+                     n_steps, max_steps, workspace, 0, stream);
 }
 
 // ---- split-bf16 (bf16x3) cells above 64 rows ---------------------------------------------------------------------------------
 namespace {
-// the shapes the mode is not built for, before any launch
-int x3_refuse(const DecPlan& p, const char* what) {
-    CTTS_CHECK_ARG(p.x3_bad == nullptr, "%s: %s is not a multiple of 32 (the split planes' K chunk)", what, p.x3_bad);
-    CTTS_CHECK_ARG(bg_supported(p), "%s: this decoder shape has no batched form (ctts_taco_decoder_max_batch is %d, bf16x3 needs %d)", what,
-                   MAX_NB, MAX_BATCH);
-    return CTTS_OK;
-}
 int bgx_pack(float* blob, size_t off, const BgMat& m, const BgSeg* segs, int nseg, int interleave_H, hipStream_t s) {
     BgxPackArgs a{};
     for (int i = 0; i < nseg; ++i) a.seg[i] = segs[i];
@@ -1468,19 +1546,8 @@ int ctts_taco_decoder_pack_bf16x3(const ctts_taco_decoder_config* cfg, const ctt
 int ctts_taco_decoder_steps_bf16x3(const ctts_taco_decoder_config* cfg, const void* packed, const uint8_t* keep_masks, float* mel_out,
                                    float* gate_out, float* align_out, float* hidden_out, int32_t batch, int32_t text_len, int32_t step0,
                                    int32_t n_steps, int32_t max_steps, void* workspace, void* stream) {
-    DecPlan p; DecWs w;
-    int rc = make_dec_plan(cfg, p); if (rc) return rc;
-    if ((rc = x3_refuse(p, "decoder bf16x3 steps"))) return rc;
-    // at or below 64 rows the step is bound by the weight stream and keeps its pipelined fp32 schedule, bit for bit
-    if (batch <= 64)
-        return ctts_taco_decoder_steps_hidden_f32(cfg, packed, keep_masks, mel_out, gate_out, align_out, hidden_out, batch, text_len, step0,
-                                                  n_steps, max_steps, workspace, stream);
-    CTTS_CHECK_ARG(packed && keep_masks && mel_out && gate_out && align_out && workspace, "decoder bf16x3 steps: NULL pointer");
-    CTTS_CHECK_ARG(batch <= MAX_BATCH && step0 >= 0 && n_steps >= 0 && step0 + n_steps <= max_steps,
-                   "decoder bf16x3 steps: batch=%d (1..%d) step0=%d n_steps=%d max_steps=%d", batch, MAX_BATCH, step0, n_steps, max_steps);
-    dec_carve(p, batch, text_len, static_cast<float*>(workspace), w);
-    return batched_steps(p, w, static_cast<const float*>(packed), keep_masks, mel_out, gate_out, align_out, hidden_out, batch, text_len,
-                         step0, n_steps, max_steps, as_stream(stream), nullptr, true);
+    return run_steps(STEPS_FREE_X3, cfg, packed, keep_masks, nullptr, mel_out, gate_out, align_out, hidden_out, batch, text_len, step0,
+                     n_steps, max_steps, workspace, 0, stream);
 }
 
 // ---- teacher-forced decoding (Decoder.forward, model.py:769-849) -------------------------------------------------------------
@@ -1516,39 +1583,15 @@ int ctts_taco_prenet_frames_f32(const ctts_taco_decoder_config* cfg, const void*
 int ctts_taco_decoder_steps_forced_f32(const ctts_taco_decoder_config* cfg, const void* packed, const float* prenet_all,
                                        float* align_out, float* hidden_out, int32_t batch, int32_t text_len, int32_t step0,
                                        int32_t n_steps, int32_t max_steps, void* workspace, size_t workspace_bytes, void* stream) {
-    DecPlan p; DecWs w;
-    int rc = make_dec_plan(cfg, p); if (rc) return rc;
-    CTTS_CHECK_ARG(packed && prenet_all && align_out && hidden_out && workspace, "forced decoder steps: NULL pointer");
-    CTTS_CHECK_ARG(bg_supported(p), "forced decoder steps: this decoder shape has no batched form (ctts_taco_decoder_max_batch is %d)", MAX_NB);
-    CTTS_CHECK_ARG(batch >= 1 && batch <= MAX_BATCH && step0 >= 0 && n_steps >= 0 && step0 + n_steps <= max_steps,
-                   "forced decoder steps: batch=%d (1..%d) step0=%d n_steps=%d max_steps=%d", batch, MAX_BATCH, step0, n_steps, max_steps);
-    CTTS_CHECK_ARG(text_len >= 1, "forced decoder steps: text_len=%d", text_len);
-    dec_carve(p, batch, text_len, static_cast<float*>(workspace), w);
-    CTTS_CHECK_ARG(w.total * sizeof(float) <= workspace_bytes, "forced decoder steps: workspace %zu bytes < required %zu",
-                   workspace_bytes, w.total * sizeof(float));
-    return batched_steps(p, w, static_cast<const float*>(packed), nullptr, nullptr, nullptr, align_out, hidden_out, batch, text_len,
-                         step0, n_steps, max_steps, as_stream(stream), prenet_all);
+    return run_steps(STEPS_FORCED, cfg, packed, nullptr, prenet_all, nullptr, nullptr, align_out, hidden_out, batch, text_len, step0, n_steps,
+                     max_steps, workspace, workspace_bytes, stream);
 }
 
 int ctts_taco_decoder_steps_forced_bf16x3(const ctts_taco_decoder_config* cfg, const void* packed, const float* prenet_all,
                                           float* align_out, float* hidden_out, int32_t batch, int32_t text_len, int32_t step0,
                                           int32_t n_steps, int32_t max_steps, void* workspace, size_t workspace_bytes, void* stream) {
-    DecPlan p; DecWs w;
-    int rc = make_dec_plan(cfg, p); if (rc) return rc;
-    if ((rc = x3_refuse(p, "forced decoder bf16x3 steps"))) return rc;
-    // at or below 64 rows the loop keeps its fp32 schedules, bit for bit
-    if (batch <= 64)
-        return ctts_taco_decoder_steps_forced_f32(cfg, packed, prenet_all, align_out, hidden_out, batch, text_len, step0, n_steps, max_steps,
-                                                  workspace, workspace_bytes, stream);
-    CTTS_CHECK_ARG(packed && prenet_all && align_out && hidden_out && workspace, "forced decoder steps: NULL pointer");
-    CTTS_CHECK_ARG(batch <= MAX_BATCH && step0 >= 0 && n_steps >= 0 && step0 + n_steps <= max_steps,
-                   "forced decoder steps: batch=%d (1..%d) step0=%d n_steps=%d max_steps=%d", batch, MAX_BATCH, step0, n_steps, max_steps);
-    CTTS_CHECK_ARG(text_len >= 1, "forced decoder steps: text_len=%d", text_len);
-    dec_carve(p, batch, text_len, static_cast<float*>(workspace), w);
-    CTTS_CHECK_ARG(w.total * sizeof(float) <= workspace_bytes, "forced decoder steps: workspace %zu bytes < required %zu",
-                   workspace_bytes, w.total * sizeof(float));
-    return batched_steps(p, w, static_cast<const float*>(packed), nullptr, nullptr, nullptr, align_out, hidden_out, batch, text_len,
-                         step0, n_steps, max_steps, as_stream(stream), prenet_all, true);
+    return run_steps(STEPS_FORCED_X3, cfg, packed, nullptr, prenet_all, nullptr, nullptr, align_out, hidden_out, batch, text_len, step0, n_steps,
+                     max_steps, workspace, workspace_bytes, stream);
 }
 
 int ctts_taco_project_frames_f32(const ctts_taco_decoder_config* cfg, const void* packed, const float* hidden, float* mel_out,

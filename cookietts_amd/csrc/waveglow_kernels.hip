@@ -888,10 +888,9 @@ int launch_upsample_squeeze(const float* mel, const float* W, const float* Wp, c
         const int chunk = ((F + nchunks - 1) / nchunks + 15) / 16 * 16;
         const int srow = (chunk + 31) / 32 * 32 + 4;           // frames f0 - 3 ... f0 + (chunk rounded to a pair of tiles)
         const int lds = UM_NMEL * srow * (int)sizeof(float);
-        // once per inference, so set on every call: the attribute belongs to the current device's copy of the kernel
-        if (lds > 64 * 1024)
-            CTTS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(upsample_squeeze_mfma_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, UM_NMEL * (UM_CHUNK_MAX + 4) * (int)sizeof(float)));
+        // the largest chunk's bytes, so that one opt-in serves every length (allow_dynamic_lds)
+        int rc;
+        if (lds > 64 * 1024 && (rc = CTTS_ALLOW_LDS(upsample_squeeze_mfma_kernel, UM_NMEL * (UM_CHUNK_MAX + 4) * (int)sizeof(float)))) return rc;
         hipLaunchKernelGGL(upsample_squeeze_mfma_kernel, dim3(UM_NMEL, (unsigned)(batch * nchunks)), dim3(512), lds, s, mel, Wp, bias,
                            spect, F, chunk, nchunks, srow, ld, pad);
         CTTS_CHECK_LAUNCH("upsample_squeeze_mfma");

@@ -34,14 +34,23 @@ def _inputs(hp, B, T, lens, n, seed):
     return memory_in, np.asarray(lens, dtype=np.int64), synthetic.prenet_dropout_masks(n, B, hp.prenet_dim, seed=seed + 1)
 
 
+_ORACLE_CASES = [(5, 37, 9), (16, 60, 9), (33, 45, 7), (64, 40, 5), (70, 40, 5)]
+# every case on the schedule the library picks for it, then the plain schedule where it is not that one
+_ORACLE_PARAMS = [pytest.param(*c, "pipelined" if c[0] <= 64 else "plain", id="-".join(map(str, c))) for c in _ORACLE_CASES] + \
+                 [pytest.param(*c, "plain", id="-".join(map(str, c)) + "-plain") for c in _ORACLE_CASES if c[0] <= 64]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,T,n", [(5, 37, 9), (16, 60, 9), (33, 45, 7), (64, 40, 5), (70, 40, 5)])
-def test_batched_decoder_matches_oracle(hip_lib_path, monkeypatch, B, T, n):
+@pytest.mark.parametrize("B,T,n,schedule", _ORACLE_PARAMS)
+def test_batched_decoder_matches_oracle(hip_lib_path, monkeypatch, tuning, B, T, n, schedule):
     """Column-tile shapes 16 / 32 / 64 / 128 items (NT = 1, 2, 4 with K split over two workgroups, 4 x 2), ragged lengths incl. texts
-    shorter than the window.
+    shorter than the window.  At 64 rows and fewer both schedules of the step: the pipelined one the library picks there, and the
+    plain one (CTTS_TACO_BG_NO_PIPE), which is the only one above 64 rows.
     (B = 5 is below the size from which the host picks this form by itself: the line is moved for the test.)"""
     import cookietts_amd.tacotron2 as t2
     monkeypatch.setattr(t2, "BATCHED_FROM", 5)
+    if schedule == "plain" and B <= 64:
+        tuning.set("CTTS_TACO_BG_NO_PIPE")
     m, hp, sd = _model()
     rng = np.random.default_rng(B)
     lens = [T] + [int(x) for x in rng.integers(18, T + 1, size=B - 1)]

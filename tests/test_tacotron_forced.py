@@ -285,14 +285,18 @@ def test_forward_on_its_own_free_running_frames_reproduces_them(hip_lib_path, B)
 
 
 @pytest.mark.gpu
-def test_blocks_rows_and_repeats(hip_lib_path):
+@pytest.mark.parametrize("schedule", ["pipelined", "plain"])
+def test_blocks_rows_and_repeats(hip_lib_path, tuning, schedule):
     """B = 18 (two 16-row tiles, ragged), T = 21, Decoder.forward.  Blocks of 8 / 8 / 5 steps (step0 > 0) equal one block of 21
     bit for bit; a repeated call is bit-equal (workspace reuse; padded rows of prenet_all stay zero); the first 17 rows of the
     18-row call equal a 17-row call bit for bit (same column-tile shape).  Against the same utterances decoded in a batch of
     their own the bound is the one test_tacotron_batched.py uses for that comparison, 2e-5; whether it is met bit for bit is
     printed.  That comparison also holds the loop's two forms to each other: 2 rows -> a 16-row tile and five launches per
     step; 18 rows -> 32 padded rows and four (the second decoder RNN and the next step's attention RNN as roles of one launch),
-    with other launch shapes, whose summation order may differ."""
+    with other launch shapes, whose summation order may differ.  Both schedules of the step: the pipelined one the library picks at
+    these sizes and the plain one (CTTS_TACO_BG_NO_PIPE)."""
+    if schedule == "plain":
+        tuning.set("CTTS_TACO_BG_NO_PIPE")
     g, hp, sd = _case("default")
     dec = _model("default").decoder
     B, T, TXT = 18, 21, 45
