@@ -196,43 +196,42 @@ int quad_ld(const Plan& p, const Geom& g) {
     for (int i = 0; i < p.c.n_layers; ++i) nt = std::max(nt, quad_geom(g, i).ntiles);
     return round_up(nt * 64, 128);
 }
-// The form is taken only where the in-layer launch runs the fp32 MFMA loop, and for utterances of at least WINOGRAD_MIN_COLS columns
-// (steps per batch item).  The test is on the utterance, never on the batch: an utterance must come out bit for bit the same
-// whatever batch it runs in (tests/test_full_size.py), and both forms are bit-identical across the kernel shapes a batch size picks.
-// The threshold is the length the A/B was run at (900 frames, profiles/r12_02_winograd_ab.txt, r12_04_winograd_sweep.txt).
-// CTTS_F32_NO_WINOGRAD: never; CTTS_F32_WINOGRAD_MIN: another threshold (0 = always).
+// ---- the in-layer form of a call ---------------------------------------------------
+// Decided once from (plan, geometry, one tuning snapshot): carve() sizes the buffers from it and WnCall launches from it.
+//   Direct            one GATE launch on the three x taps
+//   WinogradSeparate  transform, T2, T3, even, odd as launches of their own, cond rows copied for every layer
+//                     (CTTS_F32_WINOGRAD_PLAIN, or the register-staged conv-GEMM): the bit reference of WinogradPaired
+//   WinogradPaired    transform, T2 | T3 as the parts of one launch, even | odd as the parts of another
+//   WinogradLayer     transform, then the one-launch F(2,3) layer (wn_winograd_layer.hip: T2 / T3 stay in registers).  Not bit-equal
+//                     to the paired launches: ((S2 +- S3) + products) + b against ((products + b) + T2) +- T3
+//   WinogradLayerF43  quad transform, then the one-launch F(4,3) layer (1.5 C products per output and row where F(2,3) spends 2 C).
+//                     Not bit-equal to F(2,3): other products (float64 parity: tests/test_waveglow_winograd_f43_gpu.py)
+// Every test is on the utterance (columns = steps per batch item), never on the batch: an utterance must come out bit for bit the
+// same whatever batch it runs in (tests/test_full_size.py), and each form is bit-identical across the kernel shapes a batch picks.
+enum class InForm { Direct, WinogradSeparate, WinogradPaired, WinogradLayer, WinogradLayerF43 };
+
+// Each threshold is the length its A/B was run at (900 frames).  Winograd at all: profiles/r12_02_winograd_ab.txt,
+// r12_04_winograd_sweep.txt; CTTS_F32_WINOGRAD_MIN: another threshold (0 = always), CTTS_F32_NO_WINOGRAD: never.
 constexpr long long WINOGRAD_MIN_COLS = 28800;
-bool winograd_engages(const Plan& p, const Geom& g) {
-    const Tuning t = tuning();
-    if (t.f32_no_winograd || gemm_split_level(p.c.f32_gemm_mode) != 0) return false;
-    const long long min_cols = t.f32_winograd_min >= 0 ? t.f32_winograd_min : WINOGRAD_MIN_COLS;
-    return (long long)g.L >= min_cols;
-}
-
-// The one-launch Winograd layer (wn_winograd_layer.hip: T2 / T3 stay in registers) where the Winograd form engages, for utterances of
-// at least WINOGRAD_FUSED_MIN_COLS columns - the length its A/B was run at (900 frames, profiles/r17_01_winograd_fused_ab.txt); the
-// test is on the utterance alone, like the form's own.  Shorter ones keep the paired launches.  CTTS_F32_WINOGRAD_FUSED_MIN: another
-// threshold (0 = always); CTTS_F32_WINOGRAD_NO_FUSED or CTTS_F32_WINOGRAD_PLAIN: never.  Not bit-equal to the paired launches:
-// ((S2 +- S3) + products) + b against ((products + b) + T2) +- T3.
+// The one-launch layer: profiles/r17_01_winograd_fused_ab.txt; shorter utterances keep the paired launches.
+// CTTS_F32_WINOGRAD_FUSED_MIN: another threshold; CTTS_F32_WINOGRAD_NO_FUSED, _PLAIN or CTTS_F32_NO_GLDS: never.
 constexpr long long WINOGRAD_FUSED_MIN_COLS = 28800;
-bool winograd_fused_engages(const Plan& p, const Geom& g) {
-    const Tuning t = tuning();
-    if (t.f32_winograd_no_fused || t.f32_winograd_plain || t.f32_no_glds || !wn_winograd_layer_supported(p.C, p.H)) return false;
-    const long long min_cols = t.f32_winograd_fused_min >= 0 ? t.f32_winograd_fused_min : WINOGRAD_FUSED_MIN_COLS;
-    return winograd_engages(p, g) && (long long)g.L >= min_cols;
-}
-
-// The F(4,3) form of the one-launch layer (wn_winograd_layer.h, WNWG_F43: 1.5 C products per output and row where F(2,3) spends 2 C)
-// where the one-launch layer engages, for utterances of at least WINOGRAD_F43_MIN_COLS columns - the length its A/B was run at (900
-// frames, profiles/r23_01_winograd_f43_gonogo.txt); the test is on the utterance alone.  CTTS_F32_WINOGRAD_F43_MIN: another
-// threshold (0 = always); CTTS_F32_WINOGRAD_NO_F43, and whatever switches the one-launch layer off: never.  Not bit-equal to F(2,3):
-// other products (float64 parity: tests/test_waveglow_winograd_f43_gpu.py).
+// Its F(4,3) form: profiles/r23_01_winograd_f43_gonogo.txt.  CTTS_F32_WINOGRAD_F43_MIN: another threshold;
+// CTTS_F32_WINOGRAD_NO_F43, and whatever switches the one-launch layer off: never.
 constexpr long long WINOGRAD_F43_MIN_COLS = 28800;
-bool winograd_f43_engages(const Plan& p, const Geom& g) {
-    const Tuning t = tuning();
-    if (t.f32_winograd_no_f43 || !wn_winograd_layer_f43_supported(p.C, p.H) || !gemm_f32_dma_staged(p.nch_rs + p.nch1h)) return false;
-    const long long min_cols = t.f32_winograd_f43_min >= 0 ? t.f32_winograd_f43_min : WINOGRAD_F43_MIN_COLS;
-    return winograd_fused_engages(p, g) && (long long)g.L >= min_cols;
+
+InForm in_form(const Plan& p, const Geom& g, const Tuning& t) {
+    auto long_enough = [&](int knob, long long cols) { return (long long)g.L >= (knob >= 0 ? knob : cols); };
+    // only where the in-layer launch runs the fp32 MFMA loop
+    if (t.f32_no_winograd || gemm_split_level(p.c.f32_gemm_mode) != 0 || !long_enough(t.f32_winograd_min, WINOGRAD_MIN_COLS))
+        return InForm::Direct;
+    if (t.f32_winograd_plain || !gemm_f32_dma_staged(p.nch_rs + p.nch1h)) return InForm::WinogradSeparate;
+    if (t.f32_winograd_no_fused || t.f32_no_glds || !wn_winograd_layer_supported(p.C, p.H) ||
+        !long_enough(t.f32_winograd_fused_min, WINOGRAD_FUSED_MIN_COLS))
+        return InForm::WinogradPaired;
+    if (t.f32_winograd_no_f43 || !wn_winograd_layer_f43_supported(p.C, p.H) || !long_enough(t.f32_winograd_f43_min, WINOGRAD_F43_MIN_COLS))
+        return InForm::WinogradLayer;
+    return InForm::WinogradLayerF43;
 }
 
 struct Workspace {
@@ -240,14 +239,14 @@ struct Workspace {
     float* act_all;     // deferred-skip form: the gated activations of every layer of a flow ([n_layers] x act)
     float* a16;         // WN folds: layer 0's input [B][FOLD_ROWS][ld] = [audio_0; 1 on [0, L); 0]
     float* skend;       // WN folds: the skip/end accumulator [B][2 n_half][ld] between the groups of a flow
-    // Winograd in-layer form (NULL where it does not engage): V1..V4 [4][B][C][ldp], T2 / T3 [2][B][2C][ldp], h2e / h2o [2][B][H][ldp];
+    // Winograd in-layer forms (NULL in the direct form): V1..V4 [4][B][C][ldp], T2 / T3 [2][B][2C][ldp], h2e / h2o [2][B][H][ldp];
     // the F(4,3) form keeps V0..V5 [6][B][C][ldq] and h(t_0)..h(t_3) [4][B][H][ldq] in the same two buffers (sized for the larger form)
     float *wgV, *wgT, *wgH;
     int ldp, ldq;
     size_t total;  // floats
 };
 
-void carve(const Plan& p, const Geom& g, int batch, float* base, Workspace& w) {
+void carve(const Plan& p, const Geom& g, int batch, float* base, InForm in, Workspace& w) {
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o = align_up(o + n); return base ? base + r : nullptr; };
     const size_t B = batch;
@@ -265,9 +264,9 @@ void carve(const Plan& p, const Geom& g, int batch, float* base, Workspace& w) {
     w.skend = take(B * p.c.n_group * g.ld);
     w.wgV = w.wgT = w.wgH = nullptr;
     w.ldp = w.ldq = 0;
-    if (winograd_engages(p, g)) {
+    if (in != InForm::Direct) {
         w.ldp = pair_ld(p, g);
-        w.ldq = winograd_f43_engages(p, g) ? quad_ld(p, g) : 0;
+        w.ldq = in == InForm::WinogradLayerF43 ? quad_ld(p, g) : 0;
         w.wgV = take(std::max((size_t)4 * w.ldp, (size_t)6 * w.ldq) * B * p.C);
         w.wgT = take((size_t)2 * B * 2 * p.C * w.ldp);
         w.wgH = take(std::max((size_t)2 * w.ldp, (size_t)4 * w.ldq) * B * p.H);
@@ -302,15 +301,7 @@ struct ProfScope {
     ~ProfScope() { if (active) (void)hipEventRecord(stop, s); }
 };
 
-// ---- stage launchers ---------------------------------------------------------------
-GemmArgs base_args(const Plan& p, const Geom& g, int batch) {
-    GemmArgs a{};
-    a.gemm_mode = p.c.f32_gemm_mode;
-    a.ld = g.ld; a.pad = g.pad; a.L = g.L; a.ntiles = g.ntiles; a.batch = batch;
-    a.dst_ld = g.ld; a.dst_pad = g.pad;
-    return a;
-}
-
+// ---- speaker rows --------------------------------------------------------------------
 // spk[b][k*S + e][pad + l] = table_k[ids[b]][e]  (e < sdim), zero rows above: the reference concatenates the speaker
 // embedding, repeated over time, under the spectrogram (glow.py:193-196); here it is the second K segment of cond layer 0
 __global__ __launch_bounds__(256) void speaker_rows_kernel(const float* __restrict__ table, const int64_t* __restrict__ ids,
@@ -327,297 +318,7 @@ __global__ __launch_bounds__(256) void speaker_rows_kernel(const float* __restri
     spk[((size_t)b * n_flows * S + (size_t)k * S + e) * ld + n] = v;
 }
 
-int fill_speaker_rows(const Plan& p, const Geom& g, const float* blob, const int64_t* ids, float* spk, int batch,
-                      hipStream_t s) {
-    if (p.S == 0) return CTTS_OK;
-    CTTS_CHECK_ARG(ids != nullptr, "multispeaker model (speaker_embed_dim=%d) needs speaker ids (glow.py:193)",
-                   p.c.speaker_embed_dim);
-    for (int k = 0; k < p.c.n_flows; ++k)
-        hipLaunchKernelGGL(speaker_rows_kernel, dim3((g.ld + 255) / 256, p.S, batch), dim3(256), 0, s,
-                           blob + p.fl[k].spk_tab, ids, spk, k, p.c.n_flows, p.S, p.c.speaker_embed_dim, g.L, g.ld, g.pad);
-    CTTS_CHECK_LAUNCH("speaker_rows");
-    return CTTS_OK;
-}
-
-int run_cond(const Plan& p, const Geom& g, const float* blob, const float* spect, const float* spk, float* h_tmp,
-             float* h_all, int batch, hipStream_t s) {
-    const long long hstride = (long long)p.c.n_flows * p.H * g.ld;
-    GemmArgs a = base_args(p, g, batch);
-    a.A = blob + p.cond0_A; a.bias = blob + p.cond0_b;
-    a.nseg = 1; a.nch_total = p.nch0; a.MB = p.c.n_flows;
-    a.seg[0] = {spect, (long long)p.K0 * g.ld, p.K0 / GEMM_KC, 0, 0, 0};
-    if (p.S) {   // flow k (= M-block k) reads its own S embedding rows
-        CTTS_CHECK_ARG(spk != nullptr, "wn_cond: multispeaker model needs the speaker rows");
-        a.nseg = 2;
-        a.seg[1] = {spk, (long long)p.c.n_flows * p.S * g.ld, p.S / GEMM_KC, 0, p.S, 0};
-    }
-    a.dst0 = h_tmp; a.dst0_bstride = hstride; a.acc0 = 0;
-    a.dst1 = h_tmp; a.dst1_bstride = hstride; a.acc1 = 0;
-    a.split = p.c.n_flows * GEMM_BM;
-    a.M = p.c.n_flows * GEMM_BM;
-    int rc = launch_gemm_f32(GEMM_EPI_SPLIT, a, s);
-    if (rc) return rc;
-    a.A = blob + p.cond1_A; a.bias = blob + p.cond1_b;
-    a.nseg = 1; a.nch_total = p.nch1h;
-    a.seg[0] = {h_tmp, hstride, p.nch1h, 0, GEMM_BM, 0};
-    a.dst0 = h_all; a.dst1 = h_all;
-    return launch_gemm_f32(GEMM_EPI_SPLIT, a, s);
-}
-
-// WN start / end folds of the fp32 infer path (the default; CTTS_F32_NO_WN_FOLD turns them off): layer 0 reads the FOLD_ROWS-row
-// [audio_0; 1; 0] instead of x, and the skip sum is never formed - a skip/end pass per group of kept activations accumulates its
-// 2 n_half-row image, and the last one of a flow is also the flow tail (coupling, inverse 1x1, un-squeeze into `wave`).
-struct WnFold { float* a16; float* skend; float* audio; float* wave; };
-// Winograd F(2,3) form of the in-layer GEMMs that read x (the whole-infer entry points, which own these buffers)
-struct WnWinograd { float* V; float* T; float* Hc; int ldp; int ldq; };
-
-// One in-layer step in the Winograd form: transform, T2 = G2 V2, T3 = G3 V3, then the even and odd members of every pair
-//   act[t_e] = gate([W0 | C_i] [V1; h(t_e)] + b + T2 + T3),   act[t_o] = gate([-W2 | C_i] [V4; h(t_o)] + b + T2 - T3)
-// as launches of the conv-GEMM in pair space (ld = ldp, no halo); the GATE launches store to act's natural columns.
-// Default: T2 | T3 are the two parts of ONE launch and so are even | odd (GemmArgs.parts: one round peel per pair), and for
-// d % 4 == 0 the GATE launch reads the cond rows where they lie in h_all, through its pair map (GemmArgs.mseg) - the transform
-// then writes V only.  d = 2 (and d = 1, layer 0 without the start fold) read the copies h2e / h2o the transform makes.
-// CTTS_F32_WINOGRAD_PLAIN (or the register-staged kernels): cond copies for every layer, four launches, d = 2 transform one column
-// at a time.  Same bits either way: the same products summed in the same order.
-// Long utterances (winograd_fused_engages): the transform, then ONE launch of wn_winograd_layer.hip that keeps T2 / T3 in registers -
-// the same products, ((S2 +- S3) + products) + b: not the same bits.  The T planes stay in the workspace for the knob arm.
-int run_in_layer_winograd(const Plan& p, const Geom& g, const float* blob, int k, int i, const float* x, const float* h_all,
-                          float* act, const WnWinograd& wg, int batch, hipStream_t s) {
-    const auto& f = p.fl[k];
-    const PairGeom pg = pair_geom(g, i);
-    const int C = p.C, H = p.H, ldp = wg.ldp;
-    const long long hstride = (long long)p.c.n_flows * H * g.ld;
-    const size_t vplane = (size_t)batch * C * ldp, tplane = (size_t)batch * 2 * C * ldp, hplane = (size_t)batch * H * ldp;
-    const bool lean = !tuning().f32_winograd_plain && gemm_f32_dma_staged(p.nch_rs + p.nch1h);
-    const bool in_place = lean && pg.d % 4 == 0;
-    const bool fused = lean && winograd_fused_engages(p, g);
-    const float* h2 = h_all + (size_t)k * H * g.ld;
-    if (fused && wg.ldq > 0 && winograd_f43_engages(p, g)) {
-        // F(4,3): the quad transform (V0..V5, 1.5 C L floats), then ONE launch of the quad shape (the same shape at every grid size: no
-        // peel); the 128-column arm reads whole 128-column tiles, so the transform fills them
-        const PairGeom qg = quad_geom(g, i);
-        const int ldq = wg.ldq;
-        const int ncols = tuning().f32_no_small ? round_up(qg.ntiles * 64, 128) : qg.ntiles * 64;
-        int rc = launch_winograd_transform_quad(x, (long long)C * g.ld, h2, hstride, wg.V, wg.Hc, batch, C, H, qg.d, g.L, qg.Lp, g.ld, g.pad,
-                                                ldq, ncols, !in_place, s);
-        if (rc) return rc;
-        WnWinogradLayerArgs w{};
-        w.form = WNWG_F43;
-        w.A_T2 = blob + f.wq_U_A[0][i]; w.A_T3 = blob + f.wq_U_A[1][i]; w.A_T4 = blob + f.wq_U_A[2][i]; w.A_T5 = blob + f.wq_U_A[3][i];
-        w.A_e = blob + f.wq_e_A[i]; w.A_o = blob + f.wq_o_A[i];
-        w.bias = blob + f.in_b[i];
-        w.V = wg.V; w.vplane = (long long)batch * C * ldq;
-        w.Hc = wg.Hc; w.hplane = (long long)batch * H * ldq;
-        w.h2 = h2; w.h_bstride = hstride;
-        w.act = act; w.act_bstride = (long long)C * g.ld;
-        w.C = C; w.H = H; w.batch = batch;
-        w.ldp = ldq; w.Lp = qg.Lp; w.ntiles = qg.ntiles;
-        w.d = qg.d; w.L = g.L; w.ld = g.ld; w.pad = g.pad;
-        w.in_place = in_place;
-        return launch_wn_winograd_layer(w, s);
-    }
-    int rc = launch_winograd_transform(x, (long long)C * g.ld, h2, hstride, wg.V, wg.Hc, batch, C, H, pg.d, g.L, pg.Lp, g.ld, g.pad,
-                                       ldp, pg.ntiles * GEMM_BN, !in_place, lean, s);
-    if (rc) return rc;
-    if (fused) {
-        // ONE launch behind the transform: the four products of a pair block through one chunk stream, T2 / T3 in registers
-        WnWinogradLayerArgs w{};
-        w.A_T2 = blob + f.wg_T2_A[i]; w.A_T3 = blob + f.wg_T3_A[i]; w.A_e = blob + f.wg_e_A[i]; w.A_o = blob + f.wg_o_A[i];
-        w.bias = blob + f.in_b[i];
-        w.V = wg.V; w.vplane = (long long)vplane;
-        w.Hc = wg.Hc; w.hplane = (long long)hplane;
-        w.h2 = h2; w.h_bstride = hstride;
-        w.act = act; w.act_bstride = (long long)C * g.ld;
-        w.C = C; w.H = H; w.batch = batch;
-        w.ldp = ldp; w.Lp = pg.Lp; w.ntiles = pg.ntiles;
-        w.d = pg.d; w.L = g.L; w.ld = g.ld; w.pad = g.pad;
-        w.in_place = in_place;
-        return launch_wn_winograd_layer(w, s);
-    }
-    GemmArgs a{};
-    a.gemm_mode = p.c.f32_gemm_mode;
-    a.ld = ldp; a.pad = 0; a.L = pg.Lp; a.ntiles = pg.ntiles; a.batch = batch; a.MB = p.mb_in;
-    a.bias = blob + p.zero_b;
-    a.nseg = 1; a.nch_total = p.nch_rs;
-    a.dst_ld = ldp; a.dst_pad = 0; a.dst0_bstride = (long long)2 * C * ldp;
-    a.M = 2 * C; a.split = 2 * C;
-    const int np = lean ? 1 : 2;          // launches per pair
-    if (lean) {
-        a.parts = 2;
-        a.part_A = (long long)f.wg_T3_A[i] - (long long)f.wg_T2_A[i];
-        a.part_seg[0] = (long long)vplane;
-        a.part_dst0 = (long long)tplane;
-    }
-    for (int j = 0; j < np; ++j) {
-        a.A = blob + (j == 0 ? f.wg_T2_A[i] : f.wg_T3_A[i]);
-        a.seg[0] = {wg.V + (1 + j) * vplane, (long long)C * ldp, p.nch_rs, 0, 0, 0};
-        a.dst0 = wg.T + j * tplane;
-        if ((rc = launch_gemm_f32(GEMM_EPI_SPLIT, a, s))) return rc;
-    }
-    a.bias = blob + f.in_b[i];
-    a.nseg = 2; a.nch_total = p.nch_rs + p.nch1h;
-    a.split = 0; a.pairC = C;
-    a.dst0 = act; a.dst0_bstride = (long long)C * g.ld; a.dst_ld = g.ld; a.dst_pad = g.pad;
-    a.addend = wg.T; a.addend2 = wg.T + tplane; a.addend_bstride = (long long)2 * C * ldp;
-    a.map_d = pg.d; a.map_L = g.L;
-    if (lean) {
-        a.part_A = (long long)f.wg_o_A[i] - (long long)f.wg_e_A[i];
-        a.part_seg[0] = (long long)(3 * vplane);
-        a.part_seg[1] = in_place ? 0 : (long long)hplane;
-        a.part_dst0 = 0;
-    }
-    if (in_place) { a.mseg = 2; a.mseg_ld = g.ld; a.mseg_pad = g.pad; }
-    for (int j = 0; j < np; ++j) {
-        a.A = blob + (j == 0 ? f.wg_e_A[i] : f.wg_o_A[i]);
-        a.seg[0] = {wg.V + (j == 0 ? 0 : 3) * vplane, (long long)C * ldp, p.nch_rs, 0, 0, 0};
-        if (in_place) a.seg[1] = {h2, hstride, p.nch1h, 0, 0, 0};
-        else a.seg[1] = {wg.Hc + j * hplane, (long long)H * ldp, p.nch1h, 0, 0, 0};
-        a.addend2_sign = j == 0 ? 1.0f : -1.0f;
-        a.map_par = j;
-        if ((rc = launch_gemm_f32(GEMM_EPI_GATE, a, s))) return rc;
-    }
-    return CTTS_OK;
-}
-
-int run_wn_stack(const Plan& p, const Geom& g, const float* blob, int k, const float* audio, const float* h_all,
-                 float* x, float* act, float* out, int batch, hipStream_t s, float* act_all = nullptr,
-                 const WnFold* fold = nullptr, const WnWinograd* wg = nullptr, const CouplingForward* fwd = nullptr) {
-    const auto& f = p.fl[k];
-    const auto& d = p.fd[k];
-    const long long cstride = (long long)p.C * g.ld;
-    const long long hstride = (long long)p.c.n_flows * p.H * g.ld;
-    // x_0 is still formed: the res path x_1 = x_0 + W_res,0 act_0 needs it
-    int rc = launch_wn_start(audio, blob + f.start_w, blob + f.start_b, x, batch, p.C, p.c.n_group, d.ch_off,
-                             d.n_half, g.L, g.ld, g.pad, s);
-    if (rc) return rc;
-    CTTS_CHECK_ARG(fold == nullptr || act_all != nullptr, "wn_stack: the folded form needs the kept activations");
-    if (fold && (rc = launch_wn_start_ones(audio, fold->a16, batch, p.c.n_group, d.ch_off, d.n_half, g.L, g.ld, g.pad, s)))
-        return rc;
-    const int ncx = p.C / GEMM_KC;
-    // Deferred-skip form (default since round 4; CTTS_F32_NO_DEFER_SKIP = the per-layer form; the fp32 analogue of the bf16 path's): every layer's gated activation is
-    // kept, the per-layer launch computes the res rows only (x += W_res act), and the skip rows of up to four layers are
-    // ONE contraction with K = 4 C at the end of the group.  Same products, different summation order of the skip sum.
-    const bool defer = act_all != nullptr && (fold != nullptr || !tuning().f32_no_defer_skip);
-    const size_t act_stride = (size_t)batch * p.C * g.ld;
-    for (int i = 0; i < p.c.n_layers; ++i) {
-        const int dil = 1 << i;
-        if (defer) act = act_all + (size_t)(i % Plan::F32_SKIP_GROUP) * act_stride;
-        if (fold && i == 0) {
-            // layer 0 on the folded start: K = 3 taps x FOLD_ROWS + cond, same GATE epilogue and bias
-            GemmArgs a = base_args(p, g, batch);
-            a.A = blob + f.in0f_A; a.bias = blob + f.in_b[0];
-            a.nseg = 4; a.interleave = 3; a.nch_total = p.nch_in0f; a.MB = p.mb_in;
-            const long long astride = (long long)FOLD_ROWS * g.ld;
-            a.seg[0] = {fold->a16, astride, 1, -dil, 0, 0};
-            a.seg[1] = {fold->a16, astride, 1, 0, 0, 0};
-            a.seg[2] = {fold->a16, astride, 1, dil, 0, 0};
-            a.seg[3] = {h_all + (size_t)k * p.H * g.ld, hstride, p.nch1h, 0, 0, 0};
-            a.dst0 = act; a.dst0_bstride = cstride;
-            a.M = 2 * p.C; a.pairC = p.C;
-            // slot 0 keeps bracketing EVERY in-layer launch (its contract: one entry per layer); slot 3 has this one alone
-            ProfScope ps(CTTS_PROF_WN_IN, s), ps0(CTTS_PROF_WN_IN0F, s);
-            rc = launch_gemm_f32(GEMM_EPI_GATE, a, s);
-            if (rc) return rc;
-        } else if (wg) {
-            // (one slot-0 entry per layer: it brackets the transform and the four launches)
-            ProfScope ps(CTTS_PROF_WN_IN, s);
-            rc = run_in_layer_winograd(p, g, blob, k, i, x, h_all, act, *wg, batch, s);
-            if (rc) return rc;
-        } else {
-            GemmArgs a = base_args(p, g, batch);
-            a.A = blob + f.in_A[i]; a.bias = blob + f.in_b[i];
-            a.nseg = 4; a.interleave = 3; a.nch_total = p.nch_in; a.MB = p.mb_in;
-            a.seg[0] = {x, cstride, ncx, -dil, 0, 0};
-            a.seg[1] = {x, cstride, ncx, 0, 0, 0};
-            a.seg[2] = {x, cstride, ncx, dil, 0, 0};
-            a.seg[3] = {h_all + (size_t)k * p.H * g.ld, hstride, p.nch1h, 0, 0, 0};
-            a.dst0 = act; a.dst0_bstride = cstride;
-            a.M = 2 * p.C; a.pairC = p.C;
-            ProfScope ps(CTTS_PROF_WN_IN, s);
-            rc = launch_gemm_f32(GEMM_EPI_GATE, a, s);
-            if (rc) return rc;
-        }
-        if (defer) {
-            const bool last = i == p.c.n_layers - 1;
-            if (!last) {
-                GemmArgs a = base_args(p, g, batch);
-                a.A = blob + f.res_A[i]; a.bias = blob + f.res_b[i];
-                a.nseg = 1; a.nch_total = p.nch_rs; a.MB = p.mb_c();
-                a.seg[0] = {act, cstride, p.nch_rs, 0, 0, 0};
-                a.M = p.C; a.split = p.C;
-                a.dst0 = x; a.dst0_bstride = cstride; a.acc0 = 1;
-                a.dst1 = out; a.dst1_bstride = cstride; a.acc1 = 0;
-                ProfScope ps(fold ? CTTS_PROF_WN_RES_F : CTTS_PROF_WN_RS, s);
-                rc = launch_gemm_f32(GEMM_EPI_SPLIT, a, s);
-                if (rc) return rc;
-            }
-            const int gi = i / Plan::F32_SKIP_GROUP;
-            if (fold && (last || (i + 1) % Plan::F32_SKIP_GROUP == 0)) {
-                const int E = 2 * d.n_half;
-                ProfScope ps(CTTS_PROF_WN_SKEND, s);
-                rc = launch_skip_end(act_all, (long long)act_stride, p.group_layers(gi),
-                                     blob + f.skend_W + (size_t)gi * Plan::F32_SKIP_GROUP * p.C * E, fold->skend, gi == 0, last,
-                                     blob + f.skend_b, blob + f.winv, fold->audio, fold->wave, batch, p.C, p.c.n_group, d.ch_off,
-                                     d.n_half, g.L, g.ld, g.pad, s, last ? fwd : nullptr);
-                if (rc) return rc;
-            } else if (last || (i + 1) % Plan::F32_SKIP_GROUP == 0) {
-                const int nl = p.group_layers(gi);
-                GemmArgs a = base_args(p, g, batch);
-                a.A = blob + f.skip_A[gi]; a.bias = blob + f.skip_b[gi];
-                a.nseg = nl; a.nch_total = nl * p.nch_rs; a.MB = p.mb_c();
-                for (int j = 0; j < nl; ++j)
-                    a.seg[j] = {act_all + (size_t)j * act_stride, cstride, p.nch_rs, 0, 0, 0};
-                a.M = p.C; a.split = 0;
-                a.dst0 = x; a.dst0_bstride = cstride; a.acc0 = 1;
-                a.dst1 = out; a.dst1_bstride = cstride; a.acc1 = gi > 0 ? 1 : 0;
-                ProfScope ps(CTTS_PROF_WN_SKIP, s);
-                rc = launch_gemm_f32(GEMM_EPI_SPLIT, a, s);
-                if (rc) return rc;
-            }
-        } else {
-            const bool last = i == p.c.n_layers - 1;
-            GemmArgs a = base_args(p, g, batch);
-            a.A = blob + f.rs_A[i]; a.bias = blob + f.rs_b[i];
-            a.nseg = 1; a.nch_total = p.nch_rs; a.MB = p.rs_mb(i);
-            a.seg[0] = {act, cstride, p.nch_rs, 0, 0, 0};
-            a.M = p.rs_rows(i);
-            a.dst0 = x; a.dst0_bstride = cstride; a.acc0 = 1;
-            a.dst1 = out; a.dst1_bstride = cstride; a.acc1 = i > 0 ? 1 : 0;
-            a.split = last ? 0 : p.C;
-            ProfScope ps(CTTS_PROF_WN_RS, s);
-            rc = launch_gemm_f32(GEMM_EPI_SPLIT, a, s);
-            if (rc) return rc;
-        }
-    }
-    return CTTS_OK;
-}
-
-int run_flow_tail(const Plan& p, const Geom& g, const float* blob, int k, const float* out, float* audio,
-                  float* wave, int batch, hipStream_t s, const CouplingForward* fwd = nullptr) {
-    const auto& f = p.fl[k];
-    const auto& d = p.fd[k];
-    return launch_flow_tail(out, audio, wave, blob + f.end_w, blob + f.end_b, blob + f.winv, batch, p.C,
-                            p.c.n_group, d.ch_off, d.n_half, g.L, g.ld, g.pad, s, fwd);
-}
-
-// One flow of the fp32 infer loop, in the form the tuning knobs and the workspace select: the folded, deferred stack (whose last
-// skip/end pass is also the flow's tail) or the unfolded stack followed by the flow tail; the Winograd in-layer form where carve()
-// gave it buffers.  `audio` [B][n_group][L] is updated in place (or, with `wave`, the mixed rows go there un-squeezed).  The
-// whole-infer entry and the one-flow stage entry both run exactly this.  `fwd`: the forward direction (run_flow_forward) - the same
-// stack on rows a_0, and the tail, whichever kernel it is, does the forward coupling instead.
-int run_flow(const Plan& p, const Geom& g, const float* blob, int k, const Workspace& w, float* audio, const float* h_all,
-             float* wave, int batch, hipStream_t s, const CouplingForward* fwd = nullptr) {
-    const Tuning t = tuning();
-    const bool folded = !t.f32_no_wn_fold && !t.f32_no_defer_skip;
-    const WnWinograd wg{w.wgV, w.wgT, w.wgH, w.ldp, w.ldq};
-    const WnFold fw{w.a16, w.skend, audio, wave};
-    int rc = run_wn_stack(p, g, blob, k, audio, h_all, w.x, w.act, w.out, batch, s, w.act_all, folded ? &fw : nullptr,
-                          w.wgV ? &wg : nullptr, fwd);
-    if (rc || folded) return rc;        // folded: the last skip/end pass of the flow was its tail
-    return run_flow_tail(p, g, blob, k, w.out, audio, wave, batch, s, fwd);
-}
-
-// ---- forward (analysis) direction, glow.py:267-312 --------------------------------------------------------------------------
+// ---- forward (analysis) direction, glow.py:267-312: what it adds to the blob and the workspace ------------------------------
 // The forward mix matrices W_k [n_rem][n_rem] live in a blob of their own (the infer blob holds their inverses only).
 size_t fwd_mix_off(const Plan& p, int k) {
     size_t o = 0;
@@ -631,32 +332,387 @@ int fwd_log_s_rows(const Plan& p, int k) {
 }
 
 // Behind the infer workspace: the fp64 slots of the two-stage sums - ls_part [B][n_flows][nblk_ls] (one per tail workgroup) and
-// z_part [B][nblk_z]
-struct FwdWorkspace { Workspace w; double *ls_part, *z_part; int nblk_ls, nblk_z; size_t total; };
+// z_part [B][nblk_z]; total = both together, in floats
+struct FwdSums { double *ls_part, *z_part; int nblk_ls, nblk_z; size_t total; };
 
-void carve_fwd(const Plan& p, const Geom& g, int batch, float* base, FwdWorkspace& fw) {
-    carve(p, g, batch, base, fw.w);
-    fw.nblk_ls = (g.L + 255) / 256;
-    fw.nblk_z = (int)(((long long)p.c.n_group * g.L + FWD_SUMSQ_CHUNK - 1) / FWD_SUMSQ_CHUNK);
-    size_t o = fw.w.total;                              // a multiple of ALIGN_F floats = 256 bytes
+void carve_fwd(const Plan& p, const Geom& g, int batch, float* base, InForm in, Workspace& w, FwdSums& f) {
+    carve(p, g, batch, base, in, w);
+    f.nblk_ls = (g.L + 255) / 256;
+    f.nblk_z = (int)(((long long)p.c.n_group * g.L + FWD_SUMSQ_CHUNK - 1) / FWD_SUMSQ_CHUNK);
+    size_t o = w.total;                                 // a multiple of ALIGN_F floats = 256 bytes
     auto take = [&](size_t doubles) { size_t r = o; o = align_up(o + 2 * doubles); return base ? reinterpret_cast<double*>(base + r) : nullptr; };
-    fw.ls_part = take((size_t)batch * p.c.n_flows * fw.nblk_ls);
-    fw.z_part = take((size_t)batch * fw.nblk_z);
-    fw.total = o;
+    f.ls_part = take((size_t)batch * p.c.n_flows * f.nblk_ls);
+    f.z_part = take((size_t)batch * f.nblk_z);
+    f.total = o;
 }
 
-// One flow of the forward loop: the head (forward 1x1 mix of the rows still in play; flow 0 reads the waveform un-squeezed),
-// then run_flow with the forward tail.  z [B][n_group][L] is updated in place; rows above ch_off are early outputs and stay.
-// log_s_flow: NULL or this flow's rows (item stride ls_bstride).  The whole-model entry and the stage entry both run exactly this.
-int run_flow_forward(const Plan& p, const Geom& g, const float* blob, const float* fwd_blob, int k, const FwdWorkspace& fw,
-                     float* z, const float* wave, const float* h_all, float* log_s_flow, long long ls_bstride, int batch,
-                     hipStream_t s) {
-    const auto& d = p.fd[k];
-    int rc = launch_flow_head_forward(fwd_blob + fwd_mix_off(p, k), wave, z, batch, p.c.n_group, d.ch_off, d.n_rem, g.L, s);
-    if (rc) return rc;
-    const CouplingForward cf{log_s_flow, ls_bstride, fw.ls_part + (size_t)k * fw.nblk_ls, (long long)p.c.n_flows * fw.nblk_ls};
-    return run_flow(p, g, blob, k, fw.w, z, h_all, nullptr, batch, s, &cf);
+int workspace_fits(const char* what, size_t have, size_t need) {
+    if (need <= have) return CTTS_OK;
+    set_error("%s: workspace %zu bytes < required %zu", what, have, need);
+    return CTTS_E_WORKSPACE;
 }
+
+// ---- the fp32 runner ---------------------------------------------------------------
+// The WN stack of one flow comes in three forms (all the same products; the skip sum is summed in another order in each):
+//   PerLayer  one res/skip launch per layer (x += res rows, out (+)= skip rows), then the flow tail.  CTTS_F32_NO_DEFER_SKIP, and
+//             what ctts_wn_stack_f32 runs on the caller's buffers
+//   Deferred  every layer's gated activation is kept, the per-layer launch computes the res rows only, and the skip rows of up to
+//             F32_SKIP_GROUP layers are ONE contraction with K = 4 C behind the group; then the flow tail.  CTTS_F32_NO_WN_FOLD
+//   Folded    (the default) Deferred with the WN start / end folds: layer 0 reads the FOLD_ROWS-row [audio_0; 1; 0] instead of x, and
+//             the skip sum is never formed - a skip/end pass per group accumulates its 2 n_half-row image through `end`, and the
+//             last one of a flow is also the flow tail
+enum class StackForm { PerLayer, Deferred, Folded };
+
+// What a call decides once, the one builder of every launch descriptor, and a driver per stack form.
+struct WnCall {
+    Plan p; Geom g; Tuning t;
+    const float* blob = nullptr;
+    int batch = 0, frames = 0;
+    hipStream_t s = nullptr;
+    Workspace w{};                      // carved (take_workspace), or the caller's x / act / out alone (ctts_wn_stack_f32)
+    FwdSums sums{};                     // forward direction only
+    long long cstride = 0, hstride = 0; // batch-item strides of a C-row tensor and of the cond hidden of all flows
+    StackForm stack = StackForm::PerLayer;
+    InForm in = InForm::Direct;
+    float* audio = nullptr;             // [B][n_group][L], updated in place flow by flow (forward: z)
+    const float* h_all = nullptr;       // cond hidden of all flows
+
+    // ---- opening: plan and geometry, then (behind the entry's own checks) the workspace of its kind and the forms
+    int begin(const ctts_waveglow_config* cfg, const void* packed, int batch_, int frames_, void* stream) {
+        int rc = make_plan(cfg, p); if (rc) return rc;
+        rc = make_geom(p, frames_, g); if (rc) return rc;
+        t = tuning();
+        blob = static_cast<const float*>(packed); batch = batch_; frames = frames_; s = as_stream(stream);
+        cstride = (long long)p.C * g.ld;
+        hstride = (long long)p.c.n_flows * p.H * g.ld;
+        return CTTS_OK;
+    }
+    // the forms, the workspace carved for them, its size refusal; audio and h_all default to the workspace's own
+    int take_workspace(const char* what, void* workspace, size_t workspace_bytes, bool forward) {
+        in = in_form(p, g, t);
+        stack = t.f32_no_defer_skip ? StackForm::PerLayer : t.f32_no_wn_fold ? StackForm::Deferred : StackForm::Folded;
+        if (forward) carve_fwd(p, g, batch, static_cast<float*>(workspace), in, w, sums);
+        else carve(p, g, batch, static_cast<float*>(workspace), in, w);
+        audio = w.audio; h_all = w.h_all;
+        return workspace_fits(what, workspace_bytes, (forward ? sums.total : w.total) * sizeof(float));
+    }
+
+    // ---- accessors
+    const float* h(int k) const { return h_all + (size_t)k * p.H * g.ld; }            // flow k's cond rows
+    size_t act_stride() const { return (size_t)batch * p.C * g.ld; }
+    // layer i's gated activation: the one buffer of the per-layer form, else the layer's slot of its skip group (the skip launch
+    // runs behind the group; the next group reuses the slots)
+    float* act(int i) const { return stack == StackForm::PerLayer ? w.act : w.act_all + (size_t)(i % Plan::F32_SKIP_GROUP) * act_stride(); }
+    bool group_ends(int i) const { return i == p.c.n_layers - 1 || (i + 1) % Plan::F32_SKIP_GROUP == 0; }
+    // Winograd forms: layer i (d = 2^i) reads the cond rows where they lie in h_all, through the launch's pair map (GemmArgs.mseg),
+    // where d % 4 == 0; d = 2 (and d = 1, layer 0 without the start fold) and every layer of WinogradSeparate read the copies
+    // h2e / h2o the transform makes
+    bool in_place(int i) const { return in != InForm::WinogradSeparate && (1 << i) % 4 == 0; }
+    size_t plane(int rows) const { return (size_t)batch * rows * w.ldp; }           // one [B][rows][ldp] plane of wgV / wgT / wgH
+
+    // ---- descriptor builders: no GemmArgs or WnWinogradLayerArgs field is assigned anywhere else in the fp32 path
+    GemmArgs header() const {
+        GemmArgs a{};
+        a.gemm_mode = p.c.f32_gemm_mode;
+        a.ld = g.ld; a.pad = g.pad; a.L = g.L; a.ntiles = g.ntiles; a.batch = batch;
+        a.dst_ld = g.ld; a.dst_pad = g.pad;
+        return a;
+    }
+    // the GATE launch of layer i on three taps at dilation 2^i + the cond rows: taps of x, or (layer 0 of the folded stack) of
+    // a16 - K = 3 taps x FOLD_ROWS + cond, same epilogue and bias
+    GemmArgs in_gemm(int k, int i) const {
+        const auto& f = p.fl[k];
+        const bool fold0 = stack == StackForm::Folded && i == 0;
+        const int dil = 1 << i, nch = fold0 ? 1 : p.nch_rs;
+        const float* taps = fold0 ? w.a16 : w.x;
+        const long long tstride = fold0 ? (long long)FOLD_ROWS * g.ld : cstride;
+        GemmArgs a = header();
+        a.A = blob + (fold0 ? f.in0f_A : f.in_A[i]); a.bias = blob + f.in_b[i];
+        a.nseg = 4; a.interleave = 3; a.nch_total = fold0 ? p.nch_in0f : p.nch_in; a.MB = p.mb_in;
+        for (int tap = 0; tap < 3; ++tap) a.seg[tap] = {taps, tstride, nch, (tap - 1) * dil, 0, 0};
+        a.seg[3] = {h(k), hstride, p.nch1h, 0, 0, 0};
+        a.dst0 = act(i); a.dst0_bstride = cstride;
+        a.M = 2 * p.C; a.pairC = p.C;
+        return a;
+    }
+    // The SPLIT launches behind a layer contract `n` kept activations, from `acts` on, side by side along K, with a packed matrix of
+    // `rows` rows: rows below `split` add to x, the rest go to (acc1: add to) the skip sum
+    GemmArgs behind(size_t A, size_t bias, int rows, const float* acts, int n, int split, bool acc1) const {
+        GemmArgs a = header();
+        a.A = blob + A; a.bias = blob + bias;
+        a.nseg = n; a.nch_total = n * p.nch_rs; a.MB = (rows + GEMM_BM - 1) / GEMM_BM;
+        for (int j = 0; j < n; ++j) a.seg[j] = {acts + (size_t)j * act_stride(), cstride, p.nch_rs, 0, 0, 0};
+        a.M = rows; a.split = split;
+        a.dst0 = w.x; a.dst0_bstride = cstride; a.acc0 = 1;
+        a.dst1 = w.out; a.dst1_bstride = cstride; a.acc1 = acc1 ? 1 : 0;
+        return a;
+    }
+    // deferred forms, layers before the last: x += W_res,i act(i) + b
+    GemmArgs res(int k, int i) const { return behind(p.fl[k].res_A[i], p.fl[k].res_b[i], p.C, act(i), 1, p.C, false); }
+    // Deferred: the skip rows of group gi's layers, over the group's kept activations, in one contraction
+    GemmArgs skip_group(int k, int gi) const { return behind(p.fl[k].skip_A[gi], p.fl[k].skip_b[gi], p.C, w.act_all, p.group_layers(gi), 0, gi > 0); }
+    // PerLayer: res rows and skip rows of layer i in one launch (the last layer has skip rows only)
+    GemmArgs res_skip(int k, int i) const {
+        return behind(p.fl[k].rs_A[i], p.fl[k].rs_b[i], p.rs_rows(i), act(i), 1, i == p.c.n_layers - 1 ? 0 : p.C, i > 0);
+    }
+    // cond layer 0 of every flow in one launch (M-block k = flow k, which reads its own S speaker rows as a second K segment)
+    GemmArgs cond0(const float* spect, const float* spk, float* h_tmp) const {
+        GemmArgs a = header();
+        a.A = blob + p.cond0_A; a.bias = blob + p.cond0_b;
+        a.nseg = 1; a.nch_total = p.nch0; a.MB = p.c.n_flows;
+        a.seg[0] = {spect, (long long)p.K0 * g.ld, p.K0 / GEMM_KC, 0, 0, 0};
+        if (p.S) {
+            a.nseg = 2;
+            a.seg[1] = {spk, (long long)p.c.n_flows * p.S * g.ld, p.S / GEMM_KC, 0, p.S, 0};
+        }
+        a.dst0 = h_tmp; a.dst0_bstride = hstride; a.acc0 = 0;
+        a.dst1 = h_tmp; a.dst1_bstride = hstride; a.acc1 = 0;
+        a.split = p.c.n_flows * GEMM_BM;
+        a.M = p.c.n_flows * GEMM_BM;
+        return a;
+    }
+    // cond layer 1: that launch again with its own matrix, K = flow k's H rows of h_tmp, into h_all
+    GemmArgs cond1(const float* spect, const float* spk, float* h_tmp, float* h_out) const {
+        GemmArgs a = cond0(spect, spk, h_tmp);
+        a.A = blob + p.cond1_A; a.bias = blob + p.cond1_b;
+        a.nseg = 1; a.nch_total = p.nch1h;
+        a.seg[0] = {h_tmp, hstride, p.nch1h, 0, GEMM_BM, 0};
+        a.dst0 = h_out; a.dst1 = h_out;
+        return a;
+    }
+    // Winograd F(2,3) as launches of the conv-GEMM in pair space (ld = ldp, no halo):
+    //   T2 = G2 V2, T3 = G3 V3,   act[t_e] = gate([W0 | C_i] [V1; h(t_e)] + b + T2 + T3),   act[t_o] = gate([-W2 | C_i] [V4; h(t_o)] + b + T2 - T3)
+    // WinogradPaired: T2 | T3 are the two parts of launch j = 0 and so are even | odd (GemmArgs.parts: one round peel per pair);
+    // WinogradSeparate: launches j = 0, 1.  Same bits either way: the same products summed in the same order.
+    GemmArgs wg_header(int i) const {
+        const PairGeom pg = pair_geom(g, i);
+        GemmArgs a{};
+        a.gemm_mode = p.c.f32_gemm_mode;
+        a.ld = w.ldp; a.pad = 0; a.L = pg.Lp; a.ntiles = pg.ntiles; a.batch = batch; a.MB = p.mb_in;
+        a.M = 2 * p.C;
+        if (in == InForm::WinogradPaired) a.parts = 2;
+        return a;
+    }
+    GemmArgs wg_T(int k, int i, int j) const {
+        const auto& f = p.fl[k];
+        GemmArgs a = wg_header(i);
+        a.A = blob + (j == 0 ? f.wg_T2_A[i] : f.wg_T3_A[i]); a.bias = blob + p.zero_b;
+        a.nseg = 1; a.nch_total = p.nch_rs;
+        a.seg[0] = {w.wgV + (1 + j) * plane(p.C), (long long)p.C * w.ldp, p.nch_rs, 0, 0, 0};
+        a.split = 2 * p.C;
+        a.dst0 = w.wgT + j * plane(2 * p.C); a.dst0_bstride = (long long)2 * p.C * w.ldp; a.dst_ld = w.ldp; a.dst_pad = 0;
+        if (a.parts == 2) {
+            a.part_A = (long long)f.wg_T3_A[i] - (long long)f.wg_T2_A[i];
+            a.part_seg[0] = (long long)plane(p.C);
+            a.part_dst0 = (long long)plane(2 * p.C);
+        }
+        return a;
+    }
+    // (stores to act's natural columns, through the pair map of parity j)
+    GemmArgs wg_gate(int k, int i, int j) const {
+        const auto& f = p.fl[k];
+        GemmArgs a = wg_header(i);
+        a.A = blob + (j == 0 ? f.wg_e_A[i] : f.wg_o_A[i]); a.bias = blob + f.in_b[i];
+        a.nseg = 2; a.nch_total = p.nch_rs + p.nch1h;
+        a.seg[0] = {w.wgV + (j == 0 ? 0 : 3) * plane(p.C), (long long)p.C * w.ldp, p.nch_rs, 0, 0, 0};
+        if (in_place(i)) {
+            a.seg[1] = {h(k), hstride, p.nch1h, 0, 0, 0};
+            a.mseg = 2; a.mseg_ld = g.ld; a.mseg_pad = g.pad;
+        } else {
+            a.seg[1] = {w.wgH + j * plane(p.H), (long long)p.H * w.ldp, p.nch1h, 0, 0, 0};
+        }
+        a.split = 0; a.pairC = p.C;
+        a.dst0 = act(i); a.dst0_bstride = cstride; a.dst_ld = g.ld; a.dst_pad = g.pad;
+        a.addend = w.wgT; a.addend2 = w.wgT + plane(2 * p.C); a.addend_bstride = (long long)2 * p.C * w.ldp;
+        a.addend2_sign = j == 0 ? 1.0f : -1.0f;
+        a.map_d = 1 << i; a.map_L = g.L; a.map_par = j;
+        if (a.parts == 2) {
+            a.part_A = (long long)f.wg_o_A[i] - (long long)f.wg_e_A[i];
+            a.part_seg[0] = (long long)(3 * plane(p.C));
+            a.part_seg[1] = in_place(i) ? 0 : (long long)plane(p.H);
+        }
+        return a;
+    }
+    // the one-launch layer behind the transform (wn_winograd_layer.hip), F(2,3) in pair space or F(4,3) in quad space
+    WnWinogradLayerArgs wg_layer(int k, int i) const {
+        const auto& f = p.fl[k];
+        const bool f43 = in == InForm::WinogradLayerF43;
+        const PairGeom sg = f43 ? quad_geom(g, i) : pair_geom(g, i);
+        const int ldw = f43 ? w.ldq : w.ldp;
+        WnWinogradLayerArgs a{};
+        if (f43) {
+            a.form = WNWG_F43;
+            a.A_T2 = blob + f.wq_U_A[0][i]; a.A_T3 = blob + f.wq_U_A[1][i]; a.A_T4 = blob + f.wq_U_A[2][i]; a.A_T5 = blob + f.wq_U_A[3][i];
+            a.A_e = blob + f.wq_e_A[i]; a.A_o = blob + f.wq_o_A[i];
+        } else {
+            a.A_T2 = blob + f.wg_T2_A[i]; a.A_T3 = blob + f.wg_T3_A[i]; a.A_e = blob + f.wg_e_A[i]; a.A_o = blob + f.wg_o_A[i];
+        }
+        a.bias = blob + f.in_b[i];
+        a.V = w.wgV; a.vplane = (long long)batch * p.C * ldw;
+        a.Hc = w.wgH; a.hplane = (long long)batch * p.H * ldw;
+        a.h2 = h(k); a.h_bstride = hstride;
+        a.act = act(i); a.act_bstride = cstride;
+        a.C = p.C; a.H = p.H; a.batch = batch;
+        a.ldp = ldw; a.Lp = sg.Lp; a.ntiles = sg.ntiles;
+        a.d = sg.d; a.L = g.L; a.ld = g.ld; a.pad = g.pad;
+        a.in_place = in_place(i);
+        return a;
+    }
+
+    // ---- launches
+    int gemm(int prof_slot, int epi, const GemmArgs& a) const {
+        ProfScope ps(prof_slot, s);
+        return launch_gemm_f32(epi, a, s);
+    }
+    // x -> V (and, unless the layer reads them in place, the cond rows in pair / quad order).  WinogradSeparate: the d = 2 transform
+    // one column at a time; F(4,3): V0..V5 (1.5 C L floats), and the 128-column arm of the layer (CTTS_F32_NO_SMALL) reads whole
+    // 128-column tiles, so the transform fills them
+    int wg_transform(int k, int i) const {
+        if (in == InForm::WinogradLayerF43) {
+            const PairGeom qg = quad_geom(g, i);
+            const int ncols = t.f32_no_small ? round_up(qg.ntiles * 64, 128) : qg.ntiles * 64;
+            return launch_winograd_transform_quad(w.x, cstride, h(k), hstride, w.wgV, w.wgH, batch, p.C, p.H, qg.d, g.L, qg.Lp, g.ld, g.pad,
+                                                  w.ldq, ncols, !in_place(i), s);
+        }
+        const PairGeom pg = pair_geom(g, i);
+        return launch_winograd_transform(w.x, cstride, h(k), hstride, w.wgV, w.wgH, batch, p.C, p.H, pg.d, g.L, pg.Lp, g.ld, g.pad, w.ldp,
+                                         pg.ntiles * GEMM_BN, !in_place(i), in != InForm::WinogradSeparate, s);
+    }
+    // x (layer 0 of the folded stack: a16) -> act(i).  Slot CTTS_PROF_WN_IN has one entry per layer, around the transform and every
+    // launch behind it; slot WN_IN0F has the folded layer 0 alone.
+    int in_layer(int k, int i) const {
+        ProfScope ps(CTTS_PROF_WN_IN, s);
+        if (stack == StackForm::Folded && i == 0) return gemm(CTTS_PROF_WN_IN0F, GEMM_EPI_GATE, in_gemm(k, i));
+        int rc = in == InForm::Direct ? CTTS_OK : wg_transform(k, i);
+        if (rc) return rc;
+        switch (in) {
+        case InForm::Direct:
+            return launch_gemm_f32(GEMM_EPI_GATE, in_gemm(k, i), s);
+        case InForm::WinogradLayer:
+        case InForm::WinogradLayerF43:
+            return launch_wn_winograd_layer(wg_layer(k, i), s);
+        case InForm::WinogradSeparate:
+        case InForm::WinogradPaired:
+            const int np = in == InForm::WinogradPaired ? 1 : 2;          // launches per pair
+            for (int j = 0; j < np; ++j)
+                if ((rc = launch_gemm_f32(GEMM_EPI_SPLIT, wg_T(k, i, j), s))) return rc;
+            for (int j = 0; j < np; ++j)
+                if ((rc = launch_gemm_f32(GEMM_EPI_GATE, wg_gate(k, i, j), s))) return rc;
+        }
+        return rc;
+    }
+    // x_0 = W_start a_0 + b_start (glow.py:189)
+    int start(int k, const float* a_in) const {
+        const auto& f = p.fl[k];
+        const auto& d = p.fd[k];
+        return launch_wn_start(a_in, blob + f.start_w, blob + f.start_b, w.x, batch, p.C, p.c.n_group, d.ch_off, d.n_half, g.L, g.ld, g.pad, s);
+    }
+    // Folded: W_end . (skip rows of group gi) over the group's kept activations, accumulated in skend; `tail`: the flow's last pass
+    // also adds b', couples, mixes and stores to audio (or un-squeezed to `wave`)
+    int skip_end(int k, int gi, bool tail, float* wave, const CouplingForward* fwd) const {
+        const auto& f = p.fl[k];
+        const auto& d = p.fd[k];
+        ProfScope ps(CTTS_PROF_WN_SKEND, s);
+        return launch_skip_end(w.act_all, (long long)act_stride(), p.group_layers(gi),
+                               blob + f.skend_W + (size_t)gi * Plan::F32_SKIP_GROUP * p.C * 2 * d.n_half, w.skend, gi == 0, tail,
+                               blob + f.skend_b, blob + f.winv, audio, wave, batch, p.C, p.c.n_group, d.ch_off, d.n_half, g.L, g.ld,
+                               g.pad, s, tail ? fwd : nullptr);
+    }
+    // end conv on the skip sum, coupling, inverse 1x1 (+ un-squeeze into `wave`); `fwd`: the forward coupling instead, nothing mixed
+    int flow_tail(int k, const float* out, float* a_io, float* wave, const CouplingForward* fwd) const {
+        const auto& f = p.fl[k];
+        const auto& d = p.fd[k];
+        return launch_flow_tail(out, a_io, wave, blob + f.end_w, blob + f.end_b, blob + f.winv, batch, p.C, p.c.n_group, d.ch_off,
+                                d.n_half, g.L, g.ld, g.pad, s, fwd);
+    }
+
+    // ---- one driver per stack form
+    // Folded.  1. start: x_0 is still formed, the res path x_1 = x_0 + W_res,0 act_0 needs it
+    //          2. ones rows: a16 = [audio_0; 1 on [0, L); 0]
+    //          3. per layer: in-layer; before the last layer: res rows
+    //          4. behind each skip group: its skip/end pass; the last one is the flow's tail
+    int flow_folded(int k, float* wave, const CouplingForward* fwd) const {
+        const auto& d = p.fd[k];
+        int rc = start(k, audio);
+        if (rc) return rc;
+        if ((rc = launch_wn_start_ones(audio, w.a16, batch, p.c.n_group, d.ch_off, d.n_half, g.L, g.ld, g.pad, s))) return rc;
+        for (int i = 0; i < p.c.n_layers; ++i) {
+            const bool last = i == p.c.n_layers - 1;
+            if ((rc = in_layer(k, i))) return rc;
+            if (!last && (rc = gemm(CTTS_PROF_WN_RES_F, GEMM_EPI_SPLIT, res(k, i)))) return rc;
+            if (group_ends(i) && (rc = skip_end(k, i / Plan::F32_SKIP_GROUP, last, wave, fwd))) return rc;
+        }
+        return CTTS_OK;
+    }
+    // Deferred (x, out <- the stack on a_in; the flow tail follows).  1. start
+    //          2. per layer: in-layer; before the last layer: res rows
+    //          3. behind each skip group: its skip rows, one contraction into out
+    int stack_deferred(int k, const float* a_in) const {
+        int rc = start(k, a_in);
+        if (rc) return rc;
+        for (int i = 0; i < p.c.n_layers; ++i) {
+            if ((rc = in_layer(k, i))) return rc;
+            if (i < p.c.n_layers - 1 && (rc = gemm(CTTS_PROF_WN_RS, GEMM_EPI_SPLIT, res(k, i)))) return rc;
+            if (group_ends(i) && (rc = gemm(CTTS_PROF_WN_SKIP, GEMM_EPI_SPLIT, skip_group(k, i / Plan::F32_SKIP_GROUP)))) return rc;
+        }
+        return CTTS_OK;
+    }
+    // PerLayer (likewise).  1. start
+    //          2. per layer: in-layer; res and skip rows
+    int stack_per_layer(int k, const float* a_in) const {
+        int rc = start(k, a_in);
+        if (rc) return rc;
+        for (int i = 0; i < p.c.n_layers; ++i) {
+            if ((rc = in_layer(k, i))) return rc;
+            if ((rc = gemm(CTTS_PROF_WN_RS, GEMM_EPI_SPLIT, res_skip(k, i)))) return rc;
+        }
+        return CTTS_OK;
+    }
+    // One flow of the infer loop: rows of `audio` updated in place (or, with `wave`, the mixed rows go there un-squeezed).  The
+    // whole-infer entry and the one-flow stage entry both run exactly this.  `fwd`: the forward direction - the same stack on rows
+    // a_0, and the tail, whichever kernel it is, does the forward coupling instead.
+    int run_flow(int k, float* wave, const CouplingForward* fwd) const {
+        if (stack == StackForm::Folded) return flow_folded(k, wave, fwd);
+        const int rc = stack == StackForm::Deferred ? stack_deferred(k, audio) : stack_per_layer(k, audio);
+        return rc ? rc : flow_tail(k, w.out, audio, wave, fwd);
+    }
+    // One flow of the forward loop: the head (forward 1x1 mix of the rows still in play; flow 0 reads the waveform un-squeezed),
+    // then run_flow with the forward tail.  audio = z is updated in place; rows above ch_off are early outputs and stay.
+    // log_s_flow: NULL or this flow's rows (item stride ls_bstride).  The whole-model entry and the stage entry both run exactly this.
+    int run_flow_forward(const float* fwd_blob, int k, const float* wave, float* log_s_flow, long long ls_bstride) const {
+        const auto& d = p.fd[k];
+        int rc = launch_flow_head_forward(fwd_blob + fwd_mix_off(p, k), wave, audio, batch, p.c.n_group, d.ch_off, d.n_rem, g.L, s);
+        if (rc) return rc;
+        const CouplingForward cf{log_s_flow, ls_bstride, sums.ls_part + (size_t)k * sums.nblk_ls, (long long)p.c.n_flows * sums.nblk_ls};
+        return run_flow(k, nullptr, &cf);
+    }
+
+    // ---- conditioning: mel -> spect (upsampling + squeeze), the speaker rows, cond layers 0 and 1 of every flow
+    int upsample(const float* mel, float* spect) const {
+        return launch_upsample_squeeze(mel, blob + p.up_w, p.up_mfma ? blob + p.up_wp : nullptr, blob + p.up_b, spect, batch,
+                                       p.c.n_mel_channels, frames, p.c.win_length, p.c.hop_length, p.c.n_group, g.ld, g.pad, s);
+    }
+    int speaker_rows(const int64_t* ids, float* spk) const {
+        if (p.S == 0) return CTTS_OK;
+        CTTS_CHECK_ARG(ids != nullptr, "multispeaker model (speaker_embed_dim=%d) needs speaker ids (glow.py:193)", p.c.speaker_embed_dim);
+        for (int k = 0; k < p.c.n_flows; ++k)
+            hipLaunchKernelGGL(speaker_rows_kernel, dim3((g.ld + 255) / 256, p.S, batch), dim3(256), 0, s, blob + p.fl[k].spk_tab, ids,
+                               spk, k, p.c.n_flows, p.S, p.c.speaker_embed_dim, g.L, g.ld, g.pad);
+        CTTS_CHECK_LAUNCH("speaker_rows");
+        return CTTS_OK;
+    }
+    int cond(const float* spect, const float* spk, float* h_tmp, float* h_out) const {
+        CTTS_CHECK_ARG(p.S == 0 || spk != nullptr, "wn_cond: multispeaker model needs the speaker rows");
+        const int rc = launch_gemm_f32(GEMM_EPI_SPLIT, cond0(spect, spk, h_tmp), s);
+        return rc ? rc : launch_gemm_f32(GEMM_EPI_SPLIT, cond1(spect, spk, h_tmp, h_out), s);
+    }
+    int conditioning(const float* mel, const int64_t* ids) const {
+        int rc = upsample(mel, w.spect);
+        if (rc) return rc;
+        if ((rc = speaker_rows(ids, w.spk))) return rc;
+        return cond(w.spect, w.spk, w.h_tmp, w.h_all);
+    }
+};
 
 // ======================================================================================
 // bf16 variant (BASELINE config 3): WN in-layer / res-skip GEMMs on bf16 MFMA with fp32 accumulation,
@@ -1094,21 +1150,23 @@ int ctts_waveglow_pack_flow(const ctts_waveglow_config* cfg, int32_t k, const ct
                            w->rs_b[i] + (last ? 0 : C), C, p.mb_c() * GEMM_BM, gj == 0 ? 1 : 0);
         CTTS_CHECK_LAUNCH("skip_bias_f32");
     }
-    // Winograd F(2,3) in-layer form: G2, G3 (dense rows: T2 / T3 are addends in dense row order) and [W0 | C_i], [-W2 | C_i]
-    // (pair rows, like in_A); the dense scratch is reused layer by layer (one stream)
+    // one [U | C_i] GATE matrix of the Winograd forms (pair rows, like in_A; K = C + H): U [2C][C] with row stride u_ld and element
+    // stride u_step, then the cond slice of layer i
+    auto pack_gate = [&](size_t A, const float* U, long long u_ld, int u_step, int i) -> int {
+        const int nch = p.nch_rs + p.nch1h;
+        const int rc = launch_pack_a(blob + A, U, GEMM_BM, p.mb_in, nch, 0, C, GEMM_EPI_GATE, C, 2 * C, 0, u_ld, u_step, s);
+        return rc ? rc : launch_pack_a(blob + A, w->cond_w[2], GEMM_BM, p.mb_in, nch, C, H, GEMM_EPI_GATE, C, 2 * C, (long long)2 * C * i, H, 1, s);
+    };
+    // Winograd F(2,3) in-layer form: G2, G3 (dense rows: T2 / T3 are addends in dense row order) and [W0 | C_i], [-W2 | C_i];
+    // the dense scratch is reused layer by layer (one stream)
     for (int i = 0; i < p.c.n_layers; ++i) {
         float* dense = blob + f.wg_dense;
         const size_t dn = (size_t)2 * C * C;
         if ((rc = launch_winograd_g(w->in_w[i], dense, 2 * C, C, s))) return rc;
         if ((rc = launch_pack_a(blob + f.wg_T2_A[i], dense, GEMM_BM, p.mb_in, p.nch_rs, 0, C, GEMM_EPI_SPLIT, C, 2 * C, 0, C, 1, s))) return rc;
         if ((rc = launch_pack_a(blob + f.wg_T3_A[i], dense + dn, GEMM_BM, p.mb_in, p.nch_rs, 0, C, GEMM_EPI_SPLIT, C, 2 * C, 0, C, 1, s))) return rc;
-        if ((rc = launch_pack_a(blob + f.wg_e_A[i], w->in_w[i], GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, 0, C, GEMM_EPI_GATE, C, 2 * C, 0,
-                                (long long)C * ks, ks, s))) return rc;
-        if ((rc = launch_pack_a(blob + f.wg_o_A[i], dense + 2 * dn, GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, 0, C, GEMM_EPI_GATE, C, 2 * C, 0,
-                                C, 1, s))) return rc;
-        for (float* A : {blob + f.wg_e_A[i], blob + f.wg_o_A[i]})
-            if ((rc = launch_pack_a(A, w->cond_w[2], GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, C, H, GEMM_EPI_GATE, C, 2 * C,
-                                    (long long)2 * C * i, H, 1, s))) return rc;
+        if ((rc = pack_gate(f.wg_e_A[i], w->in_w[i], (long long)C * ks, ks, i))) return rc;          // W0: tap 0 of in_w
+        if ((rc = pack_gate(f.wg_o_A[i], dense + 2 * dn, C, 1, i))) return rc;
     }
     // Winograd F(4,3) form: U1..U4 (dense rows, SPLIT) and [U0 | C_i], [U5 | C_i] (pair rows, GATE) through the same dense scratch
     for (int i = 0; i < (f.wq_e_A.empty() ? 0 : p.c.n_layers); ++i) {
@@ -1117,11 +1175,8 @@ int ctts_waveglow_pack_flow(const ctts_waveglow_config* cfg, int32_t k, const ct
         if ((rc = launch_winograd_g43(w->in_w[i], dense, 2 * C, C, s))) return rc;
         for (int j = 0; j < 4; ++j)
             if ((rc = launch_pack_a(blob + f.wq_U_A[j][i], dense + (1 + j) * dn, GEMM_BM, p.mb_in, p.nch_rs, 0, C, GEMM_EPI_SPLIT, C, 2 * C, 0, C, 1, s))) return rc;
-        if ((rc = launch_pack_a(blob + f.wq_e_A[i], dense, GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, 0, C, GEMM_EPI_GATE, C, 2 * C, 0, C, 1, s))) return rc;
-        if ((rc = launch_pack_a(blob + f.wq_o_A[i], dense + 5 * dn, GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, 0, C, GEMM_EPI_GATE, C, 2 * C, 0, C, 1, s))) return rc;
-        for (float* A : {blob + f.wq_e_A[i], blob + f.wq_o_A[i]})
-            if ((rc = launch_pack_a(A, w->cond_w[2], GEMM_BM, p.mb_in, p.nch_rs + p.nch1h, C, H, GEMM_EPI_GATE, C, 2 * C,
-                                    (long long)2 * C * i, H, 1, s))) return rc;
+        if ((rc = pack_gate(f.wq_e_A[i], dense, C, 1, i))) return rc;
+        if ((rc = pack_gate(f.wq_o_A[i], dense + 5 * dn, C, 1, i))) return rc;
     }
     // WN start / end folds: layer 0 on [audio_0; 1] (K = [tap0, tap1, tap2] of one FOLD_ROWS chunk each, then the cond slice of
     // layer 0; bias in_b[0] as packed above) and the skip rows seen through `end`
@@ -1137,66 +1192,57 @@ int ctts_waveglow_pack_flow(const ctts_waveglow_config* cfg, int32_t k, const ct
 size_t ctts_waveglow_workspace_bytes(const ctts_waveglow_config* cfg, int32_t batch, int32_t frames) {
     Plan p; Geom g; Workspace w;
     if (make_plan(cfg, p) || make_geom(p, frames, g) || batch < 1) return 0;
-    carve(p, g, batch, nullptr, w);
+    carve(p, g, batch, nullptr, in_form(p, g, tuning()), w);
     return w.total * sizeof(float);
 }
 
 int ctts_upsample_squeeze_f32(const ctts_waveglow_config* cfg, const void* packed, const float* mel, float* spect,
                               int32_t batch, int32_t frames, void* stream) {
-    Plan p; Geom g;
-    int rc = make_plan(cfg, p); if (rc) return rc;
-    rc = make_geom(p, frames, g); if (rc) return rc;
+    WnCall c;
+    const int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
     CTTS_CHECK_ARG(packed && mel && spect && batch >= 1, "upsample_squeeze: bad argument");
-    const float* blob = static_cast<const float*>(packed);
-    return launch_upsample_squeeze(mel, blob + p.up_w, p.up_mfma ? blob + p.up_wp : nullptr, blob + p.up_b, spect, batch, p.c.n_mel_channels, frames,
-                                   p.c.win_length, p.c.hop_length, p.c.n_group, g.ld, g.pad, as_stream(stream));
+    return c.upsample(mel, spect);
 }
 
 int ctts_wn_cond_f32(const ctts_waveglow_config* cfg, const void* packed, const float* spect, const float* spk_rows,
                      float* h_tmp, float* h_all, int32_t batch, int32_t frames, void* stream) {
-    Plan p; Geom g;
-    int rc = make_plan(cfg, p); if (rc) return rc;
-    rc = make_geom(p, frames, g); if (rc) return rc;
+    WnCall c;
+    const int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
     CTTS_CHECK_ARG(packed && spect && h_tmp && h_all && batch >= 1, "wn_cond: bad argument");
-    return run_cond(p, g, static_cast<const float*>(packed), spect, spk_rows, h_tmp, h_all, batch, as_stream(stream));
+    return c.cond(spect, spk_rows, h_tmp, h_all);
 }
 
+// (the per-layer stack with direct in-layers on the caller's buffers, whatever the knobs say)
 int ctts_wn_stack_f32(const ctts_waveglow_config* cfg, const void* packed, int32_t flow, const float* audio,
                       const float* h_all, float* x, float* act, float* out, int32_t batch, int32_t frames,
                       void* stream) {
-    Plan p; Geom g;
-    int rc = make_plan(cfg, p); if (rc) return rc;
-    rc = make_geom(p, frames, g); if (rc) return rc;
-    CTTS_CHECK_ARG(flow >= 0 && flow < p.c.n_flows, "wn_stack: flow %d", flow);
+    WnCall c;
+    const int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
+    CTTS_CHECK_ARG(flow >= 0 && flow < c.p.c.n_flows, "wn_stack: flow %d", flow);
     CTTS_CHECK_ARG(packed && audio && h_all && x && act && out && batch >= 1, "wn_stack: bad argument");
-    return run_wn_stack(p, g, static_cast<const float*>(packed), flow, audio, h_all, x, act, out, batch,
-                        as_stream(stream));
+    c.w.x = x; c.w.act = act; c.w.out = out; c.h_all = h_all;
+    return c.stack_per_layer(flow, audio);
 }
 
 int ctts_flow_tail_f32(const ctts_waveglow_config* cfg, const void* packed, int32_t flow, const float* out,
                        float* audio, float* wave, int32_t batch, int32_t frames, void* stream) {
-    Plan p; Geom g;
-    int rc = make_plan(cfg, p); if (rc) return rc;
-    rc = make_geom(p, frames, g); if (rc) return rc;
-    CTTS_CHECK_ARG(flow >= 0 && flow < p.c.n_flows, "flow_tail: flow %d", flow);
+    WnCall c;
+    const int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
+    CTTS_CHECK_ARG(flow >= 0 && flow < c.p.c.n_flows, "flow_tail: flow %d", flow);
     CTTS_CHECK_ARG(packed && out && audio && batch >= 1, "flow_tail: bad argument");
-    return run_flow_tail(p, g, static_cast<const float*>(packed), flow, out, audio, wave, batch, as_stream(stream));
+    return c.flow_tail(flow, out, audio, wave, nullptr);
 }
 
 int ctts_waveglow_flow_f32(const ctts_waveglow_config* cfg, const void* packed, int32_t flow, float* audio,
                            const float* h_all, float* wave, int32_t batch, int32_t frames, void* workspace,
                            size_t workspace_bytes, void* stream) {
-    Plan p; Geom g; Workspace w;
-    int rc = make_plan(cfg, p); if (rc) return rc;
-    rc = make_geom(p, frames, g); if (rc) return rc;
-    CTTS_CHECK_ARG(flow >= 0 && flow < p.c.n_flows, "waveglow_flow: flow %d", flow);
+    WnCall c;
+    int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
+    CTTS_CHECK_ARG(flow >= 0 && flow < c.p.c.n_flows, "waveglow_flow: flow %d", flow);
     CTTS_CHECK_ARG(packed && audio && h_all && workspace && batch >= 1, "waveglow_flow: bad argument");
-    carve(p, g, batch, static_cast<float*>(workspace), w);
-    if (w.total * sizeof(float) > workspace_bytes) {
-        set_error("waveglow_flow: workspace %zu bytes < required %zu", workspace_bytes, w.total * sizeof(float));
-        return CTTS_E_WORKSPACE;
-    }
-    return run_flow(p, g, static_cast<const float*>(packed), flow, w, audio, h_all, wave, batch, as_stream(stream));
+    if ((rc = c.take_workspace("waveglow_flow", workspace, workspace_bytes, false))) return rc;
+    c.audio = audio; c.h_all = h_all;
+    return c.run_flow(flow, wave, nullptr);
 }
 
 size_t ctts_waveglow_forward_packed_bytes(const ctts_waveglow_config* cfg) {
@@ -1218,74 +1264,57 @@ int ctts_waveglow_pack_forward_mix(const ctts_waveglow_config* cfg, int32_t flow
 }
 
 size_t ctts_waveglow_forward_workspace_bytes(const ctts_waveglow_config* cfg, int32_t batch, int32_t frames) {
-    Plan p; Geom g; FwdWorkspace fw;
+    Plan p; Geom g; Workspace w; FwdSums f;
     if (make_plan(cfg, p) || make_geom(p, frames, g)) return 0;
     if (batch < 1) { set_error("forward_workspace_bytes: batch=%d", batch); return 0; }
-    carve_fwd(p, g, batch, nullptr, fw);
-    return fw.total * sizeof(float);
+    carve_fwd(p, g, batch, nullptr, in_form(p, g, tuning()), w, f);
+    return f.total * sizeof(float);
 }
 
 int ctts_waveglow_flow_forward_f32(const ctts_waveglow_config* cfg, const void* packed, const void* packed_fwd, int32_t flow,
                                    float* z, const float* wave, const float* h_all, float* log_s, double* sum_log_s,
                                    int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes, void* stream) {
-    Plan p; Geom g; FwdWorkspace fw;
-    int rc = make_plan(cfg, p); if (rc) return rc;
-    rc = make_geom(p, frames, g); if (rc) return rc;
-    CTTS_CHECK_ARG(flow >= 0 && flow < p.c.n_flows, "waveglow_flow_forward: flow %d", flow);
+    WnCall c;
+    int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
+    CTTS_CHECK_ARG(flow >= 0 && flow < c.p.c.n_flows, "waveglow_flow_forward: flow %d", flow);
     CTTS_CHECK_ARG(packed && packed_fwd && z && h_all && workspace && batch >= 1, "waveglow_flow_forward: bad argument");
     CTTS_CHECK_ARG(wave == nullptr || flow == 0, "waveglow_flow_forward: only flow 0 reads the waveform (flow %d)", flow);
-    carve_fwd(p, g, batch, static_cast<float*>(workspace), fw);
-    if (fw.total * sizeof(float) > workspace_bytes) {
-        set_error("waveglow_flow_forward: workspace %zu bytes < required %zu", workspace_bytes, fw.total * sizeof(float));
-        return CTTS_E_WORKSPACE;
-    }
-    hipStream_t s = as_stream(stream);
-    rc = run_flow_forward(p, g, static_cast<const float*>(packed), static_cast<const float*>(packed_fwd), flow, fw, z, wave, h_all,
-                          log_s, (long long)p.fd[flow].n_half * g.L, batch, s);
+    if ((rc = c.take_workspace("waveglow_flow_forward", workspace, workspace_bytes, true))) return rc;
+    c.audio = z; c.h_all = h_all;
+    rc = c.run_flow_forward(static_cast<const float*>(packed_fwd), flow, wave, log_s, (long long)c.p.fd[flow].n_half * c.g.L);
     if (rc || !sum_log_s) return rc;
-    return launch_sum_partials(fw.ls_part + (size_t)flow * fw.nblk_ls, (long long)p.c.n_flows * fw.nblk_ls, 0, fw.nblk_ls, sum_log_s,
-                               1, 1, batch, s);
+    const FwdSums& f = c.sums;
+    return launch_sum_partials(f.ls_part + (size_t)flow * f.nblk_ls, (long long)c.p.c.n_flows * f.nblk_ls, 0, f.nblk_ls, sum_log_s, 1, 1,
+                               batch, c.s);
 }
 
 int ctts_waveglow_forward_spk_f32(const ctts_waveglow_config* cfg, const void* packed, const void* packed_fwd, const float* mel,
                                   const float* audio, const int64_t* speaker_ids, float* z, float* log_s, double* sums,
                                   int32_t batch, int32_t frames, void* workspace, size_t workspace_bytes, void* stream) {
-    Plan p; Geom g; FwdWorkspace fw;
-    int rc = make_plan(cfg, p); if (rc) return rc;
-    rc = make_geom(p, frames, g); if (rc) return rc;
+    WnCall c;
+    int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
+    const Plan& p = c.p;
     CTTS_CHECK_ARG(packed && packed_fwd && mel && audio && z && workspace && batch >= 1, "forward: bad argument");
     CTTS_CHECK_ARG(p.S == 0 || speaker_ids != nullptr, "multispeaker model (speaker_embed_dim=%d) needs speaker ids (glow.py:193)",
                    p.c.speaker_embed_dim);
-    carve_fwd(p, g, batch, static_cast<float*>(workspace), fw);
-    if (fw.total * sizeof(float) > workspace_bytes) {
-        set_error("forward: workspace %zu bytes < required %zu", workspace_bytes, fw.total * sizeof(float));
-        return CTTS_E_WORKSPACE;
-    }
-    hipStream_t s = as_stream(stream);
-    const float* blob = static_cast<const float*>(packed);
-    const Workspace& w = fw.w;
+    if ((rc = c.take_workspace("forward", workspace, workspace_bytes, true))) return rc;
+    c.audio = z;
     // glow.py:276-282 with audio.size(1) == frames * hop keeps the columns infer's trim keeps: the same conditioning
-    rc = launch_upsample_squeeze(mel, blob + p.up_w, p.up_mfma ? blob + p.up_wp : nullptr, blob + p.up_b, w.spect, batch, p.c.n_mel_channels, frames,
-                                 p.c.win_length, p.c.hop_length, p.c.n_group, g.ld, g.pad, s);
-    if (rc) return rc;
-    rc = fill_speaker_rows(p, g, blob, speaker_ids, w.spk, batch, s);
-    if (rc) return rc;
-    rc = run_cond(p, g, blob, w.spect, w.spk, w.h_tmp, w.h_all, batch, s);
-    if (rc) return rc;
-    const int S = fwd_log_s_rows(p, p.c.n_flows);
+    if ((rc = c.conditioning(mel, speaker_ids))) return rc;
+    const int L = c.g.L, S = fwd_log_s_rows(p, p.c.n_flows);
     for (int k = 0; k < p.c.n_flows; ++k) {
-        float* ls = log_s ? log_s + (size_t)fwd_log_s_rows(p, k) * g.L : nullptr;
-        rc = run_flow_forward(p, g, blob, static_cast<const float*>(packed_fwd), k, fw, z, k == 0 ? audio : nullptr, w.h_all, ls,
-                              (long long)S * g.L, batch, s);
+        float* ls = log_s ? log_s + (size_t)fwd_log_s_rows(p, k) * L : nullptr;
+        rc = c.run_flow_forward(static_cast<const float*>(packed_fwd), k, k == 0 ? audio : nullptr, ls, (long long)S * L);
         if (rc) return rc;
     }
     if (!sums) return CTTS_OK;
-    rc = launch_sum_partials(fw.ls_part, (long long)p.c.n_flows * fw.nblk_ls, fw.nblk_ls, fw.nblk_ls, sums, p.c.n_flows + 1,
-                             p.c.n_flows, batch, s);
+    const FwdSums& f = c.sums;
+    rc = launch_sum_partials(f.ls_part, (long long)p.c.n_flows * f.nblk_ls, f.nblk_ls, f.nblk_ls, sums, p.c.n_flows + 1, p.c.n_flows,
+                             batch, c.s);
     if (rc) return rc;
-    rc = launch_sumsq_partials(z, fw.z_part, batch, (long long)p.c.n_group * g.L, fw.nblk_z, s);
+    rc = launch_sumsq_partials(z, f.z_part, batch, (long long)p.c.n_group * L, f.nblk_z, c.s);
     if (rc) return rc;
-    return launch_sum_partials(fw.z_part, fw.nblk_z, 0, fw.nblk_z, sums + p.c.n_flows, p.c.n_flows + 1, 1, batch, s);
+    return launch_sum_partials(f.z_part, f.nblk_z, 0, f.nblk_z, sums + p.c.n_flows, p.c.n_flows + 1, 1, batch, c.s);
 }
 
 int ctts_waveglow_infer_f32(const ctts_waveglow_config* cfg, const void* packed, const float* mel,
@@ -1298,32 +1327,17 @@ int ctts_waveglow_infer_f32(const ctts_waveglow_config* cfg, const void* packed,
 int ctts_waveglow_infer_spk_f32(const ctts_waveglow_config* cfg, const void* packed, const float* mel,
                                 const float* z_scaled, const int64_t* speaker_ids, float* wave, int32_t batch,
                                 int32_t frames, void* workspace, size_t workspace_bytes, void* stream) {
-    Plan p; Geom g; Workspace w;
-    int rc = make_plan(cfg, p); if (rc) return rc;
-    rc = make_geom(p, frames, g); if (rc) return rc;
+    WnCall c;
+    int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
     CTTS_CHECK_ARG(packed && mel && z_scaled && wave && workspace && batch >= 1, "infer: bad argument");
-    carve(p, g, batch, static_cast<float*>(workspace), w);
-    if (w.total * sizeof(float) > workspace_bytes) {
-        set_error("infer: workspace %zu bytes < required %zu", workspace_bytes, w.total * sizeof(float));
-        return CTTS_E_WORKSPACE;
-    }
-    hipStream_t s = as_stream(stream);
-    const float* blob = static_cast<const float*>(packed);
-    CTTS_CHECK_HIP(hipMemcpyAsync(w.audio, z_scaled, (size_t)batch * p.c.n_group * g.L * sizeof(float),
-                                  hipMemcpyDeviceToDevice, s));
-    rc = launch_upsample_squeeze(mel, blob + p.up_w, p.up_mfma ? blob + p.up_wp : nullptr, blob + p.up_b, w.spect, batch, p.c.n_mel_channels, frames,
-                                 p.c.win_length, p.c.hop_length, p.c.n_group, g.ld, g.pad, s);
-    if (rc) return rc;
-    rc = fill_speaker_rows(p, g, blob, speaker_ids, w.spk, batch, s);
-    if (rc) return rc;
-    rc = run_cond(p, g, blob, w.spect, w.spk, w.h_tmp, w.h_all, batch, s);
-    if (rc) return rc;
-    for (int k = p.c.n_flows - 1; k >= 0; --k) {
-        rc = run_flow(p, g, blob, k, w, w.audio, w.h_all, k == 0 ? wave : nullptr, batch, s);
-        if (rc) return rc;
-    }
+    if ((rc = c.take_workspace("infer", workspace, workspace_bytes, false))) return rc;
+    CTTS_CHECK_HIP(hipMemcpyAsync(c.audio, z_scaled, (size_t)batch * c.p.c.n_group * c.g.L * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    if ((rc = c.conditioning(mel, speaker_ids))) return rc;
+    for (int k = c.p.c.n_flows - 1; k >= 0; --k)
+        if ((rc = c.run_flow(k, k == 0 ? wave : nullptr, nullptr))) return rc;
     return CTTS_OK;
 }
+
 
 int ctts_last_gemm_loop(void) { return last_gemm_loop(); }
 int ctts_last_winograd_f43_width(void) { return last_wn_winograd_f43_width(); }
@@ -1461,33 +1475,29 @@ static size_t workspace_bf16_bytes_impl(const ctts_waveglow_config* cfg, int32_t
 static int infer_bf16_impl(const ctts_waveglow_config* cfg, const void* packed, const void* packed_bf16, const float* mel,
                            const float* z_scaled, const int64_t* speaker_ids, float* wave, int32_t batch, int32_t frames,
                            void* workspace, size_t workspace_bytes, void* stream, int P, int f16 = 0) {
-    Plan p; Geom g; BfWs w; BfPlan q;
-    int rc = make_plan(cfg, p); if (rc) return rc;
-    rc = make_geom(p, frames, g); if (rc) return rc;
+    WnCall c; BfWs w; BfPlan q;
+    int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
+    const Plan& p = c.p;
+    const Geom& g = c.g;
     CTTS_CHECK_ARG(packed && packed_bf16 && mel && z_scaled && wave && workspace && batch >= 1, "infer_bf16: bad argument");
     CTTS_CHECK_ARG(p.C % BGEMM_KC == 0 && p.C <= 512, "infer_bf16: n_channels=%d (multiple of 32, <= 512)", p.C);
     CTTS_CHECK_ARG(p.c.n_group <= 8, "infer_bf16: n_group=%d (the reduced-precision flow boundaries hold <= 8 channels; fp32 takes 16)", p.c.n_group);
     make_bf_plan(p, q, P, f16);
     carve_bf(p, g, batch, static_cast<char*>(workspace), w, P);
-    if (w.total_bytes > workspace_bytes) {
-        set_error("infer_bf16: workspace %zu bytes < required %zu", workspace_bytes, w.total_bytes);
-        return CTTS_E_WORKSPACE;
-    }
-    hipStream_t s = as_stream(stream);
-    const float* blob = static_cast<const float*>(packed);
+    if ((rc = workspace_fits("infer_bf16", workspace_bytes, w.total_bytes))) return rc;
+    hipStream_t s = c.s;
+    const float* blob = c.blob;
     const bf16_t* bblob = static_cast<const bf16_t*>(packed_bf16);
     CTTS_CHECK_HIP(hipMemcpyAsync(w.audio, z_scaled, (size_t)batch * p.c.n_group * g.L * sizeof(float),
                                   hipMemcpyDeviceToDevice, s));
-    rc = launch_upsample_squeeze(mel, blob + p.up_w, p.up_mfma ? blob + p.up_wp : nullptr, blob + p.up_b, w.spect, batch, p.c.n_mel_channels, frames,
-                                 p.c.win_length, p.c.hop_length, p.c.n_group, g.ld, g.pad, s);
-    if (rc) return rc;
+    if ((rc = c.upsample(mel, w.spect))) return rc;
     // cond layers 0 / 1 for all flows on bf16 MFMA: spect -> bf16 K8, then two flow-batched GEMMs whose
     // epilogues write the conditioning hidden directly in bf16 K8
     hipLaunchKernelGGL(cvt_f32_to_k8_kernel, dim3((g.ld + 255) / 256, p.K0 / 8, batch), dim3(256), 0, s, w.spect,
                        w.spect_bf, p.K0, g.ld, w.spect_lo, q.f16);
     CTTS_CHECK_LAUNCH("cvt_f32_to_k8");
     if (p.S) {
-        if ((rc = fill_speaker_rows(p, g, blob, speaker_ids, w.spk, batch, s))) return rc;
+        if ((rc = c.speaker_rows(speaker_ids, w.spk))) return rc;
         hipLaunchKernelGGL(cvt_f32_to_k8_kernel, dim3((g.ld + 255) / 256, p.c.n_flows * p.S / 8, batch), dim3(256), 0, s,
                            w.spk, w.spk_bf, p.c.n_flows * p.S, g.ld, w.spk_lo, q.f16);
         CTTS_CHECK_LAUNCH("cvt_f32_to_k8(speaker rows)");

@@ -40,6 +40,9 @@ FORMS = {
     "unfolded_winograd": [("CTTS_F32_NO_WN_FOLD", "1"), ("CTTS_F32_WINOGRAD_MIN", "0")],  # layer 0 reads x at d = 1: the
                                                                                         # transform kernel's non-vector path
     "per_layer": [("CTTS_F32_NO_DEFER_SKIP", "1")],                                     # res/skip per layer + flow tail
+    # the Winograd form on the register-staged conv-GEMM: transform, T2, T3, even, odd as launches of their own, even where the
+    # one-launch layer is asked for
+    "winograd_no_glds": [("CTTS_F32_NO_GLDS", "1"), ("CTTS_F32_WINOGRAD_MIN", "0"), ("CTTS_F32_WINOGRAD_FUSED_MIN", "0")],
 }
 
 
@@ -199,7 +202,7 @@ def _live_reference(st, k, B, F, seed):
 
 
 @pytest.mark.parametrize("F", [1, 5])
-@pytest.mark.parametrize("form", ["default", "winograd", "per_layer"])
+@pytest.mark.parametrize("form", ["default", "winograd", "per_layer", "winograd_no_glds"])
 @pytest.mark.parametrize("name", ["toy_spk_rezero", "toy_hop512_g16", "toy_hop384_g12"])
 def test_toy_flows_match_float64(toy, tuning, name, form, F):
     """toy_spk_rezero: ReZero's alpha in the res/skip rows; toy_hop512_g16: n_half up to 8 against FOLD_ROWS; toy_hop384_g12: the
