@@ -199,6 +199,14 @@ SIGNATURES = {
     "ctts_waveglow_infer_bf16": (C.c_int, [_CFG, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
     "ctts_upsample_squeeze_f32": (C.c_int, [_CFG, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
     "ctts_wn_cond_f32": (C.c_int, [_CFG, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
+    "ctts_waveglow_has_composed_cond": (C.c_int, [_CFG]),
+    "ctts_waveglow_packed_bytes_opt": (C.c_size_t, [_CFG, C.c_int32]),
+    "ctts_waveglow_pack_cond_composed": (C.c_int, [_CFG, C.c_int32, C.POINTER(WaveGlowFlowWeights), _FP, _FP]),
+    "ctts_waveglow_workspace_bytes_opt": (C.c_size_t, [_CFG, C.c_int32, C.c_int32, C.c_int32]),
+    "ctts_waveglow_infer_spk_f32_opt": (C.c_int, [_CFG, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP, C.c_size_t, C.c_int32,
+                                                 _FP]),
+    "ctts_wn_cond_composed_scratch_bytes": (C.c_size_t, [_CFG, C.c_int32, C.c_int32]),
+    "ctts_wn_cond_composed_f32": (C.c_int, [_CFG, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
     "ctts_wn_stack_f32": (C.c_int, [_CFG, _FP, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
     "ctts_flow_tail_f32": (C.c_int, [_CFG, _FP, C.c_int32, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP]),
     "ctts_waveglow_flow_f32": (C.c_int, [_CFG, _FP, C.c_int32, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP, C.c_size_t, _FP]),
@@ -382,6 +390,8 @@ SIGNATURES = {
 # any more (ABI 6): "default" / None = fp32 MFMA.
 MODEL_GEMM_MODES = {None: 0, "default": 0, "f32": 1, "bf16x3": 2, "bf16x6": 3}
 GEMM_MODES = {"f32": 1, "bf16x3": 2, "bf16x6": 3}
+# CTTS_WG_OPT_COMPOSED_COND: `options` of the ctts_waveglow_*_opt entry points (the conditioning as one GEMM from the mel frames)
+WG_OPT_COMPOSED_COND = 1
 
 
 def model_gemm_mode(mode):

@@ -42,6 +42,13 @@ enum GemmEpilogue : int {
     //   rows < split of  rs_w . act + rs_b  -> dst0 = src0 + .   (next layer's input)
     //   rows >= split                       -> dst1 (+)= .       (skip sum)
     GEMM_EPI_GATE_RS = 6,
+    // Phase-expanding store (the composed conditioning of the fp32 WaveGlow, waveglow_api.hip): the launch's columns are FRAMES and
+    // block-local row R of M-block mb is (hidden row R / P, phase R % P) of flow mb / P, P = GemmArgs.phase:
+    //   dst0[b][(mb / P) * 256 + (mb % P) * (256 / P) + R / P][dst_pad + P * n + R % P] = acc + bias
+    // A lane's four consecutive accumulator rows are four consecutive phases: one 16-byte store.  bm = 256, <= 4 segments, fp32 MFMA
+    // loop (DMA- or register-staged: same bits); block ids run over the column tiles first, so the workgroups in flight share a few
+    // M-blocks of A.  No small shape and no round peel.
+    GEMM_EPI_PHASE = 8,
 };
 
 __host__ __device__ inline bool gemm_epi_is_pair(int epi) {
@@ -171,6 +178,7 @@ struct GemmArgs {
     // Columns that map past the row are clamped to its last aligned unit (their outputs are dropped by the map_L / L tests).
     int mseg, mseg_ld, mseg_pad;
     int mseg_ch0, mseg_ch1;   // set by the launcher: the K chunks [ch0, ch1) of the launch that belong to the mapped segment
+    int phase;            // GEMM_EPI_PHASE: P, phases per column (a power of two, 4 <= P <= 256); 0 elsewhere
 };
 
 // Row of the dense weight matrix held by block-local row r of M-block mb, or -1 for padding

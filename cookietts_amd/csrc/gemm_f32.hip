@@ -114,6 +114,33 @@ __device__ __forceinline__ void split_epilogue(const GemmArgs& a, f32x16 (&acc)[
     }
 }
 
+// GEMM_EPI_PHASE store of one wave tile: row R = rloc0 + mt * 32 + 8 * rg + 4 * lhi (+ 0..3) of the M-block is (hidden row R / P,
+// phases R % P .. + 3) - P % 4 == 0, so the four rows of an accumulator register group are one 16-byte store at column P * frame + phase
+__device__ __forceinline__ void phase_epilogue(const GemmArgs& a, f32x16 (&acc)[4][2], const float* bias, int mb, int rloc0, int b,
+                                               int ncol0, int l31, int lhi) {
+    const int P = a.phase;
+    float* dst = a.dst0 + (size_t)b * a.dst0_bstride + ((size_t)(mb / P) * 256 + (size_t)(mb % P) * (256 / P)) * a.dst_ld + a.dst_pad;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const int n = ncol0 + nt * 32 + l31;                 // frame
+            if (n < a.L) {
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg) {
+                    const int rt = mt * 32 + 8 * rg + 4 * lhi;   // row within the wave tile
+                    const int R = rloc0 + rt;
+                    float4 v;
+                    v.x = acc[mt][nt][4 * rg + 0] + bias[rt + 0];
+                    v.y = acc[mt][nt][4 * rg + 1] + bias[rt + 1];
+                    v.z = acc[mt][nt][4 * rg + 2] + bias[rt + 2];
+                    v.w = acc[mt][nt][4 * rg + 3] + bias[rt + 3];
+                    *reinterpret_cast<float4*>(dst + (size_t)(R / P) * a.dst_ld + (size_t)P * n + R % P) = v;
+                }
+            }
+        }
+}
+
 // SEGS = 4: segment bases live in registers and are picked with a scalar-compare select chain (no LDS
 // round trip at the top of a chunk); SEGS = GEMM_MAX_SEG: bases come from the LDS segment table.
 // GLDS: global -> LDS staging by direct DMA (global_load_lds, 16 B per lane), three stages, two chunks ahead, counted
@@ -186,7 +213,14 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
     // mb = id % MB an XCD keeps re-using the same 1-2 weight slices in its private L2.
     int id = blockIdx.x;
     int mb, tile, b;
-    if (a.map_mode == 1) {
+    if constexpr (EPI == GEMM_EPI_PHASE) {
+        // column tiles first: M >> N here, and the workgroups in flight then share a few M-blocks of A (and the whole, small, B)
+        const int nt_ = a.ntiles * a.batch;
+        mb = id / nt_;
+        id -= mb * nt_;
+        tile = id % a.ntiles;
+        b = id / a.ntiles;
+    } else if (a.map_mode == 1) {
         // MB == 4 variant: XCD x owns the m-block PAIR {2(x&1), 2(x&1)+1} of the column tiles t = 4q + (x>>1); the
         // two m-blocks of one tile are consecutive ids of that XCD, so the B tile is fetched into 2 L2s, not 4.
         const int x = id & 7, j = id >> 3;
@@ -733,6 +767,9 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const GemmArgs a)
         }
         // 4. residual / skip epilogue
         split_epilogue<GEMM_EPI_SPLIT>(a, acc, lds + 64 * 128, a.rs_rows, /*row0=*/0, b, n0 + wn * 64, l31, lhi);
+    } else if constexpr (EPI == GEMM_EPI_PHASE) {
+        static_assert(EPI != GEMM_EPI_PHASE || (WM == 2 && SEGS == 4 && XS == 0 && !EXT), "phase store: the 256-row fp32 shape, <= 4 segments");
+        phase_epilogue(a, acc, bias, mb, wm * 128, b, n0 + wn * 64, l31, lhi);
     } else {
         split_epilogue<EPI>(a, acc, bias, a.M, mb * BM + wm * 128, b, n0 + wn * 64, l31, lhi, EXT ? (long long)part * a.part_dst0 : 0);
     }
@@ -843,6 +880,7 @@ void load_tuning_locked() {
     g_tune.f32_winograd_no_fused = on("CTTS_F32_WINOGRAD_NO_FUSED");
     g_tune.f32_winograd_f43_min = num("CTTS_F32_WINOGRAD_F43_MIN", -1);
     g_tune.f32_winograd_no_f43 = on("CTTS_F32_WINOGRAD_NO_F43");
+    g_tune.f32_cond_chain = on("CTTS_F32_COND_CHAIN");
     g_tune_loaded = true;
 }
 }  // namespace
@@ -910,6 +948,17 @@ int gemm_check_args(int epi, const GemmArgs& a) {
                        "gemm: a two-part SPLIT launch stores every row to dst0");
         CTTS_CHECK_ARG(parts == 1 || (long long)parts * a.ntiles * a.batch < (1ll << 31) / a.MB, "gemm: merged grid");
     }
+    if (epi == GEMM_EPI_PHASE) {
+        // one kernel shape, and every lane's four phases one aligned 16-byte store
+        CTTS_CHECK_ARG(a.bm == 256 && a.nseg <= 4 && a.interleave <= 1 && gemm_split_level(a.gemm_mode) == 0 && parts == 1 && !a.mseg &&
+                           a.shape_blocks == 0,
+                       "gemm: the phase store needs the fp32 launch of the 256-row shape with <= 4 segments (nseg=%d)", a.nseg);
+        CTTS_CHECK_ARG(a.phase >= 4 && a.phase <= 256 && (a.phase & (a.phase - 1)) == 0 && a.MB % a.phase == 0 && a.M == a.MB * a.bm,
+                       "gemm: phase=%d MB=%d M=%d", a.phase, a.MB, a.M);
+        CTTS_CHECK_ARG(a.dst_pad >= 0 && a.dst_pad % 4 == 0 && a.dst_ld % 4 == 0 && a.dst0_bstride % 4 == 0 &&
+                           reinterpret_cast<uintptr_t>(a.dst0) % 16 == 0 && (long long)a.phase * a.L <= a.dst_ld - a.dst_pad,
+                       "gemm: phase store dst_ld=%d dst_pad=%d phase=%d L=%d", a.dst_ld, a.dst_pad, a.phase, a.L);
+    }
     if (a.mseg) {
         // alignment of the mapped read: a lane's four pair columns must be four consecutive, 16-byte aligned natural columns
         const GemmSeg& g = a.seg[1];
@@ -949,6 +998,18 @@ int launch_gemm_f32(int epi, const GemmArgs& a_in, hipStream_t stream) {
     a.mseg_ch0 = a.mseg_ch1 = 0;
     if (a.mseg) { a.mseg_ch0 = a.seg[0].nch; a.mseg_ch1 = a.seg[0].nch + a.seg[1].nch; }
     CTTS_CHECK_ARG(!a.mseg || gemm_f32_dma_staged(a.nch_total), "gemm: the mapped segment needs the DMA-staged kernels");
+    if (epi == GEMM_EPI_PHASE) {                               // one shape, no peel: its own block order (column tiles first)
+        const bool glds = gemm_f32_dma_staged(a.nch_total);
+        const long long blocks = (long long)a.MB * a.ntiles * a.batch;
+        CTTS_CHECK_ARG(blocks > 0 && blocks < (1ll << 31), "gemm: grid %lld", blocks);
+        a.gt_limit = a.ntiles * a.batch;
+        a.map_mode = 0;
+        note_gemm_loop(0);
+        if (glds) hipLaunchKernelGGL((conv_gemm_f32_kernel<GEMM_EPI_PHASE, 2, 4, true>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((conv_gemm_f32_kernel<GEMM_EPI_PHASE, 2, 4, false>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
+        CTTS_CHECK_LAUNCH("conv_gemm_f32");
+        return CTTS_OK;
+    }
     // The shape is chosen from ONE part's block count; the small shape (and the register-staged kernels) run the parts one by one
     if (parts > 1 && (gemm_f32_small_applies(epi, a) || !gemm_f32_dma_staged(a.nch_total))) {
         for (int p = 0; p < parts; ++p)

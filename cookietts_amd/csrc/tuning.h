@@ -36,6 +36,7 @@ struct Tuning {
     int f32_winograd_f43_min;  // CTTS_F32_WINOGRAD_F43_MIN: take the F(4,3) form of the one-launch Winograd layer (quad columns, 1.5 C products per output and row) for utterances of at least this many columns; 0 = always (default in waveglow_api.hip).  Below it, and wherever the one-launch layer does not engage, the F(2,3) forms run
     bool f32_winograd_no_f43;  // CTTS_F32_WINOGRAD_NO_F43: never the F(4,3) form: the one-launch F(2,3) layer at every size it engages at (the A/B arm, bit-equal to the library before the F(4,3) form)
     bool f32_winograd_no_fused;  // CTTS_F32_WINOGRAD_NO_FUSED: never the one-launch Winograd layer: T2 | T3 and even | odd as two launches of the conv-GEMM with the T planes in HBM (the A/B arm)
+    bool f32_cond_chain;   // CTTS_F32_COND_CHAIN: WaveGlow fp32 conditioning as the chain (upsampling launch, cond layer 0, cond layer 1 through spect / h_tmp) also where the composed form applies (one GEMM from the mel frames, waveglow_api.hip): the A/B arm, bit-equal to the library before the composed form
     bool wf_no_region_split; // CTTS_WF_NO_REGION_SPLIT: the fused WaveFlow layer as ONE launch per layer (no A | M | B regions on three streams)
     bool wf_no_row_queue;  // CTTS_WF_NO_ROW_QUEUE: never the one-launch-per-row work queue of the fused WaveFlow layers
     int wf_row_queue_min;  // CTTS_WF_ROW_QUEUE_MIN: take the row queue from this many 128-column items per layer on (A/B; default in waveflow_api.hip)

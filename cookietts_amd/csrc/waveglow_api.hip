@@ -40,6 +40,12 @@ struct Plan {
     size_t up_w, up_wp, up_b, cond0_A, cond0_b, cond1_A, cond1_b;
     size_t zero_b;                      // mb_in * GEMM_BM zeros (never written; the blob is zero-filled): bias of the Winograd T launches
     bool up_mfma;
+    // Composed conditioning (cond_composed_packed below): upsampling, trim, squeeze and cond layers 0 and 1 are one linear map of the
+    // mel frames, packed as ONE conv-GEMM A panel over K = ccJ taps x n_mel, M = n_flows x ccP phases x H.  cc_A [n_flows ccP][nch_cc]
+    // A tiles, cc_b [n_flows ccP][GEMM_BM] bias in block-local row order, cc_w10 pack-time scratch: W1 W0 in double [n_flows][H][K0]
+    bool cc;                            // the blob holds it (asked for with CTTS_WG_OPT_COMPOSED_COND, and the shape allows it)
+    int ccP, ccJ, nch_cc;               // phases per frame hop / n_group, taps win / hop, K chunks ccJ n_mel / 16
+    size_t cc_A, cc_b, cc_w10;
     struct Flow {
         size_t start_w, start_b, end_w, end_b, winv, spk_tab;
         std::vector<size_t> in_A, in_b, rs_A, rs_b;
@@ -68,9 +74,12 @@ struct Plan {
     int rs_mb(int layer) const { return (rs_rows(layer) + GEMM_BM - 1) / GEMM_BM; }
 };
 
-int make_plan(const ctts_waveglow_config* cfg, Plan& p) {
+// options: CTTS_WG_OPT_* of the `_opt` entry points (0: what the entry points without the argument run)
+int make_plan(const ctts_waveglow_config* cfg, Plan& p, int options = 0) {
     CTTS_CHECK_ARG(cfg != nullptr, "config is NULL");
     p.c = *cfg;
+    CTTS_CHECK_ARG((options & ~CTTS_WG_OPT_COMPOSED_COND) == 0, "options=%d (CTTS_WG_OPT_*)", options);
+    const bool want_cc = (options & CTTS_WG_OPT_COMPOSED_COND) != 0;
     const auto& c = p.c;
     CTTS_CHECK_ARG(c.n_flows >= 1 && c.n_layers >= 1 && c.n_layers <= 12, "n_flows=%d n_layers=%d", c.n_flows, c.n_layers);
     CTTS_CHECK_ARG(gemm_mode_valid(c.f32_gemm_mode), "f32_gemm_mode=%d (CTTS_GEMM_DEFAULT / _F32 / _BF16X3 / _BF16X6)", c.f32_gemm_mode);
@@ -154,6 +163,20 @@ int make_plan(const ctts_waveglow_config* cfg, Plan& p) {
         }
         f.wg_dense = take((size_t)(f43 ? 6 : 3) * 2 * p.C * p.C);
     }
+    // composed conditioning, behind everything else (a blob without it is a prefix of one with it): single speaker, whole 16-row K
+    // chunks per tap, at most four taps (one K segment each), and P a power of two in [4, 256] - whole 16-byte stores, and an
+    // M-block holds whole hidden rows.  (A layout question only: the mode of the model's GEMMs is asked at the call, cond_composed.)
+    p.ccP = c.hop_length / c.n_group;
+    p.ccJ = c.win_length / c.hop_length;
+    p.nch_cc = p.ccJ * c.n_mel_channels / GEMM_KC;
+    p.cc = want_cc && p.S == 0 && c.n_mel_channels % GEMM_KC == 0 && p.ccJ >= 1 && p.ccJ <= 4 && p.ccP >= 4 && p.ccP <= GEMM_BM &&
+           (p.ccP & (p.ccP - 1)) == 0;
+    p.cc_A = p.cc_b = p.cc_w10 = 0;
+    if (p.cc) {
+        p.cc_A = take((size_t)c.n_flows * p.ccP * p.nch_cc * A_TILE);
+        p.cc_b = take((size_t)c.n_flows * p.ccP * GEMM_BM);
+        p.cc_w10 = take((size_t)c.n_flows * 2 * p.H * p.K0);
+    }
     p.total = o;
     return CTTS_OK;
 }
@@ -234,8 +257,29 @@ InForm in_form(const Plan& p, const Geom& g, const Tuning& t) {
     return InForm::WinogradLayerF43;
 }
 
+// ---- the conditioning form of a call -----------------------------------------------
+// Chain: the upsampling launch writes spect, cond layer 0 of every flow writes h_tmp, cond layer 1 writes h_all.
+// Composed (where the blob holds the composed matrix; CTTS_F32_COND_CHAIN: never): a copy of the mel frames with a zero left halo,
+// then ONE launch of the conv-GEMM whose phase store writes h_all - no spect, no h_tmp.  Not bit-equal to the chain: one sum over
+// ccJ n_mel products of a matrix rounded once from double, against K0 + H products through two fp32 roundings.
+// Taken where it issues fewer products than the chain.  Both launch whole 128-column tiles - the composed GEMM of frames, P H rows
+// over K = ccJ n_mel; the chain of P x as many latent columns, H rows over K0, then over H - so a short utterance, whose frames fill
+// a fraction of one tile, keeps the chain (n_mel 80, hop 256, n_group 8: below 45 frames).  A function of the utterance alone.
+bool cond_composed(const Plan& p, int frames, const Tuning& t) {
+    if (!p.cc || t.f32_cond_chain || gemm_split_level(p.c.f32_gemm_mode) != 0) return false;   // (the split-bf16 loops keep the chain)
+    const long long tiles_f = (frames + GEMM_BN - 1) / GEMM_BN, tiles_l = ((long long)frames * p.ccP + GEMM_BN - 1) / GEMM_BN;
+    return tiles_f * p.ccP * p.ccJ * p.c.n_mel_channels < tiles_l * (p.K0 + p.H);
+}
+// the padded mel [B][n_mel][ld]: frames in whole 128-column tiles behind a left halo of `pad` >= ccJ - 1 zero columns
+struct MelGeom { int ntiles, pad, ld; };
+MelGeom mel_geom(int frames) {
+    const int nt = (frames + GEMM_BN - 1) / GEMM_BN;
+    return {nt, 4, nt * GEMM_BN + 8};
+}
+
 struct Workspace {
     float *audio, *spect, *spk, *h_tmp, *h_all, *x, *act, *out;
+    float* melp;        // composed conditioning: the padded mel (then spect and h_tmp are NULL: nothing reads them)
     float* act_all;     // deferred-skip form: the gated activations of every layer of a flow ([n_layers] x act)
     float* a16;         // WN folds: layer 0's input [B][FOLD_ROWS][ld] = [audio_0; 1 on [0, L); 0]
     float* skend;       // WN folds: the skip/end accumulator [B][2 n_half][ld] between the groups of a flow
@@ -246,14 +290,15 @@ struct Workspace {
     size_t total;  // floats
 };
 
-void carve(const Plan& p, const Geom& g, int batch, float* base, InForm in, Workspace& w) {
+void carve(const Plan& p, const Geom& g, int batch, float* base, InForm in, bool composed, Workspace& w) {
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o = align_up(o + n); return base ? base + r : nullptr; };
     const size_t B = batch;
     w.audio = take(B * p.c.n_group * g.L);
-    w.spect = take(B * p.K0 * g.ld);
+    w.spect = composed ? nullptr : take(B * p.K0 * g.ld);
+    w.melp = composed ? take(B * p.c.n_mel_channels * mel_geom(g.L / p.ccP).ld) : nullptr;
     w.spk = take(B * p.c.n_flows * p.S * g.ld);          // speaker-embedding rows (glow.py:193-196), per flow
-    w.h_tmp = take(B * p.c.n_flows * p.H * g.ld);
+    w.h_tmp = composed ? nullptr : take(B * p.c.n_flows * p.H * g.ld);
     w.h_all = take(B * p.c.n_flows * p.H * g.ld);
     w.x = take(B * p.C * g.ld);
     w.act = take(B * p.C * g.ld);
@@ -318,6 +363,66 @@ __global__ __launch_bounds__(256) void speaker_rows_kernel(const float* __restri
     spk[((size_t)b * n_flows * S + (size_t)k * S + e) * ld + n] = v;
 }
 
+// ---- composed conditioning ----------------------------------------------------------
+// glow.py:318-324, 198-199 on a single-speaker model is linear in the mel: the transposed conv (kernel win = J hop, stride hop),
+// trimmed to F hop samples, gives sample hop f + u the frames f - j at taps hop j + u (j < J; frames before 0 add nothing); the
+// squeeze puts sample G t + s of channel co in row co G + s of latent column t = P f + p; cond layers 0 and 1 follow with nothing
+// between them.  So   h_k[:, P f + p] = A_{k,p} [mel[f]; mel[f-1]; ..; mel[f-J+1]] + b'_k   with
+//   A_{k,p}[r][j n_mel + ci] = sum_{co,s} (W1_k W0_k)[r][co G + s] w_up[ci][co][hop j + G p + s],   b'_k = W1_k (W0_k b_up~ + b0_k) + b1_k
+// (b_up~: b_up[co] in row co G + s).  Formed in double at pack time and rounded once.
+
+// w10 = W1 W0 in double, [H][K0]
+__global__ __launch_bounds__(256) void cond_compose_w10_kernel(const float* __restrict__ w1, const float* __restrict__ w0,
+                                                               double* __restrict__ w10, int H, int K0) {
+    const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+    if (c >= K0) return;
+    double s = 0.0;
+    for (int h = 0; h < H; ++h) s += (double)w1[(size_t)r * H + h] * (double)w0[(size_t)h * K0 + c];
+    w10[(size_t)r * K0 + c] = s;
+}
+
+// One flow's A panel in pack_a layout [P][nch][GEMM_KC][GEMM_BM]: M-block m holds hidden rows [m HR, (m + 1) HR), HR = GEMM_BM / P,
+// block-local row (r % HR) P + p; K index j n_mel + ci.  Thread = block-local row, blockIdx = (K index, M-block).
+__global__ __launch_bounds__(GEMM_BM) void cond_compose_A_kernel(const double* __restrict__ w10, const float* __restrict__ up_w,
+                                                                 float* __restrict__ A, int n_mel, int G, int hop, int win, int P,
+                                                                 int nch) {
+    const int rl = threadIdx.x, kidx = blockIdx.x, m = blockIdx.y;
+    const int r = m * (GEMM_BM / P) + rl / P, p = rl % P;
+    const int j = kidx / n_mel, ci = kidx % n_mel;
+    const float* u = up_w + (size_t)ci * n_mel * win + hop * j + G * p;
+    const double* wr = w10 + (size_t)r * n_mel * G;
+    double s = 0.0;
+    for (int co = 0; co < n_mel; ++co)
+        for (int q = 0; q < G; ++q) s += wr[co * G + q] * (double)u[(size_t)co * win + q];
+    A[(((size_t)m * nch + kidx / GEMM_KC) * GEMM_KC + kidx % GEMM_KC) * GEMM_BM + rl] = (float)s;
+}
+
+// One flow's bias [P][GEMM_BM] in the same row order; one workgroup of H = GEMM_BM threads
+__global__ __launch_bounds__(GEMM_BM) void cond_compose_bias_kernel(const float* __restrict__ w0, const float* __restrict__ b0,
+                                                                    const float* __restrict__ w1, const float* __restrict__ b1,
+                                                                    const float* __restrict__ up_b, float* __restrict__ bias, int K0,
+                                                                    int G, int P) {
+    __shared__ double t0[GEMM_BM];
+    const int r = threadIdx.x;
+    double s = b0[r];
+    for (int c = 0; c < K0; ++c) s += (double)w0[(size_t)r * K0 + c] * (double)up_b[c / G];
+    t0[r] = s;
+    __syncthreads();
+    s = b1[r];
+    for (int h = 0; h < GEMM_BM; ++h) s += (double)w1[(size_t)r * GEMM_BM + h] * t0[h];
+    const int HR = GEMM_BM / P;
+    for (int p = 0; p < P; ++p) bias[(size_t)(r / HR) * GEMM_BM + (r % HR) * P + p] = (float)s;
+}
+
+// melp[b][c][pad + f] = mel[b][c][f], zero everywhere else
+__global__ __launch_bounds__(256) void mel_pad_kernel(const float* __restrict__ mel, float* __restrict__ melp, int frames, int ld, int pad) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const size_t row = (size_t)blockIdx.z * gridDim.y + blockIdx.y;
+    if (n >= ld) return;
+    const int f = n - pad;
+    melp[row * ld + n] = f >= 0 && f < frames ? mel[row * frames + f] : 0.0f;
+}
+
 // ---- forward (analysis) direction, glow.py:267-312: what it adds to the blob and the workspace ------------------------------
 // The forward mix matrices W_k [n_rem][n_rem] live in a blob of their own (the infer blob holds their inverses only).
 size_t fwd_mix_off(const Plan& p, int k) {
@@ -335,8 +440,8 @@ int fwd_log_s_rows(const Plan& p, int k) {
 // z_part [B][nblk_z]; total = both together, in floats
 struct FwdSums { double *ls_part, *z_part; int nblk_ls, nblk_z; size_t total; };
 
-void carve_fwd(const Plan& p, const Geom& g, int batch, float* base, InForm in, Workspace& w, FwdSums& f) {
-    carve(p, g, batch, base, in, w);
+void carve_fwd(const Plan& p, const Geom& g, int batch, float* base, InForm in, bool composed, Workspace& w, FwdSums& f) {
+    carve(p, g, batch, base, in, composed, w);
     f.nblk_ls = (g.L + 255) / 256;
     f.nblk_z = (int)(((long long)p.c.n_group * g.L + FWD_SUMSQ_CHUNK - 1) / FWD_SUMSQ_CHUNK);
     size_t o = w.total;                                 // a multiple of ALIGN_F floats = 256 bytes
@@ -374,12 +479,13 @@ struct WnCall {
     long long cstride = 0, hstride = 0; // batch-item strides of a C-row tensor and of the cond hidden of all flows
     StackForm stack = StackForm::PerLayer;
     InForm in = InForm::Direct;
+    bool composed = false;              // the conditioning form (cond_composed)
     float* audio = nullptr;             // [B][n_group][L], updated in place flow by flow (forward: z)
     const float* h_all = nullptr;       // cond hidden of all flows
 
     // ---- opening: plan and geometry, then (behind the entry's own checks) the workspace of its kind and the forms
-    int begin(const ctts_waveglow_config* cfg, const void* packed, int batch_, int frames_, void* stream) {
-        int rc = make_plan(cfg, p); if (rc) return rc;
+    int begin(const ctts_waveglow_config* cfg, const void* packed, int batch_, int frames_, void* stream, int options = 0) {
+        int rc = make_plan(cfg, p, options); if (rc) return rc;
         rc = make_geom(p, frames_, g); if (rc) return rc;
         t = tuning();
         blob = static_cast<const float*>(packed); batch = batch_; frames = frames_; s = as_stream(stream);
@@ -391,8 +497,9 @@ struct WnCall {
     int take_workspace(const char* what, void* workspace, size_t workspace_bytes, bool forward) {
         in = in_form(p, g, t);
         stack = t.f32_no_defer_skip ? StackForm::PerLayer : t.f32_no_wn_fold ? StackForm::Deferred : StackForm::Folded;
-        if (forward) carve_fwd(p, g, batch, static_cast<float*>(workspace), in, w, sums);
-        else carve(p, g, batch, static_cast<float*>(workspace), in, w);
+        composed = cond_composed(p, frames, t);
+        if (forward) carve_fwd(p, g, batch, static_cast<float*>(workspace), in, composed, w, sums);
+        else carve(p, g, batch, static_cast<float*>(workspace), in, composed, w);
         audio = w.audio; h_all = w.h_all;
         return workspace_fits(what, workspace_bytes, (forward ? sums.total : w.total) * sizeof(float));
     }
@@ -478,6 +585,22 @@ struct WnCall {
         a.nseg = 1; a.nch_total = p.nch1h;
         a.seg[0] = {h_tmp, hstride, p.nch1h, 0, GEMM_BM, 0};
         a.dst0 = h_out; a.dst1 = h_out;
+        return a;
+    }
+    // The composed conditioning: columns are FRAMES of the padded mel (its own geometry), K = tap j of every mel channel as segment j
+    // at shift -j, M-block m = (flow m / P, hidden rows (m % P) 256 / P ..) x P phases; the phase store expands it into h_out
+    GemmArgs cond_composed_gemm(const float* melp, float* h_out) const {
+        const MelGeom mg = mel_geom(frames);
+        GemmArgs a{};
+        a.gemm_mode = p.c.f32_gemm_mode;
+        a.ld = mg.ld; a.pad = mg.pad; a.L = frames; a.ntiles = mg.ntiles; a.batch = batch;
+        a.A = blob + p.cc_A; a.bias = blob + p.cc_b;
+        a.nseg = p.ccJ; a.nch_total = p.nch_cc; a.MB = p.c.n_flows * p.ccP;
+        for (int j = 0; j < p.ccJ; ++j)
+            a.seg[j] = {melp, (long long)p.c.n_mel_channels * mg.ld, p.c.n_mel_channels / GEMM_KC, -j, 0, 0};
+        a.M = a.MB * GEMM_BM; a.split = a.M;
+        a.phase = p.ccP;
+        a.dst0 = h_out; a.dst0_bstride = hstride; a.dst_ld = g.ld; a.dst_pad = g.pad;
         return a;
     }
     // Winograd F(2,3) as launches of the conv-GEMM in pair space (ld = ldp, no halo):
@@ -706,7 +829,16 @@ struct WnCall {
         const int rc = launch_gemm_f32(GEMM_EPI_SPLIT, cond0(spect, spk, h_tmp), s);
         return rc ? rc : launch_gemm_f32(GEMM_EPI_SPLIT, cond1(spect, spk, h_tmp, h_out), s);
     }
+    // mel -> h_out in the composed form: the padded copy, then the one launch
+    int cond_from_mel(const float* mel, float* melp, float* h_out) const {
+        CTTS_CHECK_ARG(p.cc, "wn_cond_composed: the packed model holds no composed conditioning matrix");
+        const MelGeom mg = mel_geom(frames);
+        hipLaunchKernelGGL(mel_pad_kernel, dim3((mg.ld + 255) / 256, p.c.n_mel_channels, batch), dim3(256), 0, s, mel, melp, frames, mg.ld, mg.pad);
+        CTTS_CHECK_LAUNCH("mel_pad");
+        return launch_gemm_f32(GEMM_EPI_PHASE, cond_composed_gemm(melp, h_out), s);
+    }
     int conditioning(const float* mel, const int64_t* ids) const {
+        if (composed) return cond_from_mel(mel, w.melp, w.h_all);
         int rc = upsample(mel, w.spect);
         if (rc) return rc;
         if ((rc = speaker_rows(ids, w.spk))) return rc;
@@ -1189,10 +1321,48 @@ int ctts_waveglow_pack_flow(const ctts_waveglow_config* cfg, int32_t k, const ct
     return launch_fold_skend(w->rs_w, w->rs_b, w->end_w, w->end_b, blob + f.skend_W, blob + f.skend_b, C, p.c.n_layers, d.n_half, s);
 }
 
+size_t ctts_waveglow_packed_bytes_opt(const ctts_waveglow_config* cfg, int32_t options) {
+    Plan p;
+    if (make_plan(cfg, p, options)) return 0;
+    return p.total * sizeof(float);
+}
+
+int ctts_waveglow_has_composed_cond(const ctts_waveglow_config* cfg) {
+    Plan p;
+    return make_plan(cfg, p, CTTS_WG_OPT_COMPOSED_COND) == CTTS_OK && p.cc ? 1 : 0;
+}
+
+// this flow's ccP M-blocks of the composed conditioning, from the dense cond layers and the upsampling weights the blob already holds
+int ctts_waveglow_pack_cond_composed(const ctts_waveglow_config* cfg, int32_t k, const ctts_waveglow_flow_weights* w, void* packed,
+                                     void* stream) {
+    Plan p;
+    int rc = make_plan(cfg, p, CTTS_WG_OPT_COMPOSED_COND); if (rc) return rc;
+    CTTS_CHECK_ARG(p.cc, "pack_cond_composed: this config has no composed conditioning (ctts_waveglow_has_composed_cond)");
+    CTTS_CHECK_ARG(k >= 0 && k < p.c.n_flows, "pack_cond_composed: flow %d", k);
+    CTTS_CHECK_ARG(w && packed && w->cond_w[0] && w->cond_w[1] && w->cond_b[0] && w->cond_b[1], "pack_cond_composed: NULL pointer");
+    hipStream_t s = as_stream(stream);
+    float* blob = static_cast<float*>(packed);
+    const int H = p.H;
+    double* w10 = reinterpret_cast<double*>(blob + p.cc_w10) + (size_t)k * H * p.K0;
+    hipLaunchKernelGGL(cond_compose_w10_kernel, dim3((p.K0 + 255) / 256, H), dim3(256), 0, s, w->cond_w[1], w->cond_w[0], w10, H, p.K0);
+    hipLaunchKernelGGL(cond_compose_A_kernel, dim3(p.ccJ * p.c.n_mel_channels, p.ccP), dim3(GEMM_BM), 0, s, w10, blob + p.up_w,
+                       blob + p.cc_A + (size_t)k * p.ccP * p.nch_cc * A_TILE, p.c.n_mel_channels, p.c.n_group, p.c.hop_length,
+                       p.c.win_length, p.ccP, p.nch_cc);
+    hipLaunchKernelGGL(cond_compose_bias_kernel, dim3(1), dim3(GEMM_BM), 0, s, w->cond_w[0], w->cond_b[0], w->cond_w[1], w->cond_b[1],
+                       blob + p.up_b, blob + p.cc_b + (size_t)k * p.ccP * GEMM_BM, p.K0, p.c.n_group, p.ccP);
+    CTTS_CHECK_LAUNCH("cond_compose");
+    return CTTS_OK;
+}
+
 size_t ctts_waveglow_workspace_bytes(const ctts_waveglow_config* cfg, int32_t batch, int32_t frames) {
+    return ctts_waveglow_workspace_bytes_opt(cfg, batch, frames, 0);
+}
+
+size_t ctts_waveglow_workspace_bytes_opt(const ctts_waveglow_config* cfg, int32_t batch, int32_t frames, int32_t options) {
     Plan p; Geom g; Workspace w;
-    if (make_plan(cfg, p) || make_geom(p, frames, g) || batch < 1) return 0;
-    carve(p, g, batch, nullptr, in_form(p, g, tuning()), w);
+    if (make_plan(cfg, p, options) || make_geom(p, frames, g) || batch < 1) return 0;
+    const Tuning t = tuning();
+    carve(p, g, batch, nullptr, in_form(p, g, t), cond_composed(p, frames, t), w);
     return w.total * sizeof(float);
 }
 
@@ -1210,6 +1380,21 @@ int ctts_wn_cond_f32(const ctts_waveglow_config* cfg, const void* packed, const 
     const int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
     CTTS_CHECK_ARG(packed && spect && h_tmp && h_all && batch >= 1, "wn_cond: bad argument");
     return c.cond(spect, spk_rows, h_tmp, h_all);
+}
+
+size_t ctts_wn_cond_composed_scratch_bytes(const ctts_waveglow_config* cfg, int32_t batch, int32_t frames) {
+    Plan p;
+    if (make_plan(cfg, p, CTTS_WG_OPT_COMPOSED_COND) || !p.cc || batch < 1 || frames < 1) return 0;
+    return (size_t)batch * p.c.n_mel_channels * mel_geom(frames).ld * sizeof(float);
+}
+
+// (the composed form on the caller's buffers, whatever the knob says)
+int ctts_wn_cond_composed_f32(const ctts_waveglow_config* cfg, const void* packed, const float* mel, float* scratch, float* h_all,
+                              int32_t batch, int32_t frames, void* stream) {
+    WnCall c;
+    const int rc = c.begin(cfg, packed, batch, frames, stream, CTTS_WG_OPT_COMPOSED_COND); if (rc) return rc;
+    CTTS_CHECK_ARG(packed && mel && scratch && h_all && batch >= 1, "wn_cond_composed: bad argument");
+    return c.cond_from_mel(mel, scratch, h_all);
 }
 
 // (the per-layer stack with direct in-layers on the caller's buffers, whatever the knobs say)
@@ -1267,7 +1452,8 @@ size_t ctts_waveglow_forward_workspace_bytes(const ctts_waveglow_config* cfg, in
     Plan p; Geom g; Workspace w; FwdSums f;
     if (make_plan(cfg, p) || make_geom(p, frames, g)) return 0;
     if (batch < 1) { set_error("forward_workspace_bytes: batch=%d", batch); return 0; }
-    carve_fwd(p, g, batch, nullptr, in_form(p, g, tuning()), w, f);
+    const Tuning t = tuning();
+    carve_fwd(p, g, batch, nullptr, in_form(p, g, t), cond_composed(p, frames, t), w, f);
     return f.total * sizeof(float);
 }
 
@@ -1327,8 +1513,15 @@ int ctts_waveglow_infer_f32(const ctts_waveglow_config* cfg, const void* packed,
 int ctts_waveglow_infer_spk_f32(const ctts_waveglow_config* cfg, const void* packed, const float* mel,
                                 const float* z_scaled, const int64_t* speaker_ids, float* wave, int32_t batch,
                                 int32_t frames, void* workspace, size_t workspace_bytes, void* stream) {
+    return ctts_waveglow_infer_spk_f32_opt(cfg, packed, mel, z_scaled, speaker_ids, wave, batch, frames, workspace, workspace_bytes, 0,
+                                           stream);
+}
+
+int ctts_waveglow_infer_spk_f32_opt(const ctts_waveglow_config* cfg, const void* packed, const float* mel,
+                                    const float* z_scaled, const int64_t* speaker_ids, float* wave, int32_t batch,
+                                    int32_t frames, void* workspace, size_t workspace_bytes, int32_t options, void* stream) {
     WnCall c;
-    int rc = c.begin(cfg, packed, batch, frames, stream); if (rc) return rc;
+    int rc = c.begin(cfg, packed, batch, frames, stream, options); if (rc) return rc;
     CTTS_CHECK_ARG(packed && mel && z_scaled && wave && workspace && batch >= 1, "infer: bad argument");
     if ((rc = c.take_workspace("infer", workspace, workspace_bytes, false))) return rc;
     CTTS_CHECK_HIP(hipMemcpyAsync(c.audio, z_scaled, (size_t)batch * c.p.c.n_group * c.g.L * sizeof(float), hipMemcpyDeviceToDevice, c.s));

@@ -111,7 +111,7 @@ class WN(nn.Module):
 # arithmetic mode -> (bytes query of the 16-bit blob, its pack-flow call, workspace query, infer entry point).  Every mode packs
 # the fp32 blob too (upsampling, cond stacks, mixing); IEEE half shares the bf16 layouts, hence the bf16 size queries
 _MODES = {
-    "f32": (None, None, "ctts_waveglow_workspace_bytes", "ctts_waveglow_infer_spk_f32"),
+    "f32": (None, None, "ctts_waveglow_workspace_bytes_opt", "ctts_waveglow_infer_spk_f32_opt"),
     "bf16": ("ctts_waveglow_packed_bf16_bytes", "ctts_waveglow_pack_flow_bf16", "ctts_waveglow_workspace_bf16_bytes",
              "ctts_waveglow_infer_spk_bf16"),
     "bf16x3": ("ctts_waveglow_packed_bf16x3_bytes", "ctts_waveglow_pack_flow_bf16x3", "ctts_waveglow_workspace_bf16x3_bytes",
@@ -189,6 +189,7 @@ class WaveGlow(_cache.PackedModule):
 
         self._compute_dtype = torch.float32
         self._f32_gemm_mode = None   # None: the library default; see set_f32_gemm_mode
+        self._composed_cond = True   # ask for the composed conditioning where c_config may (False before the first call: never)
         self._fwd = None             # (the infer blob it belongs to, forward-mix blob, log det W_k [n_flows] fp32 on the host)
 
     # ------------------------------------------------------------------ plumbing ----
@@ -200,6 +201,15 @@ class WaveGlow(_cache.PackedModule):
             win_length=self.win_length, hop_length=self.hop_length, n_layers=wn['n_layers'],
             n_channels=wn['n_channels'], kernel_size=wn['kernel_size'], cond_hidden=256,
             speaker_embed_dim=wn.get('speaker_embed_dim', 0), f32_gemm_mode=_lib.model_gemm_mode(self._f32_gemm_mode))
+
+    def _options(self):
+        """CTTS_WG_OPT_* of this model's fp32 blob and calls: the composed conditioning (one GEMM from the mel frames) for the dense
+        ('normal') upsampler of a single-speaker model, where the library builds it.  The grouped upsamplers, packed as dense with
+        zero blocks, and the multispeaker models keep the chain of launches."""
+        if not (self._composed_cond and self.upsample_mode == 'normal' and not self.multispeaker and self._mode() == "f32"):
+            return 0
+        cfg = self.c_config()
+        return _lib.WG_OPT_COMPOSED_COND if _lib.lib().ctts_waveglow_has_composed_cond(C.byref(cfg)) else 0
 
     def set_f32_gemm_mode(self, mode):
         """Main loop of THIS model's fp32 GEMMs: ``"f32"`` (fp32 MFMA), ``"bf16x3"`` (split bf16: fp32 tensors, three
@@ -276,7 +286,8 @@ class WaveGlow(_cache.PackedModule):
             if p.device != device:
                 raise RuntimeError(f"parameter on {p.device}, input on {device}: move the model first")
         cfg = self.c_config()
-        nbytes = _lib.nbytes(lib.ctts_waveglow_packed_bytes, C.byref(cfg), what="unsupported WaveGlow config")
+        options = self._options()
+        nbytes = _lib.nbytes(lib.ctts_waveglow_packed_bytes_opt, C.byref(cfg), options, what="unsupported WaveGlow config")
         with torch.cuda.device(device):
             stream = _lib.stream(device)
             blob = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
@@ -335,6 +346,9 @@ class WaveGlow(_cache.PackedModule):
                     fw.speaker_embed = _cache.dev(wn.speaker_embed.weight, keep)
                 _lib.check(lib.ctts_waveglow_pack_flow(C.byref(cfg), k, C.byref(fw), _lib.ptr(blob), stream),
                            f"ctts_waveglow_pack_flow({k})")
+                if options & _lib.WG_OPT_COMPOSED_COND:       # (reads the upsampling weights packed above)
+                    _lib.check(lib.ctts_waveglow_pack_cond_composed(C.byref(cfg), k, C.byref(fw), _lib.ptr(blob), stream),
+                               f"ctts_waveglow_pack_cond_composed({k})")
                 if bblob is not None:
                     _lib.check(getattr(lib, pack16)(C.byref(cfg), k, C.byref(fw), _lib.ptr(bblob), stream), f"{pack16}({k})")
             torch.cuda.current_stream(device).synchronize()   # dense temporaries may now be freed
@@ -384,13 +398,15 @@ class WaveGlow(_cache.PackedModule):
         cfg = self.c_config()
         # (the size is part of the key: the fp32 library sizes the workspace by the in-layer form it will take, which a tuning
         #  knob flipped between two calls changes)
-        nbytes = _lib.nbytes(getattr(lib, ws_bytes), C.byref(cfg), B, F, what="workspace query failed")
+        # the fp32 entry points take this model's options (the blob was packed with them)
+        opt = (self._options(),) if mode == "f32" else ()
+        nbytes = _lib.nbytes(getattr(lib, ws_bytes), C.byref(cfg), B, F, *opt, what="workspace query failed")
         ws = self.workspace((device, B, F, mode, nbytes), lambda: nbytes)
         wave = torch.empty(B, L * self.n_group, dtype=torch.float32, device=device)
         blobs = (blob,) if bblob is None else (blob, bblob)        # the 16-bit entry points take both blobs
         with torch.cuda.device(device):
             _lib.check(getattr(lib, infer)(C.byref(cfg), *map(_lib.ptr, blobs), _lib.ptr(mel), _lib.ptr(z), _lib.ptr(ids),
-                                           _lib.ptr(wave), B, F, _lib.ptr(ws), ws.numel() * 4, _lib.stream(device)), infer)
+                                           _lib.ptr(wave), B, F, _lib.ptr(ws), ws.numel() * 4, *opt, _lib.stream(device)), infer)
         return wave.to(spect.dtype)
 
     def infer(self, spect, speaker_id=None, sigma=1.0):

@@ -67,7 +67,10 @@ extern "C" {
 #define CTTS_GEMM_F32 1      /* v_mfma_f32_32x32x2_f32: exact fp32 products */
 #define CTTS_GEMM_BF16X3 2   /* split bf16: hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16, fp32 accumulation */
 #define CTTS_GEMM_BF16X6 3   /* 3-way split (24 mantissa bits): the six products >= 2^-16 (hh, hm, mh, hl, lh, mm); fp32-grade */
-#define CTTS_N_SPEAKERS 512  /* rows of every speaker-embedding table (glow.py:129, efficient_model_ax.py:60) */
+/* `options` of the ctts_waveglow_*_opt entry points (0 = the entry point without the suffix).
+ * CTTS_WG_OPT_COMPOSED_COND: the blob holds the composed conditioning ("Composed conditioning" below) and the call may use it. */
+#define CTTS_WG_OPT_COMPOSED_COND 1
+#define CTTS_N_SPEAKERS 512 /* rows of every speaker-embedding table (glow.py:129, efficient_model_ax.py:60) */
 
 int ctts_abi_version(void);
 const char* ctts_last_error(void);
@@ -226,6 +229,37 @@ int ctts_wn_cond_f32(const ctts_waveglow_config* cfg, const void* packed, const 
 int ctts_wn_stack_f32(const ctts_waveglow_config* cfg, const void* packed, int32_t flow,
                       const float* audio, const float* h_all, float* x, float* act, float* out,
                       int32_t batch, int32_t frames, void* stream);
+/* ---- Composed conditioning (fp32 entry points) ---------------------------------------------------------------------------
+ * On a single-speaker model the conditioning is linear in the mel: a latent column t = P f + p (P = hop / n_group) sees the mel
+ * frames f .. f - J + 1 only (J = win / hop), so  h_k[:, P f + p] = A_{k,p} [mel[f]; ..; mel[f-J+1]] + b'_k  with the constant
+ * A_{k,p} = (W1_k W0_k) . (the upsampling taps of phase p) and b'_k = W1_k (W0_k b_up + b0_k) + b1_k: upsampling, trim, squeeze and
+ * cond layers 0 and 1 of every flow become a padded copy of the mel and ONE GEMM launch, at about a third of the chain's products
+ * (n_mel 80, hop 256, win 1024, n_group 8), without the spect and h_tmp buffers.
+ * Built where ctts_waveglow_has_composed_cond(cfg) says 1: speaker_embed_dim 0, n_mel % 16 == 0, J <= 4, P a power of two in
+ * [4, 256] (the model's f32_gemm_mode is asked at the call: the split-bf16 modes keep the chain).  For a model whose upsampler is
+ * the dense ConvTranspose1d.  The caller opts in:
+ *   blob of ctts_waveglow_packed_bytes_opt(cfg, CTTS_WG_OPT_COMPOSED_COND) bytes - the blob without it is its prefix, packed by the
+ *     same calls; it grows by n_flows * P * 256 * (J * n_mel + 1) floats plus pack-time scratch;
+ *   ctts_waveglow_pack_cond_composed(cfg, flow, w, ...) per flow, after ctts_waveglow_pack_upsample (whose weights it reads from the
+ *     blob): A and b' formed in double, rounded once;
+ *   ctts_waveglow_workspace_bytes_opt / ctts_waveglow_infer_spk_f32_opt with that option.  (The analysis pass,
+ *     ctts_waveglow_forward_spk_f32, has no such form: it runs the chain, on either blob.)
+ * A call takes the composed form where it issues fewer products than the chain (an utterance of a few frames fills a fraction of
+ * the GEMM's 128-frame tile: n_mel 80, P 32: from 45 frames on; a function of the utterance, never of the batch), else the chain;
+ * CTTS_F32_COND_CHAIN=1 in the environment: always the chain (A/B).  Not bit-equal to the chain (another summation order).
+ * The stage entry runs the composed form whatever the length: mel [B][n_mel][F] dense -> h_all as ctts_wn_cond_f32 writes it;
+ * scratch: ctts_wn_cond_composed_scratch_bytes (0 where the config has no composed form), any contents. */
+int ctts_waveglow_has_composed_cond(const ctts_waveglow_config* cfg);
+size_t ctts_waveglow_packed_bytes_opt(const ctts_waveglow_config* cfg, int32_t options);
+int ctts_waveglow_pack_cond_composed(const ctts_waveglow_config* cfg, int32_t flow, const ctts_waveglow_flow_weights* w,
+                                     void* packed, void* stream);
+size_t ctts_waveglow_workspace_bytes_opt(const ctts_waveglow_config* cfg, int32_t batch, int32_t frames, int32_t options);
+int ctts_waveglow_infer_spk_f32_opt(const ctts_waveglow_config* cfg, const void* packed, const float* mel,
+                                    const float* z_scaled, const int64_t* speaker_ids, float* wave, int32_t batch,
+                                    int32_t frames, void* workspace, size_t workspace_bytes, int32_t options, void* stream);
+size_t ctts_wn_cond_composed_scratch_bytes(const ctts_waveglow_config* cfg, int32_t batch, int32_t frames);
+int ctts_wn_cond_composed_f32(const ctts_waveglow_config* cfg, const void* packed, const float* mel, float* scratch,
+                              float* h_all, int32_t batch, int32_t frames, void* stream);
 /* `end` 1x1 conv + affine coupling inverse + inverse 1x1 conv (+ un-squeeze on the last
  * flow): glow.py:222,337-340,349.  Updates audio in place; if `wave` is non-NULL the
  * mixed channels are written un-squeezed to wave [B][L*n_group] instead. */
