@@ -7,6 +7,7 @@ from . import synthetic  # noqa: F401
 from ._lib import set_f32_gemm_mode  # noqa: F401
 from .alignment import alignment_metric, get_first_over_thresh  # noqa: F401
 from .audio import STFT, Denoiser, TacotronSTFT  # noqa: F401
+from .dtw import DTW  # noqa: F401  (waveglow/mel2samp.py DTW: predicted mels time-warped onto the ground truth)
 from .hifigan import Generator as HiFiGANGenerator  # noqa: F401  (hifigan.models.Generator)
 from .hifigan import load_model as load_hifigan  # noqa: F401
 from .mel_error import MelSpectrogramError  # noqa: F401  (the score of waveglow/train.py validate() and hifigan/train.py)
@@ -19,6 +20,6 @@ from .waveglow import WaveGlow, WaveGlowLoss  # noqa: F401
 from .waveglow_ax import WaveGlow as WaveFlow  # noqa: F401  (efficient_model_ax.WaveGlow, waveflow=True)
 from .waveglow_ax import WaveFlowLoss  # noqa: F401  (efficient_loss.WaveGlowLoss on WaveFlow.forward's tuple)
 
-__all__ = ["set_f32_gemm_mode", "WaveGlow", "WaveGlowLoss", "WaveGlowVocoder", "load_waveglow", "WaveFlow", "WaveFlowLoss", "HiFiGANGenerator", "load_hifigan", "Tacotron2", "Tacotron2Loss", "MelSpectrogramError", "load_model", "STFT", "TacotronSTFT", "Denoiser", "alignment_metric",
+__all__ = ["set_f32_gemm_mode", "WaveGlow", "WaveGlowLoss", "WaveGlowVocoder", "load_waveglow", "WaveFlow", "WaveFlowLoss", "HiFiGANGenerator", "load_hifigan", "Tacotron2", "Tacotron2Loss", "MelSpectrogramError", "DTW", "load_model", "STFT", "TacotronSTFT", "Denoiser", "alignment_metric",
            "get_first_over_thresh", "BestOfN", "pcm16_concat", "synthetic", "TorchMoji",
            "torchmoji_feature_encoding"]

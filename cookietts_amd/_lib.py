@@ -360,6 +360,8 @@ SIGNATURES = {
     "ctts_mel_error_workspace_bytes": (C.c_size_t, [C.POINTER(MelErrorConfig)] + [C.c_int32] * 3),
     "ctts_mel_error_f32": (C.c_int, [C.POINTER(MelErrorConfig)] + [_FP] * 6 + [C.c_int32] * 5 + [_FP] * 4 + [C.c_int32, _FP,
                                                                                                      C.c_size_t, _FP]),
+    "ctts_mel_dtw_f32": (C.c_int, [_FP] * 6 + [C.c_int32] * 5 + [_FP]),
+    "ctts_mel_dtw_generic_f32": (C.c_int, [_FP] * 6 + [C.c_int32] * 5 + [_FP]),
     "ctts_taco_stop_state_bytes": (C.c_size_t, [C.c_int32]),
     "ctts_taco_stop_reset": (C.c_int, [_FP, C.c_int32, C.c_int32, _FP]),
     "ctts_taco_stop_rule_f32": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _FP, _FP]),

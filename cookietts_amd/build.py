@@ -22,8 +22,9 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-
 # retry.hip: its double-precision score must equal the reference's Python arithmetic bit for bit - no a * b + c may fuse
 # taco_loss.hip: the same for its attention score (loss_function.py:276-283)
 # mel_error.hip: the same for its batch averages (_4_mtw/waveglow/train.py:276-278, 294-295)
+# dtw.hip: a candidate is w0 * x0 + w1 * x1 with both products rounded (mel2samp.py:105); a fused form changes which one wins a tie
 EXTRA_FLAGS = {"tacotron_persistent.hip": ["-fno-slp-vectorize"], "retry.hip": ["-ffp-contract=off"],
-               "taco_loss.hip": ["-ffp-contract=off"], "mel_error.hip": ["-ffp-contract=off"]}
+               "taco_loss.hip": ["-ffp-contract=off"], "mel_error.hip": ["-ffp-contract=off"], "dtw.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import torch
 
+from .dtw import DTW
 from .waveglow import WaveGlow
 from .waveglow_ax import WaveGlow as WaveGlowAx
 
@@ -178,16 +179,34 @@ def load_waveglow(vocoder_path, device='cuda', sigma=0.8, trust_checkpoint=False
     return vocoder, checkpoint['waveglow_config']
 
 
-def validate(model, mels, gt_audio, gt_lengths, metric, sigma, speaker_ids=None):
+def _dtw_mels(mels, dtw_target, dtw, dtw_lengths):
+    n_mel = dtw_target.shape[1] if dtw_target.dim() == 3 else -1
+    if mels.dim() != 3 or dtw_target.dim() != 3 or mels.shape[1] < n_mel or (mels.shape[0], mels.shape[2]) != (
+            dtw_target.shape[0], dtw_target.shape[2]):
+        raise ValueError(f"validate: dtw_target must be [B, n_mel, F] with n_mel <= the channels of mels {tuple(mels.shape)}, got "
+                         f"{tuple(dtw_target.shape)}")
+    scale_factor, range_ = dtw
+    aligned = DTW(mels[:, :n_mel], dtw_target.to(mels.device), scale_factor, range_, lengths=dtw_lengths)
+    return aligned if mels.shape[1] == n_mel else torch.cat((aligned, mels[:, n_mel:]), dim=1)
+
+
+def validate(model, mels, gt_audio, gt_lengths, metric, sigma, speaker_ids=None, dtw_target=None, dtw=(8, 5), dtw_lengths=None):
     """What ``_4_mtw/waveglow/train.py:188-193, 256-291`` does around the metric, for a whole batch: ``model.infer(mels, speaker_ids,
     sigma=sigma)`` in eval mode under ``torch.random.fork_rng`` with ``manual_seed(0)`` (the same z at every validation), then
     ``metric.forward`` (a :class:`~cookietts_amd.mel_error.MelSpectrogramError`) of the generated audio against ``gt_audio`` with
     ``gt_lengths``.  -> ``(average_MSE, average_MAE, result_dict)``.  The model's train / eval mode is left as it was found and the
-    global RNG state is not advanced; no file is read and nothing is plotted."""
+    global RNG state is not advanced; no file is read and nothing is plotted.
+
+    ``dtw_target`` (the ground-truth mels ``[B, n_mel, F]``) scores the vocoder on PREDICTED mels as train.py:232-236 does: the first
+    ``n_mel`` channels of ``mels`` are time-warped onto it (:func:`cookietts_amd.dtw.DTW` with ``scale_factor, range_ = dtw`` and the
+    per-item frame counts ``dtw_lengths``) before ``infer``; channels beyond ``n_mel`` (the logvar half of a ``use_logvar_channels``
+    model) pass through untouched.  Without it nothing of this runs."""
     was_training = model.training
     model.eval()
     try:
         with torch.no_grad():
+            if dtw_target is not None:
+                mels = _dtw_mels(mels, dtw_target, dtw, dtw_lengths)
             devices = [mels.device.index if mels.device.index is not None else torch.cuda.current_device()] if mels.is_cuda else []
             with torch.random.fork_rng(devices=devices):
                 torch.random.manual_seed(0)

@@ -1268,6 +1268,27 @@ int ctts_mel_error_f32(const ctts_mel_error_config* cfg, const void* packed, con
                        int32_t T_pred, int32_t T_gt, int32_t mel_frames, double* table, float* mae_map, float* pred_map,
                        float* gt_map, int32_t map_frames, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- DTW: time-warp predicted mels onto the ground truth (_4_mtw/waveglow/mel2samp.py:81-118) ----------------------------------
+ * pred, target, out: fp32 [batch][channels][frames], contiguous, on the device; out may alias neither input.  lengths: int32 [batch]
+ * on the device or NULL (every item is `frames` long).  Item b is treated exactly as the reference treats pred[b, :, :len_b] alone
+ * (its zero frames begin at len_b); columns t >= len_b of out are copied from pred.  A value of the device array outside [1, frames]
+ * is read as the nearest bound (callers that hold the lengths on the host check them there).
+ * With s = scale_factor, r = range (odd), h = r / 2: candidate j in [0, s r) at frame t is the zero-padded prediction, linearly
+ * interpolated to s times its length (align_corners=False, source index max(0, float(1 / s) (p + 0.5) - 0.5) at p = j + t s, all fp32).
+ * The (i0 - t, 1 - lambda, lambda) triple of each j is formed on the host in fp32; a candidate is w0 x0 + w1 x1 with both products rounded.
+ * The running best starts as pred itself; candidates are tried in ascending j and replace it only when their sum_c |cand - target| is
+ * STRICTLY smaller: pred wins every tie, an earlier candidate wins a tie with a later one, a NaN sum never wins.  The sums are fp32 in a
+ * fixed order (channels ascending inside each of four channel slices, slices ascending): results repeat bit for bit.
+ * choice (or NULL): int32 [batch][frames], the winning j, or -1 for the unshifted frame and for t >= len_b.
+ * l1 (or NULL): fp32 [batch][2][frames], the L1 of the unshifted frame and of the winner (0 for t >= len_b).
+ * Accepted: range odd, scale_factor >= 1, scale_factor * range <= 64, batch <= 65535; anything else is CTTS_E_ARG before any launch.
+ * One launch, no workspace, no atomics.  (8, 5), (5, 5) and (5, 3) - the reference's three option sets - run compile-time variants of
+ * the kernel; ctts_mel_dtw_generic_f32 is the same call held to the generic form (same bits; the tests say so). */
+int ctts_mel_dtw_f32(const float* pred, const float* target, const int32_t* lengths, float* out, int32_t* choice, float* l1,
+                     int32_t batch, int32_t channels, int32_t frames, int32_t scale_factor, int32_t range, void* stream);
+int ctts_mel_dtw_generic_f32(const float* pred, const float* target, const int32_t* lengths, float* out, int32_t* choice, float* l1,
+                             int32_t batch, int32_t channels, int32_t frames, int32_t scale_factor, int32_t range, void* stream);
+
 /* ---- main loop of the fp32 conv-GEMM ------------------------------------------------------------------------
  * Every fp32 path of the library (WaveGlow fp32, WaveFlow, the ax WaveGlow, conv1d / LSTM input projections, STFT)
  * goes through one conv-GEMM.  mode 0 (default): v_mfma_f32_32x32x2_f32, exact fp32 products.  mode 1 ("split bf16"):
