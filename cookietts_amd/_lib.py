@@ -382,6 +382,7 @@ SIGNATURES = {
     "ctts_last_winograd_f43_width": (C.c_int, []),
     "ctts_tuning_reload": (C.c_int, []),
     "ctts_tuning_flags": (C.c_int, []),
+    "ctts_tuning_flags_ext": (C.c_int, []),
     "ctts_profile_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "ctts_profile_bind": (C.c_int, [C.c_void_p]),
     "ctts_profile_collect": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -463,7 +464,8 @@ TUNING_BITS = {"CTTS_F32_NO_GLDS": 0, "CTTS_GEMM_NO_XCD_PAIR": 1, "CTTS_F32_WINO
                "CTTS_F32_NO_WINOGRAD": 28, "CTTS_F32_WINOGRAD_MIN": 29, "CTTS_F32_WINOGRAD_PLAIN": 30}
 # ctts_tuning_flags() is full below the sign bit: knobs added since then sit here (bit 31 = the int's sign bit) and are looked up by
 # tuning_active like the others
-TUNING_BITS_EXT = {"CTTS_WF_FWD_ROWWISE": 31}
+# (bits 32 and up are the bits of ctts_tuning_flags_ext())
+TUNING_BITS_EXT = {"CTTS_WF_FWD_ROWWISE": 31, "CTTS_F32_WINOGRAD_F63_MIN": 32, "CTTS_F32_WINOGRAD_NO_F63": 33}
 
 
 def tuning_reload():
@@ -474,6 +476,8 @@ def tuning_reload():
 def tuning_active(name):
     """True when the library currently runs with knob ``name`` set (``ctts_tuning_flags``)."""
     bit = TUNING_BITS[name] if name in TUNING_BITS else TUNING_BITS_EXT[name]
+    if bit >= 32:
+        return bool(lib().ctts_tuning_flags_ext() >> (bit - 32) & 1)
     return bool(lib().ctts_tuning_flags() >> bit & 1)
 
 

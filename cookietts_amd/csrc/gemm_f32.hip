@@ -880,6 +880,8 @@ void load_tuning_locked() {
     g_tune.f32_winograd_no_fused = on("CTTS_F32_WINOGRAD_NO_FUSED");
     g_tune.f32_winograd_f43_min = num("CTTS_F32_WINOGRAD_F43_MIN", -1);
     g_tune.f32_winograd_no_f43 = on("CTTS_F32_WINOGRAD_NO_F43");
+    g_tune.f32_winograd_f63_min = num("CTTS_F32_WINOGRAD_F63_MIN", -1);
+    g_tune.f32_winograd_no_f63 = on("CTTS_F32_WINOGRAD_NO_F63");
     g_tune.f32_cond_chain = on("CTTS_F32_COND_CHAIN");
     g_tune_loaded = true;
 }

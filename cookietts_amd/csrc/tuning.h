@@ -34,6 +34,8 @@ struct Tuning {
     bool f32_winograd_plain;  // CTTS_F32_WINOGRAD_PLAIN: the Winograd form as five launches per layer (cond rows copied into pair order for every layer, T2 / T3 and even / odd as separate launches, d = 2 transform one column at a time): the A/B arm and the tests' reference of the merged form, bit-identical
     int f32_winograd_fused_min;  // CTTS_F32_WINOGRAD_FUSED_MIN: take the one-launch Winograd layer (wn_winograd_layer.hip) for utterances of at least this many columns; 0 = always (default in waveglow_api.hip).  Below it the Winograd form, where it engages, runs as the paired launches
     int f32_winograd_f43_min;  // CTTS_F32_WINOGRAD_F43_MIN: take the F(4,3) form of the one-launch Winograd layer (quad columns, 1.5 C products per output and row) for utterances of at least this many columns; 0 = always (default in waveglow_api.hip).  Below it, and wherever the one-launch layer does not engage, the F(2,3) forms run
+    int f32_winograd_f63_min;  // CTTS_F32_WINOGRAD_F63_MIN: where the F(4,3) one-launch layer engages, run its layers with d % 4 == 0 in the F(6,3) form (hex columns, 8/6 C products per output and row) for utterances of at least this many columns; 0 = always (default in waveglow_api.hip)
+    bool f32_winograd_no_f63;  // CTTS_F32_WINOGRAD_NO_F63: never the F(6,3) form: the F(4,3) layer wherever it engages (the A/B arm, bit-equal to the library before the F(6,3) form)
     bool f32_winograd_no_f43;  // CTTS_F32_WINOGRAD_NO_F43: never the F(4,3) form: the one-launch F(2,3) layer at every size it engages at (the A/B arm, bit-equal to the library before the F(4,3) form)
     bool f32_winograd_no_fused;  // CTTS_F32_WINOGRAD_NO_FUSED: never the one-launch Winograd layer: T2 | T3 and even | odd as two launches of the conv-GEMM with the T planes in HBM (the A/B arm)
     bool f32_cond_chain;   // CTTS_F32_COND_CHAIN: WaveGlow fp32 conditioning as the chain (upsampling launch, cond layer 0, cond layer 1 through spect / h_tmp) also where the composed form applies (one GEMM from the mel frames, waveglow_api.hip): the A/B arm, bit-equal to the library before the composed form

@@ -62,6 +62,9 @@ struct Plan {
         // Winograd F(4,3) form of the one-launch layer (where wn_winograd_layer_f43_supported; empty otherwise): per layer U1..U4 in
         // SPLIT packing (K = C), [U0 | C_i] and [U5 | C_i] in GATE packing (K = C + H); wg_dense then holds the dense [6][2C][C] U0..U5
         std::vector<size_t> wq_U_A[4], wq_e_A, wq_o_A;
+        // Winograd F(6,3) form (where wn_winograd_layer_f63_supported, for the layers it can engage at: d % 4 == 0; 0 elsewhere): U1..U6
+        // in SPLIT packing, [U0 | C_i] and [U7 | C_i] in GATE packing; wg_dense then holds the dense [8][2C][C] U0..U7
+        std::vector<size_t> wh_U_A[6], wh_e_A, wh_o_A;
     };
     std::vector<Flow> fl;
     size_t total;
@@ -73,6 +76,10 @@ struct Plan {
     int rs_rows(int layer) const { return layer < c.n_layers - 1 ? 2 * C : C; }
     int rs_mb(int layer) const { return (rs_rows(layer) + GEMM_BM - 1) / GEMM_BM; }
 };
+
+// the layers the F(6,3) form can engage at: the cond rows are read in place through the hex map, four consecutive aligned columns per
+// lane (d % 4 == 0); d = 2 keeps F(4,3) (it would need six cond copies and a second transform path)
+bool f63_layer(int layer) { return (1 << layer) % 4 == 0; }
 
 // options: CTTS_WG_OPT_* of the `_opt` entry points (0: what the entry points without the argument run)
 int make_plan(const ctts_waveglow_config* cfg, Plan& p, int options = 0) {
@@ -161,7 +168,14 @@ int make_plan(const ctts_waveglow_config* cfg, Plan& p, int options = 0) {
             f.wq_e_A.push_back(take((size_t)p.mb_in * (p.nch_rs + p.nch1h) * A_TILE));
             f.wq_o_A.push_back(take((size_t)p.mb_in * (p.nch_rs + p.nch1h) * A_TILE));
         }
-        f.wg_dense = take((size_t)(f43 ? 6 : 3) * 2 * p.C * p.C);
+        const bool f63 = wn_winograd_layer_f63_supported(p.C, p.H);
+        for (int i = 0; f63 && i < c.n_layers; ++i) {
+            const bool on = f63_layer(i);
+            for (auto& u : f.wh_U_A) u.push_back(on ? take((size_t)p.mb_in * p.nch_rs * A_TILE) : 0);
+            f.wh_e_A.push_back(on ? take((size_t)p.mb_in * (p.nch_rs + p.nch1h) * A_TILE) : 0);
+            f.wh_o_A.push_back(on ? take((size_t)p.mb_in * (p.nch_rs + p.nch1h) * A_TILE) : 0);
+        }
+        f.wg_dense = take((size_t)(f63 ? 8 : f43 ? 6 : 3) * 2 * p.C * p.C);
     }
     // composed conditioning, behind everything else (a blob without it is a prefix of one with it): single speaker, whole 16-row K
     // chunks per tap, at most four taps (one K segment each), and P a power of two in [4, 256] - whole 16-byte stores, and an
@@ -219,6 +233,17 @@ int quad_ld(const Plan& p, const Geom& g) {
     for (int i = 0; i < p.c.n_layers; ++i) nt = std::max(nt, quad_geom(g, i).ntiles);
     return round_up(nt * 64, 128);
 }
+// Winograd F(6,3) form: hex-space geometry of layer i: Lh = ceil(L / 6d) d hex columns per batch item, in ntiles 64-column tiles
+PairGeom hex_geom(const Geom& g, int layer) {
+    const int d = 1 << layer;
+    const int Lh = (g.L + 6 * d - 1) / (6 * d) * d;
+    return {d, Lh, (Lh + 63) / 64};
+}
+int hex_ld(const Plan& p, const Geom& g) {
+    int nt = 0;
+    for (int i = 0; i < p.c.n_layers; ++i) nt = std::max(nt, hex_geom(g, i).ntiles);
+    return nt * 64;
+}
 // ---- the in-layer form of a call ---------------------------------------------------
 // Decided once from (plan, geometry, one tuning snapshot): carve() sizes the buffers from it and WnCall launches from it.
 //   Direct            one GATE launch on the three x taps
@@ -229,9 +254,13 @@ int quad_ld(const Plan& p, const Geom& g) {
 //                     to the paired launches: ((S2 +- S3) + products) + b against ((products + b) + T2) +- T3
 //   WinogradLayerF43  quad transform, then the one-launch F(4,3) layer (1.5 C products per output and row where F(2,3) spends 2 C).
 //                     Not bit-equal to F(2,3): other products (float64 parity: tests/test_waveglow_winograd_f43_gpu.py)
+//   WinogradLayerF63  WinogradLayerF43 whose layers with d % 4 == 0 run the F(6,3) form: hex transform, then the one-launch F(6,3) layer
+//                     (8/6 C products per output and row).  Not bit-equal to F(4,3): other products
+//                     (float64 parity: tests/test_waveglow_winograd_f63_gpu.py)
 // Every test is on the utterance (columns = steps per batch item), never on the batch: an utterance must come out bit for bit the
 // same whatever batch it runs in (tests/test_full_size.py), and each form is bit-identical across the kernel shapes a batch picks.
-enum class InForm { Direct, WinogradSeparate, WinogradPaired, WinogradLayer, WinogradLayerF43 };
+enum class InForm { Direct, WinogradSeparate, WinogradPaired, WinogradLayer, WinogradLayerF43, WinogradLayerF63 };
+bool quad_space(InForm in) { return in == InForm::WinogradLayerF43 || in == InForm::WinogradLayerF63; }
 
 // Each threshold is the length its A/B was run at (900 frames).  Winograd at all: profiles/r12_02_winograd_ab.txt,
 // r12_04_winograd_sweep.txt; CTTS_F32_WINOGRAD_MIN: another threshold (0 = always), CTTS_F32_NO_WINOGRAD: never.
@@ -242,6 +271,9 @@ constexpr long long WINOGRAD_FUSED_MIN_COLS = 28800;
 // Its F(4,3) form: profiles/r23_01_winograd_f43_gonogo.txt.  CTTS_F32_WINOGRAD_F43_MIN: another threshold;
 // CTTS_F32_WINOGRAD_NO_F43, and whatever switches the one-launch layer off: never.
 constexpr long long WINOGRAD_F43_MIN_COLS = 28800;
+// The F(6,3) form of its d % 4 == 0 layers: profiles/r34_01_winograd_f63_gonogo.txt.  CTTS_F32_WINOGRAD_F63_MIN: another threshold;
+// CTTS_F32_WINOGRAD_NO_F63, and whatever switches the F(4,3) form off: never.
+constexpr long long WINOGRAD_F63_MIN_COLS = 28800;
 
 InForm in_form(const Plan& p, const Geom& g, const Tuning& t) {
     auto long_enough = [&](int knob, long long cols) { return (long long)g.L >= (knob >= 0 ? knob : cols); };
@@ -254,7 +286,9 @@ InForm in_form(const Plan& p, const Geom& g, const Tuning& t) {
         return InForm::WinogradPaired;
     if (t.f32_winograd_no_f43 || !wn_winograd_layer_f43_supported(p.C, p.H) || !long_enough(t.f32_winograd_f43_min, WINOGRAD_F43_MIN_COLS))
         return InForm::WinogradLayer;
-    return InForm::WinogradLayerF43;
+    if (t.f32_winograd_no_f63 || !wn_winograd_layer_f63_supported(p.C, p.H) || !long_enough(t.f32_winograd_f63_min, WINOGRAD_F63_MIN_COLS))
+        return InForm::WinogradLayerF43;
+    return InForm::WinogradLayerF63;
 }
 
 // ---- the conditioning form of a call -----------------------------------------------
@@ -284,9 +318,10 @@ struct Workspace {
     float* a16;         // WN folds: layer 0's input [B][FOLD_ROWS][ld] = [audio_0; 1 on [0, L); 0]
     float* skend;       // WN folds: the skip/end accumulator [B][2 n_half][ld] between the groups of a flow
     // Winograd in-layer forms (NULL in the direct form): V1..V4 [4][B][C][ldp], T2 / T3 [2][B][2C][ldp], h2e / h2o [2][B][H][ldp];
-    // the F(4,3) form keeps V0..V5 [6][B][C][ldq] and h(t_0)..h(t_3) [4][B][H][ldq] in the same two buffers (sized for the larger form)
+    // the F(4,3) form keeps V0..V5 [6][B][C][ldq] and h(t_0)..h(t_3) [4][B][H][ldq] in the same two buffers (sized for the larger form),
+    // the F(6,3) form V0..V7 [8][B][C][ldh] (no cond copies: its layers read the cond rows in place)
     float *wgV, *wgT, *wgH;
-    int ldp, ldq;
+    int ldp, ldq, ldh;
     size_t total;  // floats
 };
 
@@ -308,11 +343,12 @@ void carve(const Plan& p, const Geom& g, int batch, float* base, InForm in, bool
     w.a16 = take(B * FOLD_ROWS * g.ld);
     w.skend = take(B * p.c.n_group * g.ld);
     w.wgV = w.wgT = w.wgH = nullptr;
-    w.ldp = w.ldq = 0;
+    w.ldp = w.ldq = w.ldh = 0;
     if (in != InForm::Direct) {
         w.ldp = pair_ld(p, g);
-        w.ldq = in == InForm::WinogradLayerF43 ? quad_ld(p, g) : 0;
-        w.wgV = take(std::max((size_t)4 * w.ldp, (size_t)6 * w.ldq) * B * p.C);
+        w.ldq = quad_space(in) ? quad_ld(p, g) : 0;
+        w.ldh = in == InForm::WinogradLayerF63 ? hex_ld(p, g) : 0;
+        w.wgV = take(std::max({(size_t)4 * w.ldp, (size_t)6 * w.ldq, (size_t)8 * w.ldh}) * B * p.C);
         w.wgT = take((size_t)2 * B * 2 * p.C * w.ldp);
         w.wgH = take(std::max((size_t)2 * w.ldp, (size_t)4 * w.ldq) * B * p.H);
     }
@@ -515,6 +551,7 @@ struct WnCall {
     // where d % 4 == 0; d = 2 (and d = 1, layer 0 without the start fold) and every layer of WinogradSeparate read the copies
     // h2e / h2o the transform makes
     bool in_place(int i) const { return in != InForm::WinogradSeparate && (1 << i) % 4 == 0; }
+    bool hex(int i) const { return in == InForm::WinogradLayerF63 && f63_layer(i); }      // layer i runs the F(6,3) form
     size_t plane(int rows) const { return (size_t)batch * rows * w.ldp; }           // one [B][rows][ldp] plane of wgV / wgT / wgH
 
     // ---- descriptor builders: no GemmArgs or WnWinogradLayerArgs field is assigned anywhere else in the fp32 path
@@ -656,14 +693,19 @@ struct WnCall {
         }
         return a;
     }
-    // the one-launch layer behind the transform (wn_winograd_layer.hip), F(2,3) in pair space or F(4,3) in quad space
+    // the one-launch layer behind the transform (wn_winograd_layer.hip), F(2,3) in pair space, F(4,3) in quad or F(6,3) in hex space
     WnWinogradLayerArgs wg_layer(int k, int i) const {
         const auto& f = p.fl[k];
-        const bool f43 = in == InForm::WinogradLayerF43;
-        const PairGeom sg = f43 ? quad_geom(g, i) : pair_geom(g, i);
-        const int ldw = f43 ? w.ldq : w.ldp;
+        const bool f43 = quad_space(in) && !hex(i);
+        const PairGeom sg = hex(i) ? hex_geom(g, i) : f43 ? quad_geom(g, i) : pair_geom(g, i);
+        const int ldw = hex(i) ? w.ldh : f43 ? w.ldq : w.ldp;
         WnWinogradLayerArgs a{};
-        if (f43) {
+        if (hex(i)) {
+            a.form = WNWG_F63;
+            a.A_T2 = blob + f.wh_U_A[0][i]; a.A_T3 = blob + f.wh_U_A[1][i]; a.A_T4 = blob + f.wh_U_A[2][i]; a.A_T5 = blob + f.wh_U_A[3][i];
+            a.A_T6 = blob + f.wh_U_A[4][i]; a.A_T7 = blob + f.wh_U_A[5][i];
+            a.A_e = blob + f.wh_e_A[i]; a.A_o = blob + f.wh_o_A[i];
+        } else if (f43) {
             a.form = WNWG_F43;
             a.A_T2 = blob + f.wq_U_A[0][i]; a.A_T3 = blob + f.wq_U_A[1][i]; a.A_T4 = blob + f.wq_U_A[2][i]; a.A_T5 = blob + f.wq_U_A[3][i];
             a.A_e = blob + f.wq_e_A[i]; a.A_o = blob + f.wq_o_A[i];
@@ -691,7 +733,11 @@ struct WnCall {
     // one column at a time; F(4,3): V0..V5 (1.5 C L floats), and the 128-column arm of the layer (CTTS_F32_NO_SMALL) reads whole
     // 128-column tiles, so the transform fills them
     int wg_transform(int k, int i) const {
-        if (in == InForm::WinogradLayerF43) {
+        if (hex(i)) {
+            const PairGeom hg = hex_geom(g, i);
+            return launch_winograd_transform_hex(w.x, cstride, w.wgV, batch, p.C, hg.d, g.L, hg.Lp, g.ld, g.pad, w.ldh, hg.ntiles * 64, s);
+        }
+        if (quad_space(in)) {
             const PairGeom qg = quad_geom(g, i);
             const int ncols = t.f32_no_small ? round_up(qg.ntiles * 64, 128) : qg.ntiles * 64;
             return launch_winograd_transform_quad(w.x, cstride, h(k), hstride, w.wgV, w.wgH, batch, p.C, p.H, qg.d, g.L, qg.Lp, g.ld, g.pad,
@@ -713,6 +759,7 @@ struct WnCall {
             return launch_gemm_f32(GEMM_EPI_GATE, in_gemm(k, i), s);
         case InForm::WinogradLayer:
         case InForm::WinogradLayerF43:
+        case InForm::WinogradLayerF63:
             return launch_wn_winograd_layer(wg_layer(k, i), s);
         case InForm::WinogradSeparate:
         case InForm::WinogradPaired:
@@ -1310,6 +1357,17 @@ int ctts_waveglow_pack_flow(const ctts_waveglow_config* cfg, int32_t k, const ct
         if ((rc = pack_gate(f.wq_e_A[i], dense, C, 1, i))) return rc;
         if ((rc = pack_gate(f.wq_o_A[i], dense + 5 * dn, C, 1, i))) return rc;
     }
+    // Winograd F(6,3) form of the layers it can engage at: U1..U6 (SPLIT) and [U0 | C_i], [U7 | C_i] (GATE) through the same dense scratch
+    for (int i = 0; i < (f.wh_e_A.empty() ? 0 : p.c.n_layers); ++i) {
+        if (!f63_layer(i)) continue;
+        float* dense = blob + f.wg_dense;
+        const size_t dn = (size_t)2 * C * C;
+        if ((rc = launch_winograd_g63(w->in_w[i], dense, 2 * C, C, s))) return rc;
+        for (int j = 0; j < 6; ++j)
+            if ((rc = launch_pack_a(blob + f.wh_U_A[j][i], dense + (1 + j) * dn, GEMM_BM, p.mb_in, p.nch_rs, 0, C, GEMM_EPI_SPLIT, C, 2 * C, 0, C, 1, s))) return rc;
+        if ((rc = pack_gate(f.wh_e_A[i], dense, C, 1, i))) return rc;
+        if ((rc = pack_gate(f.wh_o_A[i], dense + 7 * dn, C, 1, i))) return rc;
+    }
     // WN start / end folds: layer 0 on [audio_0; 1] (K = [tap0, tap1, tap2] of one FOLD_ROWS chunk each, then the cond slice of
     // layer 0; bias in_b[0] as packed above) and the skip rows seen through `end`
     if ((rc = launch_fold_in0(w->in_w[0], w->start_w, w->start_b, blob + f.in0f_w, C, d.n_half, ks, s))) return rc;
@@ -1535,6 +1593,11 @@ int ctts_waveglow_infer_spk_f32_opt(const ctts_waveglow_config* cfg, const void*
 int ctts_last_gemm_loop(void) { return last_gemm_loop(); }
 int ctts_last_winograd_f43_width(void) { return last_wn_winograd_f43_width(); }
 int ctts_tuning_reload(void) { reload_tuning(); return CTTS_OK; }
+// the knobs beyond the 32 bits of ctts_tuning_flags: bit 0 here is bit 32 there
+int ctts_tuning_flags_ext(void) {
+    const Tuning t = tuning();
+    return (t.f32_winograd_f63_min >= 0 ? 1 : 0) | (t.f32_winograd_no_f63 ? 2 : 0);
+}
 int ctts_tuning_flags(void) {
     const Tuning t = tuning();
     return (t.f32_no_glds ? 1 : 0) | (t.no_xcd_pair ? 2 : 0) | (t.bf16_no_wide ? 8 : 0) | (t.bf16_no_pp ? 16 : 0) |

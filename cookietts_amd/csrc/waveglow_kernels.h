@@ -70,4 +70,11 @@ int launch_winograd_transform_quad(const float* x, long long x_bstride, const fl
                                    int batch, int C, int H, int d, int L, int Lq, int ld, int pad, int ldq, int ncols, bool cond_rows,
                                    hipStream_t s);
 
+// Winograd F(6,3) form of the layers with d % 4 == 0 (points 0, +-1, +-2, +-1/2, inf; the algebra is at the kernels).  Pack time: dense
+// [8][rows][C] = U0..U7.  Per layer: V0..V7 [8][B][C][ldh] in hex order (Lh hex columns, zeros up to ncols); the cond rows are read
+// in place.
+int launch_winograd_g63(const float* in_w, float* dense, int rows, int C, hipStream_t s);
+int launch_winograd_transform_hex(const float* x, long long x_bstride, float* V, int batch, int C, int d, int L, int Lh, int ld, int pad,
+                                  int ldh, int ncols, hipStream_t s);
+
 }  // namespace ctts

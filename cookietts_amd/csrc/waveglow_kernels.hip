@@ -740,6 +740,92 @@ __global__ __launch_bounds__(256) void winograd_transform_quad_kernel(const floa
     }
 }
 
+// --------------------------------------------------- Winograd F(6,3) in-layer form ----
+// The same conv on the output hex t_k = t_0 + k d, k = 0..5, from the eight taps x_j = x[t_0 + (j - 1) d], j = 0..7, with the
+// interpolation points 0, +-1, +-2, +-1/2, inf:
+//   e = x2 + x6 - 17/4 x4,  o = x1 + x5 - 17/4 x3:                 V1 = e + o,  V2 = e - o
+//   e = 1/4 x2 - 5/4 x4 + x6,  o = 1/2 x1 - 5/2 x3 + 2 x5:         V3 = e + o,  V4 = e - o
+//   e = 4 x2 - 5 x4 + x6,  o = 2 x1 - 5/2 x3 + 1/2 x5:             V5 = e + o,  V6 = e - o
+//   V0 = x0 - x6 + 21/4 (x4 - x2)                                  V7 = x7 - x1 + 21/4 (x3 - x5)
+//   U0 = W0   U1, U2 = -2/9 (W0 +- W1 + W2)   U3, U4 = W0 / 90 +- W1 / 45 + 2 W2 / 45   U5, U6 = 32/45 W0 +- 16/45 W1 + 8/45 W2   U7 = W2
+//   P_j = U_j V_j, a = P1 + P2, b = P1 - P2, c = P3 + P4, e = P3 - P4, f = P5 + P6, g = P5 - P6:
+//   u[t_0] = P0 + a + c + f          u[t_1] = b + 2 e + g / 2         u[t_2] = a + 4 c + f / 4
+//   u[t_3] = b + 8 e + g / 8         u[t_4] = a + 16 c + f / 16       u[t_5] = b + 32 e + g / 32 + P7
+// 8/6 C MACs per output and row.  Hex column q of a batch item stands for t_0 = (q / d) 6d + q % d; there are Lh = ceil(L / 6d) d.
+
+// dense[j] = U_j, j = 0..7, as [rows][C] (in_w: [rows][C][3]); fp64 sums rounded once
+__global__ __launch_bounds__(256) void winograd_g63_kernel(const float* __restrict__ in_w, float* __restrict__ dense, int n) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const double w0 = in_w[(size_t)idx * 3], w1 = in_w[(size_t)idx * 3 + 1], w2 = in_w[(size_t)idx * 3 + 2];
+    dense[idx] = in_w[(size_t)idx * 3];
+    dense[(size_t)n + idx] = (float)(-2.0 * (w0 + w1 + w2) / 9.0);
+    dense[2 * (size_t)n + idx] = (float)(-2.0 * (w0 - w1 + w2) / 9.0);
+    dense[3 * (size_t)n + idx] = (float)(w0 / 90.0 + w1 / 45.0 + 2.0 * w2 / 45.0);
+    dense[4 * (size_t)n + idx] = (float)(w0 / 90.0 - w1 / 45.0 + 2.0 * w2 / 45.0);
+    dense[5 * (size_t)n + idx] = (float)(32.0 * w0 / 45.0 + 16.0 * w1 / 45.0 + 8.0 * w2 / 45.0);
+    dense[6 * (size_t)n + idx] = (float)(32.0 * w0 / 45.0 - 16.0 * w1 / 45.0 + 8.0 * w2 / 45.0);
+    dense[7 * (size_t)n + idx] = in_w[(size_t)idx * 3 + 2];
+}
+
+// x [B][C][ld] -> V0..V7 [8][B][C][ldh] in hex order (grid.y = C: the layer kernel reads the cond rows in place, the form runs
+// where d % 4 == 0).  Zero outside [0, L); columns [Lh, ncols) are written as zeros.  One thread: four hex columns of one row.
+// MODE 1: d % 4 == 0 and L % 4 == 0 - four consecutive time steps per tap, 16-byte aligned, all inside or all outside
+// MODE 0: one column at a time
+template <int MODE>
+__global__ __launch_bounds__(256) void winograd_transform_hex_kernel(const float* __restrict__ x, long long x_bstride, float* __restrict__ V,
+                                                                     int C, int d, int L, int Lh, int ld, int pad, int ldh, int ncols) {
+    const int q4 = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (q4 >= ncols) return;
+    const int row = blockIdx.y, b = blockIdx.z, B = gridDim.z;
+    const float* src = x + (size_t)b * x_bstride + (size_t)row * ld + pad;
+    float tap[8][4];                                                  // tap[j][e] = x[t_0(q4 + e) + (j - 1) d]
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tap[j][e] = 0.f;
+    if constexpr (MODE == 1) {
+        if (q4 < Lh) {
+            const int t0 = (q4 / d) * 6 * d + q4 % d;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int t = t0 + (j - 1) * d;
+                if (t < 0 || t >= L) continue;
+                const float4 v = *reinterpret_cast<const float4*>(src + t);
+                tap[j][0] = v.x; tap[j][1] = v.y; tap[j][2] = v.z; tap[j][3] = v.w;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int q = q4 + e;
+            const int t0 = (q / d) * 6 * d + q % d;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int t = t0 + (j - 1) * d;
+                tap[j][e] = (q < Lh && t >= 0 && t < L) ? src[t] : 0.f;
+            }
+        }
+    }
+    const size_t plane = (size_t)B * C * ldh;
+    float* o = V + ((size_t)b * C + row) * ldh + q4;
+    float v[8][4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float x0 = tap[0][e], x1 = tap[1][e], x2 = tap[2][e], x3 = tap[3][e], x4 = tap[4][e], x5 = tap[5][e], x6 = tap[6][e], x7 = tap[7][e];
+        const float e1 = (x2 + x6) - 4.25f * x4, o1 = (x1 + x5) - 4.25f * x3;
+        const float e2 = (0.25f * x2 + x6) - 1.25f * x4, o2 = (0.5f * x1 + 2.f * x5) - 2.5f * x3;
+        const float e3 = (4.f * x2 + x6) - 5.f * x4, o3 = (2.f * x1 + 0.5f * x5) - 2.5f * x3;
+        v[0][e] = (x0 - x6) + 5.25f * (x4 - x2);
+        v[1][e] = e1 + o1; v[2][e] = e1 - o1;
+        v[3][e] = e2 + o2; v[4][e] = e2 - o2;
+        v[5][e] = e3 + o3; v[6][e] = e3 - o3;
+        v[7][e] = (x7 - x1) + 5.25f * (x3 - x5);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) *reinterpret_cast<float4*>(o + j * plane) = make_float4(v[j][0], v[j][1], v[j][2], v[j][3]);
+}
+
 // a16[b][r][:] over the whole padded row: r < H: audio[b][ch_off + r][n], r == H: 1, other rows 0; 0 outside [pad, pad + L)
 template <int H>
 __global__ __launch_bounds__(256) void wn_start_ones_kernel(const float* __restrict__ audio, float* __restrict__ a16, int G,
@@ -1040,6 +1126,27 @@ int launch_winograd_transform_quad(const float* x, long long x_bstride, const fl
         hipLaunchKernelGGL(winograd_transform_quad_kernel<0>, grid, dim3(256), 0, s, x, x_bstride, h2, h_bstride, V, Hc, C, H, d, L, Lq,
                            ld, pad, ldq, ncols);
     CTTS_CHECK_LAUNCH("winograd_transform_quad");
+    return CTTS_OK;
+}
+
+int launch_winograd_g63(const float* in_w, float* dense, int rows, int C, hipStream_t s) {
+    const int n = rows * C;
+    hipLaunchKernelGGL(winograd_g63_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in_w, dense, n);
+    CTTS_CHECK_LAUNCH("winograd_g63");
+    return CTTS_OK;
+}
+
+int launch_winograd_transform_hex(const float* x, long long x_bstride, float* V, int batch, int C, int d, int L, int Lh, int ld, int pad,
+                                  int ldh, int ncols, hipStream_t s) {
+    CTTS_CHECK_ARG(d >= 1 && Lh % d == 0 && (long long)Lh * 6 >= L && Lh <= ncols && ncols <= ldh && ncols % 4 == 0 && ldh % 4 == 0 &&
+                       ld % 4 == 0 && pad % 4 == 0 && pad + L <= ld,
+                   "winograd_transform_hex: d=%d L=%d Lh=%d ncols=%d ldh=%d ld=%d pad=%d", d, L, Lh, ncols, ldh, ld, pad);
+    dim3 grid((ncols / 4 + 255) / 256, C, batch);
+    if (d % 4 == 0 && L % 4 == 0)
+        hipLaunchKernelGGL(winograd_transform_hex_kernel<1>, grid, dim3(256), 0, s, x, x_bstride, V, C, d, L, Lh, ld, pad, ldh, ncols);
+    else
+        hipLaunchKernelGGL(winograd_transform_hex_kernel<0>, grid, dim3(256), 0, s, x, x_bstride, V, C, d, L, Lh, ld, pad, ldh, ncols);
+    CTTS_CHECK_LAUNCH("winograd_transform_hex");
     return CTTS_OK;
 }
 

@@ -29,6 +29,17 @@
 // The F(4,3) form also runs with KD = 2: a stage holds two consecutive chunks (every phase is an even number of chunks), 16 k-step
 // regions and 32 NT MFMAs per wave between two barriers, and with NT = 2 (128 quad columns, 256 accumulator registers pinned to the
 // accumulator half of the file, one workgroup per CU).  Same products in the same order per accumulator element: bit-identical.
+//
+// F43 = 2 is the F(6,3) form on that main-loop body (NT = 1, KD = 2 only): 64 HEX columns = 384 natural columns, SIX accumulator sets
+// (192 VGPRs; 256 in all, no scratch, two workgroups per CU: profiles/r34_02_f63_resource_usage.txt) and one stream of
+// 6 n1 + 2 n2 + 4 nh chunks (C = 512, H = 256: 352 for 384 columns where F(4,3) runs 256 for 256):
+//   [0, 6 n1)          X_j += U_(j+1) . V_(j+1), j = 0..5
+//                      then a = X0 + X1, b = X0 - X1, c = X2 + X3, e = X2 - X3, f = X4 + X5, g = X4 - X5,
+//                      (X0..X5) <- (a + c + f, b + 2 e + g / 2, a + 4 c + f / 4, b + 8 e + g / 8, a + 16 c + f / 16, b + 32 e + g / 32)
+//   [.., + n2)         X0 += [U0 | C_i] . [V0; h(t_0)]   then act[t_0] = gate(X0 + b)
+//   4 x [.., + nh)     X_k += C_i . h(t_k), k = 1..4     then act[t_k]      (the cond chunks of the [U0 | C_i] panel)
+//   [.., + n2)         X5 += [U7 | C_i] . [V7; h(t_5)]   then act[t_5]
+// (interpolation points 0, +-1, +-2, +-1/2, inf: every output-side multiplier is a power of two).
 #include "wn_winograd_layer.h"
 #include "tuning.h"
 
@@ -52,7 +63,8 @@ __device__ __forceinline__ float wg_tanh(float u) {
 template <int NT, int F43, int KD, int TP>
 __global__ __launch_bounds__(256, (F43 && NT == 2) ? 1 : 2) void wn_winograd_layer_f32_kernel(const WnWinogradLayerArgs a) {
     static_assert(KD == 1 || (KD == 2 && F43 && TP), "two chunks per stage: the F(4,3) form (its phases are whole stages, see the launcher)");
-    constexpr int NI = F43 ? 4 : 2;                       // interior products = accumulator sets = natural columns per packed column
+    static_assert(F43 <= 1 || (NT == 1 && KD == 2), "the F(6,3) form: 64 hex columns, two chunks per stage");
+    constexpr int NI = 2 + 2 * F43;                       // interior products = accumulator sets = natural columns per packed column
     constexpr int BN = 64 * NT;
     constexpr int A_ST = GEMM_KC * 128;                   // floats of a chunk's A part
     constexpr int CST = A_ST + GEMM_KC * BN;              // floats per chunk
@@ -98,7 +110,8 @@ __global__ __launch_bounds__(256, (F43 && NT == 2) ? 1 : 2) void wn_winograd_lay
             const float *ap, *bp;
             if (c < c_e) {
                 const int ph = F43 ? c / n1 : (int)(c >= n1), loc = c - ph * n1;
-                ap = (ph == 0 ? a.A_T2 : ph == 1 ? a.A_T3 : ph == 2 ? a.A_T4 : a.A_T5) + ((size_t)mb_t * n1 + loc) * (GEMM_KC * 256) + loc_t;
+                ap = (ph == 0 ? a.A_T2 : ph == 1 ? a.A_T3 : ph == 2 ? a.A_T4 : ph == 3 ? a.A_T5 : ph == 4 ? a.A_T6 : a.A_T7) +
+                     ((size_t)mb_t * n1 + loc) * (GEMM_KC * 256) + loc_t;
                 bp = a.V + (1 + ph) * a.vplane + ((size_t)b * a.C + (size_t)loc * GEMM_KC) * a.ldp + n0;
             } else {
                 int ph = 0;
@@ -368,7 +381,7 @@ __global__ __launch_bounds__(256, (F43 && NT == 2) ? 1 : 2) void wn_winograd_lay
         WNWG_RUN(1, nch)
         WNWG_DRAIN()
         WNWG_GATE(X[1], 1)
-    } else {
+    } else if constexpr (F43 == 1) {
         WNWG_RUN(0, n1)
         WNWG_RUN(1, 2 * n1)
         WNWG_RUN(2, 3 * n1)
@@ -410,6 +423,42 @@ __global__ __launch_bounds__(256, (F43 && NT == 2) ? 1 : 2) void wn_winograd_lay
         WNWG_RUN(3, nch)
         WNWG_DRAIN()
         WNWG_GATE(X[3], 3)
+    } else {
+        WNWG_RUN(0, n1)
+        WNWG_RUN(1, 2 * n1)
+        WNWG_RUN(2, 3 * n1)
+        WNWG_RUN(3, 4 * n1)
+        WNWG_RUN(4, 5 * n1)
+        WNWG_RUN(5, c_e)
+        // one 16-register block of the six sets at a time, the six sums pinned where the accumulators are (see the F(4,3) form)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            asm volatile("" : "+v"(X[0][i][0]), "+v"(X[1][i][0]), "+v"(X[2][i][0]), "+v"(X[3][i][0]), "+v"(X[4][i][0]), "+v"(X[5][i][0]));
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p1 = X[0][i][0][r], p2 = X[1][i][0][r], p3 = X[2][i][0][r], p4 = X[3][i][0][r], p5 = X[4][i][0][r], p6 = X[5][i][0][r];
+                const float sa = p1 + p2, sb = p1 - p2, sc = p3 + p4, se = p3 - p4, sf = p5 + p6, sg = p5 - p6;
+                float y0 = (sa + sc) + sf, y1 = (sb + 2.0f * se) + 0.5f * sg, y2 = (sa + 4.0f * sc) + 0.25f * sf;
+                float y3 = (sb + 8.0f * se) + 0.125f * sg, y4 = (sa + 16.0f * sc) + 0.0625f * sf, y5 = (sb + 32.0f * se) + 0.03125f * sg;
+                // (one element of the six sets at a time: the file holds 192 accumulators, the main loop's state and six sums, no more)
+                asm volatile("" : "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3), "+v"(y4), "+v"(y5));
+                X[0][i][0][r] = y0; X[1][i][0][r] = y1; X[2][i][0][r] = y2; X[3][i][0][r] = y3; X[4][i][0][r] = y4; X[5][i][0][r] = y5;
+            }
+            asm volatile("" : "+v"(X[0][i][0]), "+v"(X[1][i][0]), "+v"(X[2][i][0]), "+v"(X[3][i][0]), "+v"(X[4][i][0]), "+v"(X[5][i][0]));
+        }
+        WNWG_RUN(0, ps[1])
+        WNWG_GATE(X[0], 0)
+        WNWG_RUN(1, ps[2])
+        WNWG_GATE(X[1], 1)
+        WNWG_RUN(2, ps[3])
+        WNWG_GATE(X[2], 2)
+        WNWG_RUN(3, ps[4])
+        WNWG_GATE(X[3], 3)
+        WNWG_RUN(4, ps[5])
+        WNWG_GATE(X[4], 4)
+        WNWG_RUN(5, nch)
+        WNWG_DRAIN()
+        WNWG_GATE(X[5], 5)
     }
 #undef WNWG_DRAIN
 #undef WNWG_RUN
@@ -439,6 +488,12 @@ bool wn_winograd_layer_f43_supported(int C, int H) {
     return wn_winograd_layer_supported(C, H) && 4 * (C / GEMM_KC) + 2 * ((C + H) / GEMM_KC) + 2 * (H / GEMM_KC) <= WNWG_MAX_CHUNKS;
 }
 
+// (two chunks per stage only: every phase - n1, n2 or nh chunks - a whole number of stages)
+bool wn_winograd_layer_f63_supported(int C, int H) {
+    return wn_winograd_layer_f43_supported(C, H) && H % (2 * GEMM_KC) == 0 &&
+           6 * (C / GEMM_KC) + 2 * ((C + H) / GEMM_KC) + 4 * (H / GEMM_KC) <= WNWG_MAX_CHUNKS;
+}
+
 namespace {
 thread_local int t_last_f43_width = 0;
 
@@ -461,9 +516,11 @@ int launch_wn_winograd_layer(const WnWinogradLayerArgs& a_in, hipStream_t stream
     WnWinogradLayerArgs a = a_in;
     CTTS_CHECK_ARG(wn_winograd_layer_supported(a.C, a.H), "wn_winograd_layer: C=%d H=%d", a.C, a.H);
     CTTS_CHECK_ARG(a.A_T2 && a.A_T3 && a.A_e && a.A_o && a.bias && a.V && a.act && a.batch >= 1, "wn_winograd_layer: operand not set");
-    const bool f43 = a.form == WNWG_F43;
-    const int tw = f43 ? 64 : 128;                        // columns of a tile that ntiles counts
-    CTTS_CHECK_ARG(a.form == WNWG_F23 || (f43 && wn_winograd_layer_f43_supported(a.C, a.H) && a.A_T4 && a.A_T5), "wn_winograd_layer: form %d", a.form);
+    const bool f43 = a.form == WNWG_F43, f63 = a.form == WNWG_F63;
+    const int tw = f43 || f63 ? 64 : 128;                 // columns of a tile that ntiles counts
+    CTTS_CHECK_ARG(a.form == WNWG_F23 || (f43 && wn_winograd_layer_f43_supported(a.C, a.H) && a.A_T4 && a.A_T5) ||
+                       (f63 && wn_winograd_layer_f63_supported(a.C, a.H) && a.A_T4 && a.A_T5 && a.A_T6 && a.A_T7 && a.in_place),
+                   "wn_winograd_layer: form %d", a.form);
     CTTS_CHECK_ARG(a.d >= 1 && a.L >= 1 && a.Lp >= 1 && a.ntiles >= 1 && a.Lp <= a.ntiles * tw && a.ntiles * tw <= a.ldp && a.ldp % 4 == 0 &&
                        a.ld % 4 == 0 && a.pad >= 0 && a.pad % 4 == 0 && a.L + a.pad <= a.ld,
                    "wn_winograd_layer: geometry d=%d L=%d Lp=%d ntiles=%d ldp=%d ld=%d pad=%d", a.d, a.L, a.Lp, a.ntiles, a.ldp, a.ld, a.pad);
@@ -474,6 +531,8 @@ int launch_wn_winograd_layer(const WnWinogradLayerArgs& a_in, hipStream_t stream
     a.b0 = 0;
     a.col0 = 0;
     const Tuning tn = tuning();
+    // F(6,3): 64 hex columns = 384 natural columns, two chunks per stage - the F(4,3) kernel's tile, main-loop body and occupancy
+    if (f63) return launch_wnwg_shape<1, 2, 2, 1>(a, a.ntiles, (long long)a.ntiles * a.batch, stream);
     if (f43) {
         // 64 quad columns with two chunks per stage at every grid size: 3.786 ms per config-2 layer where the parent's kernel (one chunk
         // per stage, table read by a plain load: kept as the CTTS_F32_FORCE_SMALL arm) takes 4.002 and the 128-column shape 4.233

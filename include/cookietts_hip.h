@@ -1323,7 +1323,7 @@ int ctts_last_gemm_loop(void);
 int ctts_last_winograd_f43_width(void);
 
 /* Launch-shape overrides for A/B measurements (CTTS_F32_NO_GLDS, CTTS_F32_NO_SMALL, CTTS_F32_FORCE_SMALL, CTTS_GEMM_NO_XCD_PAIR, CTTS_BF16_NO_WIDE /
- * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD, CTTS_F32_NO_WINOGRAD, CTTS_F32_WINOGRAD_MIN, CTTS_F32_WINOGRAD_PLAIN, CTTS_F32_WINOGRAD_FUSED_MIN, CTTS_F32_WINOGRAD_NO_FUSED, CTTS_F32_WINOGRAD_F43_MIN, CTTS_F32_WINOGRAD_NO_F43) never change results beyond the parity
+ * _NO_PP / _PS / _NO_PS / _WIDE_MIN, CTTS_WF_NO_FUSE, CTTS_WF_NO_VEC_INTERP, CTTS_WF_NO_REGION_SPLIT, CTTS_WF_NO_ROW_QUEUE, CTTS_F32_NO_ROUND_SPLIT, CTTS_TACO_POLL_DELAY, CTTS_TACO_NO_FUSE, CTTS_TACO_BG_NO_PIPE, CTTS_UP_NO_MFMA, CTTS_F32_NO_WN_FOLD, CTTS_F32_NO_WINOGRAD, CTTS_F32_WINOGRAD_MIN, CTTS_F32_WINOGRAD_PLAIN, CTTS_F32_WINOGRAD_FUSED_MIN, CTTS_F32_WINOGRAD_NO_FUSED, CTTS_F32_WINOGRAD_F43_MIN, CTTS_F32_WINOGRAD_NO_F43, CTTS_F32_WINOGRAD_F63_MIN, CTTS_F32_WINOGRAD_NO_F63) never change results beyond the parity
  * tolerance (CTTS_F32_NO_SPLITK changes the summation order of the fused WaveFlow layer at batch <= 2, see above; CTTS_F32_NO_WN_FOLD
  * brings back the fp32 WaveGlow WN stack without the start / end folds: WN layer 0 on the C-row x, the C-row deferred skip GEMM and the
  * C-row flow tail - the default folds W_in,0 . W_start into layer 0 and W_end . W_skip,i into a 2 n_half-row skip/end pass, which only
@@ -1344,7 +1344,13 @@ int ctts_last_winograd_f43_width(void);
  * spends 2 C, four interior products combined in registers with the exact multipliers 1, 2, 4, 8, the transformed filters formed
  * in fp64 and rounded once; the float64 parity of a flow stays inside the bound of the other forms.  CTTS_F32_WINOGRAD_NO_F43
  * keeps the F(2,3) one-launch layer at every size: the A/B arm, bit-equal to the library before the F(4,3) form; whatever
- * switches the one-launch layer off switches the F(4,3) form off with it).  The environment is read once,
+ * switches the one-launch layer off switches the F(4,3) form off with it.  Where the F(4,3) form engages, utterances of at least
+ * CTTS_F32_WINOGRAD_F63_MIN columns (default 28 800; 0 = always; the utterance alone decides) run its layers of dilation d % 4 == 0
+ * as Winograd F(6,3) on output hexes (t, t + d, .., t + 5d), interpolation points 0, +-1, +-2, +-1/2, inf: 8/6 C products per output
+ * and row, six interior products combined in registers with the exact multipliers 2^-5 .. 2^5, the transformed filters formed in fp64
+ * and rounded once; the d = 2 layer keeps F(4,3); the float64 parity of a flow stays inside the bound of the other forms.
+ * CTTS_F32_WINOGRAD_NO_F63 keeps the F(4,3) layer wherever it engages: the A/B arm, bit-equal to the library before the F(6,3)
+ * form).  The environment is read once,
  * at the first launch; this re-reads it (tests and profiling scripts that flip a knob in-process). */
 int ctts_tuning_reload(void);
 /* The knobs as the library currently sees them: bit 0 CTTS_F32_NO_GLDS, 1 CTTS_GEMM_NO_XCD_PAIR, 2 CTTS_F32_WINOGRAD_FUSED_MIN set,
@@ -1360,6 +1366,9 @@ int ctts_tuning_reload(void);
  * 31 CTTS_WF_FWD_ROWWISE (the sign bit of the int: the WaveFlow analysis pass row by row, see ctts_waveflow_forward_f32).  Bits 2, 5, 6 and 22 belonged to retired knobs until the one-launch Winograd layer (2, 5) and its F(4,3) form (6, 22) took them.
  * (Tests assert that a knob they set is the one in effect.) */
 int ctts_tuning_flags(void);
+/* The knobs beyond the int above, counted on: bit 32 CTTS_F32_WINOGRAD_F63_MIN set, 33 CTTS_F32_WINOGRAD_NO_F63 (bit 0 and 1 of this
+ * value). */
+int ctts_tuning_flags_ext(void);
 
 /* ---- in-library kernel timing (bench.py roofline leg) ---------------------------------
  * A profile is an opaque caller-owned handle (ABI 6; until ABI 5 one set of process-global slots).  A thread that has

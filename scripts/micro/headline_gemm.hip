@@ -17,6 +17,7 @@
 
 #include "../../cookietts_amd/csrc/gemm_f32.hip"
 #include "../../cookietts_amd/csrc/wn_winograd_layer.hip"
+#include "../../cookietts_amd/csrc/waveglow_kernels.hip"
 
 namespace ctts {
 void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
@@ -106,6 +107,44 @@ __global__ __launch_bounds__(256) void f43_reference_kernel(const WnWinogradLaye
         float t = 0.f, g = 0.f;
         if (k == 0 || k == 3)
             for (int kk = 0; kk < a.C; ++kk) { const float v = vq(k == 3 ? 5 : 0, kk); t = fmaf(gate(P, i, kk), v, t); g = fmaf(gate(P, 64 + i, kk), v, g); }
+        for (int kk = 0; kk < a.H; ++kk) {
+            const float v = a.h2[(size_t)b * a.h_bstride + (size_t)kk * a.ld + a.pad + tk];
+            t = fmaf(gate(P, i, a.C + kk), v, t); g = fmaf(gate(P, 64 + i, a.C + kk), v, g);
+        }
+        const float u0 = y[0][k] + t + a.bias[cb * 128 + i], u1 = y[1][k] + g + a.bias[cb * 128 + 64 + i];
+        out[(size_t)b * a.act_bstride + (size_t)ch * a.ld + a.pad + tk] = tanhf(u0) / (1.f + expf(-u1));
+    }
+}
+// The F(6,3) layer (form = WNWG_F63) the same way: six interior products, the hex map, the cond chunks of the first GATE panel for
+// the four middle members.
+__global__ __launch_bounds__(256) void f63_reference_kernel(const WnWinogradLayerArgs a, float* __restrict__ out) {
+    const int q = blockIdx.x * 256 + threadIdx.x, ch = blockIdx.y, b = blockIdx.z;
+    if (q >= a.Lp) return;
+    const int n1 = a.C / GEMM_KC, n2 = (a.C + a.H) / GEMM_KC, cb = ch >> 6, i = ch & 63;
+    auto split = [&](const float* P, int row, int kk) { return P[((size_t)(row >> 8) * n1 + kk / GEMM_KC) * (GEMM_KC * 256) + (kk % GEMM_KC) * 256 + (row & 255)]; };
+    auto gate = [&](const float* P, int r, int kk) { return P[((size_t)(cb >> 1) * n2 + kk / GEMM_KC) * (GEMM_KC * 256) + (kk % GEMM_KC) * 256 + (cb & 1) * 128 + r]; };
+    auto vq = [&](int j, int kk) { return a.V[j * a.vplane + ((size_t)b * a.C + kk) * a.ldp + q]; };
+    const float* U[6] = {a.A_T2, a.A_T3, a.A_T4, a.A_T5, a.A_T6, a.A_T7};
+    float pt[6], pg[6];
+    for (int j = 0; j < 6; ++j) {
+        float t = 0.f, g = 0.f;
+        for (int kk = 0; kk < a.C; ++kk) { const float v = vq(1 + j, kk); t = fmaf(split(U[j], ch, kk), v, t); g = fmaf(split(U[j], a.C + ch, kk), v, g); }
+        pt[j] = t; pg[j] = g;
+    }
+    float y[2][6];
+    for (int s = 0; s < 2; ++s) {
+        const float* p = s ? pg : pt;
+        const float sa = p[0] + p[1], sb = p[0] - p[1], sc = p[2] + p[3], se = p[2] - p[3], sf = p[4] + p[5], sg = p[4] - p[5];
+        y[s][0] = (sa + sc) + sf; y[s][1] = (sb + 2.f * se) + 0.5f * sg; y[s][2] = (sa + 4.f * sc) + 0.25f * sf;
+        y[s][3] = (sb + 8.f * se) + 0.125f * sg; y[s][4] = (sa + 16.f * sc) + 0.0625f * sf; y[s][5] = (sb + 32.f * se) + 0.03125f * sg;
+    }
+    for (int k = 0; k < 6; ++k) {
+        const int tk = (q / a.d) * (6 * a.d) + q % a.d + k * a.d;
+        if (tk >= a.L) continue;
+        const float* P = k == 5 ? a.A_o : a.A_e;
+        float t = 0.f, g = 0.f;
+        if (k == 0 || k == 5)
+            for (int kk = 0; kk < a.C; ++kk) { const float v = vq(k == 5 ? 7 : 0, kk); t = fmaf(gate(P, i, kk), v, t); g = fmaf(gate(P, 64 + i, kk), v, g); }
         for (int kk = 0; kk < a.H; ++kk) {
             const float v = a.h2[(size_t)b * a.h_bstride + (size_t)kk * a.ld + a.pad + tk];
             t = fmaf(gate(P, i, a.C + kk), v, t); g = fmaf(gate(P, 64 + i, a.C + kk), v, g);
@@ -234,6 +273,90 @@ int main(int argc, char** argv) {
                 f.ldp = ldq; f.Lp = Lq_of(f.d); f.ntiles = (f.Lp + 63) / 64;
                 return f;
             };
+            if (getenv("HG_F63")) {
+                // Go / no-go for the F(6,3) form of the layers with d % 4 == 0 (profiles/r34_01_winograd_f63_gonogo.txt): today's layer (the quad transform + the F(4,3) launch)
+                // against the hex transform + the F(6,3) launch (64 hex columns = 384 natural columns, 352 chunks), the library's own
+                // transform kernels on x, d = 128 and d = 8 alternating over three rotating weight slots, arms alternated HG_ROUNDS
+                // times.  First the new kernel's output is compared with f63_reference_kernel on the same packed operands.
+                //   HG_WINOGRAD=1 HG_F43=1 HG_F63=1 [HG_ROUNDS=5]
+                const int hslots = 3;
+                const size_t slot_h = (size_t)(24 * n1 + 8 * n2) * a_tile;                // U1..U6 SPLIT, [U0 | C_i], [U7 | C_i] GATE
+                if ((size_t)hslots * slot_h > (size_t)layers * 4 * nch * a_tile) return 1;
+                auto Lh_of = [&](int d) { return (Ln + 6 * d - 1) / (6 * d) * d; };
+                const int ldh = (Lh_of(128) + 63) / 64 * 64;                              // 76 tiles of 64 hex columns
+                const size_t hplane = (size_t)B * C * ldh;
+                float* Vh;
+                CK(hipMalloc(&Vh, 8 * hplane * 4));
+                auto a43 = [&](int i) {
+                    WnWinogradLayerArgs f = f43_args(i);
+                    const float* w = A + (size_t)(i % hslots) * slot_h;
+                    f.A_T2 = w; f.A_T3 = w + (size_t)4 * n1 * a_tile; f.A_T4 = w + (size_t)8 * n1 * a_tile; f.A_T5 = w + (size_t)12 * n1 * a_tile;
+                    f.A_e = w + (size_t)16 * n1 * a_tile; f.A_o = f.A_e + (size_t)4 * n2 * a_tile;
+                    return f;
+                };
+                auto a63 = [&](int i) {
+                    WnWinogradLayerArgs f = a43(i);
+                    const float* w = A + (size_t)(i % hslots) * slot_h;
+                    f.form = WNWG_F63;
+                    f.A_T6 = w + (size_t)16 * n1 * a_tile; f.A_T7 = w + (size_t)20 * n1 * a_tile;
+                    f.A_e = w + (size_t)24 * n1 * a_tile; f.A_o = f.A_e + (size_t)4 * n2 * a_tile;
+                    f.V = Vh; f.vplane = (long long)hplane;
+                    f.ldp = ldh; f.Lp = Lh_of(f.d); f.ntiles = (f.Lp + 63) / 64;
+                    return f;
+                };
+                auto layer = [&](int arm, int i, bool with_transform) {
+                    const WnWinogradLayerArgs f = arm ? a63(i) : a43(i);
+                    if (with_transform) {
+                        const int rc = arm ? launch_winograd_transform_hex(x, (long long)C * ld, Vh, B, C, f.d, Ln, f.Lp, ld, PADC, ldh, f.ntiles * 64, st)
+                                           : launch_winograd_transform_quad(x, (long long)C * ld, h, (long long)CC * ld, Vq, nullptr, B, C, CC, f.d, Ln, f.Lp, ld,
+                                                                            PADC, ldq, f.ntiles * 64, false, st);
+                        if (rc) return rc;
+                    }
+                    return launch_wn_winograd_layer(f, st);
+                };
+                unsetenv("CTTS_F32_NO_ROUND_SPLIT"); reload_tuning();
+                const size_t n = (size_t)B * C * ld;
+                for (int i = 0; i < 2; ++i) {
+                    WnWinogradLayerArgs f = a63(i);
+                    CK(hipMemsetAsync(act, 0, n * 4, st)); CK(hipMemsetAsync(act2, 0, n * 4, st)); CK(hipMemsetAsync(dmax, 0, 8, st));
+                    if (layer(1, i, true)) return 1;
+                    f.act = act;
+                    hipLaunchKernelGGL(f63_reference_kernel, dim3((unsigned)((f.Lp + 255) / 256), C, B), dim3(256), 0, st, f, act);
+                    hipLaunchKernelGGL(max_diff_kernel, dim3(4096), dim3(256), 0, st, act, act2, n, dmax);
+                    unsigned hd[2];
+                    CK(hipMemcpyAsync(hd, dmax, 8, hipMemcpyDeviceToHost, st)); CK(hipStreamSynchronize(st));
+                    float fd[2]; memcpy(fd, hd, 8);
+                    printf("d = %3d, Lh = %d, %d tiles x %d: max |F(6,3) launch - reference| = %.3e, max |reference| = %.3e\n", f.d, f.Lp, f.ntiles, B, fd[0], fd[1]);
+                    // (the interior sums enter with multipliers up to 32: fmaf chain against MFMA order at |32 e| ~ 10)
+                    if (!(fd[0] <= 1e-4f) || !(fd[1] > 0.01f)) { printf("MISMATCH\n"); return 2; }
+                }
+                const int rounds = getenv("HG_ROUNDS") ? atoi(getenv("HG_ROUNDS")) : 5, reps = 12;
+                float lo[2][2], hi[2][2], sum[2][2];
+                for (int arm = 0; arm < 2; ++arm) for (int w = 0; w < 2; ++w) { lo[arm][w] = 1e9f; hi[arm][w] = 0.f; sum[arm][w] = 0.f; }
+                static const char* names[2] = {"F(4,3) one launch", "F(6,3) one launch"};
+                for (int r = 0; r < rounds; ++r)
+                    for (int arm = 0; arm < 2; ++arm)
+                        for (int w = 0; w < 2; ++w) {
+                            for (int i = 0; i < 4; ++i) if (layer(arm, i, w)) return 1;
+                            CK(hipStreamSynchronize(st));
+                            CK(hipEventRecord(e0, st));
+                            for (int i = 0; i < reps; ++i) if (layer(arm, i, w)) return 1;
+                            CK(hipEventRecord(e1, st));
+                            CK(hipStreamSynchronize(st));
+                            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                            ms /= reps;
+                            printf("round %d  %-20s %-22s %.4f ms per layer\n", r, names[arm], w ? "+ its transform" : "launches alone", ms);
+                            lo[arm][w] = ms < lo[arm][w] ? ms : lo[arm][w]; hi[arm][w] = ms > hi[arm][w] ? ms : hi[arm][w]; sum[arm][w] += ms;
+                        }
+                for (int w = 0; w < 2; ++w) {
+                    const float s0 = hi[0][w] - lo[0][w], s1 = hi[1][w] - lo[1][w], spread = s0 > s1 ? s0 : s1;
+                    const float gain = (sum[0][w] - sum[1][w]) / rounds;
+                    printf("%s: F(4,3) %.4f ms (%.4f-%.4f), F(6,3) %.4f ms (%.4f-%.4f): gain %.4f ms = %.1f x the larger spread%s\n",
+                           w ? "per layer with its transform" : "layer launches alone", sum[0][w] / rounds, lo[0][w], hi[0][w], sum[1][w] / rounds,
+                           lo[1][w], hi[1][w], gain, gain / (spread > 0.f ? spread : 1e-9f), w ? (gain > 10.f * spread ? "  -> GO" : "  -> NO-GO") : "");
+                }
+                return 0;
+            }
             if (getenv("HG_F43_WIDE")) {
                 // Go / no-go for the shapes of the F(4,3) layer (profiles/r26_01_f43_wide_gonogo.txt): the parent's kernel (64 quad columns,
                 // one chunk per stage, chunk table read by a plain load) against the same shape with the table fetched ahead, with
